@@ -23,6 +23,9 @@ carries `host_frame` (the reference's calling convention: host frames, H2D insid
            weights; `--fp8-legs` adds the FP8 e4m3 pair) -- each 8-bit leg with an `accuracy` object: refined-pose deltas against the f16
            path, winner, teacher-forced rank, whether the 1 deg / 1 mm bar is met for >= 95 % of the hypotheses.
 
+`--dump-outputs DIR` writes what the headline's last timed step handed its caller as DIR/<name>.npy: `pose` (4x4 row-major float32)
+and, for N > 1, `winner` (the hypothesis index, float64).  The inputs are seeded, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   roofline     -- dominant kernel (the conv/linear implicit-GEMM kernel with the largest share of the step, MFMA-bound):
                   algorithmic FLOPs of its launches in one step / their HIP-event durations on the library's stream
@@ -77,6 +80,14 @@ def cpu_baseline(mesh, scene, states, n_hyp=8, reps=8):
     return dict(value=round(n_hyp * reps / dt, 3), unit="hypotheses/s", cores=threads, kind="port",
                 sample=f"{reps} x Register N={n_hyp} 640x480 refine_itr=1 (oracle C/OpenMP geometry + PyTorch-CPU fp32 "
                        f"networks, {dt:.1f} s); the reference has no CPU path for this (SURVEY.md §8d)")
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: one out_dir/<name>.npy per array (float32 / float64 only)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 FP8_LAYERS = {"conv_128", "conv_256", "conv_b2", "conv_512"}   # 3x3 trunk convolutions from encodeA.2 on run on 8-bit operands in the fp8 / int8 modes
 Q8 = ("fp8", "int8")
@@ -330,6 +341,8 @@ def rank_main(args, world):
     poses = client.all_gather(out_pose.tobytes())
     if len(set(winners)) != 1 or len(set(poses)) != 1:
         raise SystemExit(f"rank {rank}: the ranks disagree on the winner / pose ({winners}): the redundant finish must be bit-identical")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pose=syn.from_colmajor(out_pose), winner=np.array([idx.value], np.float64))
     model.profile(True)
     model.profile_reset()
     step()
@@ -388,7 +401,10 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the host-frame and Track legs (profiling runs)")
     ap.add_argument("--fp8-legs", action="store_true", help="also run the two FP8 e4m3 720p legs (experimental: the precision fails the configs[4] parity bar)")
     ap.add_argument("--track", action="store_true", help="measure Track fps (N=1 hypothesis) as the headline instead of Register")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline's last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- who am I?  (contract: `python bench.py --gpus N` alone, or one rank of `python -m torch.distributed.run ... bench.py --gpus N`)
     world_env = os.environ.get("WORLD_SIZE")
@@ -471,6 +487,8 @@ def main():
         return time.perf_counter() - t0
 
     dt = timed(step, args.steps, args.warmup)
+    if args.dump_outputs:         # now: every later leg reuses out_pose
+        dump_outputs(args.dump_outputs, pose=syn.from_colmajor(out_pose))
 
     # per-kernel-family event timing of ONE extra step (outside the timed region)
     model.profile(True)

@@ -1,5 +1,5 @@
 import os, sys, tempfile
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from foundationpose_cpp_amd import FoundationPose, synthetic as syn, weights as W
 mesh = syn.make_mesh(); scene = syn.make_scene(mesh)
 d = tempfile.mkdtemp()
