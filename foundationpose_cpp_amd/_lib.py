@@ -56,6 +56,12 @@ def lib() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(there is no CPU fallback)")
     L = C.CDLL(LIB_PATH)
+    _LIB = _declare(L)
+    return L
+
+
+def _declare(L: C.CDLL) -> C.CDLL:
+    """check that L exports the C ABI and give every fp_* entry point its signature"""
     for s in SYMBOLS:
         getattr(L, s)  # raises AttributeError if the library does not export the symbol
     L.fp_create.restype = C.c_void_p
@@ -122,7 +128,6 @@ def lib() -> C.CDLL:
         f.restype = C.c_int
     L.fp_calibration_size.argtypes = []
     L.fp_calibration_size.restype = C.c_size_t
-    _LIB = L
     return L
 
 
@@ -138,8 +143,7 @@ def test_lib() -> C.CDLL:
     if _TEST_LIB is None:
         if not os.path.exists(TEST_LIB_PATH):
             raise RuntimeError(f"{TEST_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        _TEST_LIB = C.CDLL(TEST_LIB_PATH)
-        _TEST_LIB.fp_last_error.restype = C.c_char_p
+        _TEST_LIB = _declare(C.CDLL(TEST_LIB_PATH))   # (a superset of the product: the same fp_* signatures)
     return _TEST_LIB
 
 

@@ -770,6 +770,14 @@ int fpt_model_use_graphs(fp_model *m, int on) {
   return 0;
 }
 
+// poison the current precision's network scratch (nn_scratch_poison; kind 0 quiet NaN, 1 +-largest finite) and wait for it
+int fpt_model_poison(fp_model *m, int kind) {
+  if (!m->ws) return 0;
+  if (nn_scratch_poison(m->ws, m->prec == PREC_BF16 ? DT_BF16 : DT_F16, kind, m->stream)) return 1;
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  return 0;
+}
+
 // bit 0: graphs still enabled (a failed capture disables them), bit 1: Track graph instantiated, bit 2: Register graph
 int fpt_model_graph_state(fp_model *m) { return (m->use_graphs ? 1 : 0) | (m->tg.exec ? 2 : 0) | (m->rg.exec ? 4 : 0); }
 

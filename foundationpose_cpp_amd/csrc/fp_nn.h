@@ -55,6 +55,21 @@ NNScratch *nn_scratch_create(int prec);
 void nn_scratch_free(NNScratch *);
 // debug (cross-model corruption checks): the activation arena and the f32 side buffer
 void nn_scratch_debug_info(const NNScratch *, const void **buf, size_t *bytes, const void **f32, size_t *f32_bytes);
+#ifdef FP_TEST_HOOKS
+// test build: fill every interior of the 2-byte activation arena (borders and the zero-initialised counters stay), the split-K
+// partials, the f32 side buffer and the cross-attention scratch with a poison pattern -- kind 0: quiet NaN, 1: the largest finite
+// value with alternating sign.  dt = the arena's element type (DT_F16 / DT_BF16).
+int nn_scratch_poison(NNScratch *, int dt, int kind, hipStream_t s);
+#endif
+
+// activation taps of the test build (fpt_tap_arm, tests/test_layers_gpu.py): where the forward pass copies a tensor out
+enum TapPoint {
+  TAP_NN_IN = 0, TAP_STEM = 1, TAP_ACT = 1,   // trunk activation i (1..14, the calib_record sites) = point TAP_ACT + i; 15 = tokens + pe
+  TAP_HEAD = 16, TAP_HEAD_STRIDE = 8,         // per head h (refiner: 0 trans, 1 rot; scorer: 0 = att): TAP_HEAD + 8 h + TAP_H_*
+  TAP_PDOT = 32, TAP_TRANS = 33, TAP_ROT = 34, TAP_FEAT = 35,
+  TAP_XF = 36, TAP_XQKV = 37, TAP_XATT = 38, TAP_XOUT = 39, TAP_O32 = 40, TAP_SCORES = 41, TAP_PE = 42, TAP_POINTS = 48
+};
+enum { TAP_H_QKV = 0, TAP_H_ATT = 1, TAP_H_Y1 = 2, TAP_H_X1 = 3, TAP_H_HID = 4, TAP_H_Y2 = 5, TAP_H_POOL = 6, TAP_H_LN2 = 7 };
 
 // Network input: nn_in = [2N,84,84,32] (net_input_dt elements): space-to-depth(2x2) view of the NHWC [2N,160,160,8] tensor
 // (channels r,g,b,x,y,z,0,0) with a zero border of 2, rendered crops A in images [0,N), observed crops B in [N,2N).

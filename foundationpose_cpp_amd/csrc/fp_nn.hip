@@ -1304,6 +1304,28 @@ FP_HOOK g_smallx_pf = 0;       // A/B (test build): prefetch depth of conv_small
 FP_HOOK g_smallm = 1;          // small problems (Track, a few objects) on conv_smallm_kernel: K split over the waves of a workgroup, no split-K slabs / reduce launch
 FP_HOOK g_att_variant = 1;     // 1 = attention32_kernel (8 = without the XCD remap); round-1 kernel: 2 remap + 16-B stores, 3 no XCD remap, 5 remap + 2-B stores, 7 neither
 
+// Activation taps (test build only; tests/test_layers_gpu.py): an armed tap copies the tensor a producer just wrote -- borders
+// included, behind the join of a forked left-over -- device to device into the test's buffer, on the forward pass's own stream.
+// In the product FP_TAP expands to nothing (its arguments are not evaluated).  Points: fp_nn.h, enum TapPoint.
+#ifdef FP_TEST_HOOKS
+struct TapSlot {
+  void *dst = nullptr;
+  size_t cap = 0;    // bytes the test's buffer holds
+  size_t need = 0;   // bytes the producer wrote in the last armed call (copied only when they fit)
+};
+static TapSlot g_tap[2][TAP_POINTS];   // [refiner, scorer]
+static int g_tap_pe_fused[2] = {-1, -1};   // the last call's conv_512 -> tokens fused the positional table (1) or not (0)
+static void tap(const Ctx &c, int point, const void *src, size_t bytes) {
+  TapSlot &t = g_tap[c.net->scorer ? 1 : 0][point];
+  if (!t.dst) return;
+  t.need = bytes;
+  if (bytes <= t.cap) (void)hipMemcpyAsync(t.dst, src, bytes, hipMemcpyDeviceToDevice, c.s);
+}
+#define FP_TAP(c, point, src, bytes) tap(c, point, src, bytes)
+#else
+#define FP_TAP(c, point, src, bytes) ((void)0)
+#endif
+
 // One launch = (once per launch site, element type and DEVICE) dynamic-LDS opt-in + the launch itself.
 #define FP_LAUNCH(KERN, grid, block, lds_bytes, stream, ...)                                                                        \
   do {                                                                                                                              \
@@ -1990,6 +2012,56 @@ static Arena carve(NNScratch *ws) {
   return a;
 }
 
+#ifdef FP_TEST_HOOKS
+// nn_scratch_poison (test build): 2-byte pattern over the interior of [imgs][H + 2b][W + 2b][C], alternating pos / neg by element
+__global__ void poison16_kernel(uint16_t *p, size_t imgs, int H, int W, int b, int C, uint16_t pos, uint16_t neg) {
+  const size_t n = imgs * H * W * C;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    size_t r = i / C;
+    const size_t ch = i % C, x = r % W;
+    r /= W;
+    const size_t y = r % H, img = r / H;
+    p[((img * (H + 2 * b) + y + b) * (W + 2 * b) + x + b) * C + ch] = (i & 1) ? neg : pos;
+  }
+}
+__global__ void poison32_kernel(uint32_t *p, size_t n, uint32_t pos, uint32_t neg) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = (i & 1) ? neg : pos;
+}
+int nn_scratch_poison(NNScratch *ws, int dt, int kind, hipStream_t s) {
+  const bool bf = dt == DT_BF16;
+  const uint16_t p16 = kind == 0 ? (bf ? 0x7FC0 : 0x7E00) : (bf ? 0x7F7F : 0x7BFF), n16 = kind == 0 ? p16 : (uint16_t)(p16 | 0x8000);
+  const uint32_t p32 = kind == 0 ? 0x7FC00000u : 0x7F7FFFFFu, n32 = kind == 0 ? p32 : 0xFF7FFFFFu;
+  auto grid = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)); };
+  auto fill16 = [&](void *p, size_t imgs, int H, int W, int b, int C) {
+    const size_t n = imgs * H * W * C;
+    if (n) hipLaunchKernelGGL(poison16_kernel, grid(n), dim3(256), 0, s, (uint16_t *)p, imgs, H, W, b, C, p16, n16);
+  };
+  auto fill32 = [&](float *p, size_t n) {
+    if (p && n) hipLaunchKernelGGL(poison32_kernel, grid(n), dim3(256), 0, s, (uint32_t *)p, n, p32, n32);
+  };
+  if (ws->buf) {
+    const Arena a = carve(ws);
+    const size_t cap = (size_t)ws->cap;
+    fill16(a.stem, 2 * cap, 80, 80, 1, 64);
+    for (int i = 0; i < 3; i++) {
+      fill16(a.x128[i], 2 * cap, 40, 40, 1, 128);
+      fill16(a.x256[i], cap, 40, 40, 1, 256);
+      fill16(a.x512[i], cap, 20, 20, 1, 512);
+    }
+    for (unsigned char *t : {a.tokens, a.att, a.y1, a.y2}) fill16(t, cap, 400, 1, 0, EMBED);
+    fill16(a.qkv, cap, 400, 1, 0, 3 * EMBED);
+    // f32 side buffer: the pooled rows and the partial sums of layernorm_pmean_kernel; NOT the 16 zero-initialised arrival counters
+    fill32(ws->f32, cap * EMBED);
+    fill32(ws->f32 + cap * EMBED + 16, 2 * 16 * EMBED);
+  }
+  fill32(ws->splitk, ws->splitk_cap);
+  if (ws->head_buf) fill16(ws->head_buf, (size_t)ws->head_cap * 5, 1, 1, 0, EMBED);
+  fill32(ws->head_f32, (size_t)ws->head_cap * EMBED);
+  FP_HIP_OK(hipGetLastError());
+  return 0;
+}
+#endif
+
 // the last trunk convolution writes the un-bordered token tensor; whoever did not fuse the positional table adds it here
 static void add_pos_embed(const Ctx &c, const Arena &a, int N) {
   const Net *net = c.net;
@@ -2203,44 +2275,64 @@ static int run_trunk(const Ctx &c, const Arena &a, const void *nn_in, int N, int
   const Act x0 = T(a.x128[0]), x1 = T(a.x128[1]), x2 = T(a.x128[2]), cat = T(a.x256[0]);
   // ([r5] stem + encodeA.1 in chunks of 63 / 84 / 126 images, so that the stem's output would be read back from the 256 MB memory-side
   // cache instead of HBM: 10.93 -> 11.24 / 11.13 / 11.00 ms per Register, slower with every extra launch -- EXPERIMENTS.md R5.4)
+  FP_TAP(c, TAP_NN_IN, nn_in, (size_t)NB2 * 84 * 84 * 32 * 2);
   if (run_conv(c, "conv_stem", net->a0, in, NB2, 80, 80, 2, stem, 1, true)) return 1;
+  FP_TAP(c, TAP_STEM, a.stem, (size_t)NB2 * 82 * 82 * 64 * 2);
   if (run_conv(c, "conv_a1", net->a1, stem, NB2, 80, 80, 1, x0, 1, true)) return 1;
   calib_record(c, 1, a.x128[0], P1, 128, adt);
+  FP_TAP(c, TAP_ACT + 1, a.x128[0], P1 * 128 * 2);
   // encodeA residual blocks @40x40x128; the last conv writes the a|b channel concat directly
   if (run_conv(c, "conv_128", net->ra[0][0], x0, NB2, 40, 40, 1, x1, 1, true)) return 1;
   calib_record(c, 2, a.x128[1], P1, 128, adt);
+  FP_TAP(c, TAP_ACT + 2, a.x128[1], P1 * 128 * 2);
   if (run_conv(c, "conv_128", net->ra[0][1], x1, NB2, 40, 40, 1, x2, 1, true, &x0, 1)) return 1;
   calib_record(c, 3, a.x128[2], P1, 128, adt);
+  FP_TAP(c, TAP_ACT + 3, a.x128[2], P1 * 128 * 2);
   if (run_conv(c, "conv_128", net->ra[1][0], x2, NB2, 40, 40, 1, x1, 1, true)) return 1;
   calib_record(c, 4, a.x128[1], P1, 128, adt);
+  FP_TAP(c, TAP_ACT + 4, a.x128[1], P1 * 128 * 2);
   if (run_conv(c, "conv_128", net->ra[1][1], x1, NB2, 40, 40, 1, cat, 1, true, &x2, 1, N)) return 1;
   if (n_b == 1 && N > 1) broadcast_b(c, a.x256[0], N, 256);  // image N landed in cat[0][..,128:256]; replicate it for the other hypotheses
   calib_record(c, 5, a.x256[0], P2, 256, adt);
+  FP_TAP(c, TAP_ACT + 5, a.x256[0], P2 * 256 * 2);
   // encodeAB
   const Act y1 = T(a.x256[1]), y2 = T(a.x256[2]), y0 = T(a.x256[0]);
   if (run_conv(c, "conv_256", net->rb[0][0], cat, N, 40, 40, 1, y1, 1, true)) return 1;
   calib_record(c, 6, a.x256[1], P2, 256, adt);
+  FP_TAP(c, TAP_ACT + 6, a.x256[1], P2 * 256 * 2);
   if (run_conv(c, "conv_256", net->rb[0][1], y1, N, 40, 40, 1, y2, 1, true, &cat, 1)) return 1;
   calib_record(c, 7, a.x256[2], P2, 256, adt);
+  FP_TAP(c, TAP_ACT + 7, a.x256[2], P2 * 256 * 2);
   if (run_conv(c, "conv_256", net->rb[1][0], y2, N, 40, 40, 1, y1, 1, true)) return 1;
   calib_record(c, 8, a.x256[1], P2, 256, adt);
+  FP_TAP(c, TAP_ACT + 8, a.x256[1], P2 * 256 * 2);
   if (run_conv(c, "conv_256", net->rb[1][1], y1, N, 40, 40, 1, y0, 1, true, &y2, 1)) return 1;
   calib_record(c, 9, a.x256[0], P2, 256, adt);
+  FP_TAP(c, TAP_ACT + 9, a.x256[0], P2 * 256 * 2);
   const Act z0 = T(a.x512[0]), z1 = T(a.x512[1]), z2 = T(a.x512[2]);
   if (run_conv(c, "conv_b2", net->b2, y0, N, 40, 40, 1, z0, 1, true)) return 1;
   calib_record(c, 10, a.x512[0], P5, 512, adt);
+  FP_TAP(c, TAP_ACT + 10, a.x512[0], P5 * 512 * 2);
   if (run_conv(c, "conv_512", net->rc[0][0], z0, N, 20, 20, 1, z1, 1, true)) return 1;
   calib_record(c, 11, a.x512[1], P5, 512, adt);
+  FP_TAP(c, TAP_ACT + 11, a.x512[1], P5 * 512 * 2);
   if (run_conv(c, "conv_512", net->rc[0][1], z1, N, 20, 20, 1, z2, 1, true, &z0, 1)) return 1;
   calib_record(c, 12, a.x512[2], P5, 512, adt);
+  FP_TAP(c, TAP_ACT + 12, a.x512[2], P5 * 512 * 2);
   if (run_conv(c, "conv_512", net->rc[1][0], z2, N, 20, 20, 1, z1, 1, true)) return 1;
   calib_record(c, 13, a.x512[1], P5, 512, adt);
+  FP_TAP(c, TAP_ACT + 13, a.x512[1], P5 * 512 * 2);
   // last conv writes the un-bordered token tensor [N,400,512] (2-byte type in every precision)
   const Act tok = T(a.tokens);
   bool pe_done = false;
   if (run_conv(c, "conv_512", net->rc[1][1], z1, N, 20, 20, 1, tok, 0, true, &z2, 1, 0, nullptr, net->pe, &pe_done)) return 1;
   if (!pe_done) add_pos_embed(c, a, N);
+#ifdef FP_TEST_HOOKS
+  g_tap_pe_fused[net->scorer ? 1 : 0] = pe_done ? 1 : 0;
+#endif
+  FP_TAP(c, TAP_PE, net->pe, (size_t)400 * EMBED * 2);
   calib_record(c, 14, a.tokens, (size_t)N * 400, 512, adt);
+  FP_TAP(c, TAP_ACT + 14, a.tokens, (size_t)N * 400 * 512 * 2);
   return 0;
 }
 
@@ -2273,7 +2365,11 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
     ConvGroup g_x{G, true, true}, g_in{G, false, true}, g_own{G, false, false};
     const EncLayer &T0 = net->trans, &R0 = net->rot;
     if (run_gemm(c, "gemm_qkv", net->g_in_proj, x, 2 * G, a.qkv, false, nullptr, &g_x)) return 1;
+    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv, (size_t)400 * 3 * EMBED * 2);
+    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv + (size_t)G * 3 * EMBED * 2, (size_t)400 * 3 * EMBED * 2);
     if (run_attention(c, dt, a.qkv, a.att, 2, 400, G)) return 1;
+    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_ATT, a.att, (size_t)400 * EMBED * 2);
+    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_ATT, a.att + (size_t)G * EMBED * 2, (size_t)400 * EMBED * 2);
     if (g_enc_tail && (dt == DT_F16 || dt == DT_BF16) && tail_ok(T0) && tail_ok(R0) && T0.head.out == 3 && R0.head.out == 3
 #ifdef FP_TEST_HOOKS
         && g_fuse_pose != 2
@@ -2302,6 +2398,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
         if (dt == DT_BF16) FP_LAUNCH((enc_tail_kernel<DT_BF16, 1>), dim3(50), dim3(512), kLds, c.s, q);
         else FP_LAUNCH((enc_tail_kernel<DT_F16, 1>), dim3(50), dim3(512), kLds, c.s, q);
       }
+      FP_TAP(c, TAP_PDOT, pdot, (size_t)2 * 25 * 4 * sizeof(float));
       {
         ProfScope ps(c.prof, c.s, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
         EncHeadsParams hp{pdot, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}, 1, 25, 3, 400.f};
@@ -2309,13 +2406,24 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
         hipLaunchKernelGGL(enc_heads_kernel, dim3(1), dim3(64), 0, c.s, hp, do_fuse ? *fuse : PoseUpdateFuse{}, do_fuse ? 1 : 0);
         if (do_fuse && fused_out) *fused_out = true;
       }
+      FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
+      FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
       FP_HIP_OK(hipGetLastError());
       return 0;
     }
+    [[maybe_unused]] const size_t hb = (size_t)400 * EMBED * 2, ho = (size_t)G * EMBED * 2;   // (taps: a head's 400 rows, the second head's offset)
     if (run_gemm(c, "gemm_512", net->g_out_proj, a.att, 2 * G, a.y1, false, x, &g_in)) return 1;   // + residual x (shared)
+    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_Y1, a.y1, hb);
+    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_Y1, a.y1 + ho, hb);
     run_layernorm(c, dt, a.y1, T0.ln1, a.y2, 2 * G, &R0.ln1, G);
+    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_X1, a.y2, hb);
+    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_X1, a.y2 + ho, hb);
     if (run_gemm(c, "gemm_512", net->g_lin1, a.y2, 2 * G, a.y1, true, nullptr, &g_own)) return 1;
+    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_HID, a.y1, hb);
+    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_HID, a.y1 + ho, hb);
     if (run_gemm(c, "gemm_512", net->g_lin2, a.y1, 2 * G, a.att, false, a.y2, &g_own)) return 1;   // + residual x1
+    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_Y2, a.att, hb);
+    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_Y2, a.att + ho, hb);
     // LayerNorm 2 feeds nothing but the token mean.  [r5] ONE launch: 2 x 16 workgroups normalise 25 rows each and leave partial column sums,
     // which the heads kernel adds up (layernorm_pmean_kernel).  Before: LayerNorm over 800 workgroup-rows + a 16-workgroup mean, two
     // dependent launches (11 us; the one-workgroup-per-sequence fused kernel of Register is a 20 us serial chain at two sequences)
@@ -2330,6 +2438,8 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
       ProfScope ps(c.prof, c.s, "layernorm_pmean", 0, 2.0 * 400 * EMBED * 2.0);
       if (dt == DT_BF16) hipLaunchKernelGGL(layernorm_pmean_kernel<DT_BF16>, dim3(2, kParts), dim3(256), 0, c.s, (const __bf16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
       else hipLaunchKernelGGL(layernorm_pmean_kernel<DT_F16>, dim3(2, kParts), dim3(256), 0, c.s, (const _Float16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
+      FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_POOL, psums, (size_t)kParts * EMBED * sizeof(float));   // (partial column sums: kParts x 25 rows)
+      FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_POOL, psums + kParts * EMBED, (size_t)kParts * EMBED * sizeof(float));
     } else run_layernorm(c, dt, a.att, T0.ln2, a.y1, 2 * G, &R0.ln2, G);
 #ifdef FP_TEST_HOOKS
     if (fuse && g_fuse_pose == 2 && T0.head.out == 3 && R0.head.out == 3 && T0.head.in == EMBED) {
@@ -2357,6 +2467,8 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
       } else
         hipLaunchKernelGGL(small_linear2_kernel, dim3((unsigned)((T0.head.out + 3) / 4), 2), dim3(256), 0, c.s, a, 1, T0.head.out, T0.head.in);
     }
+    FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
+    FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
     FP_HIP_OK(hipGetLastError());
     return 0;
   }
@@ -2366,7 +2478,9 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
     void *att_out[2] = {a.att, a.y1};
     for (int i = 0; i < 2; i++) {
       if (run_qkv(c, heads[i]->att.in_proj, x, (int)rows, a.qkv)) return 1;
+      FP_TAP(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv, rows * 3 * EMBED * 2);
       if (run_attention(c, dt, a.qkv, att_out[i], N, 400)) return 1;
+      FP_TAP(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_ATT, att_out[i], rows * EMBED * 2);
     }
     float *const pdot = reinterpret_cast<float *>(a.y2);   // [2][N * 5][4] f32
     {
@@ -2388,30 +2502,45 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
       if (dt == DT_BF16) FP_LAUNCH((enc_tail_kernel<DT_BF16, 5>), dim3((unsigned)(2 * q.tiles)), dim3(512), kLds, c.s, q);
       else FP_LAUNCH((enc_tail_kernel<DT_F16, 5>), dim3((unsigned)(2 * q.tiles)), dim3(512), kLds, c.s, q);
     }
+    FP_TAP(c, TAP_PDOT, pdot, (size_t)2 * N * 5 * 4 * sizeof(float));
     {
       ProfScope ps(c.prof, c.s, "small_linear", 2.0 * 2 * N * net->trans.head.out * EMBED, 0);
       EncHeadsParams hp{pdot, {net->trans.head.b, net->rot.head.b}, {trans_dev, rot_dev}, N, 5, net->trans.head.out, 400.f};
       hipLaunchKernelGGL(enc_heads_kernel, dim3((unsigned)N), dim3(64), 0, c.s, hp, PoseUpdateFuse{}, 0);
     }
+    FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
+    FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
     FP_HIP_OK(hipGetLastError());
     return 0;
   }
   for (int i = 0; i < 2; i++) {
     const EncLayer &L = *heads[i];
     // post-norm TransformerEncoderLayer: x1 = LN1(x + SA(x)); x2 = LN2(x1 + W2 relu(W1 x1))
+    [[maybe_unused]] const int tp = TAP_HEAD + i * TAP_HEAD_STRIDE;
+    [[maybe_unused]] const size_t tb = rows * EMBED * 2;
     if (run_gemm(c, "gemm_qkv", L.att.in_proj, x, (int)rows, a.qkv, false)) return 1;
+    FP_TAP(c, tp + TAP_H_QKV, a.qkv, 3 * tb);
     if (run_attention(c, dt, a.qkv, a.att, N, 400)) return 1;
+    FP_TAP(c, tp + TAP_H_ATT, a.att, tb);
     if (run_gemm(c, "gemm_512", L.att.out_proj, a.att, (int)rows, a.y1, false, x)) return 1;  // + residual x
+    FP_TAP(c, tp + TAP_H_Y1, a.y1, tb);
     run_layernorm(c, dt, a.y1, L.ln1, a.y2, rows);                                           // x1 = y2
+    FP_TAP(c, tp + TAP_H_X1, a.y2, tb);
     if (run_gemm(c, "gemm_512", L.lin1, a.y2, (int)rows, a.y1, true)) return 1;
+    FP_TAP(c, tp + TAP_H_HID, a.y1, tb);
     if (run_gemm(c, "gemm_512", L.lin2, a.y1, (int)rows, a.att, false, a.y2)) return 1;       // + residual x1
+    FP_TAP(c, tp + TAP_H_Y2, a.att, tb);
     if (N >= 96) run_layernorm_mean(c, dt, a.att, L.ln2, ws->f32, N, 400);
     else {  // few sequences: one workgroup per sequence is a serial chain (26 us at N = 32 against 9 + 9 for the two-kernel form)
       run_layernorm(c, dt, a.att, L.ln2, a.y1, rows);
+      FP_TAP(c, tp + TAP_H_LN2, a.y1, tb);
       run_token_mean(c, dt, a.y1, ws->f32, N, 400);
     }
+    FP_TAP(c, tp + TAP_H_POOL, ws->f32, (size_t)N * EMBED * sizeof(float));
     run_small_linear(c, ws->f32, L.head, outs[i], N);  // Linear(512,3) commutes with the token mean
   }
+  FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
+  FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
   FP_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -2425,10 +2554,14 @@ int scorer_features(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
   if (run_trunk(c, a, nn_in, N, N)) return 1;
   const size_t rows = (size_t)N * 400;
   if (run_qkv(c, net->att.in_proj, a.tokens, (int)rows, a.qkv)) return 1;
+  FP_TAP(c, TAP_HEAD + TAP_H_QKV, a.qkv, rows * 3 * EMBED * 2);
   if (run_attention(c, net->act_dt, a.qkv, a.att, N, 400)) return 1;
+  FP_TAP(c, TAP_HEAD + TAP_H_ATT, a.att, rows * EMBED * 2);
   // feature = mean_t(out_proj(att)) = out_proj(mean_t(att))  (out_proj is affine) -> 512x512 GEMV per hypothesis
   run_token_mean(c, net->act_dt, a.att, ws->f32, N, 400);
+  FP_TAP(c, TAP_HEAD + TAP_H_POOL, ws->f32, (size_t)N * EMBED * sizeof(float));
   run_small_linear(c, ws->f32, net->att.out_proj_f32, feat_dev, N);
+  FP_TAP(c, TAP_FEAT, feat_dev, (size_t)N * EMBED * sizeof(float));
   FP_HIP_OK(hipGetLastError());
   return 0;
 }
@@ -2450,18 +2583,24 @@ int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, co
     if (dt == DT_BF16) hipLaunchKernelGGL(cast_f32_kernel<DT_BF16>, grid, dim3(256), 0, c.s, feats_dev, (__bf16 *)xf, n);
     else hipLaunchKernelGGL(cast_f32_kernel<DT_F16>, grid, dim3(256), 0, c.s, feats_dev, (_Float16 *)xf, n);
   }
+  FP_TAP(c, TAP_XF, xf, (size_t)N * EMBED * 2);
   // att_cross: sequence = the N hypotheses, batch 1
   if (run_gemm(c, "gemm_cross", net->att_cross.in_proj, xf, N, qkv, false)) return 1;
+  FP_TAP(c, TAP_XQKV, qkv, (size_t)N * 3 * EMBED * 2);
   if (run_attention(c, dt, qkv, att, 1, N)) return 1;
+  FP_TAP(c, TAP_XATT, att, (size_t)N * EMBED * 2);
   // out_proj through the same MFMA GEMM (M = N rows), then Linear(512,1) in f32
   if (run_gemm(c, "gemm_cross", net->att_cross.out_proj, att, N, xf, false)) return 1;
+  FP_TAP(c, TAP_XOUT, xf, (size_t)N * EMBED * 2);
   {
     // Linear(512,1) on 2-byte rows: widen to f32 first (token_mean with T = 1 is a plain copy of each row)
     ProfScope ps(c.prof, c.s, "score_linear", 2.0 * N * EMBED, 0);
     if (dt == DT_BF16) hipLaunchKernelGGL(token_mean_kernel<DT_BF16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)xf, o32, 1, 1);
     else hipLaunchKernelGGL(token_mean_kernel<DT_F16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)xf, o32, 1, 1);
   }
+  FP_TAP(c, TAP_O32, o32, (size_t)N * EMBED * sizeof(float));
   run_small_linear(c, o32, net->score_lin, scores_dev, N);
+  FP_TAP(c, TAP_SCORES, scores_dev, (size_t)N * sizeof(float));
   FP_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -73,6 +73,21 @@ void decode(const unsigned char *src, size_t n, int dt, float scale, float *dst)
 
 extern "C" {
 
+// activation taps (fp_nn.h, enum TapPoint): net_kind 0 = refiner, 1 = scorer.  Armed taps stay armed until fpt_tap_clear.
+int fpt_tap_arm(int net_kind, int point, void *dst, size_t bytes) {
+  if (net_kind < 0 || net_kind > 1 || point < 0 || point >= fp::TAP_POINTS) return 1;
+  fp::g_tap[net_kind][point] = fp::TapSlot{dst, bytes, 0};
+  return 0;
+}
+void fpt_tap_clear() {
+  for (auto &k : fp::g_tap)
+    for (auto &t : k) t = fp::TapSlot{};
+  fp::g_tap_pe_fused[0] = fp::g_tap_pe_fused[1] = -1;
+}
+// bytes the producer of an armed tap wrote in the last call (copied only if they fit the buffer); 0 = not reached
+long long fpt_tap_bytes(int net_kind, int point) { return (long long)fp::g_tap[net_kind & 1][point % fp::TAP_POINTS].need; }
+// did the last 2-byte trunk of this network kind add the positional table in the epilogue of its last convolution (1) or separately (0)
+int fpt_tap_pe_fused(int net_kind) { return fp::g_tap_pe_fused[net_kind & 1]; }
 void fpt_set_att_variant(int v) { fp::g_att_variant = v; }
 void fpt_set_smallm(int v) { fp::g_smallm = v; }
 void fpt_set_smallm_maxkt(int v) { fp::g_smallm_maxkt = v; }

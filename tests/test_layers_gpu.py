@@ -1,0 +1,437 @@
+"""Every stage of the product's own forward pass against a float64 reference of that one stage (tests/layer_ref.py).
+
+The test build's activation taps (fpt_tap_arm, fp_nn.h enum TapPoint) copy each tensor out right after its producer, borders included.
+Each stage's reference is fed the exact device tensors the stage read ("teacher-forced"), so a wrong tile, a dropped K-step or a biased
+rounding fails a NAMED stage instead of nudging a pooled score.  Weights: the discriminating set (conftest disc_nets).
+
+Bound per element (matmul-shaped stages, output stored in the element type; ref = the exact float64 value, NOT rounded):
+    |got - ref| <= 0.5 ulp(|ref| + acc) + acc,   acc = C_ACC * (sum |x * w| + |bias| + |residual|),   C_ACC = 1e-6
+(layer_ref.py: ~3x the guide's f32 MFMA accumulation figure at K = 4096).  Where the reference pre-activation is below -acc, a ReLU
+output must be exactly 0.  The positional table rounds twice (conv output, then + pe), fused or not: its bound adds a second half ulp.
+Attention: P rounded to the element type before PV (layer_ref.sdpa).  LayerNorm: f32 statistics, C_LN = 1e-5 relative.
+Bias per stage: the mean signed error got - ref in ulps of |ref| + acc is within 0.05 ulp (truncation instead of RNE would be ~0.5).
+f32 outputs (pooled rows, heads, features, scores): acc alone.  The fused encoder tail (enc_tail_kernel: pdot) keeps its intermediates
+on chip, so it cannot be teacher-forced stage by stage: pdot is compared against the rounded float64 chain from its own inputs, as a
+fraction of the spread of the reference over tiles: PDOT_U = 4 unit roundoffs (the kernel and the chain round their intermediates
+independently; measured ~1.2 u in f16 and bf16 alike).
+"""
+import copy
+import ctypes as C
+import os
+from unittest import mock
+
+import numpy as np
+import pytest
+import torch
+
+import layer_ref as LR
+from foundationpose_cpp_amd import FoundationPose, _lib, synthetic as syn
+from foundationpose_cpp_amd.api import FP_PREC_BF16, FP_PREC_F16
+
+pytestmark = pytest.mark.gpu
+
+# fp_nn.h enum TapPoint
+TAP_NN_IN, TAP_STEM, TAP_ACT, TAP_HEAD, TAP_HEAD_STRIDE = 0, 1, 1, 16, 8
+TAP_PDOT, TAP_TRANS, TAP_ROT, TAP_FEAT = 32, 33, 34, 35
+TAP_XF, TAP_XQKV, TAP_XATT, TAP_XOUT, TAP_O32, TAP_SCORES, TAP_PE = 36, 37, 38, 39, 40, 41, 42
+H_QKV, H_ATT, H_Y1, H_X1, H_HID, H_Y2, H_POOL, H_LN2 = range(8)
+PDOT_U = 4      # pdot: error <= PDOT_U unit roundoffs of the element type, relative to the spread of the reference over tiles
+BIAS_ULP = 0.05
+DEV = "cuda"
+TABLE = []
+FAILS = []   # stage failures of the running test: every stage is checked, then _flush() reports them all by name
+
+
+def _typed_test_lib():
+    return _lib.test_lib()
+
+
+@pytest.fixture(scope="module")
+def tl():
+    L = _lib.test_lib()
+    L.fpt_tap_arm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    L.fpt_tap_bytes.restype = C.c_longlong
+    L.fpt_tap_bytes.argtypes = [C.c_int, C.c_int]
+    L.fpt_model_poison.argtypes = [C.c_void_p, C.c_int]
+    L.fpt_model_use_graphs.argtypes = [C.c_void_p, C.c_int]
+    yield L
+    L.fpt_tap_clear()
+    if TABLE:
+        lines = [f"{'case':<28} {'stage':<14} {'err/bound':>10} {'mean err (ulp)':>15}"] + \
+                [f"{c:<28} {s:<14} {r:>10.3f} {b:>15.4f}" for c, s, r, b in TABLE]
+        print("\n" + "\n".join(lines))
+        out = os.environ.get("FP_LAYER_TABLE")
+        if out:
+            with open(out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+
+
+@pytest.fixture(scope="module")
+def model(tl, disc_nets, syn_mesh):
+    with mock.patch.object(_lib, "lib", _typed_test_lib):    # the model on the TEST build: its taps and hooks act on this instance
+        m = FoundationPose(syn_mesh, syn.intrinsics(), disc_nets[0], disc_nets[1])
+    yield m
+    m.close()
+
+
+@pytest.fixture(scope="module")
+def scene(syn_mesh):
+    return syn.make_scene(syn_mesh)
+
+
+@pytest.fixture(scope="module")
+def crops(model, syn_mesh, scene):
+    model.upload_frame(scene.rgb, scene.depth)
+    poses = model.get_hyp_poses(scene.mask)
+    assert len(poses) == 252
+    a, b = model.render_and_transform(syn_mesh.name, poses, 1.2)
+    return a, b
+
+
+def _shapes(kind, N, NB2, five):
+    """tap point -> (shape, element tensor?) of everything one call of this network writes"""
+    s = {TAP_NN_IN: ((NB2, 84, 84, 32), 1), TAP_STEM: ((NB2, 82, 82, 64), 1), TAP_PE: ((400, 512), 1)}
+    for i in range(1, 15):
+        s[TAP_ACT + i] = (((NB2 if i <= 4 else N), 42, 42, 128 if i <= 4 else 256) if i <= 9 else (N, 22, 22, 512) if i <= 13
+                          else (N, 400, 512), 1)
+    heads = 2 if kind == 0 else 1
+    for h in range(heads):
+        b = TAP_HEAD + h * TAP_HEAD_STRIDE
+        s[b + H_QKV], s[b + H_ATT] = ((N, 400, 1536), 1), ((N, 400, 512), 1)
+        if kind == 1:
+            s[b + H_POOL] = ((N, 512), 0)
+        elif five:
+            for k in (H_Y1, H_X1, H_HID, H_Y2):
+                s[b + k] = ((N, 400, 512), 1)
+            if 1 < N < 96:
+                s[b + H_LN2] = ((N, 400, 512), 1)
+            s[b + H_POOL] = ((16, 512) if N == 1 else (N, 512), 0)
+    if kind == 0:
+        if not five:
+            s[TAP_PDOT] = ((2, 25 if N == 1 else 5 * N, 4), 0)
+        s[TAP_TRANS], s[TAP_ROT] = ((N, 3), 0), ((N, 3), 0)
+    else:
+        s[TAP_FEAT], s[TAP_O32], s[TAP_SCORES] = ((N, 512), 0), ((N, 512), 0), ((N,), 0)
+        s[TAP_XF], s[TAP_XQKV], s[TAP_XATT], s[TAP_XOUT] = ((N, 512), 1), ((N, 1536), 1), ((N, 512), 1), ((N, 512), 1)
+    return s
+
+
+def _tapped(tl, kind, N, NB2, five, dt, call):
+    """arm every tap of one call of network `kind`, run it, return {point: float64 tensor on the GPU}"""
+    tl.fpt_tap_clear()
+    edt = LR.TORCH_DT[dt]
+    bufs = {}
+    for pt, (shape, elem) in _shapes(kind, N, NB2, five).items():
+        t = torch.empty(shape, dtype=edt if elem else torch.float32, device=DEV)
+        bufs[pt] = t
+        assert tl.fpt_tap_arm(kind, pt, C.c_void_p(t.data_ptr()), t.numel() * t.element_size()) == 0
+    torch.cuda.synchronize()
+    call()
+    torch.cuda.synchronize()
+    out = {}
+    for pt, t in bufs.items():
+        got = tl.fpt_tap_bytes(kind, pt)
+        assert got == t.numel() * t.element_size(), (kind, pt, got, t.shape)    # every tap reached, with the size expected
+        out[pt] = t.to(torch.float64)
+    pe_fused = tl.fpt_tap_pe_fused(kind)
+    tl.fpt_tap_clear()
+    return out, pe_fused
+
+
+def _compare(case, stage, got, ref, acc, dt, pre=None, second_rounding=None, record=True):
+    """per-element bound + bias; returns (worst err / bound, mean error in ulps)"""
+    bound = 0.5 * LR.ulp(ref.abs() + acc, dt) + acc
+    if second_rounding is not None:      # ref = rnd(c + pe) with c itself rounded first
+        bound = bound + 0.5 * LR.ulp(second_rounding.abs() + acc, dt)
+    if pre is not None:
+        bound = torch.where(pre <= -acc, torch.zeros_like(bound), bound)
+    err = (got - ref).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+    worst = float(ratio.max())
+    bias = float(((got - ref) / LR.ulp(ref.abs() + acc, dt)).mean())
+    if record:
+        TABLE.append((case, stage, worst, bias))
+    return worst, bias
+
+
+def _assert_stage(case, stage, got, ref, acc, dt, **kw):
+    worst, bias = _compare(case, stage, got, ref, acc, dt, **kw)
+    if not worst <= 1.0:
+        FAILS.append(f"{case}: stage {stage}: err / bound = {worst:.3f}")
+    if not abs(bias) <= BIAS_ULP:
+        FAILS.append(f"{case}: stage {stage}: mean error {bias:.4f} ulp")
+
+
+def _flush():
+    msgs = list(FAILS)
+    FAILS.clear()
+    assert not msgs, "\n".join(msgs)
+
+
+def _assert_f32(case, stage, got, ref, acc):
+    err = (got - ref).abs()
+    bound = acc + 2.0 ** -24 * ref.abs()
+    worst = float((err / bound.clamp_min(1e-30)).max())
+    TABLE.append((case, stage, worst, float("nan")))
+    if not worst <= 1.0:
+        FAILS.append(f"{case}: stage {stage}: err / bound = {worst:.3f}")
+
+
+def _borders_zero(case, name, t, b=1):
+    ring = torch.cat([t[:, :b].flatten(), t[:, -b:].flatten(), t[:, :, :b].flatten(), t[:, :, -b:].flatten()])
+    if int((ring != 0).sum()):
+        FAILS.append(f"{case}: {name}: non-zero border")
+
+
+def _live(case, name, t):
+    frac = float((t > 0).double().mean())
+    if not 0.05 < frac < 0.95:
+        FAILS.append(f"{case}: {name}: fraction of ReLU outputs > 0 = {frac:.3f} (degenerate layer)")
+
+
+def check_trunk(case, w, T, N, n_b, dt, pin_cpu=False):
+    """stem, the 13 3x3 convolutions (a|b concat included), the token tensor; borders and non-degeneracy of every padded tensor"""
+    _borders_zero(case, "nn_in", T[TAP_NN_IN], 2)
+    ref, acc, pre = LR.stem(w, T[TAP_NN_IN])
+    _borders_zero(case, "stem", T[TAP_STEM])
+    _live(case, "stem", LR.interior(T[TAP_STEM]))
+    _assert_stage(case, "stem", LR.interior(T[TAP_STEM]), pre.clamp_min(0.0), acc, dt, pre=pre)
+    if pin_cpu:   # the device reference itself: image 0 again in float64 on the CPU
+        wc = LR.Weights.__new__(LR.Weights)
+        wc.st, wc.dt, wc.device = w.st, w.dt, "cpu"
+        _, _, p0 = LR.stem(wc, T[TAP_NN_IN][:1].cpu())
+        assert torch.allclose(p0, pre[:1].cpu(), rtol=0, atol=1e-6 * float(acc[:1].max())), f"{case}: stem: GPU float64 reference differs from the CPU one"
+    for i, (prefix, stride, res) in enumerate(LR.TRUNK):
+        a = i + 1
+        r = LR.interior(T[TAP_ACT + res]) if res is not None else None
+        if a == 14:
+            pe = T[TAP_PE]
+            _, acc, c = LR.tokens(w, T[TAP_ACT + 13], r, pe)
+            # rnd(rnd(c) + pe) in both forms: add_pos_embed_kernel after the conv, and the fused epilogues, which round the conv value to
+            # the element type before adding the table (same bits as the unfused form) -- the first rounding adds half an ulp of c
+            _assert_stage(case, "act14 tokens", T[TAP_ACT + 14], c + pe, acc, dt, second_rounding=c)
+            break
+        got = T[TAP_ACT + a]
+        _borders_zero(case, f"act{a}", got)
+        xin = T[TAP_ACT + i] if i > 0 else T[TAP_STEM]
+        if a == 5:
+            full, acc, pre = LR.conv3x3(w, prefix, xin, stride, res=r, out_dt=None)
+            ref, acc, pre = (LR.concat_ab(t, N, n_b) for t in (full, acc, pre))
+        else:
+            ref, acc, pre = LR.conv3x3(w, prefix, xin, stride, res=r, out_dt=None)
+        gi = LR.interior(got)
+        _live(case, f"act{a}", gi)
+        _assert_stage(case, f"act{a} {prefix}", gi, ref, acc, dt, pre=pre)
+        if pin_cpu:
+            wc = LR.Weights.__new__(LR.Weights)
+            wc.st, wc.dt, wc.device = w.st, w.dt, "cpu"
+            j = slice(0, 1) if a != 5 else slice(N, N + 1)   # (the concat: pin its b half, the last image of the conv)
+            _, _, p0 = LR.conv3x3(wc, prefix, xin[j].cpu(), stride, res=None if r is None else r[j].cpu())
+            _, ag, pg = LR.conv3x3(w, prefix, xin[j], stride, res=None if r is None else r[j])
+            assert torch.allclose(p0, pg.cpu(), rtol=0, atol=1e-6 * float(ag.max())), f"{case}: act{a}: GPU float64 reference differs from the CPU one"
+
+
+def check_heads(case, w, T, N, dt, five):
+    x = T[TAP_ACT + 14]
+    for h in range(2):
+        b = TAP_HEAD + h * TAP_HEAD_STRIDE
+        n = LR.refiner_head_names(h)
+        nm = ("trans", "rot")[h]
+        ref, acc = LR.linear(w, n["in_w"], n["in_b"], x, out_dt=None)
+        _assert_stage(case, f"{nm} qkv", T[b + H_QKV], ref, acc, dt)
+        ref, acc = LR.sdpa(T[b + H_QKV], dt, round_out=False)
+        _assert_stage(case, f"{nm} attention", T[b + H_ATT], ref, acc, dt)
+        head_w, head_b = w.f(n["head_w"]), w.f(n["head_b"])
+        out = T[TAP_TRANS if h == 0 else TAP_ROT]
+        if not five:
+            chain = LR.encoder_chain(w, h, x, T[b + H_ATT])
+            rows = 16 if N == 1 else 80
+            pref = (chain["ln2"].reshape(-1, rows, 512).sum(1) @ head_w.T)          # [tiles, O]
+            pd = T[TAP_PDOT][h, :, :3]
+            spread = pref.std(0).clamp_min(1e-12)
+            frac = float(((pd - pref).abs() / spread).max())
+            lim = PDOT_U * LR.UNIT[dt]
+            TABLE.append((case, f"{nm} pdot", frac / lim, float("nan")))
+            if not frac <= lim:
+                FAILS.append(f"{case}: stage {nm} pdot: error = {frac:.2e} of the spread over tiles")
+            tiles = pd.shape[0] // N
+            ref = pd.reshape(N, tiles, 3).sum(1) / 400.0 + head_b
+            acc = LR.C_ACC * (pd.abs().reshape(N, tiles, 3).sum(1) / 400.0 + head_b.abs())
+            _assert_f32(case, f"{nm} heads", out, ref, acc)
+            continue
+        ref, acc = LR.linear(w, n["out_w"], n["out_b"], T[b + H_ATT], res=x, out_dt=None)
+        _assert_stage(case, f"{nm} y1", T[b + H_Y1], ref, acc, dt)
+        ref, acc = LR.layernorm(w, n["ln1"], T[b + H_Y1], out_dt=None)
+        _assert_stage(case, f"{nm} ln1", T[b + H_X1], ref, acc, dt)
+        ref, acc = LR.linear(w, n["l1_w"], n["l1_b"], T[b + H_X1], relu=True, out_dt=None)
+        _assert_stage(case, f"{nm} ffn1", T[b + H_HID], ref, acc, dt)
+        ref, acc = LR.linear(w, n["l2_w"], n["l2_b"], T[b + H_HID], res=T[b + H_X1], out_dt=None)
+        _assert_stage(case, f"{nm} ffn2", T[b + H_Y2], ref, acc, dt)
+        ln2, lacc = LR.layernorm(w, n["ln2"], T[b + H_Y2], out_dt=None)
+        if 1 < N < 96:
+            _assert_stage(case, f"{nm} ln2", T[b + H_LN2], ln2, lacc, dt)
+        per = 0.5 * LR.ulp(ln2.abs() + lacc, dt) + lacc + LR.C_ACC * ln2.abs()   # rounded (or not) LN2 output, f32 sums
+        if N == 1:    # layernorm_pmean_kernel: 16 partial column sums of 25 rows
+            ref, acc = ln2.reshape(16, 25, 512).sum(1), per.reshape(16, 25, 512).sum(1)
+            _assert_f32(case, f"{nm} ln2 psums", T[b + H_POOL], ref, acc)
+            pooled = T[b + H_POOL].sum(0, keepdim=True) / 400.0
+        else:
+            _assert_f32(case, f"{nm} ln2 mean", T[b + H_POOL], ln2.mean(1), per.mean(1))
+            pooled = T[b + H_POOL]
+        ref, acc = LR.linear(w, n["head_w"], n["head_b"], pooled, out_dt=None, f32_weights=True)
+        _assert_f32(case, f"{nm} heads", out, ref, acc + LR.C_ACC * (pooled.abs() @ head_w.abs().T))
+
+
+def check_scorer(case, w, T, N, dt):
+    x = T[TAP_ACT + 14]
+    b = TAP_HEAD
+    ref, acc = LR.linear(w, "att.in_proj_weight", "att.in_proj_bias", x, out_dt=None)
+    _assert_stage(case, "qkv", T[b + H_QKV], ref, acc, dt)
+    ref, acc = LR.sdpa(T[b + H_QKV], dt, round_out=False)
+    _assert_stage(case, "attention", T[b + H_ATT], ref, acc, dt)
+    att = T[b + H_ATT]
+    _assert_f32(case, "token mean", T[b + H_POOL], att.mean(1), LR.C_ACC * att.abs().mean(1))
+    ref, acc = LR.linear(w, "att.out_proj.weight", "att.out_proj.bias", T[b + H_POOL], out_dt=None, f32_weights=True)
+    _assert_f32(case, "feat", T[TAP_FEAT], ref, acc)
+    _assert_stage(case, "cast", T[TAP_XF], T[TAP_FEAT], torch.zeros_like(T[TAP_XF]), dt)
+    ref, acc = LR.linear(w, "att_cross.in_proj_weight", "att_cross.in_proj_bias", T[TAP_XF], out_dt=None)
+    _assert_stage(case, "cross qkv", T[TAP_XQKV], ref, acc, dt)
+    ref, acc = LR.sdpa(T[TAP_XQKV][None], dt, round_out=False)
+    _assert_stage(case, "cross att", T[TAP_XATT], ref[0], acc[0], dt)
+    ref, acc = LR.linear(w, "att_cross.out_proj.weight", "att_cross.out_proj.bias", T[TAP_XATT], out_dt=None)
+    _assert_stage(case, "cross out", T[TAP_XOUT], ref, acc, dt)
+    assert torch.equal(T[TAP_O32], T[TAP_XOUT]), f"{case}: o32 is not the widened cross-attention output"
+    ref, acc = LR.linear(w, "linear.weight", "linear.bias", T[TAP_O32], out_dt=None, f32_weights=True)
+    _assert_f32(case, "scores", T[TAP_SCORES], ref.reshape(-1), acc.reshape(-1))
+
+
+def _weights(path, dt):
+    return LR.Weights(path, dt, DEV)
+
+
+def _pe_matches_table(T, dt):
+    pe = torch.from_numpy(LR.pos_table()).to(DEV, torch.float64)
+    # the device's table is the PositionalEmbedding table (its f32 arguments differ from numpy's in the last bits: t * w_i up to 399 rad)
+    assert float((T[TAP_PE] - pe).abs().max()) <= 2.0 ** -8
+
+
+def _set_prec(model, prec):
+    model.set_precision(prec)
+
+
+@pytest.mark.parametrize("prec,N,five", [(FP_PREC_F16, 1, 0), (FP_PREC_F16, 7, 0), (FP_PREC_F16, 33, 0), (FP_PREC_F16, 130, 0),
+                                         (FP_PREC_F16, 252, 0), (FP_PREC_BF16, 1, 0), (FP_PREC_BF16, 42, 0), (FP_PREC_BF16, 252, 0),
+                                         (FP_PREC_F16, 1, 1), (FP_PREC_F16, 33, 1), (FP_PREC_F16, 130, 1)])
+def test_refiner_stages_match_float64(tl, model, crops, disc_nets, prec, N, five):
+    dt = LR.BF16 if prec == FP_PREC_BF16 else LR.F16
+    case = f"refiner {'bf16' if dt else 'f16'} N={N}{' 5-launch' if five else ''}"
+    a, b = crops
+    _set_prec(model, prec)
+    try:
+        tl.fpt_set_enc_tail(0 if five else 1)
+        T, pe_fused = _tapped(tl, 0, N, 2 * N, five, dt, lambda: model.refiner_infer(a[:N], b[:N]))
+    finally:
+        tl.fpt_set_enc_tail(1)
+        _set_prec(model, FP_PREC_F16)
+    if N == 252 and dt == LR.F16:
+        assert pe_fused == 1      # the positional table in the epilogue of conv_big_pp_kernel<..., true> + conv_deep_kernel<64, ..., true>
+    _pe_matches_table(T, dt)
+    w = _weights(disc_nets[0], dt)
+    check_trunk(case, w, T, N, N, dt, pin_cpu=(N == 252 and dt == LR.F16 and not five))
+    check_heads(case, w, T, N, dt, five)
+    _flush()
+
+
+@pytest.mark.parametrize("prec,N", [(FP_PREC_F16, 1), (FP_PREC_F16, 7), (FP_PREC_F16, 42), (FP_PREC_F16, 252), (FP_PREC_BF16, 42)])
+def test_scorer_stages_match_float64(tl, model, crops, disc_nets, prec, N):
+    dt = LR.BF16 if prec == FP_PREC_BF16 else LR.F16
+    case = f"scorer {'bf16' if dt else 'f16'} N={N}"
+    a, b = crops
+    _set_prec(model, prec)
+    try:
+        T, _ = _tapped(tl, 1, N, 2 * N, False, dt, lambda: model.scorer_infer(a[:N], b[:N]))
+    finally:
+        _set_prec(model, FP_PREC_F16)
+    w = _weights(disc_nets[1], dt)
+    check_trunk(case, w, T, N, N, dt)
+    check_scorer(case, w, T, N, dt)
+    _flush()
+
+
+def test_register_shared_crop_stages_match_float64(tl, model, disc_nets, syn_mesh, scene):
+    """Register's refiner pass: 252 hypotheses that share ONE observed crop (NB2 = 253, the b half of the concat broadcast)"""
+    tl.fpt_model_use_graphs(model._h, 0)
+    try:
+        T, _ = _tapped(tl, 0, 252, 253, False, LR.F16,
+                              lambda: model.Register(scene.rgb, scene.depth, scene.mask, syn_mesh.name))
+    finally:
+        tl.fpt_model_use_graphs(model._h, 1)
+    case = "Register refiner N=252 shared-b"
+    w = _weights(disc_nets[0], LR.F16)
+    check_trunk(case, w, T, 252, 1, LR.F16)
+    check_heads(case, w, T, 252, LR.F16, False)
+    cat = LR.interior(T[TAP_ACT + 5])[..., 128:]
+    assert torch.equal(cat, cat[:1].expand_as(cat))      # every hypothesis holds the same b half
+    _flush()
+
+
+def _fails(fn):
+    FAILS.clear()
+    fn()
+    msgs = list(FAILS)
+    FAILS.clear()
+    return msgs
+
+
+def test_ablations_fail_the_named_stage(tl, model, crops, disc_nets):
+    """the checks bite: two wrong-result switches of the test build each fail their stage by name.  Also recorded: whether the
+    network-level tolerances of test_nn_gpu.py (rtol 2e-2, atol 2e-3 against the torch oracle) would have noticed."""
+    a, b = crops
+    w = _weights(disc_nets[0], LR.F16)
+    with torch.no_grad():
+        net = copy.deepcopy(disc_nets[2]).to(DEV)
+        ref_t, ref_r = net(torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV))
+    ref_t, ref_r = ref_t.cpu().numpy(), ref_r.cpu().numpy()
+    notes = []
+    for switch, val, N in (("fpt_set_qkv_ablate", 1, 252), ("fpt_set_conv_ablate", 16, 252)):
+        outs = {}
+        try:
+            getattr(tl, switch)(val)
+            T, _ = _tapped(tl, 0, N, 2 * N, False, LR.F16, lambda: outs.update(zip("tr", model.refiner_infer(a[:N], b[:N]))))
+        finally:
+            getattr(tl, switch)(0)
+        case = f"{switch}({val})"
+        if switch == "fpt_set_qkv_ablate":
+            msgs = _fails(lambda: check_heads(case, w, T, N, LR.F16, False))
+            hit = [m for m in msgs if "qkv" in m]
+        else:
+            msgs = _fails(lambda: check_trunk(case, w, T, N, N, LR.F16))
+            hit = [m for m in msgs if any(f"act{i} " in m for i in range(2, 10))]     # a 40x40 convolution
+        assert hit, msgs
+        msg = hit[0]
+        net_ok = np.allclose(outs["t"], ref_t[:N], rtol=2e-2, atol=2e-3) and np.allclose(outs["r"], ref_r[:N], rtol=2e-2, atol=2e-3)
+        notes.append(f"{case}: layer check -> {msg.splitlines()[0][:90]}; network-level tolerance {'PASSES (missed)' if net_ok else 'fails'}")
+    print("\n" + "\n".join(notes))
+
+
+def test_poisoned_scratch_changes_nothing(tl, model, crops, syn_mesh, scene):
+    """every interior of the activation arena, the split-K partials, the f32 side buffer and the cross-attention scratch poisoned before
+    each call (quiet NaN; +-largest finite, which a max()-ReLU cannot hide): the outputs equal the unpoisoned ones bit for bit, at
+    N = 252 -> 7 -> 252 on one model and for Track (eager, then the graph)"""
+    a, b = crops
+    seq = (252, 7, 252)
+    clean = [(model.refiner_infer(a[:n], b[:n]), model.scorer_infer(a[:n], b[:n])) for n in seq]
+    hyp = syn.perturb_pose(scene.gt_pose)
+    ok, clean_track = model.Track(scene.rgb, scene.depth, hyp, syn_mesh.name)
+    assert ok
+    for kind in (0, 1):
+        for n, ((t0, r0), s0) in zip(seq, clean):
+            assert tl.fpt_model_poison(model._h, kind) == 0
+            t, r = model.refiner_infer(a[:n], b[:n])
+            assert np.array_equal(t, t0) and np.array_equal(r, r0), (kind, n, "refiner")
+            assert tl.fpt_model_poison(model._h, kind) == 0
+            assert np.array_equal(model.scorer_infer(a[:n], b[:n]), s0), (kind, n, "scorer")
+        for k in range(2):
+            assert tl.fpt_model_poison(model._h, kind) == 0
+            ok, p = model.Track(scene.rgb, scene.depth, hyp, syn_mesh.name)
+            assert ok and np.array_equal(p, clean_track), (kind, k, "Track")
