@@ -1044,9 +1044,13 @@ void fp_destroy(fp_model *m) {
   destroy_model_impl(m);
 }
 
+static_assert(FP_MAX_BATCH == fp::MAX_BATCH && 42 * FP_MAX_INPLANE_STEPS <= FP_MAX_BATCH && 42 * (FP_MAX_INPLANE_STEPS + 1) > FP_MAX_BATCH,
+              "include/foundationpose_amd.h: the batch limit is fp_nn.h MAX_BATCH");
 int fp_set_inplane_steps(fp_model *m, int steps) try {
   SerialGuard serial(m ? m->device : -1);
-  FP_CHECK(m && steps >= 1 && steps <= 360, "[FoundationPose] fp_set_inplane_steps: invalid arguments");
+  FP_CHECK(m && steps >= 1, "[FoundationPose] fp_set_inplane_steps: invalid arguments");
+  FP_CHECK(steps <= FP_MAX_INPLANE_STEPS, "[FoundationPose] fp_set_inplane_steps: " + std::to_string(steps) + " steps = " + std::to_string(42 * steps) +
+           " hypotheses, above the batch limit FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + " (at most " + std::to_string(FP_MAX_INPLANE_STEPS) + " steps)");
   FP_HIP_OK(hipStreamSynchronize(m->stream));
   return set_rotation_grid(m, steps);
 } FP_CATCH_INT
@@ -1398,6 +1402,7 @@ int fp_debug_rasterize(fp_model *m, const char *target_name, const float *poses,
 // blob-mode network entry points: f32 NHWC [N,160,160,6] -> packed fp16 input
 static int pack_blobs(fp_model *m, const float *render_input, const float *transf_input, int memspace, int N) {
   FP_CHECK(render_input && transf_input && N > 0, "[FoundationPose] null network input");
+  FP_CHECK(N <= FP_MAX_BATCH, "[FoundationPose] network batch " + std::to_string(N) + " above the batch limit FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH));
   if (ensure_capacity(m, N, 0)) return 1;
   const size_t px = (size_t)N * FP_CROP_HW * FP_CROP_HW;
   const float *a = render_input, *b = transf_input;
@@ -1512,6 +1517,8 @@ int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, con
   const int n_all = m->n_hyp();
   FP_CHECK(shard_begin >= 0 && shard_count > 0 && shard_begin + shard_count <= n_all,
            "[FoundationPose] hypothesis shard out of range");
+  FP_CHECK(shard_count <= FP_MAX_BATCH, "[FoundationPose] hypothesis shard of " + std::to_string(shard_count) +
+           " above the batch limit FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH));
   const bool graphable = m->use_graphs && !m->prof.on && !m->digests && !m->calibrating && refine_itr >= 1;
   if (upload_frame_async(m, rgb, depth, memspace, H, W)) return 1;
   const int N = shard_count;
@@ -1938,6 +1945,7 @@ int fp_track_multi(fp_model *m, const void *rgb, const void *depth, int memspace
                    const char *const *target_names, int refine_itr, float *out_poses) try {
   SerialGuard serial(m ? m->device : -1);
   FP_CHECK(m != nullptr, "[FoundationPose] null model");
+  static_assert(64 <= FP_MAX_BATCH, "fp_track_multi: the object count is one network batch");
   FP_CHECK(K >= 1 && K <= 64 && hyp_poses && target_names && out_poses, "[FoundationPose] fp_track_multi: invalid arguments (1..64 objects)");
   FP_CHECK(m->refiner, "[FoundationPose] refiner weights not loaded");
   FP_CHECK(!m->track_pending, "[FoundationPose] fp_track_multi: a submitted Track has not been waited for");
@@ -2485,6 +2493,10 @@ static int net_blob_index(const fp_net *n, const char *name, bool *out) {
 static void destroy_net_impl(fp_net *n);
 fp_net *fp_net_create(const char *weights_path, int is_scorer, int max_batch) try {
   if (!weights_path || max_batch <= 0) { set_error("[FoundationPose] fp_net_create: invalid arguments"); return nullptr; }
+  if (max_batch > FP_MAX_BATCH) {
+    set_error("[FoundationPose] fp_net_create: max_batch " + std::to_string(max_batch) + " above the batch limit FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH));
+    return nullptr;
+  }
   std::string err;
   std::unique_ptr<Net, void (*)(Net *)> prepared(net_prepare(weights_path, is_scorer != 0, PREC_F16, &err), net_free);   // host phase, outside the lock
   if (!prepared) { set_error("[FoundationPose] Failed to load network weights: " + err); return nullptr; }

@@ -71,6 +71,13 @@ enum TapPoint {
 };
 enum { TAP_H_QKV = 0, TAP_H_ATT = 1, TAP_H_Y1 = 2, TAP_H_X1 = 3, TAP_H_HID = 4, TAP_H_Y2 = 5, TAP_H_POOL = 6, TAP_H_LN2 = 7 };
 
+// Batch limit (include/foundationpose_amd.h FP_MAX_BATCH; DESIGN.md "Batch limit").  conv_igemm_kernel, conv_pp_kernel, conv_big_pp_kernel,
+// conv_pp32_kernel, conv_deep_kernel and gemm_k32_kernel form their input byte offsets in 32-bit int arithmetic; the largest tensor any of
+// them may address holds 42 x 42 x 256 2-byte elements per hypothesis (encodeAB's bordered maps on N images; the 42 x 42 x 128 maps of
+// encodeA on 2N images are as large).  Every offset stays below 2^31 while N <= MAX_BATCH; refiner_forward / scorer_features refuse more.
+constexpr size_t MAX_I32_TENSOR_BYTES_PER_HYP = 42ull * 42 * 256 * 2;   // 903168
+constexpr int MAX_BATCH = (int)(((1ull << 31) - 1) / MAX_I32_TENSOR_BYTES_PER_HYP);   // 2377
+
 // Network input: nn_in = [2N,84,84,32] (net_input_dt elements): space-to-depth(2x2) view of the NHWC [2N,160,160,8] tensor
 // (channels r,g,b,x,y,z,0,0) with a zero border of 2, rendered crops A in images [0,N), observed crops B in [N,2N).
 // Outputs are device pointers.

@@ -1321,10 +1321,69 @@ static void tap(const Ctx &c, int point, const void *src, size_t bytes) {
   t.need = bytes;
   if (bytes <= t.cap) (void)hipMemcpyAsync(t.dst, src, bytes, hipMemcpyDeviceToDevice, c.s);
 }
+// image window (fpt_tap_window): nimg < 0 = whole tensors.  A per-image tap of [imgs][img_bytes] whose first N images are the hypotheses'
+// own then copies hypotheses [img0, img0 + nimg) and, when the tensor also holds observed crops (images N..), the matching ones -- or the
+// one shared crop.  Taps of cross-hypothesis or small tensors stay whole (FP_TAP).
+static int g_tap_img0 = 0, g_tap_nimg = -1;
+static void tap_imgs(const Ctx &c, int point, const void *src, size_t img_bytes, int imgs, int N) {
+  if (g_tap_nimg < 0) { tap(c, point, src, img_bytes * imgs); return; }
+  TapSlot &t = g_tap[c.net->scorer ? 1 : 0][point];
+  if (!t.dst) return;
+  const int w0 = std::min(g_tap_img0, N), w1 = std::min(N, g_tap_img0 + g_tap_nimg);
+  const int nb = imgs - N;   // observed crops: 0, 1 (shared) or N
+  const size_t wn = (size_t)(w1 - w0), nbw = nb == N ? wn : (size_t)nb;
+  t.need = w1 > w0 ? (wn + nbw) * img_bytes : 0;
+  if (!t.need || t.need > t.cap) return;
+  const unsigned char *s = static_cast<const unsigned char *>(src);
+  unsigned char *d = static_cast<unsigned char *>(t.dst);
+  (void)hipMemcpyAsync(d, s + (size_t)w0 * img_bytes, wn * img_bytes, hipMemcpyDeviceToDevice, c.s);
+  if (nbw) (void)hipMemcpyAsync(d + wn * img_bytes, s + ((size_t)N + (nb == N ? w0 : 0)) * img_bytes, nbw * img_bytes, hipMemcpyDeviceToDevice, c.s);
+}
 #define FP_TAP(c, point, src, bytes) tap(c, point, src, bytes)
+#define FP_TAP_IMGS(c, point, src, img_bytes, imgs, N) tap_imgs(c, point, src, img_bytes, imgs, N)
+
+// Launch log (test build only; fpt_launch_log_*): while armed, every network kernel launch of run_conv_dt and the other launch helpers
+// appends one record -- the schedule that ran, for the coverage test of tests/test_layers_gpu.py.  It reads the schedule decisions and
+// makes none (in particular it does not switch the profiler on, which would disable fork_rem).
+struct LaunchRec {
+  int net, prec;        // 0 refiner / 1 scorer, PREC_*
+  int side;             // 1 = launched on the side stream (fork_rem)
+  int m_begin, M;       // output rows [m_begin, M) of a convolution / GEMM launch (0, 0 elsewhere)
+  int ksplit;           // split-K slices (1 = none)
+  int pe;               // the launch adds the positional table in its epilogue
+  char name[80];        // "tag/kernel" as the profiler names it
+};
+static bool g_launch_log_on = false;
+static std::vector<LaunchRec> g_launch_log;
 #else
 #define FP_TAP(c, point, src, bytes) ((void)0)
+#define FP_TAP_IMGS(c, point, src, img_bytes, imgs, N) ((void)0)
 #endif
+
+// ProfScope of one network launch; in the test build it also appends the launch to the armed launch log.  rows() completes the
+// record of a convolution / GEMM launch (a no-op in the product).
+struct NetScope : ProfScope {
+  NetScope(const Ctx &c, const char *name, double flops = 0, double bytes = 0);
+#ifdef FP_TEST_HOOKS
+  long idx = -1;
+  void rows(int m_begin, int M, int ksplit = 1, bool pe = false, bool side = false) {
+    if (idx < 0) return;
+    LaunchRec &r = g_launch_log[(size_t)idx];
+    r.m_begin = m_begin; r.M = M; r.ksplit = ksplit; r.pe = pe ? 1 : 0; r.side = side ? 1 : 0;
+  }
+#else
+  void rows(int, int, int = 1, bool = false, bool = false) {}
+#endif
+};
+inline NetScope::NetScope(const Ctx &c, const char *name, double flops, double bytes) : ProfScope(c.prof, c.s, name, flops, bytes) {
+#ifdef FP_TEST_HOOKS
+  if (!g_launch_log_on || !c.net) return;
+  LaunchRec r{c.net->scorer ? 1 : 0, c.net->prec, 0, 0, 0, 1, 0, {}};
+  std::snprintf(r.name, sizeof(r.name), "%s", name);
+  idx = (long)g_launch_log.size();
+  g_launch_log.push_back(r);
+#endif
+}
 
 // One launch = (once per launch site, element type and DEVICE) dynamic-LDS opt-in + the launch itself.
 #define FP_LAUNCH(KERN, grid, block, lds_bytes, stream, ...)                                                                        \
@@ -1420,7 +1479,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
       bool post = p.post != nullptr;
       if constexpr (QOUT) post = false;
       if (!post) p.post = nullptr;
-      ProfScope ps(c.prof, c.s, (std::string(tag) + "/conv_smallm_kernel").c_str(), flops, bytes);
+      NetScope ps(c, (std::string(tag) + "/conv_smallm_kernel").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M, 1, post && cw == 64);
       // grid = 8 XCD lanes x ceil(workgroups / 8), see the kernel's placement rule
       const int ntl = L.Cout / cw, mtl = two ? (p.M + 31) / 32 : (p.M + 15) / 16;
       const int per_xcd = ntl >= 8 ? mtl * (ntl / 8) : (mtl + 8 / ntl - 1) / (8 / ntl);
@@ -1467,13 +1527,15 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
   if constexpr (B2 && SAME) {
     if (!grp && halo_ok && L.Cin == 32 && L.KH == 4 && L.KW == 4 && L.Cout == 64 && ipad == 2 && W == 80 && H == 80 && p.ksplit == 1 &&
         !has_res && split_imgs == 0 && (force || NB * 10 >= 300)) {
-      ProfScope ps(c.prof, c.s, (tg + "/conv_stem_halo_kernel").c_str(), flops, bytes);
+      NetScope ps(c, (tg + "/conv_stem_halo_kernel").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M);
       FP_LAUNCH((conv_stem_halo_kernel<DT>), dim3(NB * 10), dim3(256), LDS_STEM_HALO, c.s, p);
       return 0;
     }
     if (!grp && g_gemm_kernel && g_conv_variant == 0 && L.KH == 1 && L.KW == 1 && L.stride == 1 && L.pad == 0 && ipad == 0 && L.Cout % 256 == 0 &&
         p.Ktot % 32 == 0 && p.ksplit == 1 && split_imgs == 0 && ((p.M + 127) / 128) * (L.Cout / 256) >= 512) {
-      ProfScope ps(c.prof, c.s, (tg + "/gemm_k32_kernel").c_str(), flops, bytes);
+      NetScope ps(c, (tg + "/gemm_k32_kernel").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M);
       const dim3 grid(((p.M + 127) / 128) * (L.Cout / 256));
 #ifdef FP_TEST_HOOKS
       if (DT == DT_F16 && g_gemm_kernel == 11) { FP_LAUNCH((gemm_k32_kernel<1, DT_F16>), grid, dim3(256), LDS_GEMM_K32, c.s, p); return 0; }
@@ -1489,7 +1551,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
   if constexpr (B2) {
     if (!grp && halo_ok && L.KH == 3 && L.KW == 3 && L.stride == 2 && L.pad == 1 && ipad == 1 && W == 80 && H == 80 && L.Cin == 64 &&
         L.Cout == 128 && p.ksplit == 1 && !has_res && split_imgs == 0 && (force || NB * 10 >= 300)) {
-      ProfScope ps(c.prof, c.s, (tg + "/conv_s2_halo_kernel").c_str(), flops, bytes);
+      NetScope ps(c, (tg + "/conv_s2_halo_kernel").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M);
       FP_LAUNCH((conv_s2_halo_kernel<DT, ODT>), dim3(NB * 10), dim3(256), LDS_S2_HALO, c.s, p);
       return 0;
     }
@@ -1500,7 +1563,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
     const dim3 grid(NB * (H / 8) * (L.Cout / 128));
     if constexpr (B2 && !SAME) {
     } else if constexpr (B2) {
-      ProfScope ps(c.prof, c.s, (tg + "/conv_halo_kernel").c_str(), flops, bytes);
+      NetScope ps(c, (tg + "/conv_halo_kernel").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M);
 #ifdef FP_TEST_HOOKS
       if (DT == DT_F16 && g_conv_ablate == 1) { FP_LAUNCH((conv_halo_kernel<40, 1, DT_F16>), grid, dim3(256), LDS_HALO40, c.s, p); return 0; }
       if (DT == DT_F16 && g_conv_ablate == 2) { FP_LAUNCH((conv_halo_kernel<40, 2, DT_F16>), grid, dim3(256), LDS_HALO40, c.s, p); return 0; }
@@ -1514,7 +1578,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
 #endif
       FP_LAUNCH((conv_halo_kernel<40, 0, DT>), grid, dim3(256), LDS_HALO40, c.s, p);
     } else if constexpr (odt_q(ODT) == DT) {
-      ProfScope ps(c.prof, c.s, (tg + "/conv_halo8_kernel").c_str(), flops, bytes);
+      NetScope ps(c, (tg + "/conv_halo8_kernel").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M);
       if (!g_halo_wpack) p.wpack = nullptr;
       FP_LAUNCH((conv_halo8_kernel<DT, ODT>), grid, dim3(256), LDS_HALO8, c.s, p);
     }
@@ -1531,7 +1596,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
         pb.M = mt_big * 512;
         const double frac = (double)pb.M / (double)p.M;
         {
-          ProfScope ps(c.prof, c.s, (tg + "/conv_pp32_kernel<512,128>").c_str(), flops * frac, bytes * frac);
+          NetScope ps(c, (tg + "/conv_pp32_kernel<512,128>").c_str(), flops * frac, bytes * frac);
+          ps.rows(pb.m_begin, pb.M);
           FP_LAUNCH((conv_pp32_kernel<512, 128, DT, ODT>), dim3(mt_big), dim3(512), LDS_PP32, c.s, pb);
         }
         flops *= (1.0 - frac); bytes *= (1.0 - frac);
@@ -1570,7 +1636,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
       pb.M = mt_big * 256;                                // rows [0, mt_big*256)
       const double frac = (double)pb.M / (double)p.M;
       {
-        ProfScope ps(c.prof, c.s, (tg + "/conv_big_pp_kernel").c_str(), flops * frac, bytes * frac);
+        NetScope ps(c, (tg + "/conv_big_pp_kernel").c_str(), flops * frac, bytes * frac);
+        ps.rows(pb.m_begin, pb.M, 1, post_main);
         const dim3 grid(mt_big * nt2);
         bool done = false;
 #ifdef FP_TEST_HOOKS
@@ -1610,7 +1677,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
     const int n128 = L.Cout / 128;
     if (g_rem_kernel == 4) {
       const dim3 grid(((p.M - p.m_begin + 127) / 128) * n128);
-      ProfScope ps(c.prof, c.s, (tg + "/conv_deep_kernel").c_str(), flops, bytes);
+      NetScope ps(c, (tg + "/conv_deep_kernel").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M);
       FP_LAUNCH((conv_deep_kernel<128, DT, ODT>), grid, dim3(256), LDS_DEEP128, c.s, p);
       return 0;
     }
@@ -1627,7 +1695,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
         if (cascade) pb.M = p.m_begin + rows_pp;
         const double frac = cascade ? (double)rows_pp / rows : 1.0;
         {
-          ProfScope ps(c.prof, c.s, (tg + "/conv_pp_kernel(rem)").c_str(), flops * frac, bytes * frac);
+          NetScope ps(c, (tg + "/conv_pp_kernel(rem)").c_str(), flops * frac, bytes * frac);
+          ps.rows(pb.m_begin, pb.M);
           FP_LAUNCH((conv_pp_kernel<128, DT, ODT>), dim3(((pb.M - pb.m_begin + 255) / 256) * n128), dim3(512), LDS3_128, c.s, pb);
         }
         if (!cascade || rest == 0) return 0;
@@ -1635,7 +1704,8 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
         p.m_begin += rows_pp;
         rows = rest;
       }
-      ProfScope ps(c.prof, c.s, (tg + "/conv_deep_kernel").c_str(), flops, bytes);
+      NetScope ps(c, (tg + "/conv_deep_kernel").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M, 1, post_main, fork_rem);
       const hipStream_t ls = fork_rem ? c.s2 : c.s;
       bool launched = false;
       if constexpr (!QOUT) {
@@ -1653,13 +1723,15 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
     }
     if (g_rem_kernel == 1) {
       const int mt2 = (p.M - p.m_begin + 255) / 256;
-      ProfScope ps(c.prof, c.s, (tg + "/conv_pp_kernel(rem)").c_str(), flops, bytes);
+      NetScope ps(c, (tg + "/conv_pp_kernel(rem)").c_str(), flops, bytes);
+      ps.rows(p.m_begin, p.M);
       FP_LAUNCH((conv_pp_kernel<128, DT, ODT>), dim3(mt2 * n128), dim3(512), LDS3_128, c.s, p);
       return 0;
     }
   }
   if (!grp && g_conv_variant == 3 && KT >= 3 && p.ksplit == 1 && L.Cout % 128 == 0) {
-    ProfScope ps(c.prof, c.s, (tg + "/conv_pp_kernel").c_str(), flops, bytes);
+    NetScope ps(c, (tg + "/conv_pp_kernel").c_str(), flops, bytes);
+    ps.rows(p.m_begin, p.M, p.ksplit);
     FP_LAUNCH((conv_pp_kernel<128, DT, ODT>), dim3(((p.M + 255) / 256) * (L.Cout / 128)), dim3(512), LDS3_128, c.s, p);
     return 0;
   }
@@ -1667,14 +1739,17 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
       (!grp || grp->rows % 128 == 0)) {
     // short-K layers of small problems (the Linear layers of Track): a workgroup is a chain of <= 8 K-steps whose load latency the
     // two-stage tile below exposes every step; the deep ring keeps three steps in flight
-    ProfScope ps(c.prof, c.s, (tg + "/conv_deep_kernel(short-K)").c_str(), flops, bytes);
+    NetScope ps(c, (tg + "/conv_deep_kernel(short-K)").c_str(), flops, bytes);
+    ps.rows(p.m_begin, p.M, p.ksplit);
     FP_LAUNCH((conv_deep_kernel<128, DT, ODT>), dim3(mtiles * (L.Cout / 128)), dim3(256), LDS_DEEP128, c.s, p);
   } else if (L.Cout % 128 == 0 && !grp && p.ksplit > 1 && g_splitk_deep && p.kt_per >= 4) {
     // split-K slices on the deep-ring kernel (three K-steps in flight instead of one: a slice is a latency chain)
-    ProfScope ps(c.prof, c.s, (tg + "/conv_deep_kernel(split-K)").c_str(), flops, bytes);
+    NetScope ps(c, (tg + "/conv_deep_kernel(split-K)").c_str(), flops, bytes);
+    ps.rows(p.m_begin, p.M, p.ksplit);
     FP_LAUNCH((conv_deep_kernel<128, DT, ODT>), dim3(mtiles * (L.Cout / 128) * p.ksplit), dim3(256), LDS_DEEP128, c.s, p);
   } else if (L.Cout % 128 == 0) {
-    ProfScope ps(c.prof, c.s, (tg + "/conv_igemm_kernel<128>").c_str(), flops, bytes);
+    NetScope ps(c, (tg + "/conv_igemm_kernel<128>").c_str(), flops, bytes);
+    ps.rows(p.m_begin, p.M, p.ksplit);
     const dim3 grid(mtiles * (L.Cout / 128) * p.ksplit);
     bool done = false;
 #ifdef FP_TEST_HOOKS
@@ -1693,11 +1768,13 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
 #endif
     if (!done) FP_LAUNCH((conv_igemm_kernel<128, 3, DT, ODT>), grid, dim3(256), LDS_IG128, c.s, p);
   } else {
-    ProfScope ps(c.prof, c.s, (tg + "/conv_igemm_kernel<64>").c_str(), flops, bytes);
+    NetScope ps(c, (tg + "/conv_igemm_kernel<64>").c_str(), flops, bytes);
+    ps.rows(p.m_begin, p.M, p.ksplit);
     FP_LAUNCH((conv_igemm_kernel<64, 3, DT, ODT>), dim3(mtiles * (L.Cout / 64) * p.ksplit), dim3(256), LDS_IG64, c.s, p);
   }
   if (p.ksplit > 1) {
-    ProfScope ps(c.prof, c.s, (tg + "/conv_splitk_reduce_kernel").c_str(), 0, 0);
+    NetScope ps(c, (tg + "/conv_splitk_reduce_kernel").c_str(), 0, 0);
+    ps.rows(p.m_begin, p.M, p.ksplit, p.post != nullptr);
     size_t octs = (size_t)(p.M - p.m_begin) * (p.Cout / 8);
     hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((octs + 255) / 256)), dim3(256), 0, c.s, p);
   }
@@ -1818,7 +1895,7 @@ static int run_gemm(const Ctx &c, const char *tag, const ConvLayer &L, const voi
 // the QKV projection of `rows` tokens ([rows][512] -> [rows][1536]); rows % 80 == 0 and N > 1: qkv_tile_kernel, else the Linear schedule
 static int run_qkv(const Ctx &c, const ConvLayer &L, const void *x, int rows, void *qkv) {
   if (g_qkv_tile && rows % 80 == 0 && rows >= 800 && L.wstep && L.Cin == EMBED && L.Cout == 3 * EMBED && (L.dt == DT_F16 || L.dt == DT_BF16)) {
-    ProfScope ps(c.prof, c.s, "gemm_qkv/qkv_tile_kernel", 2.0 * rows * EMBED * 3.0 * EMBED, (double)rows * EMBED * 2.0 * 4.0);
+    NetScope ps(c, "gemm_qkv/qkv_tile_kernel", 2.0 * rows * EMBED * 3.0 * EMBED, (double)rows * EMBED * 2.0 * 4.0);
     QkvTileParams q{(const unsigned char *)x, L.wstep, L.bias, (unsigned char *)qkv, rows / 80};
 #ifdef FP_TEST_HOOKS
     if (g_qkv_ablate == 1) { FP_LAUNCH((qkv_tile_kernel<DT_F16, 1>), dim3((unsigned)q.tiles), dim3(512), 16 * 80 * 64, c.s, q); return 0; }
@@ -1891,7 +1968,7 @@ static void launch_attention(const Ctx &c, const void *qkv, void *out, int B, in
 static int run_attention(const Ctx &c, int dt, const void *qkv, void *out, int B, int T, int tstride = 0, int ld = 3 * EMBED) {
   if (tstride == 0) tstride = T;
   double flops = 4.0 * (double)B * HEADS * (double)T * T * HDIM;
-  ProfScope ps(c.prof, c.s, "attention", flops, (double)B * T * (1536 + 512) * 2.0);
+  NetScope ps(c, "attention", flops, (double)B * T * (1536 + 512) * 2.0);
   if (dt == DT_BF16) launch_attention<DT_BF16>(c, qkv, out, B, T, tstride, ld);
   else launch_attention<DT_F16>(c, qkv, out, B, T, tstride, ld);
   return 0;
@@ -1899,7 +1976,7 @@ static int run_attention(const Ctx &c, int dt, const void *qkv, void *out, int B
 
 static void run_layernorm(const Ctx &c, int dt, const void *x, const LNParams &ln, void *y, size_t rows, const LNParams *ln1 = nullptr,
                           size_t split_row = 0) {
-  ProfScope ps(c.prof, c.s, "layernorm", 0, (double)rows * EMBED * 4.0);
+  NetScope ps(c, "layernorm", 0, (double)rows * EMBED * 4.0);
   const dim3 grid((unsigned)((rows + 3) / 4));
   const float *g1 = ln1 ? ln1->g : ln.g, *b1 = ln1 ? ln1->b : ln.b;
   const size_t sr = ln1 ? split_row : rows;
@@ -1909,7 +1986,7 @@ static void run_layernorm(const Ctx &c, int dt, const void *x, const LNParams &l
 
 static void run_layernorm_mean(const Ctx &c, int dt, const void *x, const LNParams &ln, float *out, int B, int T, int tstride = 0,
                                const LNParams *ln1 = nullptr, int split_b = 0) {
-  ProfScope ps(c.prof, c.s, "layernorm_mean", 0, (double)B * T * EMBED * 2.0);
+  NetScope ps(c, "layernorm_mean", 0, (double)B * T * EMBED * 2.0);
   const float *g1 = ln1 ? ln1->g : ln.g, *b1 = ln1 ? ln1->b : ln.b;
   const int sb = ln1 ? split_b : B;
   if (tstride == 0) tstride = T;
@@ -1918,13 +1995,13 @@ static void run_layernorm_mean(const Ctx &c, int dt, const void *x, const LNPara
 }
 
 static void run_small_linear(const Ctx &c, const float *x, const LinearF32 &L, float *y, int B) {
-  ProfScope ps(c.prof, c.s, "small_linear", 2.0 * B * L.out * L.in, 0);
+  NetScope ps(c, "small_linear", 2.0 * B * L.out * L.in, 0);
   size_t waves = (size_t)((B + 7) / 8) * L.out;
   hipLaunchKernelGGL(small_linear_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c.s, x, L.w, L.b, y, B, L.out, L.in);
 }
 
 static void run_token_mean(const Ctx &c, int dt, const void *x, float *out, int B, int T, int tstride = 0) {
-  ProfScope ps(c.prof, c.s, "token_mean", 0, (double)B * T * EMBED * 2.0);
+  NetScope ps(c, "token_mean", 0, (double)B * T * EMBED * 2.0);
   if (dt == DT_BF16) hipLaunchKernelGGL(token_mean_kernel<DT_BF16>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)x, out, T, tstride ? tstride : T);
   else hipLaunchKernelGGL(token_mean_kernel<DT_F16>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)x, out, T, tstride ? tstride : T);
 }
@@ -2066,14 +2143,14 @@ int nn_scratch_poison(NNScratch *ws, int dt, int kind, hipStream_t s) {
 static void add_pos_embed(const Ctx &c, const Arena &a, int N) {
   const Net *net = c.net;
   size_t rows = (size_t)N * 400;
-  ProfScope ps(c.prof, c.s, "add_pos_embed", 0, (double)rows * EMBED * 4.0);
+  NetScope ps(c, "add_pos_embed", 0, (double)rows * EMBED * 4.0);
   size_t chunks = rows * (EMBED / 8);
   const dim3 grid((unsigned)((chunks + 255) / 256));
   if (net->act_dt == DT_BF16) hipLaunchKernelGGL(add_pos_embed_kernel<DT_BF16>, grid, dim3(256), 0, c.s, (__bf16 *)a.tokens, (const __bf16 *)net->pe, 400, rows);
   else hipLaunchKernelGGL(add_pos_embed_kernel<DT_F16>, grid, dim3(256), 0, c.s, (_Float16 *)a.tokens, (const _Float16 *)net->pe, 400, rows);
 }
 static void broadcast_b(const Ctx &c, unsigned char *cat, int N, int cb /* bytes of the b-half of a pixel */) {
-  ProfScope ps(c.prof, c.s, "broadcast_b", 0, (double)N * 1600 * 2 * cb);
+  NetScope ps(c, "broadcast_b", 0, (double)N * 1600 * 2 * cb);
   size_t total = (size_t)(N - 1) * 1600 * (cb / 16);
   hipLaunchKernelGGL(broadcast_b_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.s, cat, N, 42, 42, 40, 40, 1, cb);
 }
@@ -2157,7 +2234,7 @@ static int run_trunk_q8(const Ctx &c, const Arena &a, const void *nn_in, int N, 
     // [r6] the decision is per CALL (N, the hypotheses of this pass), not per layer: with NBi the 128-channel layers of a 15-hypothesis
     // pass (NB2 = 16 or 30 images) compensated while its 256- / 512-channel layers (N = 15 images) did not
     if (q != DT_I8 || !net->q8_img_comp || !L.tmat_t || !c.ws || !c.ws->img_sum || !g_q8_imgbias || N < 16) return nullptr;
-    ProfScope ps(c.prof, c.s, "q8_img_bias", 0, (double)NBi * (HW + 2) * (HW + 2) * L.Cin);
+    NetScope ps(c, "q8_img_bias", 0, (double)NBi * (HW + 2) * (HW + 2) * L.Cin);
 #ifdef FP_TEST_HOOKS
     if (g_q8_imgbias == 2) {   // A/B (test build): the three-launch form (sliced integer-atomic sums, 64-channel bias blocks, clear)
       hipLaunchKernelGGL(q8_img_sum_kernel, dim3(NBi, HW == 40 ? 6 : 2), dim3(256), 0, c.s, (const unsigned char *)xq, (HW + 2) * (HW + 2), L.Cin, c.ws->img_sum);
@@ -2183,7 +2260,7 @@ static int run_trunk_q8(const Ctx &c, const Arena &a, const void *nn_in, int N, 
   const float *const *oinv = net->act_oinv;
   float *const *scd = net->act_scale_dev;
   auto qcopy = [&](const void *x16, void *xq, int imgs, int HW, int Cc, int act) {
-    ProfScope ps(c.prof, c.s, "q8_copy", 0, (double)imgs * HW * HW * Cc * 3.0);
+    NetScope ps(c, "q8_copy", 0, (double)imgs * HW * HW * Cc * 3.0);
     const size_t octs = (size_t)imgs * HW * HW * (Cc / 8);
     const dim3 grid((unsigned)((octs + 255) / 256));
     if (q == DT_FP8) hipLaunchKernelGGL(q8_copy_kernel<DT_FP8>, grid, dim3(256), 0, c.s, (const _Float16 *)x16, (unsigned char *)xq, oinv[act], HW + 2, HW + 2, 1, Cc, octs);
@@ -2275,53 +2352,53 @@ static int run_trunk(const Ctx &c, const Arena &a, const void *nn_in, int N, int
   const Act x0 = T(a.x128[0]), x1 = T(a.x128[1]), x2 = T(a.x128[2]), cat = T(a.x256[0]);
   // ([r5] stem + encodeA.1 in chunks of 63 / 84 / 126 images, so that the stem's output would be read back from the 256 MB memory-side
   // cache instead of HBM: 10.93 -> 11.24 / 11.13 / 11.00 ms per Register, slower with every extra launch -- EXPERIMENTS.md R5.4)
-  FP_TAP(c, TAP_NN_IN, nn_in, (size_t)NB2 * 84 * 84 * 32 * 2);
+  FP_TAP_IMGS(c, TAP_NN_IN, nn_in, (size_t)84 * 84 * 32 * 2, NB2, N);
   if (run_conv(c, "conv_stem", net->a0, in, NB2, 80, 80, 2, stem, 1, true)) return 1;
-  FP_TAP(c, TAP_STEM, a.stem, (size_t)NB2 * 82 * 82 * 64 * 2);
+  FP_TAP_IMGS(c, TAP_STEM, a.stem, (size_t)82 * 82 * 64 * 2, NB2, N);
   if (run_conv(c, "conv_a1", net->a1, stem, NB2, 80, 80, 1, x0, 1, true)) return 1;
   calib_record(c, 1, a.x128[0], P1, 128, adt);
-  FP_TAP(c, TAP_ACT + 1, a.x128[0], P1 * 128 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 1, a.x128[0], (size_t)42 * 42 * 128 * 2, NB2, N);
   // encodeA residual blocks @40x40x128; the last conv writes the a|b channel concat directly
   if (run_conv(c, "conv_128", net->ra[0][0], x0, NB2, 40, 40, 1, x1, 1, true)) return 1;
   calib_record(c, 2, a.x128[1], P1, 128, adt);
-  FP_TAP(c, TAP_ACT + 2, a.x128[1], P1 * 128 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 2, a.x128[1], (size_t)42 * 42 * 128 * 2, NB2, N);
   if (run_conv(c, "conv_128", net->ra[0][1], x1, NB2, 40, 40, 1, x2, 1, true, &x0, 1)) return 1;
   calib_record(c, 3, a.x128[2], P1, 128, adt);
-  FP_TAP(c, TAP_ACT + 3, a.x128[2], P1 * 128 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 3, a.x128[2], (size_t)42 * 42 * 128 * 2, NB2, N);
   if (run_conv(c, "conv_128", net->ra[1][0], x2, NB2, 40, 40, 1, x1, 1, true)) return 1;
   calib_record(c, 4, a.x128[1], P1, 128, adt);
-  FP_TAP(c, TAP_ACT + 4, a.x128[1], P1 * 128 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 4, a.x128[1], (size_t)42 * 42 * 128 * 2, NB2, N);
   if (run_conv(c, "conv_128", net->ra[1][1], x1, NB2, 40, 40, 1, cat, 1, true, &x2, 1, N)) return 1;
   if (n_b == 1 && N > 1) broadcast_b(c, a.x256[0], N, 256);  // image N landed in cat[0][..,128:256]; replicate it for the other hypotheses
   calib_record(c, 5, a.x256[0], P2, 256, adt);
-  FP_TAP(c, TAP_ACT + 5, a.x256[0], P2 * 256 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 5, a.x256[0], (size_t)42 * 42 * 256 * 2, N, N);
   // encodeAB
   const Act y1 = T(a.x256[1]), y2 = T(a.x256[2]), y0 = T(a.x256[0]);
   if (run_conv(c, "conv_256", net->rb[0][0], cat, N, 40, 40, 1, y1, 1, true)) return 1;
   calib_record(c, 6, a.x256[1], P2, 256, adt);
-  FP_TAP(c, TAP_ACT + 6, a.x256[1], P2 * 256 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 6, a.x256[1], (size_t)42 * 42 * 256 * 2, N, N);
   if (run_conv(c, "conv_256", net->rb[0][1], y1, N, 40, 40, 1, y2, 1, true, &cat, 1)) return 1;
   calib_record(c, 7, a.x256[2], P2, 256, adt);
-  FP_TAP(c, TAP_ACT + 7, a.x256[2], P2 * 256 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 7, a.x256[2], (size_t)42 * 42 * 256 * 2, N, N);
   if (run_conv(c, "conv_256", net->rb[1][0], y2, N, 40, 40, 1, y1, 1, true)) return 1;
   calib_record(c, 8, a.x256[1], P2, 256, adt);
-  FP_TAP(c, TAP_ACT + 8, a.x256[1], P2 * 256 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 8, a.x256[1], (size_t)42 * 42 * 256 * 2, N, N);
   if (run_conv(c, "conv_256", net->rb[1][1], y1, N, 40, 40, 1, y0, 1, true, &y2, 1)) return 1;
   calib_record(c, 9, a.x256[0], P2, 256, adt);
-  FP_TAP(c, TAP_ACT + 9, a.x256[0], P2 * 256 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 9, a.x256[0], (size_t)42 * 42 * 256 * 2, N, N);
   const Act z0 = T(a.x512[0]), z1 = T(a.x512[1]), z2 = T(a.x512[2]);
   if (run_conv(c, "conv_b2", net->b2, y0, N, 40, 40, 1, z0, 1, true)) return 1;
   calib_record(c, 10, a.x512[0], P5, 512, adt);
-  FP_TAP(c, TAP_ACT + 10, a.x512[0], P5 * 512 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 10, a.x512[0], (size_t)22 * 22 * 512 * 2, N, N);
   if (run_conv(c, "conv_512", net->rc[0][0], z0, N, 20, 20, 1, z1, 1, true)) return 1;
   calib_record(c, 11, a.x512[1], P5, 512, adt);
-  FP_TAP(c, TAP_ACT + 11, a.x512[1], P5 * 512 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 11, a.x512[1], (size_t)22 * 22 * 512 * 2, N, N);
   if (run_conv(c, "conv_512", net->rc[0][1], z1, N, 20, 20, 1, z2, 1, true, &z0, 1)) return 1;
   calib_record(c, 12, a.x512[2], P5, 512, adt);
-  FP_TAP(c, TAP_ACT + 12, a.x512[2], P5 * 512 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 12, a.x512[2], (size_t)22 * 22 * 512 * 2, N, N);
   if (run_conv(c, "conv_512", net->rc[1][0], z2, N, 20, 20, 1, z1, 1, true)) return 1;
   calib_record(c, 13, a.x512[1], P5, 512, adt);
-  FP_TAP(c, TAP_ACT + 13, a.x512[1], P5 * 512 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 13, a.x512[1], (size_t)22 * 22 * 512 * 2, N, N);
   // last conv writes the un-bordered token tensor [N,400,512] (2-byte type in every precision)
   const Act tok = T(a.tokens);
   bool pe_done = false;
@@ -2332,7 +2409,7 @@ static int run_trunk(const Ctx &c, const Arena &a, const void *nn_in, int N, int
 #endif
   FP_TAP(c, TAP_PE, net->pe, (size_t)400 * EMBED * 2);
   calib_record(c, 14, a.tokens, (size_t)N * 400, 512, adt);
-  FP_TAP(c, TAP_ACT + 14, a.tokens, (size_t)N * 400 * 512 * 2);
+  FP_TAP_IMGS(c, TAP_ACT + 14, a.tokens, (size_t)400 * 512 * 2, N, N);
   return 0;
 }
 
@@ -2343,6 +2420,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
                     float *trans_dev, float *rot_dev, int shared_b, const PoseUpdateFuse *fuse, bool *fused_out) {
   if (fused_out) *fused_out = false;
   FP_CHECK(net && !net->scorer, "refiner_forward: wrong network");
+  FP_CHECK(N >= 1 && N <= MAX_BATCH, "[FoundationPose] refine-net batch " + std::to_string(N) + " outside 1..FP_MAX_BATCH = " + std::to_string(MAX_BATCH));
   FP_CHECK(net_q8_ready(net), "[FoundationPose] the 8-bit precisions need a calibration: call fp_calibrate (fp_calibrate_fp8) first");
   if (ensure_scratch(ws, N, s)) return 1;
   Ctx c{s, prof, net, ws, ws->side, ws->ev_fork, ws->ev_join};
@@ -2379,7 +2457,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
       // out_proj, LayerNorm 1, FFN1, FFN2, LayerNorm 2 + partial sums (five dependent launches, 33 us of the 202 us graph)
       float *const pdot = reinterpret_cast<float *>(a.y2);   // [2][25][4]
       {
-        ProfScope ps(c.prof, c.s, "enc_tail", 2.0 * 3.0 * 2.0 * 400.0 * EMBED * EMBED, 2.0 * 2.0 * 400.0 * EMBED * 2.0);
+        NetScope ps(c, "enc_tail", 2.0 * 3.0 * 2.0 * 400.0 * EMBED * EMBED, 2.0 * 2.0 * 400.0 * EMBED * 2.0);
         EncTailParams q{};
         q.x = (const unsigned char *)x;
         q.pdot = pdot;
@@ -2400,7 +2478,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
       }
       FP_TAP(c, TAP_PDOT, pdot, (size_t)2 * 25 * 4 * sizeof(float));
       {
-        ProfScope ps(c.prof, c.s, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
+        NetScope ps(c, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
         EncHeadsParams hp{pdot, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}, 1, 25, 3, 400.f};
         const bool do_fuse = fuse && g_fuse_pose;
         hipLaunchKernelGGL(enc_heads_kernel, dim3(1), dim3(64), 0, c.s, hp, do_fuse ? *fuse : PoseUpdateFuse{}, do_fuse ? 1 : 0);
@@ -2435,7 +2513,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
 #endif
         ;
     if (pmean) {
-      ProfScope ps(c.prof, c.s, "layernorm_pmean", 0, 2.0 * 400 * EMBED * 2.0);
+      NetScope ps(c, "layernorm_pmean", 0, 2.0 * 400 * EMBED * 2.0);
       if (dt == DT_BF16) hipLaunchKernelGGL(layernorm_pmean_kernel<DT_BF16>, dim3(2, kParts), dim3(256), 0, c.s, (const __bf16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
       else hipLaunchKernelGGL(layernorm_pmean_kernel<DT_F16>, dim3(2, kParts), dim3(256), 0, c.s, (const _Float16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
       FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_POOL, psums, (size_t)kParts * EMBED * sizeof(float));   // (partial column sums: kParts x 25 rows)
@@ -2446,7 +2524,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
       // A/B (test build): token mean + both heads + RefinePostProcess as one launch whose last workgroup runs the heads -- measured
       // no faster than the two launches (14.0 us against 6.0 + 6.6 in the replayed graph: the release / acquire pair and the 16
       // same-address atomics across XCDs cost what the launch did), DESIGN.md section 8
-      ProfScope ps(c.prof, c.s, "token_mean", 0, 2.0 * 400 * EMBED * 2.0);
+      NetScope ps(c, "token_mean", 0, 2.0 * 400 * EMBED * 2.0);
       SmallLinear2 sl{{ws->f32, ws->f32 + EMBED}, {T0.head.w, R0.head.w}, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}};
       unsigned *arrivals = reinterpret_cast<unsigned *>(ws->f32 + (size_t)ws->cap * EMBED);
       if (dt == DT_BF16) hipLaunchKernelGGL(token_mean_pose_kernel<DT_BF16>, dim3(2, EMBED / 64), dim3(384), 0, c.s, (const __bf16 *)a.y1, ws->f32, 400, G, arrivals, sl, T0.head.in, *fuse);
@@ -2458,7 +2536,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
 #endif
     if (!pmean) run_token_mean(c, dt, a.y1, ws->f32, 2, 400, G);
     {
-      ProfScope ps(c.prof, c.s, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
+      NetScope ps(c, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
       SmallLinear2 a{{pmean ? psums : ws->f32, pmean ? psums + kParts * EMBED : ws->f32 + EMBED}, {T0.head.w, R0.head.w}, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}};
       if (pmean) { a.parts = kParts; a.tokens = 400.f; }
       if (fuse && g_fuse_pose && T0.head.out == 3 && R0.head.out == 3) {
@@ -2478,13 +2556,13 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
     void *att_out[2] = {a.att, a.y1};
     for (int i = 0; i < 2; i++) {
       if (run_qkv(c, heads[i]->att.in_proj, x, (int)rows, a.qkv)) return 1;
-      FP_TAP(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv, rows * 3 * EMBED * 2);
+      FP_TAP_IMGS(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv, (size_t)400 * 3 * EMBED * 2, N, N);
       if (run_attention(c, dt, a.qkv, att_out[i], N, 400)) return 1;
-      FP_TAP(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_ATT, att_out[i], rows * EMBED * 2);
+      FP_TAP_IMGS(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_ATT, att_out[i], (size_t)400 * EMBED * 2, N, N);
     }
     float *const pdot = reinterpret_cast<float *>(a.y2);   // [2][N * 5][4] f32
     {
-      ProfScope ps(c.prof, c.s, "enc_tail", 2.0 * 3.0 * 2.0 * (double)rows * EMBED * EMBED, 2.0 * 2.0 * (double)rows * EMBED * 2.0);
+      NetScope ps(c, "enc_tail", 2.0 * 3.0 * 2.0 * (double)rows * EMBED * EMBED, 2.0 * 2.0 * (double)rows * EMBED * 2.0);
       EncTailParams q{};
       q.x = (const unsigned char *)x;
       q.pdot = pdot;
@@ -2504,7 +2582,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
     }
     FP_TAP(c, TAP_PDOT, pdot, (size_t)2 * N * 5 * 4 * sizeof(float));
     {
-      ProfScope ps(c.prof, c.s, "small_linear", 2.0 * 2 * N * net->trans.head.out * EMBED, 0);
+      NetScope ps(c, "small_linear", 2.0 * 2 * N * net->trans.head.out * EMBED, 0);
       EncHeadsParams hp{pdot, {net->trans.head.b, net->rot.head.b}, {trans_dev, rot_dev}, N, 5, net->trans.head.out, 400.f};
       hipLaunchKernelGGL(enc_heads_kernel, dim3((unsigned)N), dim3(64), 0, c.s, hp, PoseUpdateFuse{}, 0);
     }
@@ -2517,23 +2595,23 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
     const EncLayer &L = *heads[i];
     // post-norm TransformerEncoderLayer: x1 = LN1(x + SA(x)); x2 = LN2(x1 + W2 relu(W1 x1))
     [[maybe_unused]] const int tp = TAP_HEAD + i * TAP_HEAD_STRIDE;
-    [[maybe_unused]] const size_t tb = rows * EMBED * 2;
+    [[maybe_unused]] const size_t tb1 = (size_t)400 * EMBED * 2;   // (taps: one hypothesis' 400 rows)
     if (run_gemm(c, "gemm_qkv", L.att.in_proj, x, (int)rows, a.qkv, false)) return 1;
-    FP_TAP(c, tp + TAP_H_QKV, a.qkv, 3 * tb);
+    FP_TAP_IMGS(c, tp + TAP_H_QKV, a.qkv, 3 * tb1, N, N);
     if (run_attention(c, dt, a.qkv, a.att, N, 400)) return 1;
-    FP_TAP(c, tp + TAP_H_ATT, a.att, tb);
+    FP_TAP_IMGS(c, tp + TAP_H_ATT, a.att, tb1, N, N);
     if (run_gemm(c, "gemm_512", L.att.out_proj, a.att, (int)rows, a.y1, false, x)) return 1;  // + residual x
-    FP_TAP(c, tp + TAP_H_Y1, a.y1, tb);
+    FP_TAP_IMGS(c, tp + TAP_H_Y1, a.y1, tb1, N, N);
     run_layernorm(c, dt, a.y1, L.ln1, a.y2, rows);                                           // x1 = y2
-    FP_TAP(c, tp + TAP_H_X1, a.y2, tb);
+    FP_TAP_IMGS(c, tp + TAP_H_X1, a.y2, tb1, N, N);
     if (run_gemm(c, "gemm_512", L.lin1, a.y2, (int)rows, a.y1, true)) return 1;
-    FP_TAP(c, tp + TAP_H_HID, a.y1, tb);
+    FP_TAP_IMGS(c, tp + TAP_H_HID, a.y1, tb1, N, N);
     if (run_gemm(c, "gemm_512", L.lin2, a.y1, (int)rows, a.att, false, a.y2)) return 1;       // + residual x1
-    FP_TAP(c, tp + TAP_H_Y2, a.att, tb);
+    FP_TAP_IMGS(c, tp + TAP_H_Y2, a.att, tb1, N, N);
     if (N >= 96) run_layernorm_mean(c, dt, a.att, L.ln2, ws->f32, N, 400);
     else {  // few sequences: one workgroup per sequence is a serial chain (26 us at N = 32 against 9 + 9 for the two-kernel form)
       run_layernorm(c, dt, a.att, L.ln2, a.y1, rows);
-      FP_TAP(c, tp + TAP_H_LN2, a.y1, tb);
+      FP_TAP_IMGS(c, tp + TAP_H_LN2, a.y1, tb1, N, N);
       run_token_mean(c, dt, a.y1, ws->f32, N, 400);
     }
     FP_TAP(c, tp + TAP_H_POOL, ws->f32, (size_t)N * EMBED * sizeof(float));
@@ -2547,6 +2625,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
 
 int scorer_features(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, const void *nn_in, int N, float *feat_dev) {
   FP_CHECK(net && net->scorer, "scorer_features: wrong network");
+  FP_CHECK(N >= 1 && N <= MAX_BATCH, "[FoundationPose] score-net batch " + std::to_string(N) + " outside 1..FP_MAX_BATCH = " + std::to_string(MAX_BATCH));
   FP_CHECK(net_q8_ready(net), "[FoundationPose] the 8-bit precisions need a calibration: call fp_calibrate (fp_calibrate_fp8) first");
   if (ensure_scratch(ws, N, s)) return 1;
   Ctx c{s, prof, net, ws, ws->side, ws->ev_fork, ws->ev_join};
@@ -2554,9 +2633,9 @@ int scorer_features(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
   if (run_trunk(c, a, nn_in, N, N)) return 1;
   const size_t rows = (size_t)N * 400;
   if (run_qkv(c, net->att.in_proj, a.tokens, (int)rows, a.qkv)) return 1;
-  FP_TAP(c, TAP_HEAD + TAP_H_QKV, a.qkv, rows * 3 * EMBED * 2);
+  FP_TAP_IMGS(c, TAP_HEAD + TAP_H_QKV, a.qkv, (size_t)400 * 3 * EMBED * 2, N, N);
   if (run_attention(c, net->act_dt, a.qkv, a.att, N, 400)) return 1;
-  FP_TAP(c, TAP_HEAD + TAP_H_ATT, a.att, rows * EMBED * 2);
+  FP_TAP_IMGS(c, TAP_HEAD + TAP_H_ATT, a.att, (size_t)400 * EMBED * 2, N, N);
   // feature = mean_t(out_proj(att)) = out_proj(mean_t(att))  (out_proj is affine) -> 512x512 GEMV per hypothesis
   run_token_mean(c, net->act_dt, a.att, ws->f32, N, 400);
   FP_TAP(c, TAP_HEAD + TAP_H_POOL, ws->f32, (size_t)N * EMBED * sizeof(float));
@@ -2577,7 +2656,7 @@ int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, co
   unsigned char *att = p; p += (size_t)N * EMBED * 2;
   float *o32 = ws->head_f32;                  // [N,512]
   {
-    ProfScope ps(c.prof, c.s, "cast", 0, (double)N * EMBED * 6.0);
+    NetScope ps(c, "cast", 0, (double)N * EMBED * 6.0);
     size_t n = (size_t)N * EMBED;
     const dim3 grid((unsigned)((n + 255) / 256));
     if (dt == DT_BF16) hipLaunchKernelGGL(cast_f32_kernel<DT_BF16>, grid, dim3(256), 0, c.s, feats_dev, (__bf16 *)xf, n);
@@ -2594,7 +2673,7 @@ int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, co
   FP_TAP(c, TAP_XOUT, xf, (size_t)N * EMBED * 2);
   {
     // Linear(512,1) on 2-byte rows: widen to f32 first (token_mean with T = 1 is a plain copy of each row)
-    ProfScope ps(c.prof, c.s, "score_linear", 2.0 * N * EMBED, 0);
+    NetScope ps(c, "score_linear", 2.0 * N * EMBED, 0);
     if (dt == DT_BF16) hipLaunchKernelGGL(token_mean_kernel<DT_BF16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)xf, o32, 1, 1);
     else hipLaunchKernelGGL(token_mean_kernel<DT_F16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)xf, o32, 1, 1);
   }

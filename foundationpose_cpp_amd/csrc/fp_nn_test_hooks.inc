@@ -83,9 +83,34 @@ void fpt_tap_clear() {
   for (auto &k : fp::g_tap)
     for (auto &t : k) t = fp::TapSlot{};
   fp::g_tap_pe_fused[0] = fp::g_tap_pe_fused[1] = -1;
+  fp::g_tap_img0 = 0;
+  fp::g_tap_nimg = -1;
 }
 // bytes the producer of an armed tap wrote in the last call (copied only if they fit the buffer); 0 = not reached
 long long fpt_tap_bytes(int net_kind, int point) { return (long long)fp::g_tap[net_kind & 1][point % fp::TAP_POINTS].need; }
+// tap only hypotheses [img0, img0 + nimg) of the per-image tensors (fp_nn.hip, tap_imgs); nimg < 0 = whole tensors again
+int fpt_tap_window(int img0, int nimg) {
+  if (img0 < 0 || nimg == 0) return 1;
+  fp::g_tap_img0 = nimg < 0 ? 0 : img0;
+  fp::g_tap_nimg = nimg < 0 ? -1 : nimg;
+  return 0;
+}
+// launch log (fp_nn.hip, LaunchRec): arm(1) clears it and records every network launch from now on, arm(0) stops; get(i) copies record i
+// out as ints {net, prec, side, m_begin, M, ksplit, pe} and its "tag/kernel" name (name_cap bytes, NUL-terminated)
+void fpt_launch_log_arm(int on) {
+  if (on) fp::g_launch_log.clear();
+  fp::g_launch_log_on = on != 0;
+}
+int fpt_launch_log_count() { return (int)fp::g_launch_log.size(); }
+int fpt_launch_log_get(int i, int *fields7, char *name, int name_cap) {
+  if (i < 0 || i >= (int)fp::g_launch_log.size() || !fields7 || !name || name_cap <= 0) return 1;
+  const fp::LaunchRec &r = fp::g_launch_log[(size_t)i];
+  const int f[7] = {r.net, r.prec, r.side, r.m_begin, r.M, r.ksplit, r.pe};
+  std::memcpy(fields7, f, sizeof(f));
+  std::snprintf(name, (size_t)name_cap, "%s", r.name);
+  return 0;
+}
+void fpt_launch_log_clear() { fp::g_launch_log.clear(); }
 // did the last 2-byte trunk of this network kind add the positional table in the epilogue of its last convolution (1) or separately (0)
 int fpt_tap_pe_fused(int net_kind) { return fp::g_tap_pe_fused[net_kind & 1]; }
 void fpt_set_att_variant(int v) { fp::g_att_variant = v; }

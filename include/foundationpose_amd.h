@@ -37,6 +37,12 @@ extern "C" {
 
 #define FP_CROP 160            /* crop_window_H/W, D6F/src/foundationpose.cpp:34-35 */
 #define FP_NUM_HYP_DEFAULT 252 /* score_mode_poses_num_, D6F/src/foundationpose.cpp:85 */
+/* Largest number of hypotheses one network call takes (refine-net / score-net batch, Register's hypothesis count, fp_net_create's
+ * max_batch, a Register shard).  Several network kernels address activation tensors with 32-bit signed byte offsets; the largest such
+ * tensor holds 903168 bytes per hypothesis (a bordered 42x42x256 map, or two 42x42x128 maps), so 2377 hypotheses keep every offset below
+ * 2^31 ("Batch limit").  Larger batches are refused with an error before anything is launched. */
+#define FP_MAX_BATCH 2377
+#define FP_MAX_INPLANE_STEPS 56 /* 42 * 56 = 2352 <= FP_MAX_BATCH hypotheses */
 
 typedef struct fp_model fp_model;
 
@@ -83,7 +89,7 @@ fp_model *fp_create_on(int device, const fp_mesh *meshes, int n_meshes, const fl
 int fp_device(const fp_model *m);
 void fp_destroy(fp_model *m);
 const char *fp_last_error(void);
-/* number of in-plane rotations per icosphere view: 6 -> 252 hypotheses (reference), 24 -> 1008 (SURVEY.md §8a note). */
+/* number of in-plane rotations per icosphere view: 6 -> 252 hypotheses (reference), 24 -> 1008 (SURVEY.md §8a note); 1..FP_MAX_INPLANE_STEPS. */
 int fp_set_inplane_steps(fp_model *m, int steps);
 int fp_num_hypotheses(const fp_model *m);
 

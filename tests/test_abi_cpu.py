@@ -42,3 +42,14 @@ def test_product_does_not_touch_oracle():
             if f.endswith((".py", ".hip", ".h", ".cpp", "Makefile")):
                 txt = open(os.path.join(dp, f), errors="ignore").read()
                 assert "fp_oracle" not in txt and "from oracle" not in txt and "import oracle" not in txt, f
+
+
+def test_batch_limit_keeps_32_bit_offsets_in_range():
+    """FP_MAX_BATCH: the largest tensor a 32-bit-offset kernel addresses (42 x 42 x 256 2-byte elements per hypothesis, DESIGN.md
+    "Batch limit") stays below 2^31 bytes at the limit and not one hypothesis beyond; FP_MAX_INPLANE_STEPS is the last step count within"""
+    src = open(os.path.join(ROOT, "include", "foundationpose_amd.h")).read()
+    n_max = int(re.search(r"#define FP_MAX_BATCH (\d+)", src).group(1))
+    steps = int(re.search(r"#define FP_MAX_INPLANE_STEPS (\d+)", src).group(1))
+    per_hyp = 42 * 42 * 256 * 2
+    assert n_max * per_hyp < 2 ** 31 <= (n_max + 1) * per_hyp
+    assert 42 * steps <= n_max < 42 * (steps + 1)

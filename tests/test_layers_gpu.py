@@ -17,6 +17,7 @@ independently; measured ~1.2 u in f16 and bf16 alike).
 """
 import copy
 import ctypes as C
+import gc
 import os
 from unittest import mock
 
@@ -26,7 +27,7 @@ import torch
 
 import layer_ref as LR
 from foundationpose_cpp_amd import FoundationPose, _lib, synthetic as syn
-from foundationpose_cpp_amd.api import FP_PREC_BF16, FP_PREC_F16
+from foundationpose_cpp_amd.api import FP_PREC_BF16, FP_PREC_F16, FoundationPoseError
 
 pytestmark = pytest.mark.gpu
 
@@ -54,6 +55,9 @@ def tl():
     L.fpt_tap_bytes.argtypes = [C.c_int, C.c_int]
     L.fpt_model_poison.argtypes = [C.c_void_p, C.c_int]
     L.fpt_model_use_graphs.argtypes = [C.c_void_p, C.c_int]
+    L.fpt_tap_window.argtypes = [C.c_int, C.c_int]
+    L.fpt_launch_log_arm.argtypes = [C.c_int]
+    L.fpt_launch_log_get.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
     yield L
     L.fpt_tap_clear()
     if TABLE:
@@ -74,6 +78,16 @@ def model(tl, disc_nets, syn_mesh):
     m.close()
 
 
+@pytest.fixture(autouse=True)
+def _free_cached_blocks():
+    """the model grows its own buffers with hipMalloc (N up to FP_MAX_BATCH): hand the blocks torch's caching allocator keeps from the
+    previous case's taps back to the runtime, before and after every test"""
+    torch.cuda.empty_cache()
+    yield
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
 @pytest.fixture(scope="module")
 def scene(syn_mesh):
     return syn.make_scene(syn_mesh)
@@ -88,23 +102,35 @@ def crops(model, syn_mesh, scene):
     return a, b
 
 
-def _shapes(kind, N, NB2, five):
-    """tap point -> (shape, element tensor?) of everything one call of this network writes"""
-    s = {TAP_NN_IN: ((NB2, 84, 84, 32), 1), TAP_STEM: ((NB2, 82, 82, 64), 1), TAP_PE: ((400, 512), 1)}
+def _win_imgs(N, NB2, win):
+    """(hypotheses, images) a windowed tap holds: win = (img0, nimg) -> the window's hypotheses and, for a tensor on NB2 images, their
+    observed crops (one per hypothesis, or the one shared crop)"""
+    if win is None:
+        return N, NB2
+    wn = min(N, win[0] + win[1]) - win[0]
+    return wn, wn + (wn if NB2 == 2 * N else NB2 - N)
+
+
+def _shapes(kind, N, NB2, five, win=None):
+    """tap point -> (shape, element tensor?) of everything one call of this network writes.  With an image window the per-image tensors
+    (trunk, QKV, attention, the five-launch tail) hold the window's hypotheses only; the pooled rows, heads, scores and the scorer's
+    cross-hypothesis tensors stay whole."""
+    n, nb2 = _win_imgs(N, NB2, win)
+    s = {TAP_NN_IN: ((nb2, 84, 84, 32), 1), TAP_STEM: ((nb2, 82, 82, 64), 1), TAP_PE: ((400, 512), 1)}
     for i in range(1, 15):
-        s[TAP_ACT + i] = (((NB2 if i <= 4 else N), 42, 42, 128 if i <= 4 else 256) if i <= 9 else (N, 22, 22, 512) if i <= 13
-                          else (N, 400, 512), 1)
+        s[TAP_ACT + i] = (((nb2 if i <= 4 else n), 42, 42, 128 if i <= 4 else 256) if i <= 9 else (n, 22, 22, 512) if i <= 13
+                          else (n, 400, 512), 1)
     heads = 2 if kind == 0 else 1
     for h in range(heads):
         b = TAP_HEAD + h * TAP_HEAD_STRIDE
-        s[b + H_QKV], s[b + H_ATT] = ((N, 400, 1536), 1), ((N, 400, 512), 1)
+        s[b + H_QKV], s[b + H_ATT] = ((n, 400, 1536), 1), ((n, 400, 512), 1)
         if kind == 1:
             s[b + H_POOL] = ((N, 512), 0)
         elif five:
             for k in (H_Y1, H_X1, H_HID, H_Y2):
-                s[b + k] = ((N, 400, 512), 1)
+                s[b + k] = ((n, 400, 512), 1)
             if 1 < N < 96:
-                s[b + H_LN2] = ((N, 400, 512), 1)
+                s[b + H_LN2] = ((n, 400, 512), 1)
             s[b + H_POOL] = ((16, 512) if N == 1 else (N, 512), 0)
     if kind == 0:
         if not five:
@@ -116,23 +142,37 @@ def _shapes(kind, N, NB2, five):
     return s
 
 
-def _tapped(tl, kind, N, NB2, five, dt, call):
-    """arm every tap of one call of network `kind`, run it, return {point: float64 tensor on the GPU}"""
+class _Taps(dict):
+    """the tapped tensors, kept in their element type on the GPU; every read widens to float64, so that a check holds one stage's
+    float64 operands at a time (N = 1008: ~17 GB of f16 taps would be ~70 GB of float64)"""
+    def __getitem__(self, pt):
+        return dict.__getitem__(self, pt).to(torch.float64)
+
+    def raw(self, pt):
+        return dict.__getitem__(self, pt)
+
+
+def _tapped(tl, kind, N, NB2, five, dt, call, win=None):
+    """arm every tap of one call of network `kind` (win = (img0, nimg): that image window of the per-image tensors), run it, return
+    ({point: tensor on the GPU, widened to float64 when read}, pe fused)"""
     tl.fpt_tap_clear()
+    if win is not None:
+        assert tl.fpt_tap_window(*win) == 0
     edt = LR.TORCH_DT[dt]
     bufs = {}
-    for pt, (shape, elem) in _shapes(kind, N, NB2, five).items():
+    for pt, (shape, elem) in _shapes(kind, N, NB2, five, win).items():
         t = torch.empty(shape, dtype=edt if elem else torch.float32, device=DEV)
         bufs[pt] = t
         assert tl.fpt_tap_arm(kind, pt, C.c_void_p(t.data_ptr()), t.numel() * t.element_size()) == 0
     torch.cuda.synchronize()
+    torch.cuda.empty_cache()
     call()
     torch.cuda.synchronize()
-    out = {}
+    out = _Taps()
     for pt, t in bufs.items():
         got = tl.fpt_tap_bytes(kind, pt)
         assert got == t.numel() * t.element_size(), (kind, pt, got, t.shape)    # every tap reached, with the size expected
-        out[pt] = t.to(torch.float64)
+        out[pt] = t
     pe_fused = tl.fpt_tap_pe_fused(kind)
     tl.fpt_tap_clear()
     return out, pe_fused
@@ -231,7 +271,13 @@ def check_trunk(case, w, T, N, n_b, dt, pin_cpu=False):
             assert torch.allclose(p0, pg.cpu(), rtol=0, atol=1e-6 * float(ag.max())), f"{case}: act{a}: GPU float64 reference differs from the CPU one"
 
 
-def check_heads(case, w, T, N, dt, five):
+def _hyps(t, hs, per=1):
+    """rows of the window's hypotheses (hs: slice of hypotheses, None = all) of a tensor tapped whole, `per` rows per hypothesis"""
+    return t if hs is None else t[hs.start * per:hs.stop * per]
+
+
+def check_heads(case, w, T, N, dt, five, hs=None):
+    """N = the hypotheses the per-image taps hold; hs = where they sit in the whole tensors (pdot, pooled rows, heads)"""
     x = T[TAP_ACT + 14]
     for h in range(2):
         b = TAP_HEAD + h * TAP_HEAD_STRIDE
@@ -242,12 +288,12 @@ def check_heads(case, w, T, N, dt, five):
         ref, acc = LR.sdpa(T[b + H_QKV], dt, round_out=False)
         _assert_stage(case, f"{nm} attention", T[b + H_ATT], ref, acc, dt)
         head_w, head_b = w.f(n["head_w"]), w.f(n["head_b"])
-        out = T[TAP_TRANS if h == 0 else TAP_ROT]
+        out = _hyps(T[TAP_TRANS if h == 0 else TAP_ROT], hs)
         if not five:
             chain = LR.encoder_chain(w, h, x, T[b + H_ATT])
             rows = 16 if N == 1 else 80
             pref = (chain["ln2"].reshape(-1, rows, 512).sum(1) @ head_w.T)          # [tiles, O]
-            pd = T[TAP_PDOT][h, :, :3]
+            pd = _hyps(T[TAP_PDOT][h], hs, 5)[:, :3]
             spread = pref.std(0).clamp_min(1e-12)
             frac = float(((pd - pref).abs() / spread).max())
             lim = PDOT_U * LR.UNIT[dt]
@@ -276,13 +322,13 @@ def check_heads(case, w, T, N, dt, five):
             _assert_f32(case, f"{nm} ln2 psums", T[b + H_POOL], ref, acc)
             pooled = T[b + H_POOL].sum(0, keepdim=True) / 400.0
         else:
-            _assert_f32(case, f"{nm} ln2 mean", T[b + H_POOL], ln2.mean(1), per.mean(1))
-            pooled = T[b + H_POOL]
+            pooled = _hyps(T[b + H_POOL], hs)
+            _assert_f32(case, f"{nm} ln2 mean", pooled, ln2.mean(1), per.mean(1))
         ref, acc = LR.linear(w, n["head_w"], n["head_b"], pooled, out_dt=None, f32_weights=True)
         _assert_f32(case, f"{nm} heads", out, ref, acc + LR.C_ACC * (pooled.abs() @ head_w.abs().T))
 
 
-def check_scorer(case, w, T, N, dt):
+def check_scorer(case, w, T, N, dt, hs=None):
     x = T[TAP_ACT + 14]
     b = TAP_HEAD
     ref, acc = LR.linear(w, "att.in_proj_weight", "att.in_proj_bias", x, out_dt=None)
@@ -290,7 +336,7 @@ def check_scorer(case, w, T, N, dt):
     ref, acc = LR.sdpa(T[b + H_QKV], dt, round_out=False)
     _assert_stage(case, "attention", T[b + H_ATT], ref, acc, dt)
     att = T[b + H_ATT]
-    _assert_f32(case, "token mean", T[b + H_POOL], att.mean(1), LR.C_ACC * att.abs().mean(1))
+    _assert_f32(case, "token mean", _hyps(T[b + H_POOL], hs), att.mean(1), LR.C_ACC * att.abs().mean(1))
     ref, acc = LR.linear(w, "att.out_proj.weight", "att.out_proj.bias", T[b + H_POOL], out_dt=None, f32_weights=True)
     _assert_f32(case, "feat", T[TAP_FEAT], ref, acc)
     _assert_stage(case, "cast", T[TAP_XF], T[TAP_FEAT], torch.zeros_like(T[TAP_XF]), dt)
@@ -319,17 +365,47 @@ def _set_prec(model, prec):
     model.set_precision(prec)
 
 
-@pytest.mark.parametrize("prec,N,five", [(FP_PREC_F16, 1, 0), (FP_PREC_F16, 7, 0), (FP_PREC_F16, 33, 0), (FP_PREC_F16, 130, 0),
-                                         (FP_PREC_F16, 252, 0), (FP_PREC_BF16, 1, 0), (FP_PREC_BF16, 42, 0), (FP_PREC_BF16, 252, 0),
-                                         (FP_PREC_F16, 1, 1), (FP_PREC_F16, 33, 1), (FP_PREC_F16, 130, 1)])
+N_MAX = 2377             # include/foundationpose_amd.h FP_MAX_BATCH
+STEPS_MAX = 56           # FP_MAX_INPLANE_STEPS
+REFINER_CASES = [(FP_PREC_F16, 1, 0), (FP_PREC_F16, 7, 0), (FP_PREC_F16, 33, 0), (FP_PREC_F16, 130, 0), (FP_PREC_F16, 252, 0),
+                 (FP_PREC_BF16, 1, 0), (FP_PREC_BF16, 42, 0), (FP_PREC_BF16, 252, 0), (FP_PREC_F16, 1, 1), (FP_PREC_F16, 33, 1),
+                 (FP_PREC_F16, 130, 1),
+                 # inplane steps 3 / 5 / 7 / 24: other left-over sizes; 1008 = BASELINE configs[3]
+                 (FP_PREC_F16, 126, 0), (FP_PREC_F16, 210, 0), (FP_PREC_F16, 294, 0), (FP_PREC_F16, 1008, 0), (FP_PREC_BF16, 1008, 0),
+                 # fp_track_multi batches: conv_deep_kernel / conv_igemm_kernel on the small layers (3), split-K (4, 8), the 64-wide
+                 # igemm of the stem in bf16 (2), left-overs on conv_pp_kernel in bf16 (6)
+                 (FP_PREC_F16, 3, 0), (FP_PREC_F16, 4, 0), (FP_PREC_F16, 8, 0), (FP_PREC_BF16, 2, 0), (FP_PREC_BF16, 3, 0),
+                 (FP_PREC_BF16, 4, 0), (FP_PREC_BF16, 6, 0), (FP_PREC_BF16, 8, 0)]
+SCORER_CASES = [(FP_PREC_F16, 1), (FP_PREC_F16, 7), (FP_PREC_F16, 42), (FP_PREC_F16, 252), (FP_PREC_BF16, 42), (FP_PREC_F16, 210),
+                (FP_PREC_F16, 1008),
+                # bf16 conv_big_pp_kernel rounds (84); the cross-attention projections over 714 / 1386 hypotheses (conv_deep_kernel,
+                # conv_igemm_kernel<128>)
+                (FP_PREC_BF16, 84), (FP_PREC_BF16, 714), (FP_PREC_F16, 1386), (FP_PREC_BF16, 1386)]
+REGISTER_STEPS = [6, 24]    # the two shared-crop cases below
+
+
+def _inputs(crops, N):
+    """N network inputs: the 252 rendered / observed crop pairs, repeated"""
+    a, b = crops
+    if N <= len(a):
+        return a[:N], b[:N]
+    i = np.arange(N) % len(a)
+    return a[i], b[i]
+
+
+def _dt_name(dt):
+    return "bf16" if dt == LR.BF16 else "f16"
+
+
+@pytest.mark.parametrize("prec,N,five", REFINER_CASES)
 def test_refiner_stages_match_float64(tl, model, crops, disc_nets, prec, N, five):
     dt = LR.BF16 if prec == FP_PREC_BF16 else LR.F16
-    case = f"refiner {'bf16' if dt else 'f16'} N={N}{' 5-launch' if five else ''}"
-    a, b = crops
+    case = f"refiner {_dt_name(dt)} N={N}{' 5-launch' if five else ''}"
+    a, b = _inputs(crops, N)
     _set_prec(model, prec)
     try:
         tl.fpt_set_enc_tail(0 if five else 1)
-        T, pe_fused = _tapped(tl, 0, N, 2 * N, five, dt, lambda: model.refiner_infer(a[:N], b[:N]))
+        T, pe_fused = _tapped(tl, 0, N, 2 * N, five, dt, lambda: model.refiner_infer(a, b))
     finally:
         tl.fpt_set_enc_tail(1)
         _set_prec(model, FP_PREC_F16)
@@ -342,14 +418,14 @@ def test_refiner_stages_match_float64(tl, model, crops, disc_nets, prec, N, five
     _flush()
 
 
-@pytest.mark.parametrize("prec,N", [(FP_PREC_F16, 1), (FP_PREC_F16, 7), (FP_PREC_F16, 42), (FP_PREC_F16, 252), (FP_PREC_BF16, 42)])
+@pytest.mark.parametrize("prec,N", SCORER_CASES)
 def test_scorer_stages_match_float64(tl, model, crops, disc_nets, prec, N):
     dt = LR.BF16 if prec == FP_PREC_BF16 else LR.F16
-    case = f"scorer {'bf16' if dt else 'f16'} N={N}"
-    a, b = crops
+    case = f"scorer {_dt_name(dt)} N={N}"
+    a, b = _inputs(crops, N)
     _set_prec(model, prec)
     try:
-        T, _ = _tapped(tl, 1, N, 2 * N, False, dt, lambda: model.scorer_infer(a[:N], b[:N]))
+        T, _ = _tapped(tl, 1, N, 2 * N, False, dt, lambda: model.scorer_infer(a, b))
     finally:
         _set_prec(model, FP_PREC_F16)
     w = _weights(disc_nets[1], dt)
@@ -358,21 +434,233 @@ def test_scorer_stages_match_float64(tl, model, crops, disc_nets, prec, N):
     _flush()
 
 
-def test_register_shared_crop_stages_match_float64(tl, model, disc_nets, syn_mesh, scene):
-    """Register's refiner pass: 252 hypotheses that share ONE observed crop (NB2 = 253, the b half of the concat broadcast)"""
+def _register_stages(tl, model, disc_nets, syn_mesh, scene, steps, wins):
+    """Register's refiner pass: 42 * steps hypotheses that share ONE observed crop (NB2 = N + 1, the b half of the concat broadcast);
+    wins: image windows to check (None = the whole tensors)"""
+    N = 42 * steps
+    w = _weights(disc_nets[0], LR.F16)
+    model.set_inplane_steps(steps)
     tl.fpt_model_use_graphs(model._h, 0)
     try:
-        T, _ = _tapped(tl, 0, 252, 253, False, LR.F16,
-                              lambda: model.Register(scene.rgb, scene.depth, scene.mask, syn_mesh.name))
+        for win in wins:
+            T, _ = _tapped(tl, 0, N, N + 1, False, LR.F16, lambda: model.Register(scene.rgb, scene.depth, scene.mask, syn_mesh.name), win)
+            n, hs = (N, None) if win is None else (win[1], slice(win[0], win[0] + win[1]))
+            case = f"Register refiner N={N} shared-b" + ("" if win is None else f" [{hs.start}:{hs.stop}]")
+            check_trunk(case, w, T, n, 1, LR.F16)
+            check_heads(case, w, T, n, LR.F16, False, hs)
+            cat = LR.interior(T.raw(TAP_ACT + 5))[..., 128:]
+            assert torch.equal(cat, cat[:1].expand_as(cat)), case     # every hypothesis holds the same b half
+            del T, cat
     finally:
         tl.fpt_model_use_graphs(model._h, 1)
-    case = "Register refiner N=252 shared-b"
-    w = _weights(disc_nets[0], LR.F16)
-    check_trunk(case, w, T, 252, 1, LR.F16)
-    check_heads(case, w, T, 252, LR.F16, False)
-    cat = LR.interior(T[TAP_ACT + 5])[..., 128:]
-    assert torch.equal(cat, cat[:1].expand_as(cat))      # every hypothesis holds the same b half
+        model.set_inplane_steps(6)
     _flush()
+
+
+def test_register_shared_crop_stages_match_float64(tl, model, disc_nets, syn_mesh, scene):
+    _register_stages(tl, model, disc_nets, syn_mesh, scene, 6, [None])
+
+
+def test_register_shared_crop_stages_match_float64_at_1008(tl, model, disc_nets, syn_mesh, scene):
+    """inplane steps 24 (BASELINE configs[3]): NB2 = 1009 images in encodeA"""
+    _register_stages(tl, model, disc_nets, syn_mesh, scene, 24, [None])
+
+
+def _bitwise(t):
+    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def test_windowed_taps_equal_the_slice_of_the_full_taps(tl, model, crops, syn_mesh, scene):
+    """fpt_tap_window: a window's tensors are the matching rows of the full taps, bit for bit -- hypotheses with their own observed
+    crops (refiner, scorer), the shared crop (Register), and a window clamped at the last hypothesis"""
+    a, b = crops
+    N = 252
+    runs = [(0, 2 * N, lambda: model.refiner_infer(a, b)), (1, 2 * N, lambda: model.scorer_infer(a, b)),
+            (0, N + 1, lambda: model.Register(scene.rgb, scene.depth, scene.mask, syn_mesh.name))]
+    tl.fpt_model_use_graphs(model._h, 0)
+    try:
+        for kind, NB2, call in runs:
+            full, _ = _tapped(tl, kind, N, NB2, False, LR.F16, call)
+            for w0, wn in ((100, 20), (N - 5, 16)):
+                win, _ = _tapped(tl, kind, N, NB2, False, LR.F16, call, (w0, wn))
+                w1 = min(N, w0 + wn)
+                for pt in _shapes(kind, N, NB2, False):
+                    f, g = full.raw(pt), win.raw(pt)
+                    if g.shape == f.shape:
+                        exp = f
+                    elif f.shape[0] == NB2 and NB2 == 2 * N:
+                        exp = torch.cat([f[w0:w1], f[N + w0:N + w1]])
+                    elif f.shape[0] == NB2:
+                        exp = torch.cat([f[w0:w1], f[N:N + 1]])
+                    else:
+                        exp = f[w0:w1]
+                    assert torch.equal(_bitwise(g), _bitwise(exp)), (kind, NB2, pt, w0, wn)
+    finally:
+        tl.fpt_model_use_graphs(model._h, 1)
+
+
+# ---- which schedules the float64 cases reach -----------------------------------------------------------------------------------
+
+ROWS_PER_IMG = {"conv_stem": 6400, "conv_a1": 1600, "conv_128": 1600, "conv_256": 1600, "conv_b2": 400, "conv_512": 400}
+
+
+def _log_records(tl):
+    f = (C.c_int * 7)()
+    name = C.create_string_buffer(96)
+    out = []
+    for i in range(tl.fpt_launch_log_count()):
+        assert tl.fpt_launch_log_get(i, f, name, 96) == 0
+        net, prec, side, m_begin, M, ksplit, pe = list(f)
+        tag, _, kern = name.value.decode().rpartition("/")
+        out.append(dict(net=("refiner", "scorer")[net], prec=("f16", "bf16", "fp8", "int8")[prec], side=side, m_begin=m_begin, M=M,
+                        ksplit=ksplit, pe=pe, tag=tag, kernel=kern))
+    return out
+
+
+def _logged(tl, fn):
+    """the launch log of fn(): [record]"""
+    tl.fpt_launch_log_arm(1)
+    try:
+        fn()
+    finally:
+        tl.fpt_launch_log_arm(0)
+    recs = _log_records(tl)
+    tl.fpt_launch_log_clear()
+    assert recs, "no launch was logged"
+    return recs
+
+
+def _key(r):
+    """(net, precision, layer tag, kernel, stream, pe fused, split-K)"""
+    return (r["net"], r["prec"], r["tag"], r["kernel"], "side" if r["side"] else "main", r["pe"], r["ksplit"] > 1)
+
+
+def _boundary_windows(recs, N, NB2):
+    """image windows (3 hypotheses) around every hypothesis holding the first row of a launch that starts inside a layer"""
+    imgs = set()
+    for r in recs:
+        per = ROWS_PER_IMG.get(r["tag"])
+        if per and r["m_begin"] > 0:
+            i = r["m_begin"] // per
+            imgs.add(min(i, N - 1) if i < N else (i - N if NB2 == 2 * N else N - 1))
+    wins, last = [], -1
+    for i in sorted(imgs):
+        w0 = min(max(0, i - 1), N - 3)
+        if w0 > last:
+            wins.append((w0, 3))
+            last = w0 + 2
+    return wins
+
+
+def test_refiner_stages_match_float64_at_the_batch_limit(tl, model, crops, disc_nets):
+    """refiner_infer with FP_MAX_BATCH hypotheses (2 N_MAX images in encodeA): the first 2 and the last 16 hypotheses, which carry the
+    largest offsets the kernels form, and a window around every launch boundary, stage by stage in float64"""
+    a, b = _inputs(crops, N_MAX)
+    recs = _logged(tl, lambda: model.refiner_infer(a, b))
+    w = _weights(disc_nets[0], LR.F16)
+    for win in [(0, 2), (N_MAX - 16, 16)] + _boundary_windows(recs, N_MAX, 2 * N_MAX):
+        T, _ = _tapped(tl, 0, N_MAX, 2 * N_MAX, False, LR.F16, lambda: model.refiner_infer(a, b), win)
+        case = f"refiner f16 N={N_MAX} [{win[0]}:{win[0] + win[1]}]"
+        check_trunk(case, w, T, win[1], win[1], LR.F16)
+        check_heads(case, w, T, win[1], LR.F16, False, slice(win[0], win[0] + win[1]))
+        del T
+    _flush()
+
+
+def test_register_stages_match_float64_at_the_largest_inplane_steps(tl, model, disc_nets, syn_mesh, scene):
+    N = 42 * STEPS_MAX
+    model.set_inplane_steps(STEPS_MAX)
+    tl.fpt_model_use_graphs(model._h, 0)
+    try:
+        recs = _logged(tl, lambda: model.Register(scene.rgb, scene.depth, scene.mask, syn_mesh.name))
+    finally:
+        tl.fpt_model_use_graphs(model._h, 1)
+        model.set_inplane_steps(6)
+    wins = [(0, 2), (N - 16, 16)] + _boundary_windows([r for r in recs if r["net"] == "refiner"], N, N + 1)
+    _register_stages(tl, model, disc_nets, syn_mesh, scene, STEPS_MAX, wins)
+
+
+def test_batches_past_the_limit_are_refused(tl, model, disc_nets):
+    """one hypothesis past FP_MAX_BATCH: an error that names the limit, and no network launch"""
+    def refused(fn):
+        with pytest.raises(FoundationPoseError):
+            fn()
+        msg = tl.fp_last_error().decode()      # (the model runs on the test build: its error is that library's)
+        assert "FP_MAX_BATCH" in msg, msg
+
+    tl.fpt_launch_log_arm(1)
+    try:
+        refused(lambda: model.set_inplane_steps(STEPS_MAX + 1))
+        assert model.num_hypotheses == 252
+        x = np.zeros((N_MAX + 1, 160, 160, 6), np.float32)
+        refused(lambda: model.refiner_infer(x, x))
+        refused(lambda: model.scorer_infer(x, x))
+        assert tl.fpt_launch_log_count() == 0
+    finally:
+        tl.fpt_launch_log_arm(0)
+    for path, scorer in ((disc_nets[0], 0), (disc_nets[1], 1)):
+        assert not tl.fp_net_create(path.encode(), scorer, N_MAX + 1)
+        assert "FP_MAX_BATCH" in tl.fp_last_error().decode()
+    model.set_inplane_steps(STEPS_MAX)      # the largest accepted value
+    model.set_inplane_steps(6)
+
+
+def test_every_launched_schedule_is_checked_in_float64(tl, model, crops, syn_mesh, scene):
+    """every (network, precision, layer, kernel, stream, pe fused, split-K) a served batch size launches is launched by at least one
+    float64 stage case of this file.  Served: refiner and scorer at N = 1 (Track), 2..8 (fp_track_multi objects), 42 * s for every
+    accepted inplane step s, in f16 and bf16; Register (shared observed crop) at 42 * s in f16."""
+    big = _inputs(crops, 42 * STEPS_MAX)
+    covered = set()
+    for prec, N, five in REFINER_CASES:
+        _set_prec(model, prec)
+        tl.fpt_set_enc_tail(0 if five else 1)
+        try:
+            covered |= {_key(r) for r in _logged(tl, lambda: model.refiner_infer(big[0][:N], big[1][:N]))}
+        finally:
+            tl.fpt_set_enc_tail(1)
+            _set_prec(model, FP_PREC_F16)
+    for prec, N in SCORER_CASES:
+        _set_prec(model, prec)
+        try:
+            covered |= {_key(r) for r in _logged(tl, lambda: model.scorer_infer(big[0][:N], big[1][:N]))}
+        finally:
+            _set_prec(model, FP_PREC_F16)
+    a, b = _inputs(crops, N_MAX)
+    covered |= {_key(r) for r in _logged(tl, lambda: model.refiner_infer(a, b))}
+    del a, b
+
+    def register(steps):
+        model.set_inplane_steps(steps)
+        tl.fpt_model_use_graphs(model._h, 0)
+        try:
+            return _logged(tl, lambda: model.Register(scene.rgb, scene.depth, scene.mask, syn_mesh.name))
+        finally:
+            tl.fpt_model_use_graphs(model._h, 1)
+            model.set_inplane_steps(6)
+    for steps in REGISTER_STEPS + [STEPS_MAX]:
+        covered |= {_key(r) for r in register(steps) if r["net"] == "refiner"}   # (its scorer pass is a scorer case's)
+
+    first = {}    # key -> smallest served N (and how) that launches it
+    def served(keys, how, N):
+        for k in keys:
+            if k not in first or N < first[k][0]:
+                first[k] = (N, how)
+    sizes = [1] + list(range(2, 9)) + [42 * s for s in range(1, STEPS_MAX + 1)]
+    for prec in (FP_PREC_F16, FP_PREC_BF16):
+        _set_prec(model, prec)
+        try:
+            for N in sizes:
+                served({_key(r) for r in _logged(tl, lambda: model.refiner_infer(big[0][:N], big[1][:N]))}, "refiner_infer", N)
+                if N % 42 == 0:
+                    served({_key(r) for r in _logged(tl, lambda: model.scorer_infer(big[0][:N], big[1][:N]))}, "scorer_infer", N)
+        finally:
+            _set_prec(model, FP_PREC_F16)
+    for s in range(1, STEPS_MAX + 1):
+        served({_key(r) for r in register(s)}, "Register", 42 * s)
+    print("\n" + "\n".join(f"{'covered' if k in covered else 'MISSING'}  first at N={n:<5} ({how}): {k}"
+                           for k, (n, how) in sorted(first.items(), key=lambda kv: (kv[1][0], kv[0]))))
+    missing = sorted((n, how, k) for k, (n, how) in first.items() if k not in covered)
+    assert not missing, "schedules without a float64 stage case:\n" + "\n".join(f"  {k}: first at N = {n} ({how})" for n, how, k in missing)
 
 
 def _fails(fn):
