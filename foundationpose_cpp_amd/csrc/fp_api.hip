@@ -778,6 +778,29 @@ int fpt_model_poison(fp_model *m, int kind) {
   return 0;
 }
 
+// Plan-only forward pass (tests/test_layers_gpu.py): grows the model's buffers to N like a real call, then runs the host side of one
+// network call at the model's precision -- kind 0 = refiner_forward (shared_b as Register's first refine iteration), 1 = scorer_features +
+// scorer_head over N, 2 = scorer_features alone (a Register shard) -- with every network launch suppressed, so that the armed launch log
+// (fpt_launch_log_arm) holds exactly what the real call would launch.  The inputs are whatever nn_in holds: nothing is uploaded.
+int fpt_plan_forward(fp_model *m, int kind, int N, int shared_b) try {
+  FP_CHECK(m && kind >= 0 && kind <= 2 && N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fpt_plan_forward: invalid arguments");
+  FP_CHECK(kind == 0 ? m->refiner != nullptr : m->scorer != nullptr, "[FoundationPose] fpt_plan_forward: weights not loaded");
+  SerialGuard serial(m->device);
+  if (ensure_capacity(m, N, 0)) return 1;
+  struct PlanOnly {
+    PlanOnly() { nn_plan_only(true); }
+    ~PlanOnly() { nn_plan_only(false); }
+  } plan;
+  if (kind == 0) {
+    if (refiner_forward(m->stream, &m->prof, m->refiner, m->ws, m->nn_in, N, m->trans_dev, m->rot_dev, shared_b ? 1 : 0)) return 1;
+  } else {
+    if (scorer_features(m->stream, &m->prof, m->scorer, m->ws, m->nn_in, N, m->feat_dev)) return 1;
+    if (kind == 1 && scorer_head(m->stream, &m->prof, m->scorer, m->ws, m->feat_dev, N, m->scores_dev)) return 1;
+  }
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  return 0;
+} FP_CATCH_INT
+
 // bit 0: graphs still enabled (a failed capture disables them), bit 1: Track graph instantiated, bit 2: Register graph
 int fpt_model_graph_state(fp_model *m) { return (m->use_graphs ? 1 : 0) | (m->tg.exec ? 2 : 0) | (m->rg.exec ? 4 : 0); }
 

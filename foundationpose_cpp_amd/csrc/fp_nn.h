@@ -60,6 +60,9 @@ void nn_scratch_debug_info(const NNScratch *, const void **buf, size_t *bytes, c
 // partials, the f32 side buffer and the cross-attention scratch with a poison pattern -- kind 0: quiet NaN, 1: the largest finite
 // value with alternating sign.  dt = the arena's element type (DT_F16 / DT_BF16).
 int nn_scratch_poison(NNScratch *, int dt, int kind, hipStream_t s);
+// test build: plan-only mode of every forward pass while on (fpt_plan_forward): the host side runs and the launch log
+// records, no network kernel is launched
+void nn_plan_only(bool on);
 #endif
 
 // activation taps of the test build (fpt_tap_arm, tests/test_layers_gpu.py): where the forward pass copies a tensor out

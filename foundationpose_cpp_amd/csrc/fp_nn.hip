@@ -1296,6 +1296,7 @@ FP_HOOK g_halo_wpack = 1;      // conv_halo_kernel streams its weights from the 
 FP_HOOK g_att_tail = 0;        // [r5] A/B, OFF (measured slower: attention 0.555 -> 0.625 ms per Register): the 16-row tail of a 400-token sequence on attention32_skv_kernel instead of a 4th 128-row block
 FP_HOOK g_ln_pmean = 1;        // [r5] Track: LayerNorm 2 + partial token sums in one launch (layernorm_pmean_kernel) instead of layernorm + token_mean
 FP_HOOK g_qkv_ablate = 0;      // timing-only ablations of qkv_tile_kernel (test build, wrong results)
+FP_HOOK g_splitk_ablate = 0;   // test build, wrong results: conv_splitk_reduce_kernel sums all slices but the last (the float64 checks must fail)
 FP_HOOK g_qkv_tile = 1;        // [r5] QKV projections of Register (N > 1) on qkv_tile_kernel (80-token tiles resident in LDS) instead of gemm_k32_kernel
 FP_HOOK g_enc_tail = 1;        // [r5] Register (N > 1): out_proj + LayerNorm 1 + FFN + LayerNorm 2 + token sums of BOTH heads as one launch (enc_tail_kernel) instead of five per head
 FP_HOOK g_halo_wreg = 0;       // [r5] A/B, OFF (conv_256 -3 % in the stage profile, nothing on the wall clock: tools/ab_wall.py, EXPERIMENTS.md): 1 = 3x3 / 40x40 layers with >= 256 input channels on conv_halo_wreg_kernel: weights global -> registers (fragment-order copy), no weight ring, 2 barriers per chunk (2 = every such layer incl. the 128-channel ones, where it measures even)
@@ -1355,6 +1356,10 @@ struct LaunchRec {
 };
 static bool g_launch_log_on = false;
 static std::vector<LaunchRec> g_launch_log;
+// Plan-only mode (fpt_plan_forward): the host side of a forward pass runs and the launch log records what it would launch, but no
+// network kernel is issued -- FP_LAUNCH / FP_LAUNCH_RAW do nothing.  The schedule is decided exactly as in a real call.
+static bool g_plan_only = false;
+void nn_plan_only(bool on) { g_plan_only = on; }
 #else
 #define FP_TAP(c, point, src, bytes) ((void)0)
 #define FP_TAP_IMGS(c, point, src, img_bytes, imgs, N) ((void)0)
@@ -1385,12 +1390,23 @@ inline NetScope::NetScope(const Ctx &c, const char *name, double flops, double b
 #endif
 }
 
-// One launch = (once per launch site, element type and DEVICE) dynamic-LDS opt-in + the launch itself.
+// One launch = (once per launch site, element type and DEVICE) dynamic-LDS opt-in + the launch itself.  FP_LAUNCH_RAW: a network
+// launch without the opt-in.  In the test build both do nothing in plan-only mode.
+#ifdef FP_TEST_HOOKS
+#define FP_LAUNCH_SKIP g_plan_only
+#else
+#define FP_LAUNCH_SKIP false
+#endif
 #define FP_LAUNCH(KERN, grid, block, lds_bytes, stream, ...)                                                                        \
   do {                                                                                                                              \
+    if (FP_LAUNCH_SKIP) break;                                                                                                      \
     static fp::PerDeviceOnce fp_attr_once_;                                                                                         \
     fp_attr_once_.run([] { (void)hipFuncSetAttribute((const void *)(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
     hipLaunchKernelGGL((KERN), grid, block, lds_bytes, stream, __VA_ARGS__);                                                        \
+  } while (0)
+#define FP_LAUNCH_RAW(...)                       \
+  do {                                           \
+    if (!FP_LAUNCH_SKIP) hipLaunchKernelGGL(__VA_ARGS__); \
   } while (0)
 
 // a tensor as run_conv sees it: element type + (FP8) per-tensor scale, real = stored * scale
@@ -1776,7 +1792,13 @@ static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvPa
     NetScope ps(c, (tg + "/conv_splitk_reduce_kernel").c_str(), 0, 0);
     ps.rows(p.m_begin, p.M, p.ksplit, p.post != nullptr);
     size_t octs = (size_t)(p.M - p.m_begin) * (p.Cout / 8);
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((octs + 255) / 256)), dim3(256), 0, c.s, p);
+#ifdef FP_TEST_HOOKS
+    ConvParams pr = p;
+    if (g_splitk_ablate) pr.ksplit = p.ksplit - 1;   // ablation: the reduction drops the last slice
+#else
+    const ConvParams &pr = p;
+#endif
+    FP_LAUNCH_RAW(conv_splitk_reduce_kernel, dim3((unsigned)((octs + 255) / 256)), dim3(256), 0, c.s, pr);
   }
   return 0;
 }
@@ -1920,30 +1942,30 @@ static void launch_attention(const Ctx &c, const void *qkv, void *out, int B, in
   if (g_att_variant != 1) {  // the round-1 kernel (64 query rows per workgroup), kept in the test build for A/B
     const int nq = (T + 63) / 64;
     dim3 grid((unsigned)(nq * HEADS * B)), blk(256);
-    if (g_att_variant == 3) hipLaunchKernelGGL((attention_kernel<64, false, true, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
-    else if (g_att_variant == 5) hipLaunchKernelGGL((attention_kernel<64, true, false, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
-    else if (g_att_variant == 7) hipLaunchKernelGGL((attention_kernel<64, false, false, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
+    if (g_att_variant == 3) FP_LAUNCH_RAW((attention_kernel<64, false, true, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
+    else if (g_att_variant == 5) FP_LAUNCH_RAW((attention_kernel<64, true, false, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
+    else if (g_att_variant == 7) FP_LAUNCH_RAW((attention_kernel<64, false, false, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
     else if (g_att_variant == 9)  // 8 waves = 256 query rows per workgroup (K/V staged half as often; 9 % slower: the two waves of a SIMD run in lockstep)
-      hipLaunchKernelGGL((attention32_kernel<true, DT, 0, 8>), dim3((unsigned)(((T + 255) / 256) * HEADS * B)), dim3(512), 0, c.s, q, o, T, (T + 255) / 256, tstride, ld);
-    else if (g_att_variant == 10) hipLaunchKernelGGL((attention32_kernel<true, DT, 64>), dim3((unsigned)(((T + 127) / 128) * HEADS * B)), blk, 0, c.s, q, o, T, (T + 127) / 128, tstride, ld);
-    else if (g_att_variant == 8) hipLaunchKernelGGL((attention32_kernel<false, DT>), dim3((unsigned)(((T + 127) / 128) * HEADS * B)), blk, 0, c.s, q, o, T, (T + 127) / 128, tstride, ld);
+      FP_LAUNCH_RAW((attention32_kernel<true, DT, 0, 8>), dim3((unsigned)(((T + 255) / 256) * HEADS * B)), dim3(512), 0, c.s, q, o, T, (T + 255) / 256, tstride, ld);
+    else if (g_att_variant == 10) FP_LAUNCH_RAW((attention32_kernel<true, DT, 64>), dim3((unsigned)(((T + 127) / 128) * HEADS * B)), blk, 0, c.s, q, o, T, (T + 127) / 128, tstride, ld);
+    else if (g_att_variant == 8) FP_LAUNCH_RAW((attention32_kernel<false, DT>), dim3((unsigned)(((T + 127) / 128) * HEADS * B)), blk, 0, c.s, q, o, T, (T + 127) / 128, tstride, ld);
     else if (g_att_variant >= 16 && g_att_variant < 32) {
       const dim3 g32((unsigned)(((T + 127) / 128) * HEADS * B));
       const int nq32 = (T + 127) / 128;
       switch (g_att_variant - 16) {
-        case 1: hipLaunchKernelGGL((attention32_kernel<true, DT, 1>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 2: hipLaunchKernelGGL((attention32_kernel<true, DT, 2>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 4: hipLaunchKernelGGL((attention32_kernel<true, DT, 4>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 8: hipLaunchKernelGGL((attention32_kernel<true, DT, 8>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 6: hipLaunchKernelGGL((attention32_kernel<true, DT, 6>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 14: hipLaunchKernelGGL((attention32_kernel<true, DT, 14>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 15: hipLaunchKernelGGL((attention32_kernel<true, DT, 15>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 0: hipLaunchKernelGGL((attention32_kernel<true, DT, 16>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 3: hipLaunchKernelGGL((attention32_kernel<true, DT, 32>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        default: hipLaunchKernelGGL((attention32_kernel<true, DT, 0>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 1: FP_LAUNCH_RAW((attention32_kernel<true, DT, 1>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 2: FP_LAUNCH_RAW((attention32_kernel<true, DT, 2>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 4: FP_LAUNCH_RAW((attention32_kernel<true, DT, 4>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 8: FP_LAUNCH_RAW((attention32_kernel<true, DT, 8>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 6: FP_LAUNCH_RAW((attention32_kernel<true, DT, 6>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 14: FP_LAUNCH_RAW((attention32_kernel<true, DT, 14>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 15: FP_LAUNCH_RAW((attention32_kernel<true, DT, 15>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 0: FP_LAUNCH_RAW((attention32_kernel<true, DT, 16>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        case 3: FP_LAUNCH_RAW((attention32_kernel<true, DT, 32>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
+        default: FP_LAUNCH_RAW((attention32_kernel<true, DT, 0>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
       }
     }
-    else hipLaunchKernelGGL((attention_kernel<64, true, true, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
+    else FP_LAUNCH_RAW((attention_kernel<64, true, true, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
     return;
   }
 #endif
@@ -1959,11 +1981,11 @@ static void launch_attention(const Ctx &c, const void *qkv, void *out, int B, in
   const int tail = T % 128;
   if (g_att_tail && tail > 0 && tail <= 32 && T > 128) {
     const int nq_main = T / 128;
-    hipLaunchKernelGGL((attention32_kernel<true, DT>), dim3((unsigned)(nq_main * HEADS * B)), dim3(256), 0, c.s, q, o, T, nq_main, tstride, ld);
+    FP_LAUNCH_RAW((attention32_kernel<true, DT>), dim3((unsigned)(nq_main * HEADS * B)), dim3(256), 0, c.s, q, o, T, nq_main, tstride, ld);
     FP_LAUNCH((attention32_skv_kernel<true, DT>), dim3((unsigned)(HEADS * B)), dim3(256), 4 * 2 * (32 * 256 + 8 * 1056), c.s, q, o, T, 1, tstride, ld, nq_main * 4);
     return;
   }
-  hipLaunchKernelGGL((attention32_kernel<true, DT>), dim3((unsigned)(nq * HEADS * B)), dim3(256), 0, c.s, q, o, T, nq, tstride, ld);
+  FP_LAUNCH_RAW((attention32_kernel<true, DT>), dim3((unsigned)(nq * HEADS * B)), dim3(256), 0, c.s, q, o, T, nq, tstride, ld);
 }
 static int run_attention(const Ctx &c, int dt, const void *qkv, void *out, int B, int T, int tstride = 0, int ld = 3 * EMBED) {
   if (tstride == 0) tstride = T;
@@ -1980,8 +2002,8 @@ static void run_layernorm(const Ctx &c, int dt, const void *x, const LNParams &l
   const dim3 grid((unsigned)((rows + 3) / 4));
   const float *g1 = ln1 ? ln1->g : ln.g, *b1 = ln1 ? ln1->b : ln.b;
   const size_t sr = ln1 ? split_row : rows;
-  if (dt == DT_BF16) hipLaunchKernelGGL(layernorm_kernel<DT_BF16>, grid, dim3(256), 0, c.s, (const __bf16 *)x, ln.g, ln.b, (__bf16 *)y, rows, g1, b1, sr);
-  else hipLaunchKernelGGL(layernorm_kernel<DT_F16>, grid, dim3(256), 0, c.s, (const _Float16 *)x, ln.g, ln.b, (_Float16 *)y, rows, g1, b1, sr);
+  if (dt == DT_BF16) FP_LAUNCH_RAW(layernorm_kernel<DT_BF16>, grid, dim3(256), 0, c.s, (const __bf16 *)x, ln.g, ln.b, (__bf16 *)y, rows, g1, b1, sr);
+  else FP_LAUNCH_RAW(layernorm_kernel<DT_F16>, grid, dim3(256), 0, c.s, (const _Float16 *)x, ln.g, ln.b, (_Float16 *)y, rows, g1, b1, sr);
 }
 
 static void run_layernorm_mean(const Ctx &c, int dt, const void *x, const LNParams &ln, float *out, int B, int T, int tstride = 0,
@@ -1990,20 +2012,20 @@ static void run_layernorm_mean(const Ctx &c, int dt, const void *x, const LNPara
   const float *g1 = ln1 ? ln1->g : ln.g, *b1 = ln1 ? ln1->b : ln.b;
   const int sb = ln1 ? split_b : B;
   if (tstride == 0) tstride = T;
-  if (dt == DT_BF16) hipLaunchKernelGGL(layernorm_mean_kernel<DT_BF16>, dim3(B), dim3(1024), 0, c.s, (const __bf16 *)x, ln.g, ln.b, g1, b1, sb, out, T, tstride);
-  else hipLaunchKernelGGL(layernorm_mean_kernel<DT_F16>, dim3(B), dim3(1024), 0, c.s, (const _Float16 *)x, ln.g, ln.b, g1, b1, sb, out, T, tstride);
+  if (dt == DT_BF16) FP_LAUNCH_RAW(layernorm_mean_kernel<DT_BF16>, dim3(B), dim3(1024), 0, c.s, (const __bf16 *)x, ln.g, ln.b, g1, b1, sb, out, T, tstride);
+  else FP_LAUNCH_RAW(layernorm_mean_kernel<DT_F16>, dim3(B), dim3(1024), 0, c.s, (const _Float16 *)x, ln.g, ln.b, g1, b1, sb, out, T, tstride);
 }
 
 static void run_small_linear(const Ctx &c, const float *x, const LinearF32 &L, float *y, int B) {
   NetScope ps(c, "small_linear", 2.0 * B * L.out * L.in, 0);
   size_t waves = (size_t)((B + 7) / 8) * L.out;
-  hipLaunchKernelGGL(small_linear_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c.s, x, L.w, L.b, y, B, L.out, L.in);
+  FP_LAUNCH_RAW(small_linear_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, c.s, x, L.w, L.b, y, B, L.out, L.in);
 }
 
 static void run_token_mean(const Ctx &c, int dt, const void *x, float *out, int B, int T, int tstride = 0) {
   NetScope ps(c, "token_mean", 0, (double)B * T * EMBED * 2.0);
-  if (dt == DT_BF16) hipLaunchKernelGGL(token_mean_kernel<DT_BF16>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)x, out, T, tstride ? tstride : T);
-  else hipLaunchKernelGGL(token_mean_kernel<DT_F16>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)x, out, T, tstride ? tstride : T);
+  if (dt == DT_BF16) FP_LAUNCH_RAW(token_mean_kernel<DT_BF16>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)x, out, T, tstride ? tstride : T);
+  else FP_LAUNCH_RAW(token_mean_kernel<DT_F16>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)x, out, T, tstride ? tstride : T);
 }
 
 // calibration statistics of a trunk activation [pixels incl. the zero border][C]: per channel |max| (optional) and the sum of the
@@ -2059,10 +2081,10 @@ static void calib_record(const Ctx &c, int act_id, const void *buf, size_t pixel
   const unsigned char *x = (const unsigned char *)buf;
   const int groups = C / 8;
   const dim3 grid((unsigned)((size_t)1024 * groups / 256)), blk(256);   // 1024 pixel lanes per channel group
-  if (dt == DT_BF16) hipLaunchKernelGGL(chan_stats_kernel<DT_BF16>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
-  else if (dt == DT_FP8) hipLaunchKernelGGL(chan_stats_kernel<DT_FP8>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
-  else if (dt == DT_I8) hipLaunchKernelGGL(chan_stats_kernel<DT_I8>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
-  else hipLaunchKernelGGL(chan_stats_kernel<DT_F16>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
+  if (dt == DT_BF16) FP_LAUNCH_RAW(chan_stats_kernel<DT_BF16>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
+  else if (dt == DT_FP8) FP_LAUNCH_RAW(chan_stats_kernel<DT_FP8>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
+  else if (dt == DT_I8) FP_LAUNCH_RAW(chan_stats_kernel<DT_I8>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
+  else FP_LAUNCH_RAW(chan_stats_kernel<DT_F16>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
 }
 
 // arena carve (by capacity, see ensure_scratch)
@@ -2146,13 +2168,13 @@ static void add_pos_embed(const Ctx &c, const Arena &a, int N) {
   NetScope ps(c, "add_pos_embed", 0, (double)rows * EMBED * 4.0);
   size_t chunks = rows * (EMBED / 8);
   const dim3 grid((unsigned)((chunks + 255) / 256));
-  if (net->act_dt == DT_BF16) hipLaunchKernelGGL(add_pos_embed_kernel<DT_BF16>, grid, dim3(256), 0, c.s, (__bf16 *)a.tokens, (const __bf16 *)net->pe, 400, rows);
-  else hipLaunchKernelGGL(add_pos_embed_kernel<DT_F16>, grid, dim3(256), 0, c.s, (_Float16 *)a.tokens, (const _Float16 *)net->pe, 400, rows);
+  if (net->act_dt == DT_BF16) FP_LAUNCH_RAW(add_pos_embed_kernel<DT_BF16>, grid, dim3(256), 0, c.s, (__bf16 *)a.tokens, (const __bf16 *)net->pe, 400, rows);
+  else FP_LAUNCH_RAW(add_pos_embed_kernel<DT_F16>, grid, dim3(256), 0, c.s, (_Float16 *)a.tokens, (const _Float16 *)net->pe, 400, rows);
 }
 static void broadcast_b(const Ctx &c, unsigned char *cat, int N, int cb /* bytes of the b-half of a pixel */) {
   NetScope ps(c, "broadcast_b", 0, (double)N * 1600 * 2 * cb);
   size_t total = (size_t)(N - 1) * 1600 * (cb / 16);
-  hipLaunchKernelGGL(broadcast_b_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.s, cat, N, 42, 42, 40, 40, 1, cb);
+  FP_LAUNCH_RAW(broadcast_b_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.s, cat, N, 42, 42, 40, 40, 1, cb);
 }
 
 // 8-bit trunk (PREC_FP8 / PREC_INT8) [r4].  The 13 3x3 convolutions from encodeA.2 on read 8-bit operands; what differs from the
@@ -2237,15 +2259,15 @@ static int run_trunk_q8(const Ctx &c, const Arena &a, const void *nn_in, int N, 
     NetScope ps(c, "q8_img_bias", 0, (double)NBi * (HW + 2) * (HW + 2) * L.Cin);
 #ifdef FP_TEST_HOOKS
     if (g_q8_imgbias == 2) {   // A/B (test build): the three-launch form (sliced integer-atomic sums, 64-channel bias blocks, clear)
-      hipLaunchKernelGGL(q8_img_sum_kernel, dim3(NBi, HW == 40 ? 6 : 2), dim3(256), 0, c.s, (const unsigned char *)xq, (HW + 2) * (HW + 2), L.Cin, c.ws->img_sum);
-      hipLaunchKernelGGL(q8_img_bias_kernel, dim3(NBi, L.Cout / 64), dim3(256), 0, c.s, c.ws->img_sum, L.tmat_t, L.cscale, L.bias, 1.f / (float)(HW * HW), L.Cin, L.Cout, c.ws->img_bias);
+      FP_LAUNCH_RAW(q8_img_sum_kernel, dim3(NBi, HW == 40 ? 6 : 2), dim3(256), 0, c.s, (const unsigned char *)xq, (HW + 2) * (HW + 2), L.Cin, c.ws->img_sum);
+      FP_LAUNCH_RAW(q8_img_bias_kernel, dim3(NBi, L.Cout / 64), dim3(256), 0, c.s, c.ws->img_sum, L.tmat_t, L.cscale, L.bias, 1.f / (float)(HW * HW), L.Cin, L.Cout, c.ws->img_bias);
       (void)hipMemsetAsync(c.ws->img_sum, 0, (size_t)NBi * L.Cin * sizeof(int), c.s);
     } else
 #endif
     {
       // even rows x even columns of the padded image (HW + 2 is even): (HW/2 + 1)^2 lattice points, (HW/2)^2 of them interior
       const int wp2 = g_q8_imgbias == 3 ? 0 : (HW + 2) / 2;
-      hipLaunchKernelGGL(q8_img_bias_fused_kernel, dim3((NBi + Q8_BIAS_IMGS - 1) / Q8_BIAS_IMGS), dim3(1024), 0, c.s, (const unsigned char *)xq, wp2 ? wp2 * wp2 : (HW + 2) * (HW + 2), L.tmat_t, L.cscale,
+      FP_LAUNCH_RAW(q8_img_bias_fused_kernel, dim3((NBi + Q8_BIAS_IMGS - 1) / Q8_BIAS_IMGS), dim3(1024), 0, c.s, (const unsigned char *)xq, wp2 ? wp2 * wp2 : (HW + 2) * (HW + 2), L.tmat_t, L.cscale,
                          L.bias, wp2 ? 1.f / (float)((HW / 2) * (HW / 2)) : 1.f / (float)(HW * HW), L.Cin, L.Cout, c.ws->img_bias, wp2, (HW + 2) * (HW + 2), NBi);
     }
     return c.ws->img_bias;
@@ -2263,8 +2285,8 @@ static int run_trunk_q8(const Ctx &c, const Arena &a, const void *nn_in, int N, 
     NetScope ps(c, "q8_copy", 0, (double)imgs * HW * HW * Cc * 3.0);
     const size_t octs = (size_t)imgs * HW * HW * (Cc / 8);
     const dim3 grid((unsigned)((octs + 255) / 256));
-    if (q == DT_FP8) hipLaunchKernelGGL(q8_copy_kernel<DT_FP8>, grid, dim3(256), 0, c.s, (const _Float16 *)x16, (unsigned char *)xq, oinv[act], HW + 2, HW + 2, 1, Cc, octs);
-    else hipLaunchKernelGGL(q8_copy_kernel<DT_I8>, grid, dim3(256), 0, c.s, (const _Float16 *)x16, (unsigned char *)xq, oinv[act], HW + 2, HW + 2, 1, Cc, octs);
+    if (q == DT_FP8) FP_LAUNCH_RAW(q8_copy_kernel<DT_FP8>, grid, dim3(256), 0, c.s, (const _Float16 *)x16, (unsigned char *)xq, oinv[act], HW + 2, HW + 2, 1, Cc, octs);
+    else FP_LAUNCH_RAW(q8_copy_kernel<DT_I8>, grid, dim3(256), 0, c.s, (const _Float16 *)x16, (unsigned char *)xq, oinv[act], HW + 2, HW + 2, 1, Cc, octs);
   };
   // first conv of a residual block (no skip operand): 8-bit -> 8-bit with the consumer's scales folded in, or plain f16
   auto first = [&](const char *tag, const ConvLayer &L, bool on, const Act &x16, const Act &xq, int NB, int HW, const Act &y16, const Act &yq, int act, size_t P, int Cc) -> int {
@@ -2481,7 +2503,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
         NetScope ps(c, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
         EncHeadsParams hp{pdot, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}, 1, 25, 3, 400.f};
         const bool do_fuse = fuse && g_fuse_pose;
-        hipLaunchKernelGGL(enc_heads_kernel, dim3(1), dim3(64), 0, c.s, hp, do_fuse ? *fuse : PoseUpdateFuse{}, do_fuse ? 1 : 0);
+        FP_LAUNCH_RAW(enc_heads_kernel, dim3(1), dim3(64), 0, c.s, hp, do_fuse ? *fuse : PoseUpdateFuse{}, do_fuse ? 1 : 0);
         if (do_fuse && fused_out) *fused_out = true;
       }
       FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
@@ -2514,8 +2536,8 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
         ;
     if (pmean) {
       NetScope ps(c, "layernorm_pmean", 0, 2.0 * 400 * EMBED * 2.0);
-      if (dt == DT_BF16) hipLaunchKernelGGL(layernorm_pmean_kernel<DT_BF16>, dim3(2, kParts), dim3(256), 0, c.s, (const __bf16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
-      else hipLaunchKernelGGL(layernorm_pmean_kernel<DT_F16>, dim3(2, kParts), dim3(256), 0, c.s, (const _Float16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
+      if (dt == DT_BF16) FP_LAUNCH_RAW(layernorm_pmean_kernel<DT_BF16>, dim3(2, kParts), dim3(256), 0, c.s, (const __bf16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
+      else FP_LAUNCH_RAW(layernorm_pmean_kernel<DT_F16>, dim3(2, kParts), dim3(256), 0, c.s, (const _Float16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
       FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_POOL, psums, (size_t)kParts * EMBED * sizeof(float));   // (partial column sums: kParts x 25 rows)
       FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_POOL, psums + kParts * EMBED, (size_t)kParts * EMBED * sizeof(float));
     } else run_layernorm(c, dt, a.att, T0.ln2, a.y1, 2 * G, &R0.ln2, G);
@@ -2527,8 +2549,8 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
       NetScope ps(c, "token_mean", 0, 2.0 * 400 * EMBED * 2.0);
       SmallLinear2 sl{{ws->f32, ws->f32 + EMBED}, {T0.head.w, R0.head.w}, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}};
       unsigned *arrivals = reinterpret_cast<unsigned *>(ws->f32 + (size_t)ws->cap * EMBED);
-      if (dt == DT_BF16) hipLaunchKernelGGL(token_mean_pose_kernel<DT_BF16>, dim3(2, EMBED / 64), dim3(384), 0, c.s, (const __bf16 *)a.y1, ws->f32, 400, G, arrivals, sl, T0.head.in, *fuse);
-      else hipLaunchKernelGGL(token_mean_pose_kernel<DT_F16>, dim3(2, EMBED / 64), dim3(384), 0, c.s, (const _Float16 *)a.y1, ws->f32, 400, G, arrivals, sl, T0.head.in, *fuse);
+      if (dt == DT_BF16) FP_LAUNCH_RAW(token_mean_pose_kernel<DT_BF16>, dim3(2, EMBED / 64), dim3(384), 0, c.s, (const __bf16 *)a.y1, ws->f32, 400, G, arrivals, sl, T0.head.in, *fuse);
+      else FP_LAUNCH_RAW(token_mean_pose_kernel<DT_F16>, dim3(2, EMBED / 64), dim3(384), 0, c.s, (const _Float16 *)a.y1, ws->f32, 400, G, arrivals, sl, T0.head.in, *fuse);
       if (fused_out) *fused_out = true;
       FP_HIP_OK(hipGetLastError());
       return 0;
@@ -2540,10 +2562,10 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
       SmallLinear2 a{{pmean ? psums : ws->f32, pmean ? psums + kParts * EMBED : ws->f32 + EMBED}, {T0.head.w, R0.head.w}, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}};
       if (pmean) { a.parts = kParts; a.tokens = 400.f; }
       if (fuse && g_fuse_pose && T0.head.out == 3 && R0.head.out == 3) {
-        hipLaunchKernelGGL(small_linear2_pose_kernel, dim3(1), dim3(1024), 0, c.s, a, T0.head.in, *fuse);
+        FP_LAUNCH_RAW(small_linear2_pose_kernel, dim3(1), dim3(1024), 0, c.s, a, T0.head.in, *fuse);
         if (fused_out) *fused_out = true;
       } else
-        hipLaunchKernelGGL(small_linear2_kernel, dim3((unsigned)((T0.head.out + 3) / 4), 2), dim3(256), 0, c.s, a, 1, T0.head.out, T0.head.in);
+        FP_LAUNCH_RAW(small_linear2_kernel, dim3((unsigned)((T0.head.out + 3) / 4), 2), dim3(256), 0, c.s, a, 1, T0.head.out, T0.head.in);
     }
     FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
     FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
@@ -2584,7 +2606,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
     {
       NetScope ps(c, "small_linear", 2.0 * 2 * N * net->trans.head.out * EMBED, 0);
       EncHeadsParams hp{pdot, {net->trans.head.b, net->rot.head.b}, {trans_dev, rot_dev}, N, 5, net->trans.head.out, 400.f};
-      hipLaunchKernelGGL(enc_heads_kernel, dim3((unsigned)N), dim3(64), 0, c.s, hp, PoseUpdateFuse{}, 0);
+      FP_LAUNCH_RAW(enc_heads_kernel, dim3((unsigned)N), dim3(64), 0, c.s, hp, PoseUpdateFuse{}, 0);
     }
     FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
     FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
@@ -2659,8 +2681,8 @@ int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, co
     NetScope ps(c, "cast", 0, (double)N * EMBED * 6.0);
     size_t n = (size_t)N * EMBED;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (dt == DT_BF16) hipLaunchKernelGGL(cast_f32_kernel<DT_BF16>, grid, dim3(256), 0, c.s, feats_dev, (__bf16 *)xf, n);
-    else hipLaunchKernelGGL(cast_f32_kernel<DT_F16>, grid, dim3(256), 0, c.s, feats_dev, (_Float16 *)xf, n);
+    if (dt == DT_BF16) FP_LAUNCH_RAW(cast_f32_kernel<DT_BF16>, grid, dim3(256), 0, c.s, feats_dev, (__bf16 *)xf, n);
+    else FP_LAUNCH_RAW(cast_f32_kernel<DT_F16>, grid, dim3(256), 0, c.s, feats_dev, (_Float16 *)xf, n);
   }
   FP_TAP(c, TAP_XF, xf, (size_t)N * EMBED * 2);
   // att_cross: sequence = the N hypotheses, batch 1
@@ -2674,8 +2696,8 @@ int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, co
   {
     // Linear(512,1) on 2-byte rows: widen to f32 first (token_mean with T = 1 is a plain copy of each row)
     NetScope ps(c, "score_linear", 2.0 * N * EMBED, 0);
-    if (dt == DT_BF16) hipLaunchKernelGGL(token_mean_kernel<DT_BF16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)xf, o32, 1, 1);
-    else hipLaunchKernelGGL(token_mean_kernel<DT_F16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)xf, o32, 1, 1);
+    if (dt == DT_BF16) FP_LAUNCH_RAW(token_mean_kernel<DT_BF16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)xf, o32, 1, 1);
+    else FP_LAUNCH_RAW(token_mean_kernel<DT_F16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)xf, o32, 1, 1);
   }
   FP_TAP(c, TAP_O32, o32, (size_t)N * EMBED * sizeof(float));
   run_small_linear(c, o32, net->score_lin, scores_dev, N);

@@ -110,6 +110,13 @@ int fpt_launch_log_get(int i, int *fields7, char *name, int name_cap) {
   std::snprintf(name, (size_t)name_cap, "%s", r.name);
   return 0;
 }
+// every record at once: fields7 [max][7] as fpt_launch_log_get, names [max][name_cap]; returns the records copied
+int fpt_launch_log_get_all(int *fields7, char *names, int name_cap, int max) {
+  const int n = std::min(max, (int)fp::g_launch_log.size());
+  for (int i = 0; i < n; i++)
+    if (fpt_launch_log_get(i, fields7 + (size_t)i * 7, names + (size_t)i * name_cap, name_cap)) return -1;
+  return n;
+}
 void fpt_launch_log_clear() { fp::g_launch_log.clear(); }
 // did the last 2-byte trunk of this network kind add the positional table in the epilogue of its last convolution (1) or separately (0)
 int fpt_tap_pe_fused(int net_kind) { return fp::g_tap_pe_fused[net_kind & 1]; }
@@ -153,6 +160,7 @@ void fpt_set_conv_variant(int v) { fp::g_conv_variant = v; }
 void fpt_set_i8_stream(int v) { fp::g_i8_stream = v; }
 void fpt_set_q8_blocks(int v) { fp::g_q8_blocks = v & fp::Q8_BLOCKS_ALL; }   // [r6] stage mask of 8-bit networks loaded from now on (tools/q8_blocks.py)
 void fpt_set_conv_ablate(int v) { fp::g_conv_ablate = v; }
+void fpt_set_splitk_ablate(int v) { fp::g_splitk_ablate = v; }
 void fpt_set_splitk_target(int v) { fp::g_splitk_target = v; }
 void fpt_set_rem_splitk(int v) { fp::g_rem_splitk = v; }
 void fpt_set_grouped_heads(int v) { fp::g_grouped_heads = v; }

@@ -27,7 +27,7 @@ import torch
 
 import layer_ref as LR
 from foundationpose_cpp_amd import FoundationPose, _lib, synthetic as syn
-from foundationpose_cpp_amd.api import FP_PREC_BF16, FP_PREC_F16, FoundationPoseError
+from foundationpose_cpp_amd.api import FP_DEVICE, FP_HOST, FP_PREC_BF16, FP_PREC_F16, FoundationPoseError, _p
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +58,8 @@ def tl():
     L.fpt_tap_window.argtypes = [C.c_int, C.c_int]
     L.fpt_launch_log_arm.argtypes = [C.c_int]
     L.fpt_launch_log_get.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
+    L.fpt_launch_log_get_all.argtypes = [C.POINTER(C.c_int), C.c_char_p, C.c_int, C.c_int]
+    L.fpt_plan_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     yield L
     L.fpt_tap_clear()
     if TABLE:
@@ -111,7 +113,7 @@ def _win_imgs(N, NB2, win):
     return wn, wn + (wn if NB2 == 2 * N else NB2 - N)
 
 
-def _shapes(kind, N, NB2, five, win=None):
+def _shapes(kind, N, NB2, five, win=None, head=True):
     """tap point -> (shape, element tensor?) of everything one call of this network writes.  With an image window the per-image tensors
     (trunk, QKV, attention, the five-launch tail) hold the window's hypotheses only; the pooled rows, heads, scores and the scorer's
     cross-hypothesis tensors stay whole."""
@@ -137,8 +139,10 @@ def _shapes(kind, N, NB2, five, win=None):
             s[TAP_PDOT] = ((2, 25 if N == 1 else 5 * N, 4), 0)
         s[TAP_TRANS], s[TAP_ROT] = ((N, 3), 0), ((N, 3), 0)
     else:
-        s[TAP_FEAT], s[TAP_O32], s[TAP_SCORES] = ((N, 512), 0), ((N, 512), 0), ((N,), 0)
-        s[TAP_XF], s[TAP_XQKV], s[TAP_XATT], s[TAP_XOUT] = ((N, 512), 1), ((N, 1536), 1), ((N, 512), 1), ((N, 512), 1)
+        s[TAP_FEAT] = ((N, 512), 0)
+        if head:    # (scorer_head: not part of a Register shard)
+            s[TAP_O32], s[TAP_SCORES] = ((N, 512), 0), ((N,), 0)
+            s[TAP_XF], s[TAP_XQKV], s[TAP_XATT], s[TAP_XOUT] = ((N, 512), 1), ((N, 1536), 1), ((N, 512), 1), ((N, 512), 1)
     return s
 
 
@@ -152,15 +156,15 @@ class _Taps(dict):
         return dict.__getitem__(self, pt)
 
 
-def _tapped(tl, kind, N, NB2, five, dt, call, win=None):
-    """arm every tap of one call of network `kind` (win = (img0, nimg): that image window of the per-image tensors), run it, return
-    ({point: tensor on the GPU, widened to float64 when read}, pe fused)"""
+def _tapped(tl, kind, N, NB2, five, dt, call, win=None, head=True):
+    """arm every tap of one call of network `kind` (win = (img0, nimg): that image window of the per-image tensors; head = False: the
+    scorer's cross-hypothesis head does not run), run it, return ({point: tensor on the GPU, widened to float64 when read}, pe fused)"""
     tl.fpt_tap_clear()
     if win is not None:
         assert tl.fpt_tap_window(*win) == 0
     edt = LR.TORCH_DT[dt]
     bufs = {}
-    for pt, (shape, elem) in _shapes(kind, N, NB2, five, win).items():
+    for pt, (shape, elem) in _shapes(kind, N, NB2, five, win, head).items():
         t = torch.empty(shape, dtype=edt if elem else torch.float32, device=DEV)
         bufs[pt] = t
         assert tl.fpt_tap_arm(kind, pt, C.c_void_p(t.data_ptr()), t.numel() * t.element_size()) == 0
@@ -328,7 +332,8 @@ def check_heads(case, w, T, N, dt, five, hs=None):
         _assert_f32(case, f"{nm} heads", out, ref, acc + LR.C_ACC * (pooled.abs() @ head_w.abs().T))
 
 
-def check_scorer(case, w, T, N, dt, hs=None):
+def check_scorer(case, w, T, N, dt, hs=None, head=True):
+    """head = False: the per-hypothesis part alone (a Register shard ends at the pooled features)"""
     x = T[TAP_ACT + 14]
     b = TAP_HEAD
     ref, acc = LR.linear(w, "att.in_proj_weight", "att.in_proj_bias", x, out_dt=None)
@@ -339,6 +344,8 @@ def check_scorer(case, w, T, N, dt, hs=None):
     _assert_f32(case, "token mean", _hyps(T[b + H_POOL], hs), att.mean(1), LR.C_ACC * att.abs().mean(1))
     ref, acc = LR.linear(w, "att.out_proj.weight", "att.out_proj.bias", T[b + H_POOL], out_dt=None, f32_weights=True)
     _assert_f32(case, "feat", T[TAP_FEAT], ref, acc)
+    if not head:
+        return
     _assert_stage(case, "cast", T[TAP_XF], T[TAP_FEAT], torch.zeros_like(T[TAP_XF]), dt)
     ref, acc = LR.linear(w, "att_cross.in_proj_weight", "att_cross.in_proj_bias", T[TAP_XF], out_dt=None)
     _assert_stage(case, "cross qkv", T[TAP_XQKV], ref, acc, dt)
@@ -375,13 +382,24 @@ REFINER_CASES = [(FP_PREC_F16, 1, 0), (FP_PREC_F16, 7, 0), (FP_PREC_F16, 33, 0),
                  # fp_track_multi batches: conv_deep_kernel / conv_igemm_kernel on the small layers (3), split-K (4, 8), the 64-wide
                  # igemm of the stem in bf16 (2), left-overs on conv_pp_kernel in bf16 (6)
                  (FP_PREC_F16, 3, 0), (FP_PREC_F16, 4, 0), (FP_PREC_F16, 8, 0), (FP_PREC_BF16, 2, 0), (FP_PREC_BF16, 3, 0),
-                 (FP_PREC_BF16, 4, 0), (FP_PREC_BF16, 6, 0), (FP_PREC_BF16, 8, 0)]
+                 (FP_PREC_BF16, 4, 0), (FP_PREC_BF16, 6, 0), (FP_PREC_BF16, 8, 0),
+                 # the plan over every accepted N: conv_256 on conv_deep_kernel over all K-steps from 21 hypotheses (fp_track_multi)
+                 (FP_PREC_F16, 21, 0), (FP_PREC_BF16, 21, 0)]
 SCORER_CASES = [(FP_PREC_F16, 1), (FP_PREC_F16, 7), (FP_PREC_F16, 42), (FP_PREC_F16, 252), (FP_PREC_BF16, 42), (FP_PREC_F16, 210),
                 (FP_PREC_F16, 1008),
                 # bf16 conv_big_pp_kernel rounds (84); the cross-attention projections over 714 / 1386 hypotheses (conv_deep_kernel,
                 # conv_igemm_kernel<128>)
-                (FP_PREC_BF16, 84), (FP_PREC_BF16, 714), (FP_PREC_F16, 1386), (FP_PREC_BF16, 1386)]
+                (FP_PREC_BF16, 84), (FP_PREC_BF16, 714), (FP_PREC_F16, 1386), (FP_PREC_BF16, 1386),
+                # the plan over every accepted N (fp_scorer_infer, fp_net_infer, Register shards): the small-problem kernels in bf16 (1),
+                # the 64-wide stem igemm in bf16 (2), conv_deep_kernel / conv_igemm_kernel<128> (3), 2-slice split-K of conv_256 (4),
+                # left-overs on conv_pp_kernel and conv_igemm_kernel<128> in bf16 (6), 2-slice split-K of conv_b2 / conv_512 incl. the
+                # reduce that adds the positional table (8), conv_256 on conv_deep_kernel over all K-steps (21)
+                (FP_PREC_BF16, 1), (FP_PREC_BF16, 2), (FP_PREC_F16, 3), (FP_PREC_BF16, 3), (FP_PREC_F16, 4), (FP_PREC_BF16, 4),
+                (FP_PREC_BF16, 6), (FP_PREC_F16, 8), (FP_PREC_BF16, 8), (FP_PREC_F16, 21), (FP_PREC_BF16, 21)]
 REGISTER_STEPS = [6, 24]    # the two shared-crop cases below
+# Register shards (begin, count, precision) of the 252 hypotheses: the 8-GPU layout of the headline ([0:32], the ragged [224:252]) and
+# the smallest shared-crop batch in bf16 (broadcast_b of the b half)
+SHARD_CASES = [(0, 32, FP_PREC_F16), (224, 28, FP_PREC_F16), (224, 28, FP_PREC_BF16), (0, 2, FP_PREC_BF16)]
 
 
 def _inputs(crops, N):
@@ -505,13 +523,15 @@ ROWS_PER_IMG = {"conv_stem": 6400, "conv_a1": 1600, "conv_128": 1600, "conv_256"
 
 
 def _log_records(tl):
-    f = (C.c_int * 7)()
-    name = C.create_string_buffer(96)
+    n = tl.fpt_launch_log_count()
+    f = (C.c_int * (7 * max(n, 1)))()
+    names = C.create_string_buffer(96 * max(n, 1))
+    assert tl.fpt_launch_log_get_all(f, names, 96, n) == n
+    raw = names.raw
     out = []
-    for i in range(tl.fpt_launch_log_count()):
-        assert tl.fpt_launch_log_get(i, f, name, 96) == 0
-        net, prec, side, m_begin, M, ksplit, pe = list(f)
-        tag, _, kern = name.value.decode().rpartition("/")
+    for i in range(n):
+        net, prec, side, m_begin, M, ksplit, pe = f[7 * i:7 * i + 7]
+        tag, _, kern = raw[96 * i:96 * (i + 1)].split(b"\0", 1)[0].decode().rpartition("/")
         out.append(dict(net=("refiner", "scorer")[net], prec=("f16", "bf16", "fp8", "int8")[prec], side=side, m_begin=m_begin, M=M,
                         ksplit=ksplit, pe=pe, tag=tag, kernel=kern))
     return out
@@ -531,8 +551,18 @@ def _logged(tl, fn):
 
 
 def _key(r):
-    """(net, precision, layer tag, kernel, stream, pe fused, split-K)"""
-    return (r["net"], r["prec"], r["tag"], r["kernel"], "side" if r["side"] else "main", r["pe"], r["ksplit"] > 1)
+    """(net, precision, layer tag, kernel, stream, pe fused, split-K slices)"""
+    return (r["net"], r["prec"], r["tag"], r["kernel"], "side" if r["side"] else "main", r["pe"], r["ksplit"])
+
+
+PLAN_REFINER, PLAN_SCORER, PLAN_SCORER_FEATURES = 0, 1, 2    # fpt_plan_forward kinds
+
+
+def _plan(tl, model, kind, N, shared=0):
+    """the launch log of a plan-only call (fpt_plan_forward) at the model's precision: what the real call would launch"""
+    def run():
+        assert tl.fpt_plan_forward(model._h, kind, N, shared) == 0, tl.fp_last_error().decode()
+    return _logged(tl, run)
 
 
 def _boundary_windows(recs, N, NB2):
@@ -606,9 +636,14 @@ def test_batches_past_the_limit_are_refused(tl, model, disc_nets):
 
 
 def test_every_launched_schedule_is_checked_in_float64(tl, model, crops, syn_mesh, scene):
-    """every (network, precision, layer, kernel, stream, pe fused, split-K) a served batch size launches is launched by at least one
-    float64 stage case of this file.  Served: refiner and scorer at N = 1 (Track), 2..8 (fp_track_multi objects), 42 * s for every
-    accepted inplane step s, in f16 and bf16; Register (shared observed crop) at 42 * s in f16."""
+    """every (network, precision, layer, kernel, stream, pe fused, split-K slice count) an accepted batch size launches is launched by
+    at least one float64 stage case of this file.  Accepted: the plan (fpt_plan_forward, test_plan_equals_reality) of the refiner with
+    its own crops and of the scorer at every N in 1..FP_MAX_BATCH, and of the refiner with Register's shared crop at every N in
+    2..42 * FP_MAX_INPLANE_STEPS (a shard of one hypothesis takes its own crop), in f16 and bf16 -- this holds fp_track_multi (1..64
+    objects), every Register shard, fp_refiner_infer / fp_scorer_infer and fp_net_infer; and, as real calls, Track, 2..8 objects, 42 * s
+    for every accepted inplane step s, and Register at 42 * s in f16.  Distinct keys: 127 over the real calls alone (split-K as a
+    boolean; also 127 with the slice count), 180 over the whole accepted space -- the 53 more are the scorer below 42 hypotheses
+    (1..8, 21), conv_256 on conv_deep_kernel from 21 hypotheses and broadcast_b in bf16."""
     big = _inputs(crops, 42 * STEPS_MAX)
     covered = set()
     for prec, N, five in REFINER_CASES:
@@ -639,6 +674,14 @@ def test_every_launched_schedule_is_checked_in_float64(tl, model, crops, syn_mes
             model.set_inplane_steps(6)
     for steps in REGISTER_STEPS + [STEPS_MAX]:
         covered |= {_key(r) for r in register(steps) if r["net"] == "refiner"}   # (its scorer pass is a scorer case's)
+    tl.fpt_model_use_graphs(model._h, 0)
+    try:
+        for begin, count, prec in SHARD_CASES:      # (both passes of a shard are checked)
+            _set_prec(model, prec)
+            covered |= {_key(r) for r in _logged(tl, lambda: _shard_begin(model, scene, syn_mesh, begin, count))}
+    finally:
+        _set_prec(model, FP_PREC_F16)
+        tl.fpt_model_use_graphs(model._h, 1)
 
     first = {}    # key -> smallest served N (and how) that launches it
     def served(keys, how, N):
@@ -657,10 +700,162 @@ def test_every_launched_schedule_is_checked_in_float64(tl, model, crops, syn_mes
             _set_prec(model, FP_PREC_F16)
     for s in range(1, STEPS_MAX + 1):
         served({_key(r) for r in register(s)}, "Register", 42 * s)
+    n_real, n_bool = len(first), len({k[:-1] + (k[-1] > 1,) for k in first})
+    for prec in (FP_PREC_F16, FP_PREC_BF16):      # the plan over everything accepted (largest N first: the buffers grow once)
+        _set_prec(model, prec)
+        try:
+            for N in range(N_MAX, 0, -1):
+                served({_key(r) for r in _plan(tl, model, PLAN_REFINER, N)}, "plan refiner", N)
+                served({_key(r) for r in _plan(tl, model, PLAN_SCORER, N)}, "plan scorer", N)
+                if 1 < N <= 42 * STEPS_MAX:
+                    served({_key(r) for r in _plan(tl, model, PLAN_REFINER, N, 1)}, "plan refiner shared-b", N)
+        finally:
+            _set_prec(model, FP_PREC_F16)
+    print(f"\ndistinct launch keys: {n_bool} over the real calls with split-K as a boolean, {n_real} with the slice count, "
+          f"{len(first)} over the accepted space")
     print("\n" + "\n".join(f"{'covered' if k in covered else 'MISSING'}  first at N={n:<5} ({how}): {k}"
                            for k, (n, how) in sorted(first.items(), key=lambda kv: (kv[1][0], kv[0]))))
     missing = sorted((n, how, k) for k, (n, how) in first.items() if k not in covered)
     assert not missing, "schedules without a float64 stage case:\n" + "\n".join(f"  {k}: first at N = {n} ({how})" for n, how, k in missing)
+
+
+PLAN_SIZES = [1, 2, 5, 9, 14, 15, 28, 29, 32, 33, 64, 127, 252, 253, 1009, 2377]
+FIELDS = ("net", "prec", "tag", "kernel", "m_begin", "M", "ksplit", "pe", "side")
+
+
+def _same_launches(what, real, plan):
+    real, plan = [tuple(r[f] for f in FIELDS) for r in real], [tuple(r[f] for f in FIELDS) for r in plan]
+    assert real == plan, f"{what}: the plan differs from the real call\n" + "\n".join(
+        f"  {i}: real {a}  plan {b}" for i, (a, b) in enumerate(zip(real + [None] * len(plan), plan + [None] * len(real))) if a != b)
+
+
+def _shard_begin(model, scene, mesh, begin, count):
+    """fp_register_shard_begin over hypotheses [begin, begin + count) of the model's grid (refine_itr 1)"""
+    rgb, depth, mask = model._frame(scene.rgb, scene.depth, scene.mask)
+    feat, poses = C.c_void_p(), C.c_void_p()
+    model._must(model._L.fp_register_shard_begin(model._h, _p(rgb), _p(depth), _p(mask), FP_HOST, depth.shape[0], depth.shape[1],
+                                                 mesh.name.encode(), 1, begin, count, C.byref(feat), C.byref(poses)))
+    model.synchronize()
+
+
+def _shard_plan(tl, model, count):
+    """what a shard of `count` hypotheses launches: the refiner on the shared crop (own crop for one hypothesis), the scorer trunk"""
+    return _plan(tl, model, PLAN_REFINER, count, 1 if count > 1 else 0) + _plan(tl, model, PLAN_SCORER_FEATURES, count)
+
+
+def test_plan_equals_reality(tl, model, crops, disc_nets, syn_mesh, scene):
+    """fpt_plan_forward records, field for field, what the real call launches: refiner (own crops, Register's shared crop) and scorer
+    at every PLAN_SIZES N in f16 and bf16, and the served entry points fp_track_multi, fp_register_shard_begin and fp_net_infer"""
+    da, db = (torch.from_numpy(x).to(DEV) for x in crops)
+    t, r, sc = (np.zeros((N_MAX, 3), np.float32), np.zeros((N_MAX, 3), np.float32), np.zeros(N_MAX, np.float32))
+    L = model._L
+    model.set_inplane_steps(STEPS_MAX)
+    tl.fpt_model_use_graphs(model._h, 0)
+    try:
+        for prec in (FP_PREC_F16, FP_PREC_BF16):
+            _set_prec(model, prec)
+            for N in PLAN_SIZES:
+                i = torch.arange(N, device=DEV) % len(da)
+                a, b = da[i].contiguous(), db[i].contiguous()
+                torch.cuda.synchronize()
+                pa, pb = C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr())
+                real = _logged(tl, lambda: model._must(L.fp_refiner_infer(model._h, pa, pb, FP_DEVICE, N, _p(t), _p(r))))
+                _same_launches(f"refiner prec={prec} N={N}", real, _plan(tl, model, PLAN_REFINER, N))
+                real = _logged(tl, lambda: model._must(L.fp_scorer_infer(model._h, pa, pb, FP_DEVICE, N, _p(sc))))
+                _same_launches(f"scorer prec={prec} N={N}", real, _plan(tl, model, PLAN_SCORER, N))
+                del a, b
+                if N <= 42 * STEPS_MAX:
+                    real = _logged(tl, lambda: _shard_begin(model, scene, syn_mesh, 0, N))
+                    _same_launches(f"shard [0:{N}] prec={prec}", real, _shard_plan(tl, model, N))
+            _set_prec(model, FP_PREC_F16)
+        model.set_inplane_steps(6)
+        for begin, count in ((0, 32), (224, 28), (0, 1)):       # the 8-GPU shards of N = 252, a shard of one hypothesis
+            real = _logged(tl, lambda: _shard_begin(model, scene, syn_mesh, begin, count))
+            _same_launches(f"fp_register_shard_begin({begin}, {count})", real, _shard_plan(tl, model, count))
+    finally:
+        _set_prec(model, FP_PREC_F16)
+        tl.fpt_model_use_graphs(model._h, 1)
+        model.set_inplane_steps(6)
+    del da, db
+    # fp_track_multi: K objects of two meshes in alternating groups = one refiner batch of K with their own crops
+    ma, mb = syn.make_mesh(name="a"), syn.make_mesh(textured=False, name="b", subdiv=3)
+    with mock.patch.object(_lib, "lib", _typed_test_lib):
+        m2 = FoundationPose([ma, mb], syn.intrinsics(), disc_nets[0], disc_nets[1])
+    try:
+        tl.fpt_model_use_graphs(m2._h, 0)
+        base = syn.perturb_pose(scene.gt_pose)
+        for K in (9, 33, 64):
+            hyps = np.stack([base] * K)
+            hyps[:, 0, 3] += 0.001 * np.arange(K, dtype=np.float32)
+            names = [("a", "b")[(k // 3) % 2] for k in range(K)]
+            ok = []
+            real = _logged(tl, lambda: ok.append(m2.track_multi(scene.rgb, scene.depth, hyps, names)[0]))
+            assert ok == [True], m2.last_error
+            _same_launches(f"fp_track_multi K={K}", real, _plan(tl, model, PLAN_REFINER, K))
+    finally:
+        m2.close()
+    # fp_net_infer (the InferCore shim, f16) on its device blobs
+    for path, scorer in ((disc_nets[0], 0), (disc_nets[1], 1)):
+        n = tl.fp_net_create(path.encode(), scorer, 64)
+        assert n, tl.fp_last_error().decode()
+        try:
+            for blob in (b"render_input", b"transf_input"):
+                assert tl.fp_net_blob(n, blob, FP_DEVICE)
+            for batch in (7, 40):
+                real = _logged(tl, lambda: tl.fp_net_infer(n, batch, FP_DEVICE, FP_DEVICE, FP_DEVICE) == 0 or pytest.fail(tl.fp_last_error().decode()))
+                _same_launches(f"fp_net_infer scorer={scorer} batch={batch}", real, _plan(tl, model, PLAN_SCORER if scorer else PLAN_REFINER, batch))
+        finally:
+            tl.fp_net_destroy(n)
+
+
+def _register_shard_stages(tl, model, disc_nets, syn_mesh, scene, begin, count, prec):
+    """one Register shard (fp_register_shard_begin over [begin, begin + count) of the 252 hypotheses): its refiner pass on the shared crop
+    (NB2 = count + 1) and its scorer trunk, stage by stage in float64 -- and the shard's nn_in is, bit for bit, rows [begin, begin + count)
+    of the unsharded Register's nn_in plus the shared crop"""
+    dt = LR.BF16 if prec == FP_PREC_BF16 else LR.F16
+    c = count
+    case = f"shard {_dt_name(dt)} [{begin}:{begin + c}]"
+    model.set_inplane_steps(6)
+    _set_prec(model, prec)
+    tl.fpt_model_use_graphs(model._h, 0)
+    try:
+        N = model.num_hypotheses
+        full = torch.empty((N + 1, 84, 84, 32), dtype=LR.TORCH_DT[dt], device=DEV)
+        tl.fpt_tap_clear()
+        assert tl.fpt_tap_arm(0, TAP_NN_IN, C.c_void_p(full.data_ptr()), full.numel() * full.element_size()) == 0
+        torch.cuda.synchronize()
+        _shard_begin(model, scene, syn_mesh, 0, N)
+        torch.cuda.synchronize()
+        assert tl.fpt_tap_bytes(0, TAP_NN_IN) == full.numel() * full.element_size()
+        tl.fpt_tap_clear()
+        T, _ = _tapped(tl, 0, c, c + 1, False, dt, lambda: _shard_begin(model, scene, syn_mesh, begin, c))
+        exp = torch.cat([full[begin:begin + c], full[N:N + 1]])
+        assert torch.equal(_bitwise(T.raw(TAP_NN_IN)), _bitwise(exp)), f"{case}: nn_in is not the unsharded Register's"
+        del full, exp
+        w = _weights(disc_nets[0], dt)
+        check_trunk(case + " refiner", w, T, c, 1, dt)
+        check_heads(case + " refiner", w, T, c, dt, False)
+        del T
+        T, _ = _tapped(tl, 1, c, 2 * c, False, dt, lambda: _shard_begin(model, scene, syn_mesh, begin, c), head=False)
+        w = _weights(disc_nets[1], dt)
+        check_trunk(case + " scorer", w, T, c, c, dt)
+        check_scorer(case + " scorer", w, T, c, dt, head=False)
+        del T
+    finally:
+        tl.fpt_model_use_graphs(model._h, 1)
+        _set_prec(model, FP_PREC_F16)
+    _flush()
+
+
+@pytest.mark.parametrize("begin,count,prec", SHARD_CASES)
+def test_register_shard_stages_match_float64(tl, model, disc_nets, syn_mesh, scene, begin, count, prec):
+    """the 8-GPU layout of the N = 252 headline: the first shard [0:32] and the ragged last one [224:252]; a shard of two in bf16"""
+    _register_shard_stages(tl, model, disc_nets, syn_mesh, scene, begin, count, prec)
+
+
+# trunk layer tag -> the names check_trunk gives its stages
+SPLIT_STAGES = {"conv_stem": ["stem"], "conv_a1": ["act1"], "conv_128": [f"act{i}" for i in range(2, 6)],
+                "conv_256": [f"act{i}" for i in range(6, 10)], "conv_b2": ["act10"], "conv_512": [f"act{i}" for i in range(11, 15)]}
 
 
 def _fails(fn):
@@ -681,7 +876,11 @@ def test_ablations_fail_the_named_stage(tl, model, crops, disc_nets):
         ref_t, ref_r = net(torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV))
     ref_t, ref_r = ref_t.cpu().numpy(), ref_r.cpu().numpy()
     notes = []
-    for switch, val, N in (("fpt_set_qkv_ablate", 1, 252), ("fpt_set_conv_ablate", 16, 252)):
+    # split-K: the trunk layers the plan of N = 8 splits (and with how many slices); dropping the last slice must fail exactly those
+    split = {(r["tag"], r["ksplit"]) for r in _plan(tl, model, PLAN_REFINER, 8) if r["ksplit"] > 1 and r["tag"] in SPLIT_STAGES}
+    assert split, "no split-K trunk layer at N = 8"
+    split_stages = [st for tag, _ in split for st in SPLIT_STAGES[tag]]
+    for switch, val, N in (("fpt_set_qkv_ablate", 1, 252), ("fpt_set_conv_ablate", 16, 252), ("fpt_set_splitk_ablate", 1, 8)):
         outs = {}
         try:
             getattr(tl, switch)(val)
@@ -692,6 +891,15 @@ def test_ablations_fail_the_named_stage(tl, model, crops, disc_nets):
         if switch == "fpt_set_qkv_ablate":
             msgs = _fails(lambda: check_heads(case, w, T, N, LR.F16, False))
             hit = [m for m in msgs if "qkv" in m]
+        elif switch == "fpt_set_splitk_ablate":
+            msgs = _fails(lambda: check_trunk(case, w, T, N, N, LR.F16))
+            named = [m for m in msgs if any(f"stage {st} " in m or f"stage {st}:" in m for st in split_stages)]
+            hit = named
+            assert named == msgs, (split, msgs)                                        # only the split layers fail ...
+            T0, _ = _tapped(tl, 0, N, 2 * N, False, LR.F16, lambda: model.refiner_infer(a[:N], b[:N]))
+            clean = _fails(lambda: check_trunk(case + " off", w, T0, N, N, LR.F16))
+            assert not clean, clean                                                    # ... and pass without the switch
+            del T0
         else:
             msgs = _fails(lambda: check_trunk(case, w, T, N, N, LR.F16))
             hit = [m for m in msgs if any(f"act{i} " in m for i in range(2, 10))]     # a 40x40 convolution
