@@ -16,7 +16,11 @@ carries `host_frame` (the reference's calling convention: host frames, H2D insid
            is a localhost socket (foundationpose_cpp_amd/rendezvous.py).  Fewer devices than ranks is an error, never a smaller run.  The line also carries `n1008` = BASELINE configs[3] (1008
            hypotheses sharded the same way).  `--weak` keeps 252 hypotheses PER GPU (252*N in total) instead; `--hyps M` picks
            any total.
-  Extra legs of the default N = 1 run (outside the headline's timed region, a few steps each, every one with its own roofline):
+
+A plain run does only what the headline needs: set up, warm up, time the --steps steps, write --dump-outputs, print the JSON line.
+`--full` adds everything else, all of it after the headline's timed region: the per-kernel profile step behind `roofline` and `stage_ms`,
+the MFMA micro-benchmark, the CPU baseline, `n1008` (N > 1 as well) and these extra legs of the N = 1 run (a few steps each, every one
+with its own roofline):
            `host_frame`, `track` (incl. pipelined / batched serving), `track_bf16` (configs[1]), `track_int8`, and configs[4] at 1280x720:
            `f16_720p`, `f16_720p_untextured` (the configs[4] path: f16) and the EXPERIMENTAL 8-bit legs `int8_720p`,
            `int8_720p_untextured` (8-bit trunk convolutions calibrated on 16 OTHER frames, measured on a held-out one, DISCRIMINATING synthetic
@@ -26,7 +30,7 @@ carries `host_frame` (the reference's calling convention: host frames, H2D insid
 `--dump-outputs DIR` writes what the headline's last timed step handed its caller as DIR/<name>.npy: `pose` (4x4 row-major float32)
 and, for N > 1, `winner` (the hypothesis index, float64).  The inputs are seeded, so two builds can be compared output for output.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0; with `--full` it carries two extra objects:
   roofline     -- dominant kernel (the conv/linear implicit-GEMM kernel with the largest share of the step, MFMA-bound):
                   algorithmic FLOPs of its launches in one step / their HIP-event durations on the library's stream
                   (fp_profile_*), vs the 2.5 PFLOP/s dense fp16 MFMA peak (and vs the rate a register-resident MFMA
@@ -343,13 +347,15 @@ def rank_main(args, world):
         raise SystemExit(f"rank {rank}: the ranks disagree on the winner / pose ({winners}): the redundant finish must be bit-identical")
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, pose=syn.from_colmajor(out_pose), winner=np.array([idx.value], np.float64))
-    model.profile(True)
-    model.profile_reset()
-    step()
-    prof = model.profile_report()
-    model.profile(False)
+    prof = None
+    if args.full:                 # per-kernel-family event timing of ONE extra step
+        model.profile(True)
+        model.profile_reset()
+        step()
+        prof = model.profile_report()
+        model.profile(False)
     n1008 = None
-    if not args.no_extras and args.hyps == 0 and not args.weak:      # BASELINE configs[3]: 1008 hypotheses sharded the same way
+    if args.full and not args.no_extras and args.hyps == 0 and not args.weak:      # BASELINE configs[3]: 1008 hypotheses sharded the same way
         model.set_inplane_steps(24)
         k8 = max(3, args.steps // 4)
         t8 = client.all_max(timed(step, k8, 1))
@@ -359,7 +365,6 @@ def rank_main(args, world):
                  "workload": f"BASELINE configs[3]: Register N=1008 sharded, {-(-1008 // world)}/GPU, {Wd}x{H}, refine_itr=1, {args.dtype}"}
     res = None
     if rank == 0:
-        roof, stages, dom, dv = analyse_profile(prof, args.dtype, min(per, n_total), 2)
         res = {
             "metric": f"pose-hypotheses/sec (Register N={n_total}, {Wd}x{H})", "value": round(n_total * args.steps / dt, 2), "unit": "hypotheses/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
@@ -373,8 +378,11 @@ def rank_main(args, world):
                                      "control plane: localhost socket rendezvous (ncclUniqueId, barriers, max over ranks), no torch in the ranks",
                        "baseline": "reference README.md:37-41 Register 2.8 fps x 252 = 705.6 hyp/s on RTX 4060 (TensorRT fp16)"},
             "rccl_ranks_seen": int(seen.value), "per_rank_ms": [round(x, 3) for x in per_rank_ms], "winner": winners[0],
-            "roofline": dict(roof, what=f"rank 0's slice of {min(per, n_total)} hypotheses"), "stage_ms": stages,
         }
+        if prof is not None:
+            roof, stages, dom, dv = analyse_profile(prof, args.dtype, min(per, n_total), 2)
+            res["roofline"] = dict(roof, what=f"rank 0's slice of {min(per, n_total)} hypotheses")
+            res["stage_ms"] = stages
         if n1008 is not None:
             res["n1008"] = n1008
     model.close()
@@ -396,15 +404,20 @@ def main():
                     help="network precision: f16 = the reference's TensorRT --fp16 engines (headline); bf16 = BASELINE configs[1]; "
                          "fp8 / int8 = 8-bit trunk convolutions (e4m3 / integers), BASELINE configs[4] (use with --width 1280 --height 720)")
     ap.add_argument("--untextured", action="store_true", help="the reference's 2x2 grey fallback texture (configs[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-mfma-peak", action="store_true", help="skip the MFMA micro-benchmark (profiling runs)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-frame and Track legs (profiling runs)")
-    ap.add_argument("--fp8-legs", action="store_true", help="also run the two FP8 e4m3 720p legs (experimental: the precision fails the configs[4] parity bar)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: per-kernel profile and roofline, MFMA micro-benchmark, CPU baseline, "
+                         "the extra legs (host frames, Track, n1008, the other BASELINE configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-mfma-peak", action="store_true", help="with --full: skip the MFMA micro-benchmark (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the host-frame, Track and n1008 legs (profiling runs)")
+    ap.add_argument("--fp8-legs", action="store_true", help="with --full: also run the two FP8 e4m3 720p legs (experimental: the precision fails the configs[4] parity bar)")
     ap.add_argument("--track", action="store_true", help="measure Track fps (N=1 hypothesis) as the headline instead of Register")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline's last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.fp8_legs and not args.full:
+        ap.error("--fp8-legs adds legs to a --full run")
 
     # ---- who am I?  (contract: `python bench.py --gpus N` alone, or one rank of `python -m torch.distributed.run ... bench.py --gpus N`)
     world_env = os.environ.get("WORLD_SIZE")
@@ -490,17 +503,19 @@ def main():
     if args.dump_outputs:         # now: every later leg reuses out_pose
         dump_outputs(args.dump_outputs, pose=syn.from_colmajor(out_pose))
 
+    # ---- --full from here on: nothing below feeds the headline
     # per-kernel-family event timing of ONE extra step (outside the timed region)
-    model.profile(True)
-    model.profile_reset()
-    step()
-    prof = model.profile_report()
-    model.profile(False)
+    if args.full:
+        model.profile(True)
+        model.profile_reset()
+        step()
+        prof = model.profile_report()
+        model.profile(False)
 
     # ---- extra legs on one GPU (outside the headline's timed region): the reference's calling convention (host frames,
     # H2D inside the call: speed_register / speed_track, simple_tests/src/test_foundationpose.cpp:118-127,145-154) and Track
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         def register_host():
             ok, _ = model.Register(scene.rgb, scene.depth, scene.mask, mesh.name)
             assert ok, model.last_error
@@ -579,7 +594,7 @@ def main():
 
     # ---- BASELINE configs[3]: 1008 hypotheses (42 views x 24 in-plane steps) sharded exactly like the headline; every rank takes part
     n1008 = None
-    if not args.track and not args.no_extras and args.hyps == 0 and not args.weak:
+    if args.full and not args.track and not args.no_extras and args.hyps == 0 and not args.weak:
         model.set_inplane_steps(24)
 
         k8 = max(3, args.steps // 4)
@@ -589,9 +604,9 @@ def main():
                  "ms_per_step": round(t8 / k8 * 1e3, 3), "steps": k8, "n_gpus": world, "scaling": "strong",
                  "workload": f"BASELINE configs[3]: Register N=1008 sharded, {-(-1008 // world)}/GPU, {Wd}x{H}, refine_itr=1, f16"}
 
-    # ---- the other BASELINE configs as short legs of the one default run (one GPU): configs[4] FP8 1280x720 textured + untextured,
+    # ---- the other BASELINE configs as short legs of the one --full run (one GPU): configs[4] FP8 1280x720 textured + untextured,
     # configs[1] bf16 Track -- each on its own model / precision, each with its own roofline
-    if not args.no_extras and not args.track and args.dtype == "f16" and (Wd, H) == (640, 480):
+    if args.full and not args.no_extras and not args.track and args.dtype == "f16" and (Wd, H) == (640, 480):
         # The 8-bit legs run the DISCRIMINATING synthetic weight set (tests/golden/disc_calib_seed9.npz applied to the seed-9 draws, numpy
         # only): under the headline's plain seed-7 draws the 252 scores agree to 3e-5 and "winner matches" says nothing.  Same
         # architecture, same FLOPs -- the timing does not depend on the weight values.
@@ -746,9 +761,10 @@ def main():
     if n1008 is not None:
         extras["n1008"] = n1008
 
-    if rank == 0:
-        units = 1 if args.track else n_total
-        ms = dt / args.steps * 1e3
+    units = 1 if args.track else n_total
+    ms = dt / args.steps * 1e3
+    roofline, stages = None, None
+    if args.full:
         roof, stages, dom, dv = analyse_profile(prof, args.dtype, n_total // world if world > 1 else n_total, 1 if args.track else 2)
         traffic, traffic_src = None, None
         pmc_path = os.path.join(ROOT, "profiles", PMC_FILE)
@@ -842,46 +858,46 @@ def main():
                                                "clock / 2.4 GHz: the package's power limit, not the schedule, is the largest factor (DESIGN.md section 8)"}
             except Exception as e:   # evidence only: never fail the bench over it
                 clock_probe = {"error": str(e)}
-        res = {
-            "metric": "Track fps (N=1)" if args.track else f"pose-hypotheses/sec (Register N={n_total}, {Wd}x{H})",
-            "value": round(units * args.steps / dt, 2),
-            "unit": "frames/s" if args.track else "hypotheses/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
-            "higher_is_better": True,
-            "scaling": "weak" if args.weak and args.hyps == 0 else "strong",
-            # the reference's number is timed around the host-frame call (speed_register): compare like with like when that leg ran
-            "vs_baseline": None if args.track else round((extras["host_frame"]["value"] if "host_frame" in extras and n_total == 252
-                                                          else units * args.steps / dt) / BASELINE_HYP_S, 3),
-            "dtype": args.dtype, "data": "synthetic",
-            "config": {
-                "workload": (f"Track N=1 {Wd}x{H}" if args.track else
-                             f"Register N={n_total} hypotheses" + (f" sharded, {-(-n_total // world)}/GPU," if world > 1 else ",") +
-                             f" {Wd}x{H} refine_itr=1, frame resident in HBM"),
-                "mesh": f"synthetic ellipsoid V=2562 F=5120, {'2x2 grey (untextured)' if args.untextured else '512x512 texture'}",
-                "weights": "synthetic (seed 7)",
-                "precision": PRECISION_TEXT[args.dtype],
-                "calibration": "16 frames of OTHER synthetic scenes (fp_calibrate_begin / _add_frame / _finish); the bench frame is not among them" if args.dtype in Q8 else None,
-                "parallelism": f"hyp-shard x{world}" if world > 1 else "single GPU",
-                "collective": "none",
-                "baseline": "reference README.md:37-41 Register 2.8 fps x 252 = 705.6 hyp/s on RTX 4060 (TensorRT fp16), timed around the host-frame "
-                            "call; vs_baseline = host_frame.value / 705.6 when that leg ran (N=1 default run), else value / 705.6",
-            },
-            "roofline": dict(roof, **{
-                "peak_measured": measured_peak, "peak_measured_clock_mhz": measured_mhz, "peak_measured_detail": peak_detail,
-                "peak_measured_what": "register-resident f16 MFMA micro-benchmark on this box (fp8 MFMAs: 2x)",
-                "frac_of_measured": round(roof["achieved"] / (measured_peak * (2 if dv.get("fp8") else 1)), 4) if measured_peak else None,
-                "clock_probe": clock_probe,
-                "recomputed_from_profiles": recomputed,
-                "traffic": traffic, "traffic_source": traffic_src,
-                "traffic_kind": "committed rocprofv3 PMC passes of the same command (profiles/), NOT measured by this run" if traffic else None,
-            }),
-            "stage_ms": stages,
-        }
-        res.update(extras)
-        if not args.no_cpu_baseline and world == 1:
-            res["cpu_baseline"] = cpu_baseline(mesh, scene, states)
-    else:
-        res = None
+        roofline = dict(roof, **{
+            "peak_measured": measured_peak, "peak_measured_clock_mhz": measured_mhz, "peak_measured_detail": peak_detail,
+            "peak_measured_what": "register-resident f16 MFMA micro-benchmark on this box (fp8 MFMAs: 2x)",
+            "frac_of_measured": round(roof["achieved"] / (measured_peak * (2 if dv.get("fp8") else 1)), 4) if measured_peak else None,
+            "clock_probe": clock_probe,
+            "recomputed_from_profiles": recomputed,
+            "traffic": traffic, "traffic_source": traffic_src,
+            "traffic_kind": "committed rocprofv3 PMC passes of the same command (profiles/), NOT measured by this run" if traffic else None,
+        })
+    res = {
+        "metric": "Track fps (N=1)" if args.track else f"pose-hypotheses/sec (Register N={n_total}, {Wd}x{H})",
+        "value": round(units * args.steps / dt, 2),
+        "unit": "frames/s" if args.track else "hypotheses/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
+        "higher_is_better": True,
+        "scaling": "weak" if args.weak and args.hyps == 0 else "strong",
+        # the reference's number is timed around the host-frame call (speed_register): compare like with like when that leg ran
+        "vs_baseline": None if args.track else round((extras["host_frame"]["value"] if "host_frame" in extras and n_total == 252
+                                                      else units * args.steps / dt) / BASELINE_HYP_S, 3),
+        "dtype": args.dtype, "data": "synthetic",
+        "config": {
+            "workload": (f"Track N=1 {Wd}x{H}" if args.track else
+                         f"Register N={n_total} hypotheses" + (f" sharded, {-(-n_total // world)}/GPU," if world > 1 else ",") +
+                         f" {Wd}x{H} refine_itr=1, frame resident in HBM"),
+            "mesh": f"synthetic ellipsoid V=2562 F=5120, {'2x2 grey (untextured)' if args.untextured else '512x512 texture'}",
+            "weights": "synthetic (seed 7)",
+            "precision": PRECISION_TEXT[args.dtype],
+            "calibration": "16 frames of OTHER synthetic scenes (fp_calibrate_begin / _add_frame / _finish); the bench frame is not among them" if args.dtype in Q8 else None,
+            "parallelism": f"hyp-shard x{world}" if world > 1 else "single GPU",
+            "collective": "none",
+            "baseline": "reference README.md:37-41 Register 2.8 fps x 252 = 705.6 hyp/s on RTX 4060 (TensorRT fp16), timed around the host-frame "
+                        "call; vs_baseline = host_frame.value / 705.6 when that leg ran (N=1 --full run), else value / 705.6",
+        },
+    }
+    if roofline is not None:
+        res["roofline"] = roofline
+        res["stage_ms"] = stages
+    res.update(extras)
+    if args.full and not args.no_cpu_baseline and world == 1:
+        res["cpu_baseline"] = cpu_baseline(mesh, scene, states)
     model.close()
     # RCCL prints a version banner through C stdio (flushed only at exit when stdout is a pipe): every rank pushes its buffered
     # output out, THEN rank 0 prints, so that the JSON line is the last line of the job's stdout
@@ -890,8 +906,7 @@ def main():
         C.CDLL(None).fflush(None)
     except OSError:
         pass
-    if res is not None:
-        print(json.dumps(res), flush=True)
+    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":

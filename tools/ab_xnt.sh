@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B build of the product library WITH the non-temporal LDS-DMA policy on the halo kernels' input tiles (FP_X_NT=1; the product
 # default is 0) -> tools/_bin/libfp_xnt.so;
-# run:  FP_LIB_PATH=tools/_bin/libfp_xnt.so python bench.py --no-extras --no-cpu-baseline
+# run:  FP_LIB_PATH=tools/_bin/libfp_xnt.so python bench.py --full --no-extras --no-cpu-baseline
 set -e
 cd "$(dirname "$0")/../foundationpose_cpp_amd/csrc"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -Wno-unused-function -I../../include"
