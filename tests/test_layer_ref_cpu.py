@@ -10,15 +10,7 @@ import torch
 from foundationpose_cpp_amd import weights as W
 from oracle import nets_torch as NT
 import layer_ref as LR
-
-
-def nn_in_from_blobs(a, b):
-    """the device's network input: [2N, 84, 84, 32] = space-to-depth 2x2 of [2N, 160, 160, 8] (6 channels + 2 zero) with a border of 2"""
-    x = np.concatenate([a, b], 0)
-    x8 = np.zeros(x.shape[:3] + (8,), np.float64)
-    x8[..., :6] = x
-    s2d = x8.reshape(-1, 80, 2, 80, 2, 8).transpose(0, 1, 3, 2, 4, 5).reshape(-1, 80, 80, 32)
-    return torch.from_numpy(np.pad(s2d, ((0, 0), (2, 2), (2, 2), (0, 0))))
+from nn_in_ref import nn_in_from_blobs      # the layout of the device's network input (tests/test_nn_in_ref_cpu.py holds it to the address formula)
 
 
 @pytest.fixture(scope="module")
