@@ -8,8 +8,8 @@
 // Source layout [r4]: one translation unit (kernel templates must be visible where they are launched), four textual parts --
 //   fp_nn_conv_kernels.inc       the convolution / Linear schedules        fp_nn_attention_kernels.inc   attention
 //   fp_nn_small_kernels.inc      LayerNorm, token mean, small Linear ...   fp_nn_test_hooks.inc          fpt_* hooks (test build only)
-// and this file: element types and helpers, weights (loading, layouts, 8-bit quantisation), scratch, schedule selection and launch
-// (run_conv_dt), the two forward passes.
+// and this file: element types and helpers, weights (loading, layouts, 8-bit quantisation), scratch, the convolution / Linear schedule
+// (plan_conv: pure host arithmetic, which kernels run a layer over which rows; run_conv: executes the plan's steps), the two forward passes.
 //
 // Kernels (DESIGN.md section 4.2 has the why and the measurements)
 //   All convolution / Linear schedules are the same contraction D^T[channel][pixel] = W * X^T on
@@ -32,6 +32,7 @@
 //                               weights global -> registers from a copy in MFMA-fragment order, pixels through a per-wave LDS-DMA
 //                               ring -- both in the one address shape the vector L1 serves at full rate (tools/bench_tcp.hip).
 //     conv_pp / conv_smallm kernels: earlier schedules kept behind fpt_set_conv_variant / fpt_set_smallm for A/B.
+//     Which of them runs where is plan_conv's decision alone; fpt_plan_conv asks it without a GPU (tests/test_conv_plan_cpu.py).
 //   Weight layouts [r3]: besides the row-major [Cout][K] copy every layer carries the copies its schedules stream from -- fragment
 //   order (conv_smallx), LDS-stage order for gemm_k32 / conv_halo / conv_halo8 / conv_big_pp / conv_deep + conv_pp (pack_stage_w,
 //   pack_stage_w128): a wave's 2-4 LDS-DMA pieces of a stage are ONE contiguous run, so one address and one M0 serve them (the
@@ -582,15 +583,6 @@ static bool upload_layouts(Net *net, const std::vector<unsigned char> &elems, in
 // the running sums r_j = sum_k d_k m_j[c(k)] stay near zero for EVERY frame j: the mean error cancels by construction, also for
 // scenes whose channel means are (near) combinations of the calibration frames'.  Weights further from .5 round to nearest, which
 // keeps the per-pixel (de-meaned) error where it was.
-#ifdef FP_TEST_HOOKS
-// [r5] A/B (fpt_set_rem_fork): the left-over rows of conv_512 / conv_b2 on a side stream next to the 256x256 rounds.  OFF: measured
-// SLOWER (tools/ab_wall.py fpt_set_rem_fork 0 1 0 1: Register 10.85 -> 11.20 ms) -- a deep-ring workgroup needs a whole CU (147 KB of
-// LDS), so it waits for a 256x256 tile to finish, then holds that CU out of the next round: the rounds lose their lock-step and end in
-// a tail longer than the 35 us the lone launch took.
-static int g_rem_fork = 0;
-#else
-static constexpr int g_rem_fork = 0;
-#endif
 #ifdef FP_TEST_HOOKS
 static float g_q8_headroom = 1.25f;   // INT8 activation scale = |max| * headroom / 255 (tools/q8_multi.py --headroom)
 // imgbias: the per-image first-order compensation (q8_img_bias_kernel); wclip / efr: the row-step search / rounding form of quantise_q8
@@ -1156,14 +1148,9 @@ struct NNScratch {
   // threads never share it
   float *splitk = nullptr;
   size_t splitk_cap = 0;
-  hipStream_t side = nullptr;                       // (Ctx::s2)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int *img_sum = nullptr;      // INT8 networks: [2 * cap][512] per-image channel sums (integer atomics; zero between uses) ...
   float *img_bias = nullptr;   // ... and the per-image bias made from them (q8_img_*_kernel)
   ~NNScratch() {
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (side) (void)hipStreamDestroy(side);
     if (img_sum) (void)hipFree(img_sum);
     if (img_bias) (void)hipFree(img_bias);
     if (splitk) (void)hipFree(splitk);
@@ -1199,11 +1186,6 @@ void nn_scratch_debug_info(const NNScratch *w, const void **buf, size_t *bytes, 
 }
 
 static int ensure_scratch(NNScratch *ws, int N, hipStream_t s) {
-  if (!ws->side && g_rem_fork) {   // (first call of a model is eager, never inside a capture)
-    FP_HIP_OK(hipStreamCreateWithFlags(&ws->side, hipStreamNonBlocking));
-    FP_HIP_OK(hipEventCreateWithFlags(&ws->ev_fork, hipEventDisableTiming));
-    FP_HIP_OK(hipEventCreateWithFlags(&ws->ev_join, hipEventDisableTiming));
-  }
   if (N <= ws->cap) return 0;
   if (ws->buf) (void)hipFree(ws->buf);
   if (ws->f32) (void)hipFree(ws->f32);
@@ -1252,14 +1234,11 @@ struct Ctx {
   Profiler *prof;
   const Net *net;
   NNScratch *ws = nullptr;  // owner of the split-K slab (null only in the single-threaded test hooks)
-  // [r5] side stream for the left-over rows of a long-K layer (fork before the 256x256 rounds, join behind them): nullptr = off
-  hipStream_t s2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
 
 // A/B and ablation switches exist only in the test build (libfoundationpose_amd_test.so, -DFP_TEST_HOOKS); in the product
-// they are compile-time constants, so the alternative branches and their kernel instantiations are not in the library
-// and nothing can flip a schedule under a running model.
+// they are compile-time constants, so nothing can flip a schedule under a running model.  (A kernel that only a switch reaches is
+// kept out of the product by #ifdef FP_TEST_HOOKS around its launch: a constant condition alone still instantiates it.)
 #ifdef FP_TEST_HOOKS
 #define FP_HOOK static int
 static unsigned long long *g_clk_probe = nullptr;
@@ -1269,44 +1248,281 @@ static NNScratch g_hook_ws;  // split-K slab of the fpt_* test hooks
 static constexpr unsigned long long *g_clk_probe = nullptr;
 #endif
 FP_HOOK g_conv_variant = 0;    // 0 default; 7 force / 8 disable the resident-halo kernels; 3 = 256x128 ping-pong everywhere; 5 = 256x256 rounds without
-                               // the halo kernels; 10..25 = conv_igemm_kernel<128> fragment-read / ablation variants
+                               // the halo kernels
 FP_HOOK g_conv_ablate = 0;     // timing-only ablations (wrong results) of conv_big_pp_kernel / conv_halo_kernel
-FP_HOOK g_rem_kernel = 3;      // rows the full 256x256 rounds of a long-K layer leave over: 3 = conv_deep_kernel<64>, 4 = <128>, 1 = 256x128 ping-pong, 0 = 128x128 2-stage
-FP_HOOK g_rem_small = 1;       // long-K layers too small for one full 256x256 round take the left-over path as a whole
-FP_HOOK g_gemm_kernel = 1;     // Linear layers on gemm_k32_kernel (0 = the 256x256 ping-pong tile + left-overs; 11 / 12 / 14 ablations)
-FP_HOOK g_grouped_heads = 1;   // the refiner's two heads as one launch per layer when N == 1 (Track)
-FP_HOOK g_rem_splitk = 0;      // split-K for left-over rows.  Measured -0.1 ms per Register, but OFF: a row's fp32 summation order would then
-                               // depend on where it falls in the batch, and sharded and unsharded Register must pick the same near-tied winner
-FP_HOOK g_splitk_target = 128; // workgroups a split-K launch aims for (tools/ab_track.py: 96-128 best, 256 is 6 % slower)
-FP_HOOK g_splitk_min_kt = 9;    // layers with fewer 128-byte K-steps never split
-FP_HOOK g_splitk_deep = 1;      // split-K slices of at least 4 K-steps on conv_deep_kernel<128> (0 = conv_igemm_kernel<128>)
-FP_HOOK g_att_skv = 1;          // small attention grids on attention32_skv_kernel (keys split over the waves of a workgroup)
-FP_HOOK g_gemm_deep = 1;         // short-K layers of small problems on conv_deep_kernel<128> instead of the two-stage 128x128 tile
-FP_HOOK g_splitk_mid = 1;        // two split-K slices for long-K layers with 97..128 tiles (batches of ~8 objects)
-FP_HOOK g_small_deep = 18;     // small problems (Track): conv_deep_kernel<64> over ALL K-steps instead of split-K + reduce when K has at most this many 128-byte steps
-FP_HOOK g_smallm_maxkt = 80;   // the small-problem kernel takes layers with fewer 128-byte K-steps than this: every layer of both networks (72 for conv_512); 40 was the limit of its first version
-FP_HOOK g_conv_lds_store = 0;  // conv_big_pp_kernel: epilogue stores staged through LDS (whole 128-byte lines per store instruction).  OFF: measured [r3] conv_512 3.205 -> 3.227 / 3.184 -> 3.180 ms, i.e. nothing -- the 256x256 tile's store burst is not bound by the store shape (unlike gemm_k32_kernel's, -6 %)
-FP_HOOK g_gemm_lds_store = 1;  // gemm_k32_kernel: output rows leave through LDS as whole 256-byte runs instead of 64-byte pieces per store instruction
-FP_HOOK g_smallm_maxt16 = 1024; // ... and with at most this many 16-pixel x 64-channel tiles (the grouped QKV of Track has 1200)
 FP_HOOK g_fuse_pose = 1;       // Track: 1 = both Linear(512,3) heads + RefinePostProcess in one kernel (small_linear2_pose_kernel), 0 = two kernels, 2 = A/B: the token mean in that kernel too (token_mean_pose_kernel, last-arriver; not faster)
-FP_HOOK g_gemm_wpack = 1;      // gemm_k32_kernel streams its weights from the stage-order copy (one address + one M0 per four LDS-DMA pieces)
-FP_HOOK g_deep_wpack = 1;      // conv_deep_kernel streams its weights from the stage-order copy
-FP_HOOK g_big_wpack = 1;       // conv_big_pp_kernel streams its weights from the stage-order copy
-FP_HOOK g_halo_wpack = 1;      // conv_halo_kernel streams its weights from the stage-order copy
-FP_HOOK g_att_tail = 0;        // [r5] A/B, OFF (measured slower: attention 0.555 -> 0.625 ms per Register): the 16-row tail of a 400-token sequence on attention32_skv_kernel instead of a 4th 128-row block
 FP_HOOK g_ln_pmean = 1;        // [r5] Track: LayerNorm 2 + partial token sums in one launch (layernorm_pmean_kernel) instead of layernorm + token_mean
 FP_HOOK g_qkv_ablate = 0;      // timing-only ablations of qkv_tile_kernel (test build, wrong results)
 FP_HOOK g_splitk_ablate = 0;   // test build, wrong results: conv_splitk_reduce_kernel sums all slices but the last (the float64 checks must fail)
 FP_HOOK g_qkv_tile = 1;        // [r5] QKV projections of Register (N > 1) on qkv_tile_kernel (80-token tiles resident in LDS) instead of gemm_k32_kernel
 FP_HOOK g_enc_tail = 1;        // [r5] Register (N > 1): out_proj + LayerNorm 1 + FFN + LayerNorm 2 + token sums of BOTH heads as one launch (enc_tail_kernel) instead of five per head
-FP_HOOK g_halo_wreg = 0;       // [r5] A/B, OFF (conv_256 -3 % in the stage profile, nothing on the wall clock: tools/ab_wall.py, EXPERIMENTS.md): 1 = 3x3 / 40x40 layers with >= 256 input channels on conv_halo_wreg_kernel: weights global -> registers (fragment-order copy), no weight ring, 2 barriers per chunk (2 = every such layer incl. the 128-channel ones, where it measures even)
 FP_HOOK g_i8_stream = 0;       // test build A/B: 1 = INT8 networks with an 8-bit residual stream (run_trunk_i8; faster, but its common-mode error is frame-specific: DESIGN.md section 4.4)
-FP_HOOK g_smallx_pf = 0;       // A/B (test build): prefetch depth of conv_smallx_kernel<2,4> (4 or 2; 0 = the default 3)
-FP_HOOK g_smallm = 1;          // small problems (Track, a few objects) on conv_smallm_kernel: K split over the waves of a workgroup, no split-K slabs / reduce launch
+FP_HOOK g_smallm = 1;          // small problems (Track, a few objects) on conv_smallx_kernel: K split over the waves of a workgroup, no split-K slabs / reduce launch
+                               // (0 = off, 2 = for every size, 3 = its first version, conv_smallm_kernel)
 FP_HOOK g_att_variant = 1;     // 1 = attention32_kernel (8 = without the XCD remap); round-1 kernel: 2 remap + 16-B stores, 3 no XCD remap, 5 remap + 2-B stores, 7 neither
 
+// Thresholds of the convolution schedule (plan_conv).  They were A/B switches until their experiments settled (EXPERIMENTS.md).
+static constexpr int SPLITK_TARGET = 128;   // workgroups a split-K launch aims for (96-128 best, 256 is 6 % slower)
+static constexpr int SPLITK_MIN_KT = 9;     // layers with fewer 128-byte K-steps never split
+static constexpr int SMALL_DEEP_MAXKT = 18; // small problems (Track): conv_deep_kernel<64> over ALL K-steps instead of split-K + reduce when K has at most this many 128-byte steps
+static constexpr int SMALLM_MAXKT = 80;     // the small-problem kernel takes layers with fewer 128-byte K-steps than this: every layer of both networks (72 for conv_512); 40 was the limit of its first version
+static constexpr int SMALLM_MAXT16 = 1024;  // ... and with at most this many 16-pixel x 64-channel tiles (the grouped QKV of Track has 1200)
+// Settled the other way, and therefore not in the schedule: split-K for left-over rows (measured -0.1 ms per Register, but a row's fp32
+// summation order would then depend on where it falls in the batch, and sharded and unsharded Register must pick the same near-tied
+// winner); the left-over rows on a side stream next to the 256x256 rounds (measured SLOWER, Register 10.85 -> 11.20 ms: a deep-ring
+// workgroup needs a whole CU, 147 KB of LDS, so it waits for a 256x256 tile to finish, then holds that CU out of the next round: the
+// rounds lose their lock-step and end in a tail longer than the 35 us the lone launch took); conv_big_pp_kernel's epilogue stores staged
+// through LDS (measured [r3] conv_512 3.205 -> 3.227 / 3.184 -> 3.180 ms, i.e. nothing -- the 256x256 tile's store burst is not bound by
+// the store shape, unlike gemm_k32_kernel's, -6 %); the 16-row tail of a 400-token sequence on attention32_skv_kernel (attention 0.555 ->
+// 0.625 ms per Register); 3x3 / 40x40 weights global -> registers (conv_256 -3 % in the stage profile, nothing on the wall clock).
+
+// =================================================================================================
+// the convolution / Linear schedule
+// =================================================================================================
+// plan_conv decides which kernels run a layer, over which rows, with how many split-K slices and whether the positional table is
+// fused; run_conv executes the steps.  The plan is plain host arithmetic on the problem's shape: it can be asked without a GPU
+// (fpt_plan_conv, tests/test_conv_plan_cpu.py).
+
+enum ConvKernel {
+  CK_SMALLX, CK_SMALLM, CK_STEM_HALO, CK_GEMM_K32, CK_S2_HALO, CK_HALO, CK_HALO8, CK_PP32, CK_BIG_PP, CK_PP, CK_DEEP64, CK_DEEP128,
+  CK_IGEMM128, CK_IGEMM64, CK_SPLITK_REDUCE
+};
+
+struct ConvProblem {
+  int Cin = 0, Cout = 0, KH = 0, KW = 0, stride = 1, pad = 0, algo_K = 0;   // the layer (ConvLayer)
+  bool wfrag = false, wpack = false;   // the layer carries the fragment-order / gemm_k32_kernel's stage-order copy of its weights
+  int NB = 0, H = 0, W = 0, ipad = 0;  // input [NB, H + 2 * ipad, W + 2 * ipad, Cin]
+  int dt = DT_F16, odt = DT_F16;       // element type of the operands / of the output (DT_DUAL_*, DT_QS_* ... included)
+  bool has_res = false;
+  int split_imgs = 0;
+  int grp_rows = 0;                    // rows per weight group (ConvGroup), 0 = none
+  bool post = false;                   // a positional table is offered (ConvParams::post)
+  int conv_variant = 0, conv_ablate = 0, smallm = 1;   // the test build's switches (g_conv_variant, g_conv_ablate, g_smallm)
+};
+
+struct ConvStep {
+  int kernel = 0;               // ConvKernel
+  const char *name = "";        // as the profiler and the launch log name it
+  int mi = 0, ni = 0;           // conv_smallx_kernel / conv_smallm_kernel: <MI, NI>
+  bool post = false;            // the POST instantiation (the reduce: ConvParams::post): the step adds the positional table
+  bool deep = false;            // conv_smallm_kernel: DEEP
+  bool wpack = false;           // gemm_k32_kernel: WPACK
+  int ablate = 0;               // test build: the timing-only ablation instantiated (0 = the real kernel)
+  int m_begin = 0, M = 0;       // output rows [m_begin, M)
+  int ksplit = 1, kt_per = 0;   // split-K slices and 128-byte K-steps per slice
+  unsigned grid = 0;
+  int block = 256, lds = 0;     // threads per workgroup, dynamic LDS bytes
+  double flops = 0, bytes = 0;  // the step's share of the layer (profiler)
+};
+
+struct ConvPlan {
+  static constexpr int MAX_STEPS = 4;   // pp32 rounds -> 256x256 rounds -> ping-pong rounds -> deep-ring left-over; or a split-K launch + its reduce
+  int n = 0;
+  ConvStep step[MAX_STEPS];
+  bool post_fused = false;      // every output row got the positional table (otherwise none did, and the caller adds it)
+};
+
+// output size of a layer on an H x W input
+static void conv_out_hw(int KH, int KW, int stride, int pad, int H, int W, int *OH, int *OW) {
+  *OH = (H + 2 * pad - KH) / stride + 1;
+  *OW = (W + 2 * pad - KW) / stride + 1;
+  if (KH == 4 && pad == 2 && stride == 1) { *OH = H; *OW = W; }  // s2d stem: asymmetric padding (2 before, 1 after)
+}
+
+static int plan_conv(const ConvProblem &q, ConvPlan *plan) {
+  *plan = ConvPlan{};
+  const bool B2 = !is_q8(q.dt);            // 2-byte element type: the 64-byte-row kernels exist
+  const bool SAME = q.dt == q.odt;         // kernels without an ODT parameter write their operand type
+  const bool QOUT = odt_q(q.odt) >= 0;     // an 8-bit tensor is written (alone or next to the f16 stream tensor): no POST instantiation
+  const bool grp = q.grp_rows > 0;
+  int OH, OW;
+  conv_out_hw(q.KH, q.KW, q.stride, q.pad, q.H, q.W, &OH, &OW);
+  const int M = q.NB * OH * OW, Ktot = q.KH * q.KW * q.Cin, Cout = q.Cout;
+  const int cin_b = q.Cin * elem_bytes(q.dt), KT = Ktot * elem_bytes(q.dt) / 128;
+  double flops = 2.0 * (double)M * Cout * (q.algo_K > 0 ? q.algo_K : Ktot);
+  double bytes = ((double)q.NB * q.H * q.W * q.Cin + (double)M * Cout * (q.has_res ? 2 : 1) + (double)Cout * Ktot) * elem_bytes(q.dt);
+  constexpr int LDS_IG128 = 2 * (128 * 128 + 128 * 128), LDS_IG64 = 2 * (128 * 128 + 64 * 128);
+  constexpr int LDS3_128 = 3 * (256 * 128 + 128 * 128);
+  constexpr int LDS_BIG = 2 * (256 * 128 + 256 * 128);
+  constexpr int LDS_HALO40 = ((10 * 42 + 7) / 8) * 1024 + 3 * 128 * 64;
+  constexpr int LDS_HALO8 = ((10 * 42 + 7) / 8) * 1024 + 128 * 128;
+  constexpr int LDS_STEM_HALO = ((11 * 84 + 15) / 16) * 1024 + 3 * 64 * 64;
+  constexpr int LDS_DEEP64 = 6 * (64 + 128) * 128, LDS_DEEP128 = 4 * (128 + 128) * 128;
+  constexpr int LDS_GEMM_K32 = 3 * (128 + 256) * 64;
+  constexpr int LDS_S2_HALO = ((9 * 41 + 7) / 8) * 1024 + 3 * 128 * 64;
+  constexpr int LDS_PP32 = 4 * (512 + 128) * 64;
+  int m_begin = 0, ksplit = 1, kt_per = KT;
+  // a step over rows [m_begin, m_end) that takes the share `frac` of what is left of the layer's flops and bytes
+  bool overflow = false;
+  const auto add = [&](int kernel, const char *name, int m_end, int grid, int block, int lds, double frac = 1.0) -> ConvStep & {
+    overflow = overflow || plan->n == ConvPlan::MAX_STEPS;
+    ConvStep &st = plan->step[overflow ? ConvPlan::MAX_STEPS - 1 : plan->n++];
+    st = ConvStep{};
+    st.kernel = kernel; st.name = name;
+    st.m_begin = m_begin; st.M = m_end; st.ksplit = ksplit; st.kt_per = kt_per;
+    st.grid = (unsigned)grid; st.block = block; st.lds = lds;
+    st.flops = flops * frac; st.bytes = bytes * frac;
+    flops *= (1.0 - frac); bytes *= (1.0 - frac);
+    return st;
+  };
+  const auto finish = [&]() {
+    FP_CHECK(!overflow, "plan_conv: more steps than ConvPlan holds");
+    return 0;
+  };
+
+  // ---- small problems: one launch per layer, the K-steps split over the four waves of a workgroup (conv_smallx_kernel)
+  if (B2 || Cout % 128 == 0) {                            // (FP8 layers all have Cout % 128 == 0: 64-channel tiles only)
+    const int cw = (Cout % 128 == 0) ? 64 : 32;           // channels per workgroup = the block of the host-side row permutation
+    const int t16 = ((M + 15) / 16) * (Cout / cw);
+    // Measured on Track (tools/profile_track.sh, profiles/r03g_track_timeline.txt): 5.6-7.2 us for the layers of up to 18 K-steps, 8.5-9.1
+    // for the 36-step ones, 10.2-10.6 for conv_512 (72 steps; 12.8 + 5.5 us as split-K + reduce).  The first version
+    // (conv_smallm_kernel: both operands global -> registers in MFMA-operand shape, 64 clocks of the vector L1 per instruction) lost on
+    // the long-K layers (21 us); smallm = 3 selects it for A/B (2-byte types), smallm = 2 forces the small-problem kernel for every size.
+    if (q.smallm && q.wfrag && (KT < SMALLM_MAXKT || q.smallm >= 2) && q.conv_variant == 0 && q.conv_ablate == 0 && Cout % cw == 0 &&
+        t16 <= SMALLM_MAXT16 * (64 / cw) && (!grp || q.grp_rows % 32 == 0) && ((Cout / cw) % 8 == 0 || 8 % (Cout / cw) == 0)) {
+      const int t32 = ((M + 31) / 32) * (Cout / cw);
+      const bool two = t32 >= 160;                        // 32-pixel tiles halve the weight stream once they still fill the chip
+      // grid = 8 XCD lanes x ceil(workgroups / 8), see the kernel's placement rule
+      const int ntl = Cout / cw, mtl = two ? (M + 31) / 32 : (M + 15) / 16;
+      const int per_xcd = ntl >= 8 ? mtl * (ntl / 8) : (mtl + 8 / ntl - 1) / (8 / ntl);
+      const int mi = two ? 2 : 1, ni = cw == 64 ? 4 : 2;
+      const bool first = q.smallm == 3 && B2;
+      ConvStep &st = add(first ? CK_SMALLM : CK_SMALLX, "conv_smallm_kernel", M, 8 * per_xcd, 256,
+                         first ? 3 * ni * mi * 1024 : 4 * (mi == 1 ? 4 : 3) * mi * 2048 + 3 * ni * mi * 1024);
+      st.mi = mi; st.ni = ni;
+      st.deep = KT >= 32;                                 // every wave has >= 8 K-steps >= 2 * PF (PF = 4 / 3)
+      st.post = q.post && !QOUT && cw == 64;              // (no 32-channel layer carries a positional table)
+      plan->post_fused = st.post;
+      return finish();
+    }
+  }
+  const bool small_deep = !grp && KT >= 4 && KT <= SMALL_DEEP_MAXKT && Cout % 128 == 0 && ((M + 63) / 64) * (Cout / 128) >= 40 &&
+                          ((M + 63) / 64) * (Cout / 128) <= 256;
+  // split-K for small problems (Track, N <= ~8): a 128x128 tile count far below the 512 workgroup slots of the chip
+  // would leave most CUs idle while a few walk up to 72 K-steps; give every CU a slice instead (2-byte types only)
+  if (!small_deep && KT >= SPLITK_MIN_KT && B2) {
+    const int tiles = ((M + 127) / 128) * (Cout % 128 == 0 ? Cout / 128 : Cout / 64);
+    // a little above the split-K range (a batch of ~8 objects): long-K layers still leave half the chip idle for 72 K-steps;
+    // two slices per tile while the grid fits one round of the 256 CUs
+    const int target = tiles <= 96 ? SPLITK_TARGET : (tiles <= 128 && KT >= 36) ? 2 * tiles : 0;
+    const int S = std::min(std::max(target / tiles, 1), KT / 2);
+    if (target && S > 1) {
+      kt_per = (KT + S - 1) / S;
+      ksplit = (KT + kt_per - 1) / kt_per;
+    }
+  }
+  const bool halo_ok = q.conv_variant == 0 || q.conv_variant == 7;
+  const bool force = q.conv_variant == 7;
+  if (B2 && SAME && !grp && halo_ok && q.Cin == 32 && q.KH == 4 && q.KW == 4 && Cout == 64 && q.ipad == 2 && q.W == 80 && q.H == 80 && ksplit == 1 &&
+      !q.has_res && q.split_imgs == 0 && (force || q.NB * 10 >= 300)) {
+    add(CK_STEM_HALO, "conv_stem_halo_kernel", M, q.NB * 10, 256, LDS_STEM_HALO);
+    return finish();
+  }
+  if (B2 && SAME && !grp && q.conv_variant == 0 && q.KH == 1 && q.KW == 1 && q.stride == 1 && q.pad == 0 && q.ipad == 0 && Cout % 256 == 0 &&
+      Ktot % 32 == 0 && ksplit == 1 && q.split_imgs == 0 && ((M + 127) / 128) * (Cout / 256) >= 512) {
+    add(CK_GEMM_K32, "gemm_k32_kernel", M, ((M + 127) / 128) * (Cout / 256), 256, LDS_GEMM_K32).wpack = q.wpack;
+    return finish();
+  }
+  if (B2 && !grp && halo_ok && q.KH == 3 && q.KW == 3 && q.stride == 2 && q.pad == 1 && q.ipad == 1 && q.W == 80 && q.H == 80 && q.Cin == 64 &&
+      Cout == 128 && ksplit == 1 && !q.has_res && q.split_imgs == 0 && (force || q.NB * 10 >= 300)) {
+    add(CK_S2_HALO, "conv_s2_halo_kernel", M, q.NB * 10, 256, LDS_S2_HALO);
+    return finish();
+  }
+  // 3x3 / stride 1 on 40x40 maps with the input tile resident in LDS; measured crossover vs the implicit-GEMM tiles: ~32 hypotheses
+  // (conv_halo_kernel writes its operand type, conv_halo8_kernel the 8-bit type of its operands, alone or next to the f16 stream)
+  if ((B2 ? SAME : odt_q(q.odt) == q.dt) && !grp && halo_ok && q.KH == 3 && q.KW == 3 && q.stride == 1 && q.pad == 1 && q.ipad == 1 && q.W == 40 &&
+      q.H % 8 == 0 && cin_b % 128 == 0 && Cout % 128 == 0 && ksplit == 1 && (force || q.NB * (q.H / 8) * (Cout / 128) >= 300)) {
+    const int grid = q.NB * (q.H / 8) * (Cout / 128);
+    if (B2) {
+      const int a = q.conv_ablate;
+      add(CK_HALO, "conv_halo_kernel", M, grid, 256, LDS_HALO40).ablate = (q.dt == DT_F16 && (a == 1 || a == 2 || a == 8 || a == 16 || a == 32)) ? a : 0;
+    } else {
+      add(CK_HALO8, "conv_halo8_kernel", M, grid, 256, LDS_HALO8);
+    }
+    return finish();
+  }
+  if (B2 && !grp && (q.conv_variant == 0 || q.conv_variant == 8) && Cout == 128 && ksplit == 1 && KT >= 4 && KT <= 80) {
+    // 512x128 ping-pong tiles (conv_pp32_kernel) for as many FULL rounds of the 256 CUs as the problem has; the remaining
+    // rows go to the kernels below
+    const int mt_big = (M / 512 / 256) * 256;
+    if (mt_big > 0) {
+      add(CK_PP32, "conv_pp32_kernel<512,128>", mt_big * 512, mt_big, 512, LDS_PP32, (double)(mt_big * 512) / (double)M);
+      m_begin = mt_big * 512;
+      if (m_begin >= M) return finish();
+    }
+  }
+  bool post_main = false;  // the positional table is added by the 256x256 rounds + deep-ring left-over
+  // (encodeA.1 has 128 output channels: no 256-wide instantiation of the f16 -> 8-bit boundary)
+  if (!(q.dt == DT_F16 && QOUT) && !grp && (q.conv_variant == 5 || q.conv_variant == 0 || q.conv_variant == 8) && Cout % 256 == 0 && ksplit == 1 && KT >= 2) {
+    // 256x256 tiles for as many FULL rounds of the 256 CUs as the problem has, the remaining rows on smaller tiles
+    const int nt2 = Cout / 256;
+    const int mt_all = M / 256;                           // whole 256-row m-tiles
+    const int mt_big = (mt_all * nt2 / 256) * 256 / nt2;  // m-tiles covered by full rounds
+    const int rows_left = M - mt_big * 256;
+    // the positional table is fused only when every row takes a schedule that implements it: the 256x256 rounds + the deep-ring
+    // kernel for the left-over (N = 252); otherwise nobody adds it here and the caller launches add_pos_embed_kernel
+    post_main = q.post && !QOUT && mt_big > 0 && q.conv_variant == 0 && q.conv_ablate == 0 && KT >= 16 &&
+                (rows_left == 0 || ((rows_left + 63) / 64) * (Cout / 128) <= 256);
+    if (mt_big > 0) {
+      const int a = q.conv_ablate;
+      ConvStep &st = add(CK_BIG_PP, "conv_big_pp_kernel", mt_big * 256, mt_big * nt2, 512, LDS_BIG, (double)(mt_big * 256) / (double)M);
+      st.ablate = (q.dt == DT_F16 && (a == 1 || a == 2 || a == 3 || a == 4 || a == 8 || a == 16)) ? a : 0;
+      st.post = post_main;
+      m_begin = mt_big * 256;
+      if (m_begin >= M) { plan->post_fused = post_main; return finish(); }
+    }
+  }
+  // on the remaining paths only the deep-ring left-over behind fused 256x256 rounds and the split-K reduce implement the table
+  plan->post_fused = q.post && (post_main || ksplit > 1);
+  if (!grp && (m_begin > 0 || M >= 8192 || small_deep) && (KT >= 16 || small_deep) && ksplit == 1 && Cout % 128 == 0) {
+    // left-over rows on an otherwise idle chip (and long-K layers too small for one full 256x256 round as a whole): a lone workgroup
+    // per CU walks all K-steps, so per-step latency is what counts: conv_512 left-overs 61 us per launch on the 2-stage 128x128 tile,
+    // 55 us on the 256x128 ping-pong, 39 us on conv_deep_kernel<64> (neutral-to-slower for the 8-step Linear layers, hence KT >= 16)
+    const int n128 = Cout / 128;
+    // conv_deep_kernel owns its CU, so it only pays while its grid is a single round (<= 256 workgroups).  A larger
+    // left-over (mid-sized batches) first takes full rounds of the 256x128 ping-pong kernel, then the deep kernel.
+    int rows = M - m_begin;
+    if (((rows + 63) / 64) * n128 > 256) {
+      const int mt_pp = (((rows + 255) / 256) * n128 / 256) * 256 / n128;  // 256-row m-tiles in full rounds
+      const int rows_pp = std::min(mt_pp * 256, rows);
+      const int rest = rows - rows_pp;
+      const bool cascade = mt_pp > 0 && ((rest + 63) / 64) * n128 <= 256;
+      const int m_end = cascade ? m_begin + rows_pp : M;
+      add(CK_PP, "conv_pp_kernel(rem)", m_end, ((m_end - m_begin + 255) / 256) * n128, 512, LDS3_128, cascade ? (double)rows_pp / rows : 1.0);
+      if (!cascade || rest == 0) return finish();
+      m_begin += rows_pp;
+      rows = rest;
+    }
+    add(CK_DEEP64, "conv_deep_kernel", M, ((rows + 63) / 64) * n128, 256, LDS_DEEP64).post = post_main;
+    return finish();
+  }
+  if (!grp && q.conv_variant == 3 && KT >= 3 && ksplit == 1 && Cout % 128 == 0) {
+    add(CK_PP, "conv_pp_kernel", M, ((M + 255) / 256) * (Cout / 128), 512, LDS3_128);
+    return finish();
+  }
+  const int mtiles = (M - m_begin + 127) / 128;
+  if (Cout % 128 == 0 && ksplit == 1 && m_begin == 0 && KT >= 4 && KT <= 8 && mtiles * (Cout / 128) <= 128 && (!grp || q.grp_rows % 128 == 0)) {
+    // short-K layers of small problems (the Linear layers of Track): a workgroup is a chain of <= 8 K-steps whose load latency the
+    // two-stage tile below exposes every step; the deep ring keeps three steps in flight
+    add(CK_DEEP128, "conv_deep_kernel(short-K)", M, mtiles * (Cout / 128), 256, LDS_DEEP128);
+  } else if (Cout % 128 == 0 && !grp && ksplit > 1 && kt_per >= 4) {
+    // split-K slices on the deep-ring kernel (three K-steps in flight instead of one: a slice is a latency chain)
+    add(CK_DEEP128, "conv_deep_kernel(split-K)", M, mtiles * (Cout / 128) * ksplit, 256, LDS_DEEP128);
+  } else if (Cout % 128 == 0) {
+    add(CK_IGEMM128, "conv_igemm_kernel<128>", M, mtiles * (Cout / 128) * ksplit, 256, LDS_IG128);
+  } else {
+    add(CK_IGEMM64, "conv_igemm_kernel<64>", M, mtiles * (Cout / 64) * ksplit, 256, LDS_IG64);
+  }
+  if (ksplit > 1) {
+    const size_t octs = (size_t)(M - m_begin) * (Cout / 8);
+    flops = 0; bytes = 0;
+    add(CK_SPLITK_REDUCE, "conv_splitk_reduce_kernel", M, (int)((octs + 255) / 256), 256, 0).post = q.post;
+  }
+  return finish();
+}
+
 // Activation taps (test build only; tests/test_layers_gpu.py): an armed tap copies the tensor a producer just wrote -- borders
-// included, behind the join of a forked left-over -- device to device into the test's buffer, on the forward pass's own stream.
+// included -- device to device into the test's buffer, on the forward pass's own stream.
 // In the product FP_TAP expands to nothing (its arguments are not evaluated).  Points: fp_nn.h, enum TapPoint.
 #ifdef FP_TEST_HOOKS
 struct TapSlot {
@@ -1343,12 +1559,12 @@ static void tap_imgs(const Ctx &c, int point, const void *src, size_t img_bytes,
 #define FP_TAP(c, point, src, bytes) tap(c, point, src, bytes)
 #define FP_TAP_IMGS(c, point, src, img_bytes, imgs, N) tap_imgs(c, point, src, img_bytes, imgs, N)
 
-// Launch log (test build only; fpt_launch_log_*): while armed, every network kernel launch of run_conv_dt and the other launch helpers
+// Launch log (test build only; fpt_launch_log_*): while armed, every network kernel launch of run_conv and the other launch helpers
 // appends one record -- the schedule that ran, for the coverage test of tests/test_layers_gpu.py.  It reads the schedule decisions and
-// makes none (in particular it does not switch the profiler on, which would disable fork_rem).
+// makes none.
 struct LaunchRec {
   int net, prec;        // 0 refiner / 1 scorer, PREC_*
-  int side;             // 1 = launched on the side stream (fork_rem)
+  int side;             // always 0 (kept for the layout of the record: a side stream was an experiment once)
   int m_begin, M;       // output rows [m_begin, M) of a convolution / GEMM launch (0, 0 elsewhere)
   int ksplit;           // split-K slices (1 = none)
   int pe;               // the launch adds the positional table in its epilogue
@@ -1365,19 +1581,13 @@ void nn_plan_only(bool on) { g_plan_only = on; }
 #define FP_TAP_IMGS(c, point, src, img_bytes, imgs, N) ((void)0)
 #endif
 
-// ProfScope of one network launch; in the test build it also appends the launch to the armed launch log.  rows() completes the
-// record of a convolution / GEMM launch (a no-op in the product).
+// ProfScope of one network launch; in the test build it also appends the launch to the armed launch log.  The second form is a step
+// of a convolution / Linear plan: "tag/kernel", and the record's rows, slices and positional table straight from the step.
 struct NetScope : ProfScope {
   NetScope(const Ctx &c, const char *name, double flops = 0, double bytes = 0);
+  NetScope(const Ctx &c, const char *tag, const ConvStep &st);
 #ifdef FP_TEST_HOOKS
   long idx = -1;
-  void rows(int m_begin, int M, int ksplit = 1, bool pe = false, bool side = false) {
-    if (idx < 0) return;
-    LaunchRec &r = g_launch_log[(size_t)idx];
-    r.m_begin = m_begin; r.M = M; r.ksplit = ksplit; r.pe = pe ? 1 : 0; r.side = side ? 1 : 0;
-  }
-#else
-  void rows(int, int, int = 1, bool = false, bool = false) {}
 #endif
 };
 inline NetScope::NetScope(const Ctx &c, const char *name, double flops, double bytes) : ProfScope(c.prof, c.s, name, flops, bytes) {
@@ -1387,6 +1597,13 @@ inline NetScope::NetScope(const Ctx &c, const char *name, double flops, double b
   std::snprintf(r.name, sizeof(r.name), "%s", name);
   idx = (long)g_launch_log.size();
   g_launch_log.push_back(r);
+#endif
+}
+inline NetScope::NetScope(const Ctx &c, const char *tag, const ConvStep &st) : NetScope(c, (std::string(tag) + "/" + st.name).c_str(), st.flops, st.bytes) {
+#ifdef FP_TEST_HOOKS
+  if (idx < 0) return;
+  LaunchRec &r = g_launch_log[(size_t)idx];
+  r.m_begin = st.m_begin; r.M = st.M; r.ksplit = st.ksplit; r.pe = st.post ? 1 : 0;
 #endif
 }
 
@@ -1422,389 +1639,157 @@ struct ConvGroup {  // two weight groups along M (see ConvParams::grp_rows); L h
   bool in_shared = false, res_shared = false;
 };
 
-// DT = element type of the layer's operands; ODT = of its output.  ODT != DT only for the two layers at the FP8 boundary
-// (encodeA.1: f16 -> FP8, the last encodeAB conv: FP8 -> f16 tokens); those instantiate only the schedules they can reach.
-template <int DT, int ODT>
-static int run_conv_dt(const Ctx &c, const char *tag, const ConvLayer &L, ConvParams &p, int NB, int H, int W, int ipad,
-                       bool has_res, int split_imgs, const ConvGroup *grp) {
-  constexpr bool B2 = !is_q8(DT);    // 2-byte element type: the 64-byte-row kernels exist
-  constexpr bool SAME = DT == ODT;   // kernels without an ODT parameter write their operand type
-  constexpr bool QOUT = odt_q(ODT) >= 0;   // an 8-bit tensor is written (alone or next to the f16 stream tensor)
-  const int KT = p.krow_b / 128;
-  bool post_main = false;  // ConvParams::post handled by the 256x256 rounds + deep-ring left-over (see below)
-  bool fork_rem = false;   // the left-over launch goes to the side stream (forked before the 256x256 rounds)
-  double flops = 2.0 * (double)p.M * p.Cout * (L.algo_K > 0 ? L.algo_K : p.Ktot);
-  double bytes = ((double)NB * H * W * L.Cin + (double)p.M * p.Cout * (has_res ? 2 : 1) + (double)p.Cout * p.Ktot) * elem_bytes(DT);
-  constexpr int LDS_IG128 = 2 * (128 * 128 + 128 * 128), LDS_IG64 = 2 * (128 * 128 + 64 * 128);
-  constexpr int LDS3_128 = 3 * (256 * 128 + 128 * 128);
-  constexpr int LDS_BIG = 2 * (256 * 128 + 256 * 128);
-  constexpr int LDS_HALO40 = ((10 * 42 + 7) / 8) * 1024 + 3 * 128 * 64;
-  [[maybe_unused]] constexpr int LDS_HALO40W = ((10 * 42 + 7) / 8) * 1024;
-  constexpr int LDS_HALO8 = ((10 * 42 + 7) / 8) * 1024 + 128 * 128;
-  constexpr int LDS_STEM_HALO = ((11 * 84 + 15) / 16) * 1024 + 3 * 64 * 64;
-  constexpr int LDS_DEEP64 = 6 * (64 + 128) * 128, LDS_DEEP128 = 4 * (128 + 128) * 128;
-  constexpr int LDS_GEMM_K32 = 3 * (128 + 256) * 64;
-  constexpr int LDS_S2_HALO = ((9 * 41 + 7) / 8) * 1024 + 3 * 128 * 64;
-  constexpr int LDS_PP32 = 4 * (512 + 128) * 64;
-  int mtiles = (p.M + 127) / 128;
-  // split-K for small problems (Track, N <= ~8): a 128x128 tile count far below the 512 workgroup slots of the chip
-  // would leave most CUs idle while a few walk up to 72 K-steps; give every CU a slice instead
-  // (also used for the rows a 256x256 / 512x128 launch leaves over: `target` workgroups on an otherwise idle chip)
-  auto plan_splitk = [&](int rows, int target) -> int {
-    const int mt = (rows + 127) / 128;
-    const int tiles = mt * (L.Cout % 128 == 0 ? L.Cout / 128 : L.Cout / 64);
-    if (KT < g_splitk_min_kt || is_q8(DT)) return 0;
-    if (tiles > 96) {
-      // a little above the split-K range (a batch of ~8 objects): long-K layers still leave half the chip idle for 72 K-steps;
-      // two slices per tile while the grid fits one round of the 256 CUs
-      if (!(g_splitk_mid && tiles <= 128 && KT >= 36)) return 0;
-      target = 2 * tiles;
-    }
-    int S = std::min(std::max(target / tiles, 1), KT / 2);
-    if (S <= 1) return 0;
-    p.kt_per = (KT + S - 1) / S;
-    p.ksplit = (KT + p.kt_per - 1) / p.kt_per;
-    size_t need = (size_t)p.ksplit * rows * p.Cout;
-#ifdef FP_TEST_HOOKS
-    NNScratch *sk = c.ws ? c.ws : &g_hook_ws;
-#else
-    NNScratch *sk = c.ws;
-#endif
-    if (need > sk->splitk_cap) {
-      if (sk->splitk) (void)hipFree(sk->splitk);
-      sk->splitk = nullptr; sk->splitk_cap = 0;
-      g_alloc_epoch++;
-      FP_HIP_OK(hipMalloc((void **)&sk->splitk, need * sizeof(float)));
-      sk->splitk_cap = need;
-    }
-    p.partial = sk->splitk;
-    return 0;
-  };
-  // ---- small problems: one launch per layer, the K-steps split over the four waves of a workgroup (conv_smallx_kernel)
-  if (B2 || L.Cout % 128 == 0) {                         // (FP8 layers all have Cout % 128 == 0: 64-channel tiles only)
-    const int cw = (L.Cout % 128 == 0) ? 64 : 32;         // channels per workgroup = the block of the host-side row permutation
-    const int t16 = ((p.M + 15) / 16) * (L.Cout / cw);
-    // Measured on Track (tools/profile_track.sh, profiles/r03g_track_timeline.txt): 5.6-7.2 us for the layers of up to 18 K-steps, 8.5-9.1
-    // for the 36-step ones, 10.2-10.6 for conv_512 (72 steps; 12.8 + 5.5 us as split-K + reduce).  The first version
-    // (conv_smallm_kernel: both operands global -> registers in MFMA-operand shape, 64 clocks of the vector L1 per instruction) lost on
-    // the long-K layers (21 us); g_smallm = 3 selects it for A/B, g_smallm = 2 forces the small-problem kernel for every size.
-    if (g_smallm && L.wfrag && (KT < g_smallm_maxkt || g_smallm >= 2) && g_conv_variant == 0 && g_conv_ablate == 0 && L.Cout % cw == 0 && t16 <= g_smallm_maxt16 * (64 / cw) &&
-        (!grp || grp->rows % 32 == 0) && ((L.Cout / cw) % 8 == 0 || 8 % (L.Cout / cw) == 0)) {
-      const int t32 = ((p.M + 31) / 32) * (L.Cout / cw);
-      const bool two = t32 >= 160;                        // 32-pixel tiles halve the weight stream once they still fill the chip
-      bool post = p.post != nullptr;
-      if constexpr (QOUT) post = false;
-      if (!post) p.post = nullptr;
-      NetScope ps(c, (std::string(tag) + "/conv_smallm_kernel").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M, 1, post && cw == 64);
-      // grid = 8 XCD lanes x ceil(workgroups / 8), see the kernel's placement rule
-      const int ntl = L.Cout / cw, mtl = two ? (p.M + 31) / 32 : (p.M + 15) / 16;
-      const int per_xcd = ntl >= 8 ? mtl * (ntl / 8) : (mtl + 8 / ntl - 1) / (8 / ntl);
-      const dim3 grid(8 * per_xcd);
-      const bool deep = KT >= 32;                          // every wave has >= 8 K-steps >= 2 * PF (PF = 4 / 3)
+template <int MI, int NI, int DT, int ODT, bool POST>
+static void launch_conv_small(const Ctx &c, const ConvStep &st, const ConvParams &p) {
 #ifdef FP_TEST_HOOKS   // A/B (g_smallm == 3): the first version, input fragments global -> registers in operand shape
-#define FP_SMALLM_DIRECT(MI_, NI_, POST_)                                                                                     \
-    if (g_smallx_pf && MI_ == 2 && NI_ == 4 && !POST_ && DT == DT_F16 && ODT == DT_F16) {                                     \
-      if (g_smallx_pf == 4) FP_LAUNCH((conv_smallx_kernel<2, 4, DT_F16, DT_F16, false, 4>), grid, dim3(256), 4 * 4 * 2 * 2048 + 3 * 4 * 2 * 1024, c.s, p); \
-      else FP_LAUNCH((conv_smallx_kernel<2, 4, DT_F16, DT_F16, false, 2>), grid, dim3(256), 4 * 2 * 2 * 2048 + 3 * 4 * 2 * 1024, c.s, p); \
-      break;                                                                                                                  \
-    }                                                                                                                         \
-    if (g_smallm == 3) {                                                                                                      \
-      if (deep) FP_LAUNCH((conv_smallm_kernel<MI_, NI_, DT, ODT, POST_, true>), grid, dim3(256), 3 * NI_ * MI_ * 1024, c.s, p); \
-      else FP_LAUNCH((conv_smallm_kernel<MI_, NI_, DT, ODT, POST_, false>), grid, dim3(256), 3 * NI_ * MI_ * 1024, c.s, p);    \
-      break;                                                                                                                  \
+  if constexpr (!is_q8(DT)) {
+    if (st.kernel == CK_SMALLM) {
+      if (st.deep) FP_LAUNCH((conv_smallm_kernel<MI, NI, DT, ODT, POST, true>), dim3(st.grid), dim3(256), st.lds, c.s, p);
+      else FP_LAUNCH((conv_smallm_kernel<MI, NI, DT, ODT, POST, false>), dim3(st.grid), dim3(256), st.lds, c.s, p);
+      return;
     }
-#else
-#define FP_SMALLM_DIRECT(MI_, NI_, POST_)
+  }
 #endif
-#define FP_SMALLM(MI_, NI_, POST_)                                                                                          \
-  do {                                                                                                                      \
-    if constexpr (B2) { FP_SMALLM_DIRECT(MI_, NI_, POST_) }                                                                 \
-    FP_LAUNCH((conv_smallx_kernel<MI_, NI_, DT, ODT, POST_>), grid, dim3(256),                                              \
-              4 * ((MI_) == 1 ? 4 : 3) * (MI_) * 2048 + 3 * NI_ * MI_ * 1024, c.s, p);                                      \
-  } while (0)
+  FP_LAUNCH((conv_smallx_kernel<MI, NI, DT, ODT, POST>), dim3(st.grid), dim3(256), st.lds, c.s, p);
+}
+
+// One step of a plan on its kernel.  DT = element type of the layer's operands; ODT = of its output.  ODT != DT only for the layers at
+// the 8-bit boundaries (encodeA.1: f16 -> 8-bit, the last encodeAB conv: 8-bit -> f16 tokens) and the scaled / dual 8-bit outputs; every
+// pair instantiates only the kernels plan_conv can choose for it.
+template <int DT, int ODT>
+static int launch_conv_step(const Ctx &c, const ConvStep &st, const ConvParams &p) {
+  constexpr bool B2 = !is_q8(DT), SAME = DT == ODT, QOUT = odt_q(ODT) >= 0;   // as in plan_conv
+  const dim3 grid(st.grid), block((unsigned)st.block);
+  switch (st.kernel) {
+    case CK_SMALLX:
+    case CK_SMALLM:
       if constexpr (!QOUT) {
-        if (post && cw == 64) { if (two) FP_SMALLM(2, 4, true); else FP_SMALLM(1, 4, true); return 0; }
-        if (post) p.post = nullptr;                      // (no 32-channel layer carries a positional table)
-      }
-      if (cw == 64) { if (two) FP_SMALLM(2, 4, false); else FP_SMALLM(1, 4, false); }
-      else if constexpr (B2) { if (two) FP_SMALLM(2, 2, false); else FP_SMALLM(1, 2, false); }
-#undef FP_SMALLM
-#undef FP_SMALLM_DIRECT
-      return 0;
-    }
-  }
-  const bool small_deep = !grp && g_small_deep > 0 && KT >= 4 && KT <= g_small_deep && L.Cout % 128 == 0 && ((p.M + 63) / 64) * (L.Cout / 128) >= 40 &&
-                          ((p.M + 63) / 64) * (L.Cout / 128) <= 256;
-  if (!small_deep && plan_splitk(p.M, g_splitk_target)) return 1;
-  const std::string tg(tag);
-  const bool halo_ok = g_conv_variant == 0 || g_conv_variant == 7;
-  const bool force = g_conv_variant == 7;
-  if constexpr (B2 && SAME) {
-    if (!grp && halo_ok && L.Cin == 32 && L.KH == 4 && L.KW == 4 && L.Cout == 64 && ipad == 2 && W == 80 && H == 80 && p.ksplit == 1 &&
-        !has_res && split_imgs == 0 && (force || NB * 10 >= 300)) {
-      NetScope ps(c, (tg + "/conv_stem_halo_kernel").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M);
-      FP_LAUNCH((conv_stem_halo_kernel<DT>), dim3(NB * 10), dim3(256), LDS_STEM_HALO, c.s, p);
-      return 0;
-    }
-    if (!grp && g_gemm_kernel && g_conv_variant == 0 && L.KH == 1 && L.KW == 1 && L.stride == 1 && L.pad == 0 && ipad == 0 && L.Cout % 256 == 0 &&
-        p.Ktot % 32 == 0 && p.ksplit == 1 && split_imgs == 0 && ((p.M + 127) / 128) * (L.Cout / 256) >= 512) {
-      NetScope ps(c, (tg + "/gemm_k32_kernel").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M);
-      const dim3 grid(((p.M + 127) / 128) * (L.Cout / 256));
-#ifdef FP_TEST_HOOKS
-      if (DT == DT_F16 && g_gemm_kernel == 11) { FP_LAUNCH((gemm_k32_kernel<1, DT_F16>), grid, dim3(256), LDS_GEMM_K32, c.s, p); return 0; }
-      if (DT == DT_F16 && g_gemm_kernel == 12) { FP_LAUNCH((gemm_k32_kernel<2, DT_F16>), grid, dim3(256), LDS_GEMM_K32, c.s, p); return 0; }
-      if (DT == DT_F16 && g_gemm_kernel == 14) { FP_LAUNCH((gemm_k32_kernel<4, DT_F16>), grid, dim3(256), LDS_GEMM_K32, c.s, p); return 0; }
-#endif
-      if (g_gemm_lds_store && g_gemm_wpack && L.wpack) FP_LAUNCH((gemm_k32_kernel<0, DT, true, true>), grid, dim3(256), LDS_GEMM_K32, c.s, p);
-      else if (g_gemm_lds_store) FP_LAUNCH((gemm_k32_kernel<0, DT, true>), grid, dim3(256), LDS_GEMM_K32, c.s, p);
-      else FP_LAUNCH((gemm_k32_kernel<0, DT>), grid, dim3(256), LDS_GEMM_K32, c.s, p);
-      return 0;
-    }
-  }
-  if constexpr (B2) {
-    if (!grp && halo_ok && L.KH == 3 && L.KW == 3 && L.stride == 2 && L.pad == 1 && ipad == 1 && W == 80 && H == 80 && L.Cin == 64 &&
-        L.Cout == 128 && p.ksplit == 1 && !has_res && split_imgs == 0 && (force || NB * 10 >= 300)) {
-      NetScope ps(c, (tg + "/conv_s2_halo_kernel").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M);
-      FP_LAUNCH((conv_s2_halo_kernel<DT, ODT>), dim3(NB * 10), dim3(256), LDS_S2_HALO, c.s, p);
-      return 0;
-    }
-  }
-  // 3x3 / stride 1 on 40x40 maps with the input tile resident in LDS; measured crossover vs the implicit-GEMM tiles: ~32 hypotheses
-  if ((SAME || (!B2 && odt_q(ODT) == DT)) && !grp && halo_ok && L.KH == 3 && L.KW == 3 && L.stride == 1 && L.pad == 1 && ipad == 1 && W == 40 && H % 8 == 0 &&
-      p.cin_b % 128 == 0 && L.Cout % 128 == 0 && p.ksplit == 1 && (force || NB * (H / 8) * (L.Cout / 128) >= 300)) {
-    const dim3 grid(NB * (H / 8) * (L.Cout / 128));
-    if constexpr (B2 && !SAME) {
-    } else if constexpr (B2) {
-      NetScope ps(c, (tg + "/conv_halo_kernel").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M);
-#ifdef FP_TEST_HOOKS
-      if (DT == DT_F16 && g_conv_ablate == 1) { FP_LAUNCH((conv_halo_kernel<40, 1, DT_F16>), grid, dim3(256), LDS_HALO40, c.s, p); return 0; }
-      if (DT == DT_F16 && g_conv_ablate == 2) { FP_LAUNCH((conv_halo_kernel<40, 2, DT_F16>), grid, dim3(256), LDS_HALO40, c.s, p); return 0; }
-      if (DT == DT_F16 && g_conv_ablate == 8) { FP_LAUNCH((conv_halo_kernel<40, 8, DT_F16>), grid, dim3(256), LDS_HALO40, c.s, p); return 0; }
-      if (DT == DT_F16 && g_conv_ablate == 16) { FP_LAUNCH((conv_halo_kernel<40, 16, DT_F16>), grid, dim3(256), LDS_HALO40, c.s, p); return 0; }
-      if (DT == DT_F16 && g_conv_ablate == 32) { FP_LAUNCH((conv_halo_kernel<40, 32, DT_F16>), grid, dim3(256), LDS_HALO40, c.s, p); return 0; }
-#endif
-      if (!g_halo_wpack) p.wpack = nullptr;
-#ifdef FP_TEST_HOOKS
-      if (g_halo_wreg && p.wfrag && g_conv_ablate == 0 && (p.cin_b >= 512 || g_halo_wreg == 2)) { FP_LAUNCH((conv_halo_wreg_kernel<DT>), grid, dim3(256), LDS_HALO40W, c.s, p); return 0; }
-#endif
-      FP_LAUNCH((conv_halo_kernel<40, 0, DT>), grid, dim3(256), LDS_HALO40, c.s, p);
-    } else if constexpr (odt_q(ODT) == DT) {
-      NetScope ps(c, (tg + "/conv_halo8_kernel").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M);
-      if (!g_halo_wpack) p.wpack = nullptr;
-      FP_LAUNCH((conv_halo8_kernel<DT, ODT>), grid, dim3(256), LDS_HALO8, c.s, p);
-    }
-    return 0;
-  }
-  if constexpr (B2) {
-    if (!grp && (g_conv_variant == 0 || g_conv_variant == 8) && L.Cout == 128 && p.ksplit == 1 && KT >= 4 && KT <= 80) {
-      // 512x128 ping-pong tiles (conv_pp32_kernel) for as many FULL rounds of the 256 CUs as the problem has; the remaining
-      // rows go to the kernels below
-      const int mt_all = p.M / 512;
-      const int mt_big = (mt_all / 256) * 256;
-      if (mt_big > 0) {
-        ConvParams pb = p;
-        pb.M = mt_big * 512;
-        const double frac = (double)pb.M / (double)p.M;
-        {
-          NetScope ps(c, (tg + "/conv_pp32_kernel<512,128>").c_str(), flops * frac, bytes * frac);
-          ps.rows(pb.m_begin, pb.M);
-          FP_LAUNCH((conv_pp32_kernel<512, 128, DT, ODT>), dim3(mt_big), dim3(512), LDS_PP32, c.s, pb);
+        if (st.post && st.ni == 4) {
+          if (st.mi == 2) launch_conv_small<2, 4, DT, ODT, true>(c, st, p); else launch_conv_small<1, 4, DT, ODT, true>(c, st, p);
+          return 0;
         }
-        flops *= (1.0 - frac); bytes *= (1.0 - frac);
-        p.m_begin = mt_big * 512;
-        if (p.m_begin >= p.M) return 0;
-        mtiles = (p.M - p.m_begin + 127) / 128;
-        if (g_rem_splitk && plan_splitk(p.M - p.m_begin, 384)) return 1;
       }
-    }
-  }
-  if constexpr (!(DT == DT_F16 && QOUT))  // (encodeA.1 has 128 output channels: no 256-wide instantiation of the f16 -> 8-bit boundary)
-  if (!grp && (g_conv_variant == 5 || g_conv_variant == 0 || g_conv_variant == 8) && L.Cout % 256 == 0 && p.ksplit == 1 && KT >= 2) {
-    // 256x256 tiles for as many FULL rounds of the 256 CUs as the problem has, the remaining rows on smaller tiles
-    const int nt2 = L.Cout / 256;
-    const int mt_all = p.M / 256;                         // whole 256-row m-tiles
-    const int mt_big = (mt_all * nt2 / 256) * 256 / nt2;  // m-tiles covered by full rounds
-    if (p.post) {
-      // the positional table is fused only when every row takes a schedule that implements it: the 256x256 rounds + the deep-ring
-      // kernel for the left-over (N = 252); otherwise nobody adds it here and the caller launches add_pos_embed_kernel
-      const int rows_left = p.M - mt_big * 256;
-      post_main = mt_big > 0 && g_conv_variant == 0 && g_conv_ablate == 0 && g_rem_kernel == 3 && KT >= 16 &&
-                  (rows_left == 0 || ((rows_left + 63) / 64) * (L.Cout / 128) <= 256);
-      if (!post_main) p.post = nullptr;
-    }
-    // [r5] the left-over rows run NEXT TO the full rounds, on the side stream: a lone deep-ring launch leaves 100 of the 256 CUs idle for
-    // 35-40 us behind every conv_512 / conv_b2; forked, its workgroups take CUs as the 256x256 tiles release them (disjoint rows, same inputs)
-    if (mt_big > 0) {
-      const int rows_left = p.M - mt_big * 256;
-      fork_rem = g_rem_fork && c.s2 && !(c.prof && c.prof->on) && rows_left > 0 && g_rem_kernel == 3 && KT >= 16 && L.Cout % 128 == 0 &&
-                 ((rows_left + 63) / 64) * (L.Cout / 128) <= 256 && g_conv_variant == 0 && g_conv_ablate == 0 && !g_rem_splitk;
-      if (fork_rem) {
-        FP_HIP_OK(hipEventRecord(c.ev_fork, c.s));
-        FP_HIP_OK(hipStreamWaitEvent(c.s2, c.ev_fork, 0));
+      if (st.post) break;
+      if (st.ni == 4) {
+        if (st.mi == 2) launch_conv_small<2, 4, DT, ODT, false>(c, st, p); else launch_conv_small<1, 4, DT, ODT, false>(c, st, p);
+        return 0;
       }
-      ConvParams pb = p;
-      pb.M = mt_big * 256;                                // rows [0, mt_big*256)
-      const double frac = (double)pb.M / (double)p.M;
-      {
-        NetScope ps(c, (tg + "/conv_big_pp_kernel").c_str(), flops * frac, bytes * frac);
-        ps.rows(pb.m_begin, pb.M, 1, post_main);
-        const dim3 grid(mt_big * nt2);
-        bool done = false;
+      if constexpr (B2) {
+        if (st.mi == 2) launch_conv_small<2, 2, DT, ODT, false>(c, st, p); else launch_conv_small<1, 2, DT, ODT, false>(c, st, p);
+        return 0;
+      }
+      break;
+    case CK_STEM_HALO:
+      if constexpr (B2 && SAME) { FP_LAUNCH((conv_stem_halo_kernel<DT>), grid, block, st.lds, c.s, p); return 0; }
+      break;
+    case CK_GEMM_K32:
+      if constexpr (B2 && SAME) {
+        if (st.wpack) FP_LAUNCH((gemm_k32_kernel<0, DT, true, true>), grid, block, st.lds, c.s, p);
+        else FP_LAUNCH((gemm_k32_kernel<0, DT, true>), grid, block, st.lds, c.s, p);
+        return 0;
+      }
+      break;
+    case CK_S2_HALO:
+      if constexpr (B2) { FP_LAUNCH((conv_s2_halo_kernel<DT, ODT>), grid, block, st.lds, c.s, p); return 0; }
+      break;
+    case CK_HALO:
+      if constexpr (B2 && SAME) {
 #ifdef FP_TEST_HOOKS
-        if (DT == DT_F16 && g_conv_ablate) {
-          done = true;
-          switch (g_conv_ablate) {
-            case 1: FP_LAUNCH((conv_big_pp_kernel<1, DT_F16>), grid, dim3(512), LDS_BIG, c.s, pb); break;
-            case 2: FP_LAUNCH((conv_big_pp_kernel<2, DT_F16>), grid, dim3(512), LDS_BIG, c.s, pb); break;
-            case 3: FP_LAUNCH((conv_big_pp_kernel<3, DT_F16>), grid, dim3(512), LDS_BIG, c.s, pb); break;
-            case 4: FP_LAUNCH((conv_big_pp_kernel<4, DT_F16>), grid, dim3(512), LDS_BIG, c.s, pb); break;
-            case 8: FP_LAUNCH((conv_big_pp_kernel<8, DT_F16>), grid, dim3(512), LDS_BIG, c.s, pb); break;
-            case 16: FP_LAUNCH((conv_big_pp_kernel<16, DT_F16>), grid, dim3(512), LDS_BIG, c.s, pb); break;
-            default: done = false;
-          }
+        switch (st.ablate) {
+          case 1: FP_LAUNCH((conv_halo_kernel<40, 1, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 2: FP_LAUNCH((conv_halo_kernel<40, 2, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 8: FP_LAUNCH((conv_halo_kernel<40, 8, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 16: FP_LAUNCH((conv_halo_kernel<40, 16, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 32: FP_LAUNCH((conv_halo_kernel<40, 32, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          default: break;
+        }
+#endif
+        FP_LAUNCH((conv_halo_kernel<40, 0, DT>), grid, block, st.lds, c.s, p);
+        return 0;
+      }
+      break;
+    case CK_HALO8:
+      if constexpr (!B2 && odt_q(ODT) == DT) { FP_LAUNCH((conv_halo8_kernel<DT, ODT>), grid, block, st.lds, c.s, p); return 0; }
+      break;
+    case CK_PP32:
+      if constexpr (B2) { FP_LAUNCH((conv_pp32_kernel<512, 128, DT, ODT>), grid, block, st.lds, c.s, p); return 0; }
+      break;
+    case CK_BIG_PP:
+      if constexpr (!(DT == DT_F16 && QOUT)) {
+#ifdef FP_TEST_HOOKS
+        switch (st.ablate) {
+          case 1: FP_LAUNCH((conv_big_pp_kernel<1, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 2: FP_LAUNCH((conv_big_pp_kernel<2, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 3: FP_LAUNCH((conv_big_pp_kernel<3, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 4: FP_LAUNCH((conv_big_pp_kernel<4, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 8: FP_LAUNCH((conv_big_pp_kernel<8, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          case 16: FP_LAUNCH((conv_big_pp_kernel<16, DT_F16>), grid, block, st.lds, c.s, p); return 0;
+          default: break;
         }
 #endif
         if constexpr (!QOUT) {
-          if (!done && post_main) { FP_LAUNCH((conv_big_pp_kernel<0, DT, ODT, true>), grid, dim3(512), LDS_BIG, c.s, pb); done = true; }
+          if (st.post) { FP_LAUNCH((conv_big_pp_kernel<0, DT, ODT, true>), grid, block, st.lds, c.s, p); return 0; }
         }
-        if constexpr (!QOUT && B2) {
-          if (!done && g_conv_lds_store) { FP_LAUNCH((conv_big_pp_kernel<0, DT, ODT, false, true>), grid, dim3(512), LDS_BIG, c.s, pb); done = true; }
-        }
-        if (!done) FP_LAUNCH((conv_big_pp_kernel<0, DT, ODT>), grid, dim3(512), LDS_BIG, c.s, pb);
+        if (st.post) break;
+        FP_LAUNCH((conv_big_pp_kernel<0, DT, ODT>), grid, block, st.lds, c.s, p);
+        return 0;
       }
-      flops *= (1.0 - frac); bytes *= (1.0 - frac);
-      p.m_begin = mt_big * 256;
-      if (p.m_begin >= p.M) return 0;
-      mtiles = (p.M - p.m_begin + 127) / 128;
-      if (g_rem_splitk && plan_splitk(p.M - p.m_begin, 384)) return 1;
-    }
-  }
-  if (p.post && !post_main && p.ksplit == 1) p.post = nullptr;  // only the split-K reduce implements it on the remaining paths
-  if (!grp && (p.m_begin > 0 || (g_rem_small && p.M >= 8192) || small_deep) && g_rem_kernel && (KT >= 16 || small_deep) && p.ksplit == 1 && L.Cout % 128 == 0) {
-    // left-over rows on an otherwise idle chip: a lone workgroup per CU walks all K-steps, so per-step latency is what
-    // counts: conv_512 left-overs 61 us per launch on the 2-stage 128x128 tile, 55 us on the 256x128 ping-pong, 39 us on
-    // conv_deep_kernel<64> (neutral-to-slower for the 8-step Linear layers, hence KT >= 16)
-    const int n128 = L.Cout / 128;
-    if (g_rem_kernel == 4) {
-      const dim3 grid(((p.M - p.m_begin + 127) / 128) * n128);
-      NetScope ps(c, (tg + "/conv_deep_kernel").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M);
-      FP_LAUNCH((conv_deep_kernel<128, DT, ODT>), grid, dim3(256), LDS_DEEP128, c.s, p);
+      break;
+    case CK_PP:
+      FP_LAUNCH((conv_pp_kernel<128, DT, ODT>), grid, block, st.lds, c.s, p);
       return 0;
-    }
-    if (g_rem_kernel == 3) {
-      // conv_deep_kernel owns its CU, so it only pays while its grid is a single round (<= 256 workgroups).  A larger
-      // left-over (mid-sized batches) first takes full rounds of the 256x128 ping-pong kernel, then the deep kernel.
-      int rows = p.M - p.m_begin;
-      if (((rows + 63) / 64) * n128 > 256) {
-        const int mt_pp = (((rows + 255) / 256) * n128 / 256) * 256 / n128;  // 256-row m-tiles in full rounds
-        const int rows_pp = std::min(mt_pp * 256, rows);
-        const int rest = rows - rows_pp;
-        const bool cascade = mt_pp > 0 && ((rest + 63) / 64) * n128 <= 256;
-        ConvParams pb = p;
-        if (cascade) pb.M = p.m_begin + rows_pp;
-        const double frac = cascade ? (double)rows_pp / rows : 1.0;
-        {
-          NetScope ps(c, (tg + "/conv_pp_kernel(rem)").c_str(), flops * frac, bytes * frac);
-          ps.rows(pb.m_begin, pb.M);
-          FP_LAUNCH((conv_pp_kernel<128, DT, ODT>), dim3(((pb.M - pb.m_begin + 255) / 256) * n128), dim3(512), LDS3_128, c.s, pb);
-        }
-        if (!cascade || rest == 0) return 0;
-        flops *= (1.0 - frac); bytes *= (1.0 - frac);
-        p.m_begin += rows_pp;
-        rows = rest;
-      }
-      NetScope ps(c, (tg + "/conv_deep_kernel").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M, 1, post_main, fork_rem);
-      const hipStream_t ls = fork_rem ? c.s2 : c.s;
-      bool launched = false;
+    case CK_DEEP64:
       if constexpr (!QOUT) {
-        if (post_main) {
-          FP_LAUNCH((conv_deep_kernel<64, DT, ODT, true>), dim3(((rows + 63) / 64) * n128), dim3(256), LDS_DEEP64, ls, p);
-          launched = true;
-        }
+        if (st.post) { FP_LAUNCH((conv_deep_kernel<64, DT, ODT, true>), grid, block, st.lds, c.s, p); return 0; }
       }
-      if (!launched) FP_LAUNCH((conv_deep_kernel<64, DT, ODT>), dim3(((rows + 63) / 64) * n128), dim3(256), LDS_DEEP64, ls, p);
-      if (fork_rem) {   // join: the layer's consumers wait for both parts
-        FP_HIP_OK(hipEventRecord(c.ev_join, c.s2));
-        FP_HIP_OK(hipStreamWaitEvent(c.s, c.ev_join, 0));
-      }
+      if (st.post) break;
+      FP_LAUNCH((conv_deep_kernel<64, DT, ODT>), grid, block, st.lds, c.s, p);
       return 0;
-    }
-    if (g_rem_kernel == 1) {
-      const int mt2 = (p.M - p.m_begin + 255) / 256;
-      NetScope ps(c, (tg + "/conv_pp_kernel(rem)").c_str(), flops, bytes);
-      ps.rows(p.m_begin, p.M);
-      FP_LAUNCH((conv_pp_kernel<128, DT, ODT>), dim3(mt2 * n128), dim3(512), LDS3_128, c.s, p);
+    case CK_DEEP128:
+      FP_LAUNCH((conv_deep_kernel<128, DT, ODT>), grid, block, st.lds, c.s, p);
       return 0;
-    }
-  }
-  if (!grp && g_conv_variant == 3 && KT >= 3 && p.ksplit == 1 && L.Cout % 128 == 0) {
-    NetScope ps(c, (tg + "/conv_pp_kernel").c_str(), flops, bytes);
-    ps.rows(p.m_begin, p.M, p.ksplit);
-    FP_LAUNCH((conv_pp_kernel<128, DT, ODT>), dim3(((p.M + 255) / 256) * (L.Cout / 128)), dim3(512), LDS3_128, c.s, p);
-    return 0;
-  }
-  if (L.Cout % 128 == 0 && p.ksplit == 1 && g_gemm_deep && p.m_begin == 0 && KT >= 4 && KT <= 8 && mtiles * (L.Cout / 128) <= 128 &&
-      (!grp || grp->rows % 128 == 0)) {
-    // short-K layers of small problems (the Linear layers of Track): a workgroup is a chain of <= 8 K-steps whose load latency the
-    // two-stage tile below exposes every step; the deep ring keeps three steps in flight
-    NetScope ps(c, (tg + "/conv_deep_kernel(short-K)").c_str(), flops, bytes);
-    ps.rows(p.m_begin, p.M, p.ksplit);
-    FP_LAUNCH((conv_deep_kernel<128, DT, ODT>), dim3(mtiles * (L.Cout / 128)), dim3(256), LDS_DEEP128, c.s, p);
-  } else if (L.Cout % 128 == 0 && !grp && p.ksplit > 1 && g_splitk_deep && p.kt_per >= 4) {
-    // split-K slices on the deep-ring kernel (three K-steps in flight instead of one: a slice is a latency chain)
-    NetScope ps(c, (tg + "/conv_deep_kernel(split-K)").c_str(), flops, bytes);
-    ps.rows(p.m_begin, p.M, p.ksplit);
-    FP_LAUNCH((conv_deep_kernel<128, DT, ODT>), dim3(mtiles * (L.Cout / 128) * p.ksplit), dim3(256), LDS_DEEP128, c.s, p);
-  } else if (L.Cout % 128 == 0) {
-    NetScope ps(c, (tg + "/conv_igemm_kernel<128>").c_str(), flops, bytes);
-    ps.rows(p.m_begin, p.M, p.ksplit);
-    const dim3 grid(mtiles * (L.Cout / 128) * p.ksplit);
-    bool done = false;
+    case CK_IGEMM128:
+      FP_LAUNCH((conv_igemm_kernel<128, 3, DT, ODT>), grid, block, st.lds, c.s, p);
+      return 0;
+    case CK_IGEMM64:
+      FP_LAUNCH((conv_igemm_kernel<64, 3, DT, ODT>), grid, block, st.lds, c.s, p);
+      return 0;
+    case CK_SPLITK_REDUCE: {
 #ifdef FP_TEST_HOOKS
-    if (DT == DT_F16 && g_conv_variant >= 10) {
-      done = true;
-      switch (g_conv_variant) {
-        case 10: FP_LAUNCH((conv_igemm_kernel<128, 0, DT_F16>), grid, dim3(256), LDS_IG128, c.s, p); break;
-        case 11: FP_LAUNCH((conv_igemm_kernel<128, 1, DT_F16>), grid, dim3(256), LDS_IG128, c.s, p); break;
-        case 12: FP_LAUNCH((conv_igemm_kernel<128, 2, DT_F16>), grid, dim3(256), LDS_IG128, c.s, p); break;
-        case 17: FP_LAUNCH((conv_igemm_kernel<128, 7, DT_F16>), grid, dim3(256), LDS_IG128, c.s, p); break;   // no loads
-        case 21: FP_LAUNCH((conv_igemm_kernel<128, 11, DT_F16>), grid, dim3(256), LDS_IG128, c.s, p); break;  // no MFMAs
-        case 25: FP_LAUNCH((conv_igemm_kernel<128, 15, DT_F16>), grid, dim3(256), LDS_IG128, c.s, p); break;  // neither
-        default: done = false;
-      }
-    }
-#endif
-    if (!done) FP_LAUNCH((conv_igemm_kernel<128, 3, DT, ODT>), grid, dim3(256), LDS_IG128, c.s, p);
-  } else {
-    NetScope ps(c, (tg + "/conv_igemm_kernel<64>").c_str(), flops, bytes);
-    ps.rows(p.m_begin, p.M, p.ksplit);
-    FP_LAUNCH((conv_igemm_kernel<64, 3, DT, ODT>), dim3(mtiles * (L.Cout / 64) * p.ksplit), dim3(256), LDS_IG64, c.s, p);
-  }
-  if (p.ksplit > 1) {
-    NetScope ps(c, (tg + "/conv_splitk_reduce_kernel").c_str(), 0, 0);
-    ps.rows(p.m_begin, p.M, p.ksplit, p.post != nullptr);
-    size_t octs = (size_t)(p.M - p.m_begin) * (p.Cout / 8);
-#ifdef FP_TEST_HOOKS
-    ConvParams pr = p;
-    if (g_splitk_ablate) pr.ksplit = p.ksplit - 1;   // ablation: the reduction drops the last slice
+      ConvParams pr = p;
+      if (g_splitk_ablate) pr.ksplit = p.ksplit - 1;   // ablation: the reduction drops the last slice
 #else
-    const ConvParams &pr = p;
+      const ConvParams &pr = p;
 #endif
-    FP_LAUNCH_RAW(conv_splitk_reduce_kernel, dim3((unsigned)((octs + 255) / 256)), dim3(256), 0, c.s, pr);
+      FP_LAUNCH_RAW(conv_splitk_reduce_kernel, grid, block, 0, c.s, pr);
+      return 0;
+    }
   }
+  FP_CHECK(false, std::string("run_conv: the plan chose ") + st.name + " for element types that have no such kernel");
+}
+
+// the fp32 partial slabs of a split-K launch: grown on demand (also in plan-only mode: a planned call leaves the model as a real one would)
+static int ensure_splitk(const Ctx &c, size_t need, float **slab) {
+#ifdef FP_TEST_HOOKS
+  NNScratch *sk = c.ws ? c.ws : &g_hook_ws;
+#else
+  NNScratch *sk = c.ws;
+#endif
+  if (need > sk->splitk_cap) {
+    if (sk->splitk) (void)hipFree(sk->splitk);
+    sk->splitk = nullptr; sk->splitk_cap = 0;
+    g_alloc_epoch++;
+    FP_HIP_OK(hipMalloc((void **)&sk->splitk, need * sizeof(float)));
+    sk->splitk_cap = need;
+  }
+  *slab = sk->splitk;
   return 0;
 }
 
+using ConvLaunch = int (*)(const Ctx &, const ConvStep &, const ConvParams &);
+
 // post / post_fused: a positional table the layer may add to its output (see ConvParams::post); *post_fused tells the
-// caller whether the schedule that ran did (otherwise the caller launches add_pos_embed_kernel)
+// caller whether the plan did (otherwise the caller launches add_pos_embed_kernel)
 // out2 / oinv (8-bit networks): the layer also writes the 8-bit copy of its f16 output, value * oinv[channel] (DT_DUAL_*)
 static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act &in, int NB, int H, int W, int ipad,
                     const Act &out, int opad, bool relu, const Act *res = nullptr, int rpad = 0, int split_imgs = 0,
@@ -1819,7 +1804,7 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
   FP_CHECK(!rscale || (res && res->dt == DT_I8 && L.dt == DT_I8 && !out2 && !grp), "run_conv: unsupported 8-bit residual");
   FP_CHECK(!out2 || (out.dt == DT_F16 && is_q8(out2->dt) && oinv && !grp && !post), "run_conv: unsupported dual output");
   FP_CHECK(out2 || !oinv || (is_q8(out.dt) && (out.dt == L.dt || (L.dt == DT_F16 && out.dt == DT_I8)) && !grp && !post), "run_conv: unsupported scaled 8-bit output");
-  p.post = (const unsigned char *)post;
+  p.post = nullptr;
   if (post_fused) *post_fused = false;
   FP_CHECK(in.dt == L.dt, "run_conv: input element type does not match the layer's weights");
   FP_CHECK(!is_q8(L.dt) || L.cscale, "run_conv: 8-bit layer without scales");
@@ -1830,15 +1815,13 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
   p.res_shared = grp && grp->res_shared;
   p.grp_w_bytes = grp ? (unsigned)((size_t)L.Cout * L.KH * L.KW * L.Cin * es) : 0;
   FP_CHECK(!grp || (grp->rows % 128 == 0 && L.KH == 1 && L.KW == 1 && NB == 2 * grp->rows && !is_q8(L.dt)), "grouped launch: unsupported shape");
-  p.in = (const unsigned char *)in.p; p.w = L.w; p.wfrag = L.wfrag; p.wpack = L.wpack; p.wpack128 = g_big_wpack ? L.wpack128 : nullptr; p.wdeep = g_deep_wpack ? L.wdeep : nullptr; p.bias = L.bias; p.cscale = is_q8(L.dt) ? L.cscale : nullptr;
+  p.in = (const unsigned char *)in.p; p.w = L.w; p.wfrag = L.wfrag; p.wpack = L.wpack; p.wpack128 = L.wpack128; p.wdeep = L.wdeep; p.bias = L.bias; p.cscale = is_q8(L.dt) ? L.cscale : nullptr;
   p.res = res ? (const unsigned char *)res->p : nullptr; p.out = (unsigned char *)out.p;
   p.out_dt = out.dt; p.res_dt = res ? res->dt : out.dt;
   p.NB = NB; p.H = H; p.W = W; p.Cin = L.Cin;
   p.KH = L.KH; p.KW = L.KW; p.stride = L.stride; p.pad = L.pad;
   p.ipad = ipad; p.opad = opad; p.rpad = rpad;
-  p.OH = (H + 2 * L.pad - L.KH) / L.stride + 1;
-  p.OW = (W + 2 * L.pad - L.KW) / L.stride + 1;
-  if (L.KH == 4 && L.pad == 2 && L.stride == 1) { p.OH = H; p.OW = W; }  // s2d stem: asymmetric padding (2 before, 1 after)
+  conv_out_hw(L.KH, L.KW, L.stride, L.pad, H, W, &p.OH, &p.OW);
   p.Cout = L.Cout;
   p.M = NB * p.OH * p.OW;
   p.Ktot = L.KH * L.KW * L.Cin;
@@ -1866,45 +1849,66 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
       if (2 * kt + 1 < 160) { p.koff32[2 * kt] = p.koff[kt]; p.koff32[2 * kt + 1] = p.koff[kt] + 64; }
     }
   }
-  const bool hr = res != nullptr;
   FP_CHECK(!res || res->dt == (rscale ? DT_I8 : is_q8(L.dt) ? DT_F16 : L.dt), "run_conv: the residual must have the layer's operand type (f16 for the 8-bit layers)");
   FP_CHECK(!post || (opad == 0 && split_imgs == 0 && !is_q8(out.dt) && post_fused), "run_conv: positional table on an unsupported layer");
-  struct PostReport {  // the split-K decision is taken inside run_conv_dt (p.ksplit)
-    ConvParams &p; bool *flag;
-    ~PostReport() { if (flag) *flag = p.post != nullptr; }  // (run_conv_dt clears p.post when no schedule that ran implements it)
-  } post_report{p, post_fused};
+
+  // the output type as the kernels' ODT parameter, and the instantiations of that <DT, ODT> pair
+  int odt = -1;
+  ConvLaunch launch = nullptr;
+#define FP_CONV_PAIR(DT_, ODT_) (odt = ODT_, launch = &launch_conv_step<DT_, ODT_>)
   if (out2) {
-    if (L.dt == DT_FP8 && out2->dt == DT_FP8) return run_conv_dt<DT_FP8, DT_DUAL_FP8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-    if (L.dt == DT_I8 && out2->dt == DT_I8) return run_conv_dt<DT_I8, DT_DUAL_I8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-    if (L.dt == DT_F16 && out2->dt == DT_FP8) return run_conv_dt<DT_F16, DT_DUAL_FP8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-    if (L.dt == DT_F16 && out2->dt == DT_I8) return run_conv_dt<DT_F16, DT_DUAL_I8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-    FP_CHECK(false, "run_conv: unsupported combination of operand / dual-output element types");
-  }
+    if (L.dt == DT_FP8 && out2->dt == DT_FP8) FP_CONV_PAIR(DT_FP8, DT_DUAL_FP8);
+    else if (L.dt == DT_I8 && out2->dt == DT_I8) FP_CONV_PAIR(DT_I8, DT_DUAL_I8);
+    else if (L.dt == DT_F16 && out2->dt == DT_FP8) FP_CONV_PAIR(DT_F16, DT_DUAL_FP8);
+    else if (L.dt == DT_F16 && out2->dt == DT_I8) FP_CONV_PAIR(DT_F16, DT_DUAL_I8);
+  } else if (rscale) {   // (run_trunk_i8) the residual is the 8-bit stream copy
 #ifdef FP_TEST_HOOKS
-  if (rscale) {   // (run_trunk_i8) the residual is the 8-bit stream copy
-    if (oinv) return run_conv_dt<DT_I8, DT_QSR_I8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-    FP_CHECK(out.dt == DT_F16, "run_conv: 8-bit residual with an unsupported output type");
-    return run_conv_dt<DT_I8, DT_F16RQ_I8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-  }
+    FP_CHECK(oinv || out.dt == DT_F16, "run_conv: 8-bit residual with an unsupported output type");
+    if (oinv) FP_CONV_PAIR(DT_I8, DT_QSR_I8); else FP_CONV_PAIR(DT_I8, DT_F16RQ_I8);
 #else
-  FP_CHECK(!rscale, "run_conv: 8-bit residual operands exist in the test build only");
+    FP_CHECK(false, "run_conv: 8-bit residual operands exist in the test build only");
 #endif
-  if (oinv) {   // 8-bit output alone, scaled in the epilogue
-    if (L.dt == DT_FP8) return run_conv_dt<DT_FP8, DT_QS_FP8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
+  } else if (oinv) {   // 8-bit output alone, scaled in the epilogue
+    if (L.dt == DT_FP8) FP_CONV_PAIR(DT_FP8, DT_QS_FP8);
+    else if (L.dt == DT_F16) {
 #ifdef FP_TEST_HOOKS
-    if (L.dt == DT_F16) return run_conv_dt<DT_F16, DT_QS_I8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);   // (encodeA.1 in run_trunk_i8)
+      FP_CONV_PAIR(DT_F16, DT_QS_I8);   // (encodeA.1 in run_trunk_i8)
 #else
-    FP_CHECK(L.dt != DT_F16, "run_conv: f16 -> scaled 8-bit alone exists in the test build only");
+      FP_CHECK(false, "run_conv: f16 -> scaled 8-bit alone exists in the test build only");
 #endif
-    return run_conv_dt<DT_I8, DT_QS_I8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
+    } else FP_CONV_PAIR(DT_I8, DT_QS_I8);
   }
-  if (L.dt == DT_FP8 && out.dt == DT_FP8) return run_conv_dt<DT_FP8, DT_FP8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-  if (L.dt == DT_FP8 && out.dt == DT_F16) return run_conv_dt<DT_FP8, DT_F16>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-  if (L.dt == DT_I8 && out.dt == DT_I8) return run_conv_dt<DT_I8, DT_I8>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-  if (L.dt == DT_I8 && out.dt == DT_F16) return run_conv_dt<DT_I8, DT_F16>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-  if (L.dt == DT_BF16 && out.dt == DT_BF16) return run_conv_dt<DT_BF16, DT_BF16>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-  if (L.dt == DT_F16 && out.dt == DT_F16) return run_conv_dt<DT_F16, DT_F16>(c, tag, L, p, NB, H, W, ipad, hr, split_imgs, grp);
-  FP_CHECK(false, "run_conv: unsupported combination of operand / output element types");
+  else if (L.dt == DT_FP8 && out.dt == DT_FP8) FP_CONV_PAIR(DT_FP8, DT_FP8);
+  else if (L.dt == DT_FP8 && out.dt == DT_F16) FP_CONV_PAIR(DT_FP8, DT_F16);
+  else if (L.dt == DT_I8 && out.dt == DT_I8) FP_CONV_PAIR(DT_I8, DT_I8);
+  else if (L.dt == DT_I8 && out.dt == DT_F16) FP_CONV_PAIR(DT_I8, DT_F16);
+  else if (L.dt == DT_BF16 && out.dt == DT_BF16) FP_CONV_PAIR(DT_BF16, DT_BF16);
+  else if (L.dt == DT_F16 && out.dt == DT_F16) FP_CONV_PAIR(DT_F16, DT_F16);
+#undef FP_CONV_PAIR
+  FP_CHECK(launch, "run_conv: unsupported combination of operand / output element types");
+
+  ConvProblem q;
+  q.Cin = L.Cin; q.Cout = L.Cout; q.KH = L.KH; q.KW = L.KW; q.stride = L.stride; q.pad = L.pad; q.algo_K = L.algo_K;
+  q.wfrag = L.wfrag != nullptr; q.wpack = L.wpack != nullptr;
+  q.NB = NB; q.H = H; q.W = W; q.ipad = ipad;
+  q.dt = L.dt; q.odt = odt;
+  q.has_res = res != nullptr; q.split_imgs = split_imgs;
+  q.grp_rows = grp ? grp->rows : 0;
+  q.post = post != nullptr;
+  q.conv_variant = g_conv_variant; q.conv_ablate = g_conv_ablate; q.smallm = g_smallm;
+  ConvPlan plan;
+  if (plan_conv(q, &plan)) return 1;
+  if (post_fused) *post_fused = plan.post_fused;
+  for (int i = 0; i < plan.n; i++) {
+    const ConvStep &st = plan.step[i];
+    p.m_begin = st.m_begin; p.M = st.M;
+    p.ksplit = st.ksplit; p.kt_per = st.kt_per;
+    p.post = st.post ? (const unsigned char *)post : nullptr;
+    if (st.ksplit > 1 && ensure_splitk(c, (size_t)st.ksplit * (st.M - st.m_begin) * L.Cout, &p.partial)) return 1;
+    NetScope ps(c, tag, st);
+    if (launch(c, st, p)) return 1;
+  }
+  return 0;
 }
 
 // plain GEMM rows x Cin -> rows x Cout (Linear layer) on unpadded buffers
@@ -1970,19 +1974,9 @@ static void launch_attention(const Ctx &c, const void *qkv, void *out, int B, in
   }
 #endif
   const int nq = (T + 127) / 128;
-  if (g_att_skv && nq * HEADS * B <= 64 && T > 32) {  // a small grid of long latency chains: split the keys over the waves instead
+  if (nq * HEADS * B <= 64 && T > 32) {  // a small grid of long latency chains: split the keys over the waves instead
     const int nq32 = (T + 31) / 32;
     FP_LAUNCH((attention32_skv_kernel<true, DT>), dim3((unsigned)(nq32 * HEADS * B)), dim3(256), 4 * 2 * (32 * 256 + 8 * 1056), c.s, q, o, T, nq32, tstride, ld);
-    return;
-  }
-  // [r5] a sequence of 400 tokens is 3 query blocks of 128 rows + 16 rows: the 4th block's workgroup stages every key tile for one half-
-  // empty wave.  That tail goes to the split-KV kernel instead (its four waves share the 13 key blocks): one more launch, 25 % fewer
-  // workgroups in the main one.  (Small grids take the split-KV kernel for ALL rows, above: the tail rows come out the same either way.)
-  const int tail = T % 128;
-  if (g_att_tail && tail > 0 && tail <= 32 && T > 128) {
-    const int nq_main = T / 128;
-    FP_LAUNCH_RAW((attention32_kernel<true, DT>), dim3((unsigned)(nq_main * HEADS * B)), dim3(256), 0, c.s, q, o, T, nq_main, tstride, ld);
-    FP_LAUNCH((attention32_skv_kernel<true, DT>), dim3((unsigned)(HEADS * B)), dim3(256), 4 * 2 * (32 * 256 + 8 * 1056), c.s, q, o, T, 1, tstride, ld, nq_main * 4);
     return;
   }
   FP_LAUNCH_RAW((attention32_kernel<true, DT>), dim3((unsigned)(nq * HEADS * B)), dim3(256), 0, c.s, q, o, T, nq, tstride, ld);
@@ -2436,7 +2430,7 @@ static int run_trunk(const Ctx &c, const Arena &a, const void *nn_in, int N, int
 }
 
 bool refiner_fuses_pose(const Net *net) {
-  return net && !net->scorer && g_grouped_heads && g_fuse_pose && net->trans.head.out == 3 && net->rot.head.out == 3;
+  return net && !net->scorer && g_fuse_pose && net->trans.head.out == 3 && net->rot.head.out == 3;
 }
 int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, const void *nn_in, int N,
                     float *trans_dev, float *rot_dev, int shared_b, const PoseUpdateFuse *fuse, bool *fused_out) {
@@ -2445,7 +2439,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
   FP_CHECK(N >= 1 && N <= MAX_BATCH, "[FoundationPose] refine-net batch " + std::to_string(N) + " outside 1..FP_MAX_BATCH = " + std::to_string(MAX_BATCH));
   FP_CHECK(net_q8_ready(net), "[FoundationPose] the 8-bit precisions need a calibration: call fp_calibrate (fp_calibrate_fp8) first");
   if (ensure_scratch(ws, N, s)) return 1;
-  Ctx c{s, prof, net, ws, ws->side, ws->ev_fork, ws->ev_join};
+  Ctx c{s, prof, net, ws};
   const Arena a = carve(ws);
   if (run_trunk(c, a, nn_in, N, shared_b ? 1 : N)) return 1;
   const int dt = net->act_dt;
@@ -2457,7 +2451,7 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
     return L.att.out_proj.wstep && L.lin1.wstep && L.lin2.wstep && L.head.in == EMBED && L.head.out <= 3 && L.att.out_proj.Cin == EMBED && L.lin1.Cin == EMBED &&
            L.lin1.Cout == EMBED && L.lin2.Cin == EMBED && L.lin2.Cout == EMBED && L.att.out_proj.dt == dt && L.lin1.dt == dt && L.lin2.dt == dt;
   };
-  if (N == 1 && g_grouped_heads) {
+  if (N == 1) {
     // Track: both heads in ONE launch per layer (Track is bound by its ~65 dependent launches, not by work).  Rows
     // [0,400) = translation head, [512,912) = rotation head (groups padded to the 128-row tile; the rows in between
     // carry don't-care values that no valid row ever reads: every op here is row-wise, attention is per sequence).
@@ -2650,7 +2644,7 @@ int scorer_features(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
   FP_CHECK(N >= 1 && N <= MAX_BATCH, "[FoundationPose] score-net batch " + std::to_string(N) + " outside 1..FP_MAX_BATCH = " + std::to_string(MAX_BATCH));
   FP_CHECK(net_q8_ready(net), "[FoundationPose] the 8-bit precisions need a calibration: call fp_calibrate (fp_calibrate_fp8) first");
   if (ensure_scratch(ws, N, s)) return 1;
-  Ctx c{s, prof, net, ws, ws->side, ws->ev_fork, ws->ev_join};
+  Ctx c{s, prof, net, ws};
   const Arena a = carve(ws);
   if (run_trunk(c, a, nn_in, N, N)) return 1;
   const size_t rows = (size_t)N * 400;
@@ -2670,7 +2664,7 @@ int scorer_features(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
 int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, const float *feats_dev, int n_total, float *scores_dev) {
   FP_CHECK(net && net->scorer, "scorer_head: wrong network");
   if (ensure_head_scratch(ws, n_total)) return 1;
-  Ctx c{s, prof, net, ws, ws->side, ws->ev_fork, ws->ev_join};
+  Ctx c{s, prof, net, ws};
   const int N = n_total, dt = net->act_dt;
   unsigned char *p = ws->head_buf;
   unsigned char *xf = p; p += (size_t)N * EMBED * 2;

@@ -1590,205 +1590,6 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const ConvParams p) {
   });
 }
 
-#ifdef FP_TEST_HOOKS   // (A/B only: no wall-clock gain, EXPERIMENTS.md R5.2)
-// -------------------------------------------------------------------------------------------------
-// conv_halo_wreg_kernel [r5]: conv_halo_kernel<40> with the WEIGHTS streamed global -> registers instead of through an LDS ring.
-// Why: the resident-halo loop is LDS / MFMA co-limited (DESIGN.md section 4.2: per 32-wide K-step a wave reads 4 weight + 10 pixel
-// fragments = 14 KB for 40 MFMAs; two workgroups per CU need 896 of the 1280 LDS clocks a step pair has) and it meets at a workgroup
-// barrier EVERY K-step only because the weight ring is shared.  Here a wave fetches its own four 16-row weight fragments of a step
-// with four global_load_dwordx4 from the copy in MFMA-fragment order (ConvParams::wfrag: 1 KB of consecutive bytes per instruction,
-// the one address shape the vector L1 serves at full rate; the wave with the same channel half hits the lines its partner fetched),
-// two register sets, the set of step s+2 requested when the last MFMA of step s has been issued:
-//   * LDS reads per K-step: 14 -> 10 KB per wave (-29 %), LDS = the 53 KB halo tile alone;
-//   * barriers: 2 per 64-channel chunk (tile landed / tile free for the refill) instead of 19 -- the waves of a workgroup drift
-//     freely over the 18 K-steps of a chunk;
-//   * no M0 traffic, no weight DMA in the loop.
-// Same arithmetic in the same order as conv_halo_kernel (bit-identical results: the A/B test compares them).
-// -------------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(256, 2) void conv_halo_wreg_kernel(const ConvParams p) {
-  static_assert(!is_q8(DT), "2-byte element types (64-channel chunks)");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int TW = 40, TH = 8, HC = TW + 2, HPX = (TH + 2) * HC;
-  constexpr int HPIECES = (HPX + 7) / 8;
-  constexpr int HPER = (HPIECES + 3) / 4;  // halo DMA pieces per wave
-  constexpr int MI = TW / 4, NI = 4;
-  static_assert(MI == 10, "group split written for 10 pixel fragments");
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int n_tiles = p.Cout / 128;
-  int logical;
-  {
-    const int nblk = gridDim.x, b = blockIdx.x;
-    const int xcd = b & 7, within = b >> 3, q = nblk >> 3, r = nblk & 7;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
-  const int mt = logical / n_tiles, nt = logical - mt * n_tiles;
-  const int tiles_per_img = p.H / TH;
-  const int img = mt / tiles_per_img, ty0 = (mt - img * tiles_per_img) * TH;
-  const int n0 = nt * 128;
-  const int IHp = p.H + 2;
-  const unsigned char *in_b = p.in + ((size_t)(img * IHp + ty0) * HC) * p.cin_b;
-  const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
-
-  auto issue_halo = [&](int chunk) {   // as in conv_halo_kernel
-    const unsigned char *src = in_b + chunk * 128;
-    int lane8;
-    asm volatile("v_lshrrev_b32 %0, 3, %1" : "=v"(lane8) : "v"(lane));
-#pragma unroll
-    for (int i = 0; i < HPER; i++) {
-      const int piece = wave + 4 * i;
-      if (piece < HPIECES) {
-        int q = min(piece * 8 + lane8, HPX - 1);
-        int hy = q / HC, hx = q - hy * HC;
-        int g = ((hx >> 1) & 1) | ((hy & 3) << 1);
-        unsigned off = (unsigned)(q * p.cin_b + (((lane & 7) ^ g) << 4));
-        glds16_asm_x(src + off, lds_base + piece * 1024);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  };
-  const int my_halo = (HPIECES - wave + 3) / 4;   // halo DMA instructions this wave issues per chunk (13 or 14)
-  (void)my_halo;
-  // weight fragments: 16-row tile (n0 + wn*64)/16 + ni of the fragment-order copy, K-step s at + s KB, lane at + 16 lane
-  const unsigned char *wbase = p.wfrag + (size_t)((n0 + wn * 64) >> 4) * ((size_t)16 * p.krow_b) + lane * 16;
-  const size_t wtile = (size_t)16 * p.krow_b;
-  i4 wreg[2][NI];
-  auto load_w = [&](int s, i4 (&w)[NI]) {
-    const unsigned char *wp = wbase + (size_t)s * 1024;
-#pragma unroll
-    for (int ni = 0; ni < NI; ni++) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(w[ni]) : "v"(wp + ni * wtile) : "memory");
-  };
-
-  f4 acc[NI][MI];
-#pragma unroll
-  for (int a = 0; a < NI; a++)
-#pragma unroll
-    for (int b = 0; b < MI; b++) acc[a][b] = (f4){0.f, 0.f, 0.f, 0.f};
-
-  const int li = lane & 15, dy = li >> 2, dx = li & 3, kg = lane >> 4;
-  const int S = p.krow_b >> 6;   // 32-wide K-steps: 18 per 64-channel chunk (9 taps x 2)
-  const int nch = p.cin_b >> 7;
-  issue_halo(0);
-  load_w(0, wreg[0]);
-  load_w(1, wreg[1]);
-  if (p.clk && tid == 0) { p.clk[blockIdx.x * 4] = __builtin_readcyclecounter(); p.clk[blockIdx.x * 4 + 1] = wall_clock64(); }
-  // LDS address of the pixel fragments of (tap, ks): fragment i at + i * 512
-  auto xaddr = [&](int tap, int ks) -> const unsigned char * {
-    const int ky = tap / 3, kx = tap - ky * 3;
-    const int ty = wm * 4 + dy + ky, tx = dx + kx;
-    const int g = ((tx >> 1) & 1) | ((ty & 3) << 1);
-    return smem + (ty * HC + tx) * 128 + (((ks * 4 + kg) ^ g) << 4);
-  };
-  // Software pipeline over the K-steps [r5]: the pixel fragments 0-4 of step s+1 are requested under the last two MFMA groups of step
-  // s (into the registers those groups' predecessors have released), so a step starts with its operands on the way instead of an
-  // exposed LDS round trip; only a chunk's first step (the tile has just been refilled) pays it.
-  i4 xa[3], xb[2];
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // halo tile of chunk 0 + W(0) (issue order: tile, W(0), W(1))
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  {
-    const unsigned char *x0 = xaddr(0, 0);
-#pragma unroll
-    for (int i = 0; i < 3; i++) xa[i] = *reinterpret_cast<const i4 *>(x0 + i * 512);
-#pragma unroll
-    for (int i = 0; i < 2; i++) xb[i] = *reinterpret_cast<const i4 *>(x0 + (3 + i) * 512);
-  }
-  int s = 0;
-  for (int ch = 0; ch < nch; ch++) {
-    for (int tap = 0; tap < 9; tap++) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++, s++) {
-        i4 (&wf)[NI] = wreg[ks];
-        const unsigned char *xs = xaddr(tap, ks);
-        const bool chunk_end = tap == 8 && ks == 1;
-        const unsigned char *xn = chunk_end ? xs : (ks == 0 ? xaddr(tap, 1) : xaddr(tap + 1, 0));
-        // W(s) landed: only the four loads of W(s+1) are younger
-        if (s + 1 < S) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int ni = 0; ni < NI; ni++) asm volatile("" : "+v"(wf[ni]));
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ni = 0; ni < NI; ni++)
-#pragma unroll
-          for (int i = 0; i < 3; i++) acc[ni][i] = mfma32<DT>(wf[ni], xa[i], acc[ni][i]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 3; i++) xa[i] = *reinterpret_cast<const i4 *>(xs + (5 + i) * 512);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ni = 0; ni < NI; ni++)
-#pragma unroll
-          for (int i = 0; i < 2; i++) acc[ni][3 + i] = mfma32<DT>(wf[ni], xb[i], acc[ni][3 + i]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 2; i++) xb[i] = *reinterpret_cast<const i4 *>(xs + (8 + i) * 512);
-        __builtin_amdgcn_sched_barrier(0);
-        const bool refill = chunk_end && ch + 1 < nch;
-        if (refill) {  // the last reads of this chunk's tile are issued: when every wave's have RETURNED the tile is free -- refill it under the MFMAs
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          issue_halo(ch + 1);
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ni = 0; ni < NI; ni++)
-#pragma unroll
-          for (int i = 0; i < 3; i++) acc[ni][5 + i] = mfma32<DT>(wf[ni], xa[i], acc[ni][5 + i]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!chunk_end) {
-#pragma unroll
-          for (int i = 0; i < 3; i++) xa[i] = *reinterpret_cast<const i4 *>(xn + i * 512);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ni = 0; ni < NI; ni++)
-#pragma unroll
-          for (int i = 0; i < 2; i++) acc[ni][8 + i] = mfma32<DT>(wf[ni], xb[i], acc[ni][8 + i]);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!chunk_end) {
-#pragma unroll
-          for (int i = 0; i < 2; i++) xb[i] = *reinterpret_cast<const i4 *>(xn + (3 + i) * 512);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // the step's last MFMA is issued (operands are read at issue): its weight registers take the step after next
-        if (s + 2 < S) load_w(s + 2, wf);
-        if (refill) {
-          // the next chunk's tile: issue order W(s+1), tile, W(s+2) -- when only W(s+2) is outstanding the tile has landed
-          asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-          const unsigned char *x0 = xaddr(0, 0);
-#pragma unroll
-          for (int i = 0; i < 3; i++) xa[i] = *reinterpret_cast<const i4 *>(x0 + i * 512);
-#pragma unroll
-          for (int i = 0; i < 2; i++) xb[i] = *reinterpret_cast<const i4 *>(x0 + (3 + i) * 512);
-        }
-      }
-    }
-  }
-  if (p.clk && tid == 0) { p.clk[blockIdx.x * 4 + 2] = __builtin_readcyclecounter(); p.clk[blockIdx.x * 4 + 3] = wall_clock64(); }
-  conv_epilogue_px<MI, NI, DT, DT>(p, acc, n0 + wn * 64, lane, [&](int mi, int &oimg, int &oh, int &ow) {
-    oimg = img;
-    oh = ty0 + wm * 4 + dy;
-    ow = mi * 4 + dx;
-    return true;
-  });
-}
-
-#endif
 // -------------------------------------------------------------------------------------------------
 // conv_halo8_kernel: the FP8 (e4m3) sibling of conv_halo_kernel<40>: 3x3 / stride 1 on 40x40 maps, input tile + halo of a
 // 128-CHANNEL chunk (again 128 bytes per pixel, so the halo layout, its DMA and its swizzle are byte-identical) resident
@@ -2480,7 +2281,7 @@ __global__ __launch_bounds__(256, 2) void conv_deep_kernel(const ConvParams p) {
 }
 
 // split-K reduction + the conv epilogue: out = relu(sum_s partial[s] + bias + res); thread = (pixel, 8 channels).  2-byte networks
-// only: the 8-bit layers never split K across workgroups (run_conv_dt: plan_splitk).
+// only: the 8-bit layers never split K across workgroups (plan_conv).
 __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParams p) {
   const int nq = p.Cout / 8;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -122,19 +122,13 @@ void fpt_launch_log_clear() { fp::g_launch_log.clear(); }
 int fpt_tap_pe_fused(int net_kind) { return fp::g_tap_pe_fused[net_kind & 1]; }
 void fpt_set_att_variant(int v) { fp::g_att_variant = v; }
 void fpt_set_smallm(int v) { fp::g_smallm = v; }
-void fpt_set_smallm_maxkt(int v) { fp::g_smallm_maxkt = v; }
-void fpt_set_smallx_pf(int v) { fp::g_smallx_pf = v; }
-void fpt_set_gemm_wpack(int v) { fp::g_gemm_wpack = v; }
 void fpt_set_fuse_pose(int v) { fp::g_fuse_pose = v; }
-void fpt_set_halo_wpack(int v) { fp::g_halo_wpack = v; }
 void fpt_set_q8_headroom(float v) { fp::g_q8_headroom = v; }
 void fpt_set_q8_wq(int wclip, int efr, int imgbias) { fp::g_q8_wclip = wclip; fp::g_q8_efr = efr; fp::g_q8_imgbias = imgbias; }
-void fpt_set_halo_wreg(int v) { fp::g_halo_wreg = v; }
 void fpt_set_ln_pmean(int v) { fp::g_ln_pmean = v; }
 void fpt_set_enc_tail(int v) { fp::g_enc_tail = v; }
 void fpt_set_qkv_tile(int v) { fp::g_qkv_tile = v; }
 void fpt_set_qkv_ablate(int v) { fp::g_qkv_ablate = v; }
-void fpt_set_att_tail(int v) { fp::g_att_tail = v; }
 // HOST-ONLY (no HIP call: runs without a GPU, tests/test_quantiser_cpu.py): the INT8 weight quantiser of fp_nn.hip on rows [Cout][taps][Cin]
 // with the activation scales s_in [Cin] folded in and (m_int != null) the calibration frames' mean integer activations [J][Cin]:
 // -> q [Cout][taps][Cin] int8, sw [Cout], tmat_t [Cin][Cout] (tap sums of the rounding errors, transposed)
@@ -150,29 +144,36 @@ int fpt_quantise_i8(const float *rows, int Cout, int ntaps, int Cin, const float
   std::memcpy(tmat_t_out, tm.data(), tm.size() * sizeof(float));
   return 0;
 }
-void fpt_set_rem_fork(int v) { fp::g_rem_fork = v; }
-void fpt_set_big_wpack(int v) { fp::g_big_wpack = v; }
-void fpt_set_deep_wpack(int v) { fp::g_deep_wpack = v; }
-void fpt_set_smallm_maxt16(int v) { fp::g_smallm_maxt16 = v; }
-void fpt_set_gemm_lds_store(int v) { fp::g_gemm_lds_store = v; }
-void fpt_set_conv_lds_store(int v) { fp::g_conv_lds_store = v; }
+// HOST-ONLY (no HIP call: runs without a GPU, tests/test_conv_plan_cpu.py): the schedule plan_conv chooses for one convolution / Linear
+// layer under the current switches.  shape10 = {Cin, Cout, KH, KW, stride, pad, NB, H, W, ipad}; dt / odt = element type of the operands /
+// the kernels' output type (fp_nn.h, DT_*); flags: 1 = residual, 2 = a positional table is offered, 4 / 8 = the layer carries the
+// fragment-order / gemm_k32_kernel's stage-order copy of its weights.  Returns the number of steps (-1 = no plan) and copies up to `max`
+// of them out: fields11 [max][11] = the launch-log record {net = -1, prec = -1, side = 0, m_begin, M, ksplit, pe} + {kernel (ConvKernel),
+// kt_per, grid, LDS bytes}, names [max][name_cap]; *post_fused = every row got the positional table.
+int fpt_plan_conv(const int *shape10, int dt, int odt, int flags, int split_imgs, int grp_rows, int *fields11, char *names, int name_cap, int max, int *post_fused) {
+  fp::ConvProblem q;
+  q.Cin = shape10[0]; q.Cout = shape10[1]; q.KH = shape10[2]; q.KW = shape10[3]; q.stride = shape10[4]; q.pad = shape10[5];
+  q.NB = shape10[6]; q.H = shape10[7]; q.W = shape10[8]; q.ipad = shape10[9];
+  q.dt = dt; q.odt = odt;
+  q.has_res = (flags & 1) != 0; q.post = (flags & 2) != 0; q.wfrag = (flags & 4) != 0; q.wpack = (flags & 8) != 0;
+  q.split_imgs = split_imgs; q.grp_rows = grp_rows;
+  q.conv_variant = fp::g_conv_variant; q.conv_ablate = fp::g_conv_ablate; q.smallm = fp::g_smallm;
+  fp::ConvPlan plan;
+  if (fp::plan_conv(q, &plan)) return -1;
+  for (int i = 0; i < plan.n && i < max; i++) {
+    const fp::ConvStep &st = plan.step[i];
+    const int f[11] = {-1, -1, 0, st.m_begin, st.M, st.ksplit, st.post ? 1 : 0, st.kernel, st.kt_per, (int)st.grid, st.lds};
+    std::memcpy(fields11 + (size_t)i * 11, f, sizeof(f));
+    std::snprintf(names + (size_t)i * name_cap, (size_t)name_cap, "%s", st.name);
+  }
+  if (post_fused) *post_fused = plan.post_fused ? 1 : 0;
+  return plan.n;
+}
 void fpt_set_conv_variant(int v) { fp::g_conv_variant = v; }
 void fpt_set_i8_stream(int v) { fp::g_i8_stream = v; }
 void fpt_set_q8_blocks(int v) { fp::g_q8_blocks = v & fp::Q8_BLOCKS_ALL; }   // [r6] stage mask of 8-bit networks loaded from now on (tools/q8_blocks.py)
 void fpt_set_conv_ablate(int v) { fp::g_conv_ablate = v; }
 void fpt_set_splitk_ablate(int v) { fp::g_splitk_ablate = v; }
-void fpt_set_splitk_target(int v) { fp::g_splitk_target = v; }
-void fpt_set_rem_splitk(int v) { fp::g_rem_splitk = v; }
-void fpt_set_grouped_heads(int v) { fp::g_grouped_heads = v; }
-void fpt_set_gemm_kernel(int v) { fp::g_gemm_kernel = v; }
-void fpt_set_rem_kernel(int v) { fp::g_rem_kernel = v; }
-void fpt_set_rem_small(int v) { fp::g_rem_small = v; }
-void fpt_set_small_deep(int v) { fp::g_small_deep = v; }
-void fpt_set_splitk_mid(int v) { fp::g_splitk_mid = v; }
-void fpt_set_gemm_deep(int v) { fp::g_gemm_deep = v; }
-void fpt_set_att_skv(int v) { fp::g_att_skv = v; }
-void fpt_set_splitk_deep(int v) { fp::g_splitk_deep = v; }
-void fpt_set_splitk_min_kt(int v) { fp::g_splitk_min_kt = v; }
 void fpt_set_raster_strip_rows(int r) { fp::set_raster_strip_rows(r); }
 void fpt_set_raster_strip_threads(int t) { fp::set_raster_strip_threads(t); }
 void fpt_set_tri_rows_tall(int v) { fp::set_tri_rows_tall(v); }

@@ -274,7 +274,7 @@ def test_scorer_matches_torch(model, nets, syn_mesh, syn_scene):
 
 def test_product_library_schedules_by_batch_size(model, nets, syn_mesh, syn_scene):
     """Round-3 review, weak #11: the kernel-level schedule tests run on the TEST build (fpt_* hooks); this one drives the PRODUCT
-    library (`model` = libfoundationpose_amd.so through the C ABI) at the batch sizes where run_conv_dt changes schedule layer by layer
+    library (`model` = libfoundationpose_amd.so through the C ABI) at the batch sizes where plan_conv changes schedule layer by layer
     -- 1 (Track: conv_smallx_kernel, grouped heads, split-key attention), 3 and 12 (small-problem / mid-sized implicit-GEMM paths), 33
     (the resident-halo kernels switch on), 64 and 130 (256x256 ping-pong rounds + ping-pong cascade + deep-ring left-overs) -- against
     the torch fp32 networks: what ships is what is tested.  One set of crops, prefixes of it (the networks are per-hypothesis)."""

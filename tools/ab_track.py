@@ -1,5 +1,5 @@
 """A/B of a library test hook on Track (N = 1, hipGraph replay), same process / same box.
-    python tools/ab_track.py fpt_set_splitk_target 256 128 512"""
+    python tools/ab_track.py fpt_set_smallm 1 0 3"""
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from foundationpose_cpp_amd import FoundationPose, synthetic as syn, weights as W, _lib

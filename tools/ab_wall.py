@@ -1,5 +1,5 @@
 """Wall-clock A/B of a library test hook on the graph-replayed Register (N = 252) and Track, same process / same box: the graphs are
-re-captured after every switch.   python tools/ab_wall.py fpt_set_rem_side 0 1 0 1"""
+re-captured after every switch.   python tools/ab_wall.py fpt_set_enc_tail 0 1 0 1"""
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--ablate", type=int, default=0)
     ap.add_argument("--only", default="")
     ap.add_argument("--clock", action="store_true")
-    ap.add_argument("--hook", nargs=2, action="append", default=[], metavar=("NAME", "VALUE"), help="test hook to set first, e.g. --hook fpt_set_halo2 0")
+    ap.add_argument("--hook", nargs=2, action="append", default=[], metavar=("NAME", "VALUE"), help="test hook to set first, e.g. --hook fpt_set_smallm 0")
     ap.add_argument("--fp8", action="store_true", help="e4m3 operands and output (scales 1/16)")
     ap.add_argument("--res", action="store_true", help="with a residual input (the second conv of a residual block)")
     ap.add_argument("--variant", type=int, default=0, help="0 auto, 1 = 128-px 2-stage kernel, 2 = 256-px 3-stage kernel")

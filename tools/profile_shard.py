@@ -17,7 +17,7 @@ m = FoundationPose(mesh, scene.K, rp, sp)
 rgb, depth, mask = (torch.from_numpy(a).to(dev) for a in (scene.rgb, scene.depth, scene.mask))
 H, Wd = scene.depth.shape
 be = HipShardBackend(m, dev)
-if len(sys.argv) > 3:   # optional test hook: python tools/profile_shard.py 32 fpt_set_rem_small 1
+if len(sys.argv) > 3:   # optional test hook: python tools/profile_shard.py 32 fpt_set_enc_tail 0
     from foundationpose_cpp_amd import _lib
     for hk, hv in zip(sys.argv[2::2], sys.argv[3::2]):   # any number of hook / value pairs
         getattr(_lib.lib(), hk)(int(hv))  # needs _lib.use_test_lib() (done at import above)
