@@ -114,7 +114,7 @@ int main(int argc, char **argv) {
   const int reps = std::atoi(arg(argc, argv, "--reps", mode == "speed_track" ? "5000" : "50"));
   if (root.empty() || refiner.empty() || scorer.empty()) {
     std::fprintf(stderr, "usage: fp_demo --data DIR --refiner R.fpw --scorer S.fpw [--mesh M.obj] [--out DIR] "
-                         "[--mode test|speed_register|speed_track] [--reps N] [--refine-itr N] [--plots]\n");
+                         "[--mode test|speed_register|speed_track] [--reps N] [--refine-itr N] [--plots] [--fit [TOL_MM]] [--lost-below SHARE]\n");
     return 2;
   }
   float K[9];
@@ -141,6 +141,13 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "%s\n", e.what());
     return 1;
   }
+  // --fit [TOL_MM]: pose fit per frame in the pose log (n_model, inlier / front / behind shares of the model) + a LOST? marker when the
+  // inlier share is under --lost-below.  Track's record describes the pose the frame started from (the previous frame's answer).
+  const bool fit = flag(argc, argv, "--fit");
+  const char *fit_arg = arg(argc, argv, "--fit", "5");
+  const float fit_mm = fit && fit_arg[0] != '-' ? (float)std::atof(fit_arg) : 5.0f;
+  const double lost_below = std::atof(arg(argc, argv, "--lost-below", "0.5"));
+  if (fit && !fpm->SetPoseFit(true, fit_mm * 1e-3f)) { std::fprintf(stderr, "%s\n", fpm->last_error().c_str()); return 1; }
   Frame f0;
   if (!read_frame(root, ids[0], H, W, true, f0)) { std::fprintf(stderr, "%s\n", fp_last_error()); return 1; }
   const fp_amd::ImageU8 rgb0{f0.rgb.data(), H, W, 3}, mask0{f0.mask.data(), H, W, 1};
@@ -178,9 +185,14 @@ int main(int argc, char **argv) {
   FILE *log = std::fopen((out + "/poses.txt").c_str(), "w");
   if (!log) { std::fprintf(stderr, "cannot write %s/poses.txt\n", out.c_str()); return 1; }
   const bool all_plots = flag(argc, argv, "--plots");
-  auto emit = [&](const std::string &id, const fp_amd::Pose &p, Frame &f, bool plot) {
+  auto emit = [&](const std::string &id, const fp_amd::Pose &p, Frame &f, bool plot, const fp_pose_fit *r) {
     std::fprintf(log, "%s", id.c_str());
     for (float v : p) std::fprintf(log, " %.9g", v);
+    if (r) {
+      const double n = r->n_model > 0 ? (double)r->n_model : 1.0, in = r->n_inlier / n;
+      std::fprintf(log, " fit %d %.4f %.4f %.4f%s", r->n_model, in, r->n_front / n, r->n_behind / n, in < lost_below ? " LOST?" : "");
+      if (in < lost_below) std::printf("%s: LOST? inliers %.2f front %.2f behind %.2f of %d model pixels\n", id.c_str(), in, r->n_front / n, r->n_behind / n, r->n_model);
+    }
     std::fprintf(log, "\n");
     if (plot) {
       fp_amd::Pose box = pose_mesh2bbox(p, meshes[0].center, ob);
@@ -189,7 +201,10 @@ int main(int argc, char **argv) {
     }
   };
   std::printf("first Pose (%s): t = %.5f %.5f %.5f\n", ids[0].c_str(), pose[12], pose[13], pose[14]);
-  emit(ids[0], pose, f0, true);
+  fp_pose_fit rec;
+  std::vector<fp_pose_fit> recs;
+  if (fit && !fpm->LastRegisterFit(rec)) { std::fprintf(stderr, "%s\n", fpm->last_error().c_str()); return 1; }
+  emit(ids[0], pose, f0, true, fit ? &rec : nullptr);
   FpsCounter c;
   c.Start();
   Frame f;
@@ -201,7 +216,9 @@ int main(int argc, char **argv) {
       return 1;
     }
     c.Count(1);
-    emit(ids[i], tp, f, all_plots || i + 1 == ids.size());
+    const bool have = fit && refine_itr >= 1;
+    if (have && !fpm->LastTrackFit(recs)) { std::fprintf(stderr, "%s\n", fpm->last_error().c_str()); return 1; }
+    emit(ids[i], tp, f, all_plots || i + 1 == ids.size(), have ? &recs[0] : nullptr);
     pose = tp;  // out_pose = track_pose (test_foundationpose.cpp:101)
   }
   std::fclose(log);

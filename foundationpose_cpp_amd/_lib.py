@@ -23,7 +23,15 @@ SYMBOLS = [
     "fp_mesh_load_obj", "fp_mesh_free", "fp_mesh_view", "fp_mesh_orient_bounds",
     "fp_image_read_png", "fp_frame_size", "fp_read_rgb_depth_mask", "fp_read_cam_k", "fp_image_write_png_rgb",
     "fp_draw_bbox3d", "fp_set_precision", "fp_get_precision", "fp_calibrate_fp8", "fp_calibrate", "fp_calibrate_begin", "fp_calibrate_add_frame", "fp_calibrate_finish", "fp_calibrate_abort", "fp_calibrate_frames", "fp_calibration_size", "fp_get_calibration_blob", "fp_set_calibration_blob", "fp_get_calibration", "fp_set_calibration", "fp_set_float_model", "fp_get_float_model", "fp_net_create", "fp_net_destroy", "fp_net_max_batch", "fp_net_blob", "fp_net_infer",
+    "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
 ]
+
+
+class FpPoseFit(C.Structure):
+    """fp_pose_fit of include/foundationpose_amd.h"""
+    _fields_ = [("n_model", C.c_int32), ("n_observed", C.c_int32), ("n_inlier", C.c_int32), ("n_front", C.c_int32),
+                ("n_behind", C.c_int32), ("reserved", C.c_int32), ("sum_dz_q20", C.c_int64), ("mean_dz_m", C.c_float),
+                ("tol_n", C.c_float)]
 
 
 class FpMesh(C.Structure):
@@ -121,6 +129,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_calibrate": [vp, vp, vp, vp, ci, ci, ci, cs, ci], "fp_calibrate_begin": [vp, ci], "fp_calibrate_add_frame": [vp, vp, vp, vp, ci, ci, ci, cs],
         "fp_calibrate_finish": [vp], "fp_calibrate_abort": [vp], "fp_calibrate_frames": [vp], "fp_get_calibration_blob": [vp, ci, vp, C.c_size_t], "fp_set_calibration_blob": [vp, vp, C.c_size_t],
         "fp_get_calibration": [vp, vp], "fp_set_calibration": [vp, vp], "fp_set_float_model": [vp, ci], "fp_get_float_model": [vp],
+        "fp_set_pose_fit": [vp, ci, cf], "fp_get_pose_fit": [vp, vp, vp], "fp_last_track_fit": [vp, vp, ci],
+        "fp_last_register_fit": [vp, vp, vp, ci], "fp_pose_fit_eval": [vp, cs, vp, ci, cf, cf, vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

@@ -10,6 +10,7 @@ column-major float[16] happens here.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -23,6 +24,36 @@ CROP = 160
 
 class FoundationPoseError(RuntimeError):
     pass
+
+
+@dataclasses.dataclass(frozen=True)
+class PoseFit:
+    """fp_pose_fit (include/foundationpose_amd.h): pixel counts of one hypothesis' rendered crop against the depth observed under it"""
+    n_model: int
+    n_observed: int
+    n_inlier: int
+    n_front: int
+    n_behind: int
+    sum_dz_q20: int
+    mean_dz_m: float
+    tol_n: float
+
+    @property
+    def inlier_share(self) -> float:
+        """inliers per model pixel (0 without a model pixel): low = occluded, gone, or the pose is off the surface"""
+        return self.n_inlier / self.n_model if self.n_model else 0.0
+
+    @property
+    def front_share(self) -> float:
+        return self.n_front / self.n_model if self.n_model else 0.0
+
+    @property
+    def behind_share(self) -> float:
+        return self.n_behind / self.n_model if self.n_model else 0.0
+
+
+def _fit(r) -> PoseFit:
+    return PoseFit(r.n_model, r.n_observed, r.n_inlier, r.n_front, r.n_behind, r.sum_dz_q20, float(r.mean_dz_m), float(r.tol_n))
 
 
 def _p(a):
@@ -288,6 +319,39 @@ class FoundationPose:
         idx = C.c_int(-1)
         self._must(self._L.fp_argmax(self._h, _p(s), len(s), C.byref(idx)))
         return idx.value
+
+    # ---- pose fit (include/foundationpose_amd.h "pose fit") --------------------------------------
+    def set_pose_fit(self, on: bool, tol_m: float = 0.005):
+        """Track / Register also report how well the depth under the pose agrees with the model (default off); tol_m in metres."""
+        self._must(self._L.fp_set_pose_fit(self._h, 1 if on else 0, tol_m))
+
+    @property
+    def pose_fit_config(self):
+        """-> (on, tol_m)"""
+        on, tol = C.c_int(0), C.c_float(0)
+        self._must(self._L.fp_get_pose_fit(self._h, C.byref(on), C.byref(tol)))
+        return bool(on.value), tol.value
+
+    def last_track_fit(self, K: int = 1):
+        """records of the last Track (one) / track_multi (K): each describes the pose the last refine iteration STARTED from"""
+        out = (_lib.FpPoseFit * K)()
+        self._must(self._L.fp_last_track_fit(self._h, out, K))
+        return [_fit(r) for r in out]
+
+    def last_register_fit(self, all_hypotheses: bool = False):
+        """-> the winner's record, or (winner, [record per hypothesis]) of the last Register: the FINAL poses at crop ratio 1.1"""
+        win = _lib.FpPoseFit()
+        n = self.num_hypotheses if all_hypotheses else 0
+        every = (_lib.FpPoseFit * max(n, 1))()
+        self._must(self._L.fp_last_register_fit(self._h, C.byref(win), every if all_hypotheses else None, n))
+        return (_fit(win), [_fit(r) for r in every]) if all_hypotheses else _fit(win)
+
+    def pose_fit(self, target_name: str, poses, crop_ratio: float = 1.2, tol_m: float = 0.005):
+        """records of any poses [N,4,4] on the uploaded frame (stage operator; the option need not be on)"""
+        p = to_colmajor(np.asarray(poses, np.float32).reshape(-1, 4, 4))
+        out = (_lib.FpPoseFit * len(p))()
+        self._must(self._L.fp_pose_fit_eval(self._h, target_name.encode(), _p(p), len(p), crop_ratio, tol_m, out))
+        return [_fit(r) for r in out]
 
     # ---- float model of the rendering stage (1 = contracted like nvcc -fmad=true, default; 0 = separate roundings) ----
     def set_float_model(self, fmad: int):

@@ -83,6 +83,14 @@ __global__ void publish_result_kernel(const int *__restrict__ argmax, const int 
   if (i < 18) out_mapped[i] = v;
   __threadfence_system();
 }
+// its neighbour for the pose fit: the winner's record into the model's pinned block (a second tiny publish, no copy command)
+__global__ void publish_fit_kernel(const int *__restrict__ argmax, const PoseFitRec *__restrict__ recs, int N, PoseFitRec *__restrict__ out_mapped) {
+  const int i = argmax[0];
+  PoseFitRec r = {0, 0, 0, 0, 0, 0, 0};
+  if (i >= 0 && i < N) r = recs[i];
+  *out_mapped = r;
+  __threadfence_system();
+}
 hipError_t memcpy_sync(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
   std::lock_guard<std::mutex> lk(g_util_mu);
   hipStream_t s = nullptr;
@@ -468,6 +476,19 @@ struct fp_model {
   float *poses_pinned = nullptr;
   int poses_pinned_cap = 0;
   unsigned long long *digests = nullptr;  // [16] device, debug checkpoints (null = off)
+
+  // pose fit (fp_set_pose_fit).  Nothing below is allocated before the option is first used.
+  bool fit_on = false;
+  float fit_tol_m = 0.005f;
+  unsigned long long *fit_acc = nullptr;   // device [FP_MAX_BATCH, 4]: zeroed once, left zeroed by every launch of the kernel
+  PoseFitRec *fit_rec = nullptr;           // device [2 * FP_MAX_BATCH]: Register's records | fp_pose_fit_eval's
+  PoseFitRec *fit_io = nullptr, *fit_io_dev = nullptr;   // host-pinned, device-mapped [64 Track records | the Register winner's]
+  int fit_track_n = 0;                     // records the last Track left in fit_io (0: none, fit_track_why says why)
+  std::string fit_track_why = "no Track has run", fit_reg_why = "no Register has run";
+  float fit_track_tol[64] = {0}, fit_track_diam[64] = {0};
+  int fit_reg_pending = 0;                 // fp_register_shard_begin enqueued the kernel over this many (= all) hypotheses
+  int fit_reg_n = 0, fit_reg_index = -1;   // records of the last Register in fit_rec (0: none) and its winner
+  float fit_reg_tol = 0, fit_reg_diam = 0;
 
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
   // into a hipGraph and replayed.  The graph bakes buffer addresses, so it is keyed by g_alloc_epoch.
@@ -944,6 +965,44 @@ static OutMode nn_mode(const fp_model *m) {
   return n && net_input_dt(n) == DT_BF16 ? OUT_BF16X8 : OUT_F16X8;
 }
 
+// ---- pose fit ----
+// buffers of the pose fit, allocated at the first use of the option (sized for the largest batch: 76 KB + 152 KB + 2 KB pinned)
+static int ensure_fit(fp_model *m) {
+  if (m->fit_acc && m->fit_rec && m->fit_io) return 0;
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  if (!m->fit_acc) {
+    if (dev_alloc(&m->fit_acc, (size_t)FP_MAX_BATCH * 4)) return 1;
+    FP_HIP_OK(hipMemsetAsync(m->fit_acc, 0, (size_t)FP_MAX_BATCH * 4 * sizeof(unsigned long long), m->stream));   // once: the kernel leaves them zeroed
+  }
+  if (!m->fit_rec && dev_alloc(&m->fit_rec, (size_t)2 * FP_MAX_BATCH)) return 1;
+  if (!m->fit_io) {
+    FP_HIP_OK(hipHostMalloc((void **)&m->fit_io, 65 * sizeof(PoseFitRec), hipHostMallocCoherent));
+    FP_HIP_OK(hipHostGetDevicePointer((void **)&m->fit_io_dev, m->fit_io, 0));
+  }
+  g_alloc_epoch++;
+  return 0;
+}
+static float fit_tol_n(float tol_m, float diameter) { return tol_m / (diameter / 2); }   // formed once, in f32
+static void fit_record(fp_pose_fit *o, const PoseFitRec &r, float tol_n, float diameter) {
+  o->n_model = r.n_model; o->n_observed = r.n_observed; o->n_inlier = r.n_inlier; o->n_front = r.n_front; o->n_behind = r.n_behind;
+  o->reserved = 0;
+  o->sum_dz_q20 = r.sum_dz_q20;
+  o->mean_dz_m = r.n_inlier ? (float)((double)r.sum_dz_q20 / 1048576.0 / (double)r.n_inlier * (double)(diameter / 2)) : 0.0f;
+  o->tol_n = tol_n;
+}
+// the kernel over N hypotheses whose rendered images start at `a` and observed images at `b`, one image apart each
+static int enqueue_pose_fit(fp_model *m, const __half *a, const __half *b, int N, const PoseFitTol &tol, PoseFitRec *out) {
+  ProfScope ps(&m->prof, m->stream, "pose_fit", 0, (double)N * 2 * FP_CROP_HW * FP_CROP_HW * 16);
+  launch_pose_fit(m->stream, a, FP_NN_IN_IMG_HALFS, b, FP_NN_IN_IMG_HALFS, N, tol, nn_mode(m), m->fit_acc, out);
+  FP_HIP_OK(hipGetLastError());
+  return 0;
+}
+static PoseFitTol fit_tol_uniform(float tol_n) {
+  PoseFitTol t = {};
+  t.v[0] = tol_n; t.uniform = 1;
+  return t;
+}
+
 static void destroy_model_impl(fp_model *m);
 fp_model *fp_create_on(int device, const fp_mesh *meshes, int n_meshes, const float K[9], const char *refiner_weights,
                        const char *scorer_weights, int max_h, int max_w) try {
@@ -1054,6 +1113,8 @@ static void destroy_model_impl(fp_model *m) {
   if (m->frame_dev) (void)hipFree(m->frame_dev);
   dev_free(m->grid_dev); dev_free(m->samp_state); dev_free(m->samp_vals); dev_free(m->mask_dev);
   if (m->digests) (void)hipFree(m->digests);
+  dev_free(m->fit_acc); dev_free(m->fit_rec);
+  if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
     if (m->scorer_p[i]) net_free(m->scorer_p[i]);
@@ -1500,13 +1561,15 @@ int fp_argmax(fp_model *m, const float *scores, int N, int *index_out) try {
 // shared_b: all N poses have the same translation (fresh sampler output), so the observed crop -- which depends only on
 // the translation (foundationpose_render.cpp:59, foundationpose_render.cu:78-80) -- is computed and encoded once.
 // poses_in / result_out (Track): the poses are read from / the refined poses also written to host-pinned memory
+// fit_out (Track with the pose fit on, last iteration): the fit of the poses this iteration STARTS from, behind render_and_crop
 static int refine_iteration(fp_model *m, Target *t, int N, bool shared_b, const float *poses_in = nullptr, float *result_out = nullptr,
-                            unsigned *done_flag = nullptr) {
+                            unsigned *done_flag = nullptr, PoseFitRec *fit_out = nullptr) {
   RoctxRange range("refine_iteration (render + crop @1.2, refine-net, pose update)");
   const size_t half = (size_t)N * FP_NN_IN_IMG_HALFS;
   if (render_and_crop(m, t, N, 1.2f /* refine_mode_crop_ratio_ foundationpose.cpp:87 */, nn_mode(m), m->nn_in,
                       m->nn_in + half, nullptr, nullptr, shared_b ? 1 : N, poses_in))
     return 1;
+  if (fit_out && !shared_b && enqueue_pose_fit(m, m->nn_in, m->nn_in + half, N, fit_tol_uniform(fit_tol_n(m->fit_tol_m, t->mesh.diameter)), fit_out)) return 1;
   checkpoint(m, 0, m->recs, (size_t)N * sizeof(PoseRec));
   checkpoint(m, 1, m->clip, (size_t)N * t->mesh.V * 16);
   checkpoint(m, 2, m->attr, (size_t)N * t->mesh.V * 16);
@@ -1543,6 +1606,12 @@ int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, con
   FP_CHECK(shard_count <= FP_MAX_BATCH, "[FoundationPose] hypothesis shard of " + std::to_string(shard_count) +
            " above the batch limit FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH));
   const bool graphable = m->use_graphs && !m->prof.on && !m->digests && !m->calibrating && refine_itr >= 1;
+  m->fit_reg_n = 0; m->fit_reg_pending = 0;
+  m->fit_reg_why = m->fit_on ? "the last Register failed" : "the last Register ran with the pose fit off (fp_set_pose_fit)";
+  // the pose fit covers a Register whose hypotheses all live on this model: a smaller shard computes none
+  const bool fit = m->fit_on && shard_begin == 0 && shard_count == n_all;
+  if (m->fit_on && !fit) m->fit_reg_why = "the last Register was sharded: a shard smaller than the hypothesis grid computes no pose fit";
+  if (fit && ensure_fit(m)) return 1;
   if (upload_frame_async(m, rgb, depth, memspace, H, W)) return 1;
   const int N = shard_count;
   if (sample_hypotheses_async(m, t, mask, memspace, shard_begin, N)) return 1;
@@ -1555,6 +1624,8 @@ int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, con
           if (render_and_crop(m, t, N, 1.1f /* score_mode_crop_ratio_ foundationpose.cpp:88 */, nn_mode(m), m->nn_in,
                               m->nn_in + half, nullptr, nullptr))
             return 1;
+          // the fit of the FINAL poses: only reads the score pass's input
+          if (fit && enqueue_pose_fit(m, m->nn_in, m->nn_in + half, N, fit_tol_uniform(fit_tol_n(m->fit_tol_m, t->mesh.diameter)), m->fit_rec)) return 1;
         }
         RoctxRange r3("score-net trunk + self-attention");
         checkpoint(m, 8, m->clip, (size_t)N * t->mesh.V * 16);
@@ -1568,6 +1639,7 @@ int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, con
     return 1;
   if (feat_dev) *feat_dev = m->feat_dev;
   if (poses_dev) *poses_dev = m->poses_dev;
+  if (fit) { m->fit_reg_pending = N; m->fit_reg_tol = fit_tol_n(m->fit_tol_m, t->mesh.diameter); m->fit_reg_diam = t->mesh.diameter; }
   if (m->defer_begin_sync) return 0;  // fp_register_ex: one synchronisation at the very end
   // synchronises: the returned buffers are complete (and the GPU lock may be released); reports the sampler's verdict
   if (sampler_status(m)) {
@@ -1583,6 +1655,10 @@ int fp_register_shard_finish(fp_model *m, const float *all_feat_dev, const float
   FP_CHECK(m && m->scorer && all_feat_dev && all_poses_dev && N_total > 0 && out_pose,
            "[FoundationPose] fp_register_shard_finish: invalid arguments");
   RoctxRange range("fp_register_shard_finish (cross-hypothesis head + arg-max)");
+  // (the records of a begin over all hypotheses belong to this finish when it ranks exactly those, from the model's own buffers)
+  const bool fit = m->fit_reg_pending > 0 && m->fit_reg_pending == N_total && all_poses_dev == m->poses_dev && m->fit_io_dev;
+  if (m->fit_reg_pending > 0 && !fit) m->fit_reg_why = "the last Register was sharded: its finish ranked other hypotheses than its begin fitted";
+  m->fit_reg_pending = 0; m->fit_reg_n = 0;
   float *scores = m->scores_dev;
   if (N_total > m->cap) {  // gathered hypotheses of all ranks: a persistent buffer, not a malloc/free per Register
     if (N_total > m->scores_all_cap) {
@@ -1612,6 +1688,10 @@ int fp_register_shard_finish(fp_model *m, const float *all_feat_dev, const float
     hipLaunchKernelGGL(fp::publish_result_kernel, dim3(1), dim3(64), 0, m->stream, m->argmax_dev, m->defer_begin_sync ? m->samp_state + 6 : nullptr, m->best_pose_dev, m->result_pinned_dev);
     if (hipGetLastError() != hipSuccess) rc = 1;
   }
+  if (!rc && fit) {
+    hipLaunchKernelGGL(fp::publish_fit_kernel, dim3(1), dim3(1), 0, m->stream, m->argmax_dev, m->fit_rec, N_total, m->fit_io_dev + 64);
+    if (hipGetLastError() != hipSuccess) rc = 1;
+  }
   if (!rc && scores_host &&
       hipMemcpyAsync(scores_host, scores, (size_t)N_total * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess)
     rc = 1;
@@ -1627,6 +1707,7 @@ int fp_register_shard_finish(fp_model *m, const float *all_feat_dev, const float
   if (!rc) {
     std::memcpy(out_pose, &res[2], 64);
     if (best_index) *best_index = res[0];
+    if (fit) { m->fit_reg_n = N_total; m->fit_reg_index = res[0]; }
   }
   if (rc && g_last_error.empty()) set_error("[FoundationPose] fp_register_shard_finish failed");
   return rc;
@@ -1839,6 +1920,11 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
   FP_CHECK(m->refiner, "[FoundationPose] refiner weights not loaded");
   FP_CHECK(hyp_pose, "[FoundationPose] Track: null pose");
   FP_CHECK(!m->track_pending, "[FoundationPose] fp_track_submit: the previous submission has not been waited for");
+  m->fit_track_n = 0;
+  m->fit_track_why = !m->fit_on ? "the last Track ran with the pose fit off (fp_set_pose_fit)"
+                     : refine_itr <= 0 ? "the last Track ran with refine_itr <= 0: nothing was rendered, so there is no record" : "the last Track failed";
+  const bool fit = m->fit_on && refine_itr >= 1;
+  if (fit && ensure_fit(m)) return 1;
   const bool graphable = m->use_graphs && !m->prof.on && !m->digests && !m->calibrating && refine_itr >= 1;
   // a single refine iteration reads the frame only inside the observed-crop window of the hypothesis (ComputeCropWindowTF,
   // foundationpose_render.cpp:25-70, restated on the host in double with a margin): host frames upload just those rows
@@ -1900,7 +1986,7 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
         for (int it = 0; it < refine_itr; it++) {
           const bool last = it == refine_itr - 1;
           if (refine_iteration(m, t, 1, false, it == 0 ? m->track_io_dev : nullptr, last ? m->track_io_dev + 16 : nullptr,
-                               last ? reinterpret_cast<unsigned *>(m->track_io_dev + 32) : nullptr))
+                               last ? reinterpret_cast<unsigned *>(m->track_io_dev + 32) : nullptr, last && fit ? m->fit_io_dev : nullptr))
             return 1;
         }
         return 0;
@@ -1908,6 +1994,7 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
     return 1;
   m->track_flag_armed = armed;
   m->track_pending = true;
+  if (fit) { m->fit_track_n = 1; m->fit_track_tol[0] = fit_tol_n(m->fit_tol_m, t->mesh.diameter); m->fit_track_diam[0] = t->mesh.diameter; }
   return 0;
 }
 
@@ -1980,6 +2067,15 @@ int fp_track_multi(fp_model *m, const void *rgb, const void *depth, int memspace
     targets[i] = t;
     maxV = std::max(maxV, (size_t)t->mesh.V);
   }
+  m->fit_track_n = 0;
+  m->fit_track_why = !m->fit_on ? "the last Track ran with the pose fit off (fp_set_pose_fit)"
+                     : refine_itr <= 0 ? "the last Track ran with refine_itr <= 0: nothing was rendered, so there is no record" : "the last Track failed";
+  const bool fit = m->fit_on && refine_itr >= 1;
+  PoseFitTol fit_tol = {};   // per object: the meshes' diameters differ
+  if (fit) {
+    if (ensure_fit(m)) return 1;
+    for (int i = 0; i < K; i++) fit_tol.v[i] = fit_tol_n(m->fit_tol_m, targets[i]->mesh.diameter);
+  }
   if (upload_frame_async(m, rgb, depth, memspace, H, W)) return 1;
   if (refine_itr <= 0) {
     FP_HIP_OK(hipStreamSynchronize(m->stream));
@@ -2011,6 +2107,8 @@ int fp_track_multi(fp_model *m, const void *rgb, const void *depth, int memspace
               return 1;
             o += n;
           }
+          // one launch over all K objects: object o's crop is image K + o, its threshold its own mesh's
+          if (fit && it == refine_itr - 1 && enqueue_pose_fit(m, m->nn_in, m->nn_in + (size_t)K * IMG, K, fit_tol, m->fit_io_dev)) return 1;
           if (refiner_forward(m->stream, &m->prof, m->refiner, m->ws, m->nn_in, K, m->trans_dev, m->rot_dev, 0)) return 1;
           for (int o = 0; o < K;) {
             int n = 1;
@@ -2026,6 +2124,10 @@ int fp_track_multi(fp_model *m, const void *rgb, const void *depth, int memspace
     return 1;
   FP_HIP_OK(hipStreamSynchronize(m->stream));
   std::memcpy(out_poses, m->multi_io + 64 * 16, (size_t)K * 64);
+  if (fit) {
+    for (int i = 0; i < K; i++) { m->fit_track_tol[i] = fit_tol.v[i]; m->fit_track_diam[i] = targets[i]->mesh.diameter; }
+    m->fit_track_n = K;
+  }
   return 0;
 } FP_CATCH_INT
 
@@ -2045,6 +2147,75 @@ int fp_track_ex(fp_model *m, const void *rgb, const void *depth, int memspace, i
 int fp_track(fp_model *m, const uint8_t *rgb, const float *depth, int H, int W, const float hyp_pose[16],
              const char *target_name, int refine_itr, float out_pose[16]) try {
   return fp_track_ex(m, rgb, depth, FP_HOST, H, W, hyp_pose, target_name, refine_itr, out_pose);
+} FP_CATCH_INT
+
+// ---- pose fit: the option, the getters of the last call's records, the stage operator
+int fp_set_pose_fit(fp_model *m, int on, float tol_m) try {
+  LifeExclusive life;   // may destroy the captured graphs: not while another thread is inside a call
+  FP_CHECK(m != nullptr, "[FoundationPose] null model");
+  FP_CHECK(std::isfinite(tol_m) && tol_m > 0.0f, "[FoundationPose] fp_set_pose_fit: tol_m must be finite and > 0 (metres)");
+  DeviceScope on_device(m->device);
+  if ((on != 0) == m->fit_on && tol_m == m->fit_tol_m) return 0;
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  m->fit_on = on != 0;
+  m->fit_tol_m = tol_m;
+  invalidate_graphs(m);   // the kernel and its threshold are part of the captured bodies
+  return 0;
+} FP_CATCH_INT
+int fp_get_pose_fit(const fp_model *m, int *on, float *tol_m) try {
+  FP_CHECK(m != nullptr, "[FoundationPose] null model");
+  if (on) *on = m->fit_on ? 1 : 0;
+  if (tol_m) *tol_m = m->fit_tol_m;
+  return 0;
+} FP_CATCH_INT
+
+int fp_last_track_fit(fp_model *m, fp_pose_fit *out, int K) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && out, "[FoundationPose] fp_last_track_fit: invalid arguments");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_last_track_fit: the submitted Track has not been waited for (fp_track_wait)");
+  FP_CHECK(m->fit_track_n > 0, "[FoundationPose] fp_last_track_fit: no record: " + m->fit_track_why);
+  FP_CHECK(K >= m->fit_track_n, "[FoundationPose] fp_last_track_fit: the last Track left " + std::to_string(m->fit_track_n) + " records, room for " + std::to_string(K));
+  for (int i = 0; i < m->fit_track_n; i++) fit_record(out + i, m->fit_io[i], m->fit_track_tol[i], m->fit_track_diam[i]);
+  return 0;
+} FP_CATCH_INT
+
+int fp_last_register_fit(fp_model *m, fp_pose_fit *winner, fp_pose_fit *all, int N) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && (winner || all), "[FoundationPose] fp_last_register_fit: invalid arguments");
+  FP_CHECK(m->fit_reg_n > 0, "[FoundationPose] fp_last_register_fit: no record: " + m->fit_reg_why);
+  FP_CHECK(!all || N >= m->fit_reg_n, "[FoundationPose] fp_last_register_fit: the last Register left " + std::to_string(m->fit_reg_n) + " records, room for " + std::to_string(N));
+  if (winner) fit_record(winner, m->fit_io[64], m->fit_reg_tol, m->fit_reg_diam);
+  if (all) {   // diagnostic path: a device -> host copy on the model's stream
+    std::vector<PoseFitRec> recs((size_t)m->fit_reg_n);
+    FP_HIP_OK(hipMemcpyAsync(recs.data(), m->fit_rec, recs.size() * sizeof(PoseFitRec), hipMemcpyDeviceToHost, m->stream));
+    FP_HIP_OK(hipStreamSynchronize(m->stream));
+    for (int i = 0; i < m->fit_reg_n; i++) fit_record(all + i, recs[(size_t)i], m->fit_reg_tol, m->fit_reg_diam);
+  }
+  return 0;
+} FP_CATCH_INT
+
+int fp_pose_fit_eval(fp_model *m, const char *target_name, const float *poses, int N, float crop_ratio, float tol_m, fp_pose_fit *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && poses && out && N > 0, "[FoundationPose] fp_pose_fit_eval: invalid arguments");
+  FP_CHECK(N <= FP_MAX_BATCH, "[FoundationPose] fp_pose_fit_eval: " + std::to_string(N) + " poses, above the batch limit FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH));
+  FP_CHECK(std::isfinite(tol_m) && tol_m > 0.0f, "[FoundationPose] fp_pose_fit_eval: tol_m must be finite and > 0 (metres)");
+  FP_CHECK(std::isfinite(crop_ratio) && crop_ratio > 0.0f, "[FoundationPose] fp_pose_fit_eval: crop_ratio must be finite and > 0");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_pose_fit_eval: a submitted Track has not been waited for (fp_track_wait)");
+  FP_CHECK(m->depth != nullptr, "[FoundationPose] fp_pose_fit_eval: no frame uploaded");
+  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  Target *t = m->find(target_name ? target_name : "");
+  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  if (ensure_fit(m) || upload_poses(m, t, poses, N)) return 1;
+  const size_t half = (size_t)N * FP_NN_IN_IMG_HALFS;
+  if (render_and_crop(m, t, N, crop_ratio, nn_mode(m), m->nn_in, m->nn_in + half, nullptr, nullptr)) return 1;
+  const float tol_n = fit_tol_n(tol_m, t->mesh.diameter);
+  PoseFitRec *recs_dev = m->fit_rec + FP_MAX_BATCH;   // (Register's records stay readable)
+  if (enqueue_pose_fit(m, m->nn_in, m->nn_in + half, N, fit_tol_uniform(tol_n), recs_dev)) return 1;
+  std::vector<PoseFitRec> recs((size_t)N);
+  FP_HIP_OK(hipMemcpyAsync(recs.data(), recs_dev, recs.size() * sizeof(PoseFitRec), hipMemcpyDeviceToHost, m->stream));
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  for (int i = 0; i < N; i++) fit_record(out + i, recs[(size_t)i], tol_n, t->mesh.diameter);
+  return 0;
 } FP_CATCH_INT
 
 int fp_set_precision(fp_model *m, int precision) try {

@@ -1298,4 +1298,89 @@ void launch_pack_f32x6(hipStream_t s, const float *in, void *out, size_t pixels,
   else hipLaunchKernelGGL(pack_f32x6_kernel<OUT_F16X8>, grid, dim3(256), 0, s, in, reinterpret_cast<uint4 *>(out), pixels);
 }
 
+// ---------------------------------------------------------------------------------------------
+// pose fit: how well does the depth under a hypothesis agree with the model rendered at it
+// ---------------------------------------------------------------------------------------------
+
+// The z channel of one 16-byte network-input pixel (r,g,b,x | y,z,0,0 as four dwords: z is the upper half of dword 2), widened
+// exactly to f32, and whether x, y and z are all zero (+-0; a NaN is not zero).
+template <int MODE> __device__ __forceinline__ float fit_z(const uint4 &u) {
+  if constexpr (MODE == OUT_BF16X8) return __uint_as_float(u.z & 0xffff0000u);
+  else return __half2float(__ushort_as_half((unsigned short)(u.z >> 16)));
+}
+__device__ __forceinline__ bool fit_xyz_zero(const uint4 &u) { return (((u.y >> 16) | u.z | (u.z >> 16)) & 0x7fffu) == 0; }
+
+// One hypothesis per blockIdx.y, split over gridDim.x workgroups.  The interior of an image is 80 runs of 320 consecutive 16-byte
+// units (one run per space-to-depth row, s2d_index), so unit u of the interior sits at ((row + 2) * 84 + 2) * 4 + col with
+// row = u / 320, col = u % 320: a wave reads 1 KB per image and instruction, and no pixel coordinates are needed for a sum.
+// Every quantity is an integer, so the result does not depend on the order of the adds: a thread counts in registers, a wave adds
+// its lanes up, wave 0 adds the workgroup's waves up through LDS and issues three 64-bit atomic adds on the hypothesis' accumulator
+// (the five counts fit 16 bits each: at most 25 600 pixels).  The workgroup that draws the last ticket of its hypothesis takes the
+// totals with atomic exchanges against zero -- which also leaves accumulator and ticket zeroed for the next launch, so no memset
+// ever runs in front of this kernel (the host zeroes the block once, when it allocates it) -- and stores the record.
+template <int MODE>
+__global__ __launch_bounds__(256) void pose_fit_kernel(const uint4 *__restrict__ img_a, size_t a_stride, const uint4 *__restrict__ img_b,
+                                                       size_t b_stride, const PoseFitTol tol, unsigned long long *__restrict__ acc,
+                                                       PoseFitRec *__restrict__ out) {
+  constexpr int P = CROP / 2 + 2 * FP_NN_IN_BORDER, RUN = (CROP / 2) * 4, UNITS = CROP * CROP;
+  const int n = blockIdx.y;
+  const float tol_n = tol.v[tol.uniform ? 0 : n];
+  const uint4 *__restrict__ A = img_a + (size_t)n * a_stride;
+  const uint4 *__restrict__ B = img_b + (size_t)n * b_stride;
+  unsigned n_model = 0, n_obs = 0, n_in = 0, n_front = 0, n_behind = 0;
+  long long sum = 0;
+  for (int u = blockIdx.x * 256 + threadIdx.x; u < UNITS; u += gridDim.x * 256) {
+    const int row = u / RUN, col = u - row * RUN;
+    const int at = ((row + FP_NN_IN_BORDER) * P + FP_NN_IN_BORDER) * 4 + col;
+    const uint4 a = A[at], b = B[at];
+    const bool model = !fit_xyz_zero(a);
+    const bool obs = model && ((b.z >> 16) & 0x7fffu) != 0;
+    const float d = fit_z<MODE>(b) - fit_z<MODE>(a);
+    const bool in = obs && fabsf(d) <= tol_n, front = obs && d < -tol_n, behind = obs && d > tol_n;
+    n_model += model; n_obs += obs; n_in += in; n_front += front; n_behind += behind;
+    if (in) sum += (long long)rintf(d * 1048576.0f);
+  }
+  unsigned long long c0 = (unsigned long long)n_model | (unsigned long long)n_obs << 16 | (unsigned long long)n_in << 32 | (unsigned long long)n_front << 48;
+  unsigned long long c1 = n_behind, c2 = (unsigned long long)sum;
+  for (int off = 32; off > 0; off >>= 1) {
+    c0 += __shfl_down(c0, off, 64);
+    c1 += __shfl_down(c1, off, 64);
+    c2 += __shfl_down(c2, off, 64);
+  }
+  __shared__ unsigned long long part[4][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { part[wave][0] = c0; part[wave][1] = c1; part[wave][2] = c2; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  unsigned long long *a4 = acc + (size_t)n * 4;
+  atomicAdd(a4 + 0, part[0][0] + part[1][0] + part[2][0] + part[3][0]);
+  atomicAdd(a4 + 1, part[0][1] + part[1][1] + part[2][1] + part[3][1]);
+  atomicAdd(a4 + 2, part[0][2] + part[1][2] + part[2][2] + part[3][2]);
+  // the three adds have been performed before the ticket is drawn (fence, then the wait spelled out)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (atomicAdd(a4 + 3, 1ull) != (unsigned long long)gridDim.x - 1) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  const unsigned long long t0 = atomicExch(a4 + 0, 0ull), t1 = atomicExch(a4 + 1, 0ull), t2 = atomicExch(a4 + 2, 0ull);
+  atomicExch(a4 + 3, 0ull);
+  PoseFitRec r;
+  r.n_model = (int)(t0 & 0xffff); r.n_observed = (int)(t0 >> 16 & 0xffff); r.n_inlier = (int)(t0 >> 32 & 0xffff); r.n_front = (int)(t0 >> 48);
+  r.n_behind = (int)t1; r.reserved = 0; r.sum_dz_q20 = (long long)t2;
+  out[n] = r;
+  __threadfence_system();   // (Track's records live in host-pinned memory)
+}
+
+int pose_fit_split(int N) {
+  // Register's batches: about eight workgroups per CU keep enough loads in flight to stream from HBM; Track's few hypotheses:
+  // 100 workgroups of one pixel pair per thread instead of a 0.9 MB latency chain through one CU
+  return std::max(1, std::min(100, 2048 / std::max(N, 1)));
+}
+void launch_pose_fit(hipStream_t s, const void *img_a, size_t a_stride_halfs, const void *img_b, size_t b_stride_halfs, int N,
+                     const PoseFitTol &tol, OutMode mode, unsigned long long *acc, PoseFitRec *out) {
+  const dim3 grid(pose_fit_split(N), N);
+  const uint4 *a = reinterpret_cast<const uint4 *>(img_a), *b = reinterpret_cast<const uint4 *>(img_b);
+  if (mode == OUT_BF16X8) hipLaunchKernelGGL(pose_fit_kernel<OUT_BF16X8>, grid, dim3(256), 0, s, a, a_stride_halfs / 8, b, b_stride_halfs / 8, tol, acc, out);
+  else hipLaunchKernelGGL(pose_fit_kernel<OUT_F16X8>, grid, dim3(256), 0, s, a, a_stride_halfs / 8, b, b_stride_halfs / 8, tol, acc, out);
+}
+
 }  // namespace fp

@@ -239,6 +239,22 @@ void launch_sampler(hipStream_t s, const float *filtered_depth, const uint8_t *m
 // f32 [N,160,160,6] -> the networks' 2-byte s2d input tensor (blob-mode entry points); mode = OUT_F16X8 / OUT_BF16X8
 void launch_pack_f32x6(hipStream_t s, const float *in, void *out, size_t pixels, OutMode mode);
 
+// pose fit: per hypothesis n, image A = img_a + n * a_stride (rendered) against image B = img_b + n * b_stride
+// (observed), both single images of the networks' input tensor in `mode`'s element type; strides in elements.  tol: the f32
+// threshold per hypothesis (uniform: v[0] for all; otherwise N <= 64).  acc: [N, 4] 64-bit accumulators that are ZERO on entry and
+// zero again when the kernel has finished (the host zeroes them once, at allocation); out: [N] records, device or host-mapped.
+struct PoseFitTol {
+  float v[64];
+  int uniform;
+};
+struct PoseFitRec {   // the integer part of fp_pose_fit (include/foundationpose_amd.h)
+  int32_t n_model, n_observed, n_inlier, n_front, n_behind, reserved;
+  long long sum_dz_q20;
+};
+int pose_fit_split(int N);   // workgroups per hypothesis
+void launch_pose_fit(hipStream_t s, const void *img_a, size_t a_stride, const void *img_b, size_t b_stride, int N, const PoseFitTol &tol,
+                     OutMode mode, unsigned long long *acc, PoseFitRec *out);
+
 // host helpers (fp_host.cpp part of fp_api.hip)
 std::vector<float> make_rotation_grid(int min_views, int inplane_steps);
 

@@ -121,6 +121,43 @@ int fp_register_ex(fp_model *m, const void *rgb, const void *depth, const void *
 int fp_track_ex(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W,
                 const float hyp_pose[16], const char *target_name, int refine_itr, float out_pose[16]);
 
+/* ---- pose fit: is the answer any good? (new; the reference has no counterpart) ---------------------------------------------
+ * Track returns a pose on every frame and Register the best of its hypotheses, whatever the frame shows.  With this option on, the
+ * calls also compare, per hypothesis, the model rendered at the pose with the depth observed under it -- the two 160x160 crops the
+ * networks are fed anyway, both in units of (p - t_hyp) / (diameter / 2) -- and report integer counts.
+ * A crop pixel is a MODEL pixel when the rendered (x, y, z) is not (0, 0, 0); it is OBSERVED when, in addition, the observed z is not
+ * 0 (no valid depth, outside the frame and more than two diameters away all read 0).  With d = observed z - rendered z (one f32
+ * subtraction) and tol_n = (float)tol_m / ((float)diameter / 2), an observed pixel is an INLIER when |d| <= tol_n, in FRONT when
+ * d < -tol_n (something nearer than the model: an occluder) and BEHIND when d > tol_n (the surface is not where the model says).
+ * The record is bit-reproducible: the same frame and pose give the same record on every call. */
+typedef struct fp_pose_fit {
+  int32_t n_model, n_observed, n_inlier, n_front, n_behind; /* n_observed == n_inlier + n_front + n_behind */
+  int32_t reserved;
+  int64_t sum_dz_q20;   /* sum over inliers of rint((B.z - A.z) * 2^20), normalised units */
+  float   mean_dz_m;    /* host-derived: sum_dz_q20 / 2^20 / n_inlier * diam/2; 0 when n_inlier == 0 */
+  float   tol_n;        /* the f32 threshold the kernel used */
+} fp_pose_fit;
+/* Default off; tol_m in metres, finite and > 0 (a few times the sensor's depth noise).  While off, nothing is launched or allocated
+ * for it.  Toggling, or changing tol_m, drops the captured graphs (the next two calls of each kind run eagerly / capture again). */
+int fp_set_pose_fit(fp_model *m, int on, float tol_m);
+int fp_get_pose_fit(const fp_model *m, int *on, float *tol_m);
+/* The records of the last fp_track / _ex / _submit + _wait (one record) or fp_track_multi (one per object, in order) that ran with the
+ * option on; out holds K >= that many.  A record describes the pose the LAST refine iteration STARTED FROM, against this frame: with
+ * refine_itr == 1 that is the caller's hyp_pose -- usually the previous frame's answer -- so a lost object shows one frame late, and
+ * costs no extra rendering.  (fp_pose_fit_eval scores any pose, the returned one included.)  Fails when the last Track had the
+ * option off, refine_itr <= 0, failed, or has not been waited for. */
+int fp_last_track_fit(fp_model *m, fp_pose_fit *out, int K);
+/* The records of the last fp_register / _ex, or fp_register_shard_begin over ALL hypotheses + fp_register_shard_finish, that ran with
+ * the option on: they describe the FINAL (refined) poses at the score pass's crop ratio 1.1.  winner = the record of the returned
+ * pose; all (may be NULL) = every hypothesis, N >= fp_num_hypotheses() records, fetched with a diagnostic device -> host copy.
+ * Out of scope: fp_register_sharded and shards smaller than the grid compute no fit (the winner's crop lives on one rank only);
+ * the call fails after them.  The 8-bit precisions feed the networks the same 2-byte input tensor, so the records do not change. */
+int fp_last_register_fit(fp_model *m, fp_pose_fit *winner, fp_pose_fit *all, int N);
+/* Stage operator: the records of N (1..FP_MAX_BATCH) poses (host [N*16]) of `target_name` on the uploaded frame at `crop_ratio`
+ * (Track refines at 1.2, Register scores at 1.1), through the same render / crop kernels and the same fit kernel, whether the option
+ * is on or off.  Refuses a partially uploaded frame like the other stage operators. */
+int fp_pose_fit_eval(fp_model *m, const char *target_name, const float *poses, int N, float crop_ratio, float tol_m, fp_pose_fit *out);
+
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 
 /* UploadDataToDevice + convert_depth_to_xyz_map (src/foundationpose.cpp:267-315, src/foundationpose_utils.cu:3-32). */

@@ -149,6 +149,23 @@ public:
   bool SetCalibration(const std::array<float, 32> &amax) { return ok(fp_set_calibration(h_, amax.data())); }
   // float model of the rendering stage: FP_FLOAT_FMAD (default: contracted like the reference's nvcc build) or FP_FLOAT_SEPARATE
   bool SetFloatModel(int model) { return ok(fp_set_float_model(h_, model)); }
+  // pose fit (foundationpose_amd.h "pose fit"): Track / Register also count how much of the model the depth under the pose agrees with.
+  // LastTrackFit: one record per tracked object, of the pose the last refine iteration STARTED from (one frame late with refine_itr 1);
+  // LastRegisterFit: the returned pose's record (all: every hypothesis'); PoseFit: any poses on the uploaded frame (fp_upload_frame)
+  bool SetPoseFit(bool on, float tol_m = 0.005f) { return ok(fp_set_pose_fit(h_, on ? 1 : 0, tol_m)); }
+  bool LastTrackFit(std::vector<fp_pose_fit> &out, size_t objects = 1) {
+    out.resize(objects);
+    return ok(fp_last_track_fit(h_, out.data(), (int)objects));
+  }
+  bool LastRegisterFit(fp_pose_fit &winner, std::vector<fp_pose_fit> *all = nullptr) {
+    if (all) all->resize((size_t)fp_num_hypotheses(h_));
+    return ok(fp_last_register_fit(h_, &winner, all ? all->data() : nullptr, all ? (int)all->size() : 0));
+  }
+  bool PoseFit(const std::string &target_name, const std::vector<Pose> &poses, std::vector<fp_pose_fit> &out, float crop_ratio = 1.2f,
+               float tol_m = 0.005f) {
+    out.resize(poses.size());
+    return ok(fp_pose_fit_eval(h_, target_name.c_str(), poses.empty() ? nullptr : poses[0].data(), (int)poses.size(), crop_ratio, tol_m, out.data()));
+  }
 
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
