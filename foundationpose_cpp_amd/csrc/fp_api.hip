@@ -199,11 +199,6 @@ const RoctxApi &roctx_api() {
 void roctx_push(const char *name) { if (roctx_api().push) (void)roctx_api().push(name); }
 void roctx_pop() { if (roctx_api().pop) (void)roctx_api().pop(); }
 #ifdef FP_TEST_HOOKS
-static int g_upload_cols = 1;   // A/B (fpt_set_upload_cols): Track from host frames uploads the crop window's rectangle, not whole rows (1: packed into pinned memory with its frame record and fetched by a kernel; 3: the same with one 1-D copy command; 2: two 2-D copies straight from the caller's pageable frame)
-#else
-static constexpr int g_upload_cols = 1;
-#endif
-#ifdef FP_TEST_HOOKS
 static int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;   // A/B (fpt_set_calib_opts): steps of the 8-bit calibration
 static int g_vertex_crop = 1;   // A/B (fpt_set_vertex_crop): Track's crop warp (and, unless 2, the triangles' row ranges) inside the vertex launch
 static int g_tri_rows_all_batches = 0;   // A/B (fpt_set_tri_rows(2)): size the buffer for large batches too
@@ -351,6 +346,16 @@ static void dev_free(T *&p) {
   if (p) (void)hipFree(p);
   p = nullptr;
 }
+// pinned host memory and the device's address of it; a block whose device address cannot be had is freed again (*host stays as it was)
+template <typename T>
+static hipError_t pinned_mapped_alloc(T **host, T **dev, size_t bytes, unsigned flags) {
+  T *h = nullptr;
+  hipError_t e = hipHostMalloc((void **)&h, bytes, flags);
+  if (e != hipSuccess) return e;
+  if ((e = hipHostGetDevicePointer((void **)dev, h, 0)) != hipSuccess) { (void)hipHostFree(h); return e; }
+  *host = h;
+  return hipSuccess;
+}
 
 }  // namespace fp
 
@@ -367,6 +372,24 @@ struct CalibFrame {
   std::vector<float> depth;
   int H = 0, W = 0;
   std::string target;
+};
+
+// the calibration record of one 8-bit precision (fp_calibrate; what fp_get_calibration_blob carries), [refiner, scorer] each: the
+// per-channel |max| of the 15 trunk activations of the f16 networks the precision was quantised with ([15][512]) and the corrections
+// solved against them (bias [13][512], token [512], output layer: refiner [8] = trans 3 | rot 3 | 0 0, scorer [512])
+struct CalibRecord {
+  std::vector<float> amax[2], bias_fix[2], tok_fix[2], out_fix[2];
+  // [r5] per-frame channel means of the f16 trunk activations ([slots][15][512], slots <= 16: frame f goes to slot f % slots): the
+  // INT8 weights are rounded with error feedback against them (fp_nn.hip quantise_q8)
+  std::vector<float> fmeans[2];
+  int slots = 0;
+  bool valid() const { return !amax[0].empty(); }   // (a default-constructed record: the precision is not calibrated)
+};
+
+// what a begin leaves on the model for the finish of a LATER call: every begin starts from a cleared record, every finish takes it
+struct RegisterPending {
+  bool sampler = false;   // packed protocol: the begin ran the sampler and left its verdict to the finish
+  int fit_n = 0;          // the begin enqueued the pose fit over this many (= all) hypotheses
 };
 
 struct fp_model {
@@ -400,8 +423,7 @@ struct fp_model {
   size_t win_cap = 0;             // bytes of either block (0: no window path)
   FrameRef frame_pub = {nullptr, nullptr};                 // last published value
   unsigned frame_pub_count = 0;
-  float *multi_io = nullptr, *multi_io_dev = nullptr;  // host-pinned [K poses in | K poses out] of fp_track_multi
-  int multi_io_cap = 0;
+  float *multi_io = nullptr, *multi_io_dev = nullptr;  // host-pinned [64 poses in | 64 poses out] of fp_track_multi
   std::vector<Target *> mg_sig;                        // the object sequence the multi-object graph was captured for
   bool track_pending = false;  // fp_track_submit without its fp_track_wait
   bool frame_partial = false;  // the model's copy of a host frame holds only the rows Track needed (stage operators refuse it)
@@ -431,8 +453,7 @@ struct fp_model {
   // one read-back per Register: device [pose16] + pinned host mirror {idx, sampler status, pose16}
   float *best_pose_dev = nullptr;
   int *result_pinned = nullptr, *result_pinned_dev = nullptr;  // 18 words, device-mapped [r6]: publish_result_kernel writes them (no D2H copy command)
-  bool defer_begin_sync = false;  // fp_register_ex: shard_begin leaves its synchronisation to shard_finish
-  bool shard_sampler_pending = false;  // packed shard protocol: begin ran the sampler, finish reports its verdict
+  RegisterPending reg_pending;
   float *scores_all = nullptr;  // scores of the gathered hypotheses of every rank (sharded Register)
   int scores_all_cap = 0;
   float *gath_feat = nullptr, *gath_poses = nullptr;  // [n_total,512] / [n_total,16] unpacked from the all-gathered rows
@@ -453,22 +474,10 @@ struct fp_model {
   bool fmad = true;
   Net *refiner = nullptr, *scorer = nullptr;  // = refiner_p[prec], scorer_p[prec]
   NNScratch *ws = nullptr;                    // = ws_p[prec]
-  bool calibrating = false;
-  // calibration of the 8-bit precisions (fp_calibrate): [refiner, scorer] per-channel |max| / mean of the 15 trunk activations of
-  // the f16 networks on the calibration frame ([15][512] each), and per 8-bit precision the solved corrections (bias [13][512], token
-  // [512]); they are applied to a precision's networks when those are loaded / re-calibrated
   int calib_session_prec = -1;                 // fp_calibrate_begin .. fp_calibrate_finish: the precision being calibrated (-1: no session)
   std::vector<CalibFrame> calib_frames; // host copies of the session's frames
-  // the |max| record each 8-bit precision was quantised with (empty = not calibrated).  Per precision: two precisions may have been
-  // calibrated on different frames, and a blob must carry the statistics ITS corrections were solved against
-  std::vector<float> calib_amax_q[N_PREC][2];
-  bool calibrated(int prec) const { return prec >= 0 && prec < N_PREC && !calib_amax_q[prec][0].empty(); }
-  std::vector<float> calib_bias_fix[N_PREC][2], calib_tok_fix[N_PREC][2];
-  std::vector<float> calib_out_fix[N_PREC][2];   // output-layer correction: refiner [8] (trans 3 | rot 3 | 0 0), scorer [512]
-  // [r5] per-frame channel means of the f16 trunk activations ([slots][15][512], slots <= FP_CALIB_SLOTS: frame f goes to slot f % slots):
-  // the INT8 weights are rounded with error feedback against them (fp_nn.hip quantise_q8), so a record must carry them
-  std::vector<float> calib_fmeans[N_PREC][2];
-  int calib_slots[N_PREC] = {0};
+  CalibRecord calib[N_PREC];   // (per precision: each may have been calibrated on other frames; applied when its networks are loaded / re-calibrated)
+  bool calibrated(int prec) const { return prec >= 0 && prec < N_PREC && calib[prec].valid(); }
   // pinned staging for hypothesis poses: Register returns from its asynchronous section while the H2D copy may still be
   // queued, so the source must outlive the call (a local std::vector did not: found by the two-model serving test)
   float *track_io = nullptr, *track_io_dev = nullptr;  // host-pinned [hypothesis 16 | refined pose 16 | done flag] of Track and its device address
@@ -486,7 +495,6 @@ struct fp_model {
   int fit_track_n = 0;                     // records the last Track left in fit_io (0: none, fit_track_why says why)
   std::string fit_track_why = "no Track has run", fit_reg_why = "no Register has run";
   float fit_track_tol[64] = {0}, fit_track_diam[64] = {0};
-  int fit_reg_pending = 0;                 // fp_register_shard_begin enqueued the kernel over this many (= all) hypotheses
   int fit_reg_n = 0, fit_reg_index = -1;   // records of the last Register in fit_rec (0: none) and its winner
   float fit_reg_tol = 0, fit_reg_diam = 0;
 
@@ -519,7 +527,16 @@ __global__ void fp_digest_kernel(const uint32_t *p, size_t n, unsigned long long
   for (; i < n; i += (size_t)gridDim.x * blockDim.x) acc += (unsigned long long)p[i] * (2654435761ull + 2 * (i % 1000003ull));
   if (acc) atomicAdd(out, acc);
 }
-static void checkpoint(fp_model *m, int slot, const void *buf, size_t bytes);
+static void checkpoint(fp_model *m, int slot, const void *buf, size_t bytes) {
+#ifndef FP_TEST_HOOKS
+  (void)m; (void)slot; (void)buf; (void)bytes;
+  return;
+#endif
+  if (!m->digests || !buf) return;
+  hipLaunchKernelGGL(fp_digest_kernel, dim3(512), dim3(256), 0, m->stream, (const uint32_t *)buf, bytes / 4, m->digests + slot);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) std::fprintf(stderr, "checkpoint %d (%p, %zu B): %s\n", slot, buf, bytes, hipGetErrorString(e));
+}
 
 static int ensure_capacity(fp_model *m, int N, size_t V) {
   if (N > m->cap) {
@@ -624,17 +641,6 @@ static int render_and_crop(fp_model *m, Target *t, int N, float crop_ratio, OutM
   return 0;
 }
 
-static void checkpoint(fp_model *m, int slot, const void *buf, size_t bytes) {
-#ifndef FP_TEST_HOOKS
-  (void)m; (void)slot; (void)buf; (void)bytes;
-  return;
-#endif
-  if (!m->digests || !buf) return;
-  hipLaunchKernelGGL(fp_digest_kernel, dim3(512), dim3(256), 0, m->stream, (const uint32_t *)buf, bytes / 4, m->digests + slot);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) std::fprintf(stderr, "checkpoint %d (%p, %zu B): %s\n", slot, buf, bytes, hipGetErrorString(e));
-}
-
 static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W, int row0 = 0, int row1 = -1, int col0 = 0, int col1 = -1);
 static int set_rotation_grid(fp_model *m, int steps);
 
@@ -651,6 +657,9 @@ static void invalidate_graphs(fp_model *m) {
   drop_graph(m->rg);
   drop_graph(m->mg);
 }
+
+// whether a call's launch chain may be captured and replayed: not while profiling events or debug digests sit between the launches
+static bool graphable(const fp_model *m, int refine_itr) { return m->use_graphs && !m->prof.on && !m->digests && refine_itr >= 1; }
 
 // Runs `body` (a chain of launches on m->stream reading / writing only model-owned buffers): eagerly the first time a
 // (target, H, W, itr, n) configuration is seen, captured into a hipGraph on the second call once allocations have
@@ -714,7 +723,7 @@ __global__ void unpack_shards_kernel(const float *__restrict__ gathered, int n_t
 // thread of the process is inside a Register / Track call capturing or replaying its graphs.  (Two of ~20 runs of the widened
 // concurrency test died with SIGSEGV inside fp_register_shard_begin on two threads while the main thread was inside fp_create;
 // the calls themselves share nothing but the HIP runtime.)  Calls still run concurrently with each other; GPU work already enqueued
-// keeps running during a creation.  Nested entry points (fp_register_ex -> shard_begin) take it once (thread-local depth).
+// keeps running during a creation.  A guard nested inside another of the same thread takes it once (thread-local depth).
 static std::shared_mutex g_life_rw;
 static thread_local int g_life_depth = 0;
 struct LifeExclusive {   // (entry points nested inside -- fp_calibrate_fp8 runs a Register -- see depth > 0 and take nothing)
@@ -783,7 +792,6 @@ extern "C" {
 void fpt_set_calib_opts(int sweeps, int tok, int out) { g_calib_sweeps = sweeps; g_calib_tok = tok; g_calib_out = out; }
 void fpt_set_vertex_crop(int v) { g_vertex_crop = v; }
 void fpt_set_tri_rows(int v) { g_tri_rows = v != 0; g_tri_rows_all_batches = v == 2; }
-void fpt_set_upload_cols(int v) { g_upload_cols = v; }
 // A/B hook: hipGraph replay of the Track / Register bodies on or off for one model
 int fpt_model_use_graphs(fp_model *m, int on) {
   m->use_graphs = on != 0;
@@ -943,14 +951,14 @@ static int select_precision(fp_model *m, int prec) {
   }
   if ((prec == PREC_FP8 || prec == PREC_INT8) && m->calibrated(prec)) {
     Net *nets[2] = {m->refiner_p[prec], m->scorer_p[prec]};
+    const CalibRecord &r = m->calib[prec];
     for (int k = 0; k < 2; k++)
       if (nets[k] && !net_q8_ready(nets[k]) &&
-          net_apply_q8(nets[k], m->calib_amax_q[prec][k].data(), m->calib_bias_fix[prec][k].empty() ? nullptr : m->calib_bias_fix[prec][k].data(),
-                       m->calib_tok_fix[prec][k].empty() ? nullptr : m->calib_tok_fix[prec][k].data(), true,
-                       m->calib_slots[prec] ? m->calib_fmeans[prec][k].data() : nullptr, m->calib_slots[prec]))
+          net_apply_q8(nets[k], r.amax[k].data(), r.bias_fix[k].empty() ? nullptr : r.bias_fix[k].data(),
+                       r.tok_fix[k].empty() ? nullptr : r.tok_fix[k].data(), true, r.slots ? r.fmeans[k].data() : nullptr, r.slots))
         return 1;
     for (int k = 0; k < 2; k++)
-      if (nets[k] && !m->calib_out_fix[prec][k].empty() && net_q8_set_out_fix(nets[k], m->calib_out_fix[prec][k].data())) return 1;
+      if (nets[k] && !r.out_fix[k].empty() && net_q8_set_out_fix(nets[k], r.out_fix[k].data())) return 1;
   }
   if (!m->ws_p[prec]) m->ws_p[prec] = nn_scratch_create(prec);
   m->prec = prec;
@@ -975,10 +983,7 @@ static int ensure_fit(fp_model *m) {
     FP_HIP_OK(hipMemsetAsync(m->fit_acc, 0, (size_t)FP_MAX_BATCH * 4 * sizeof(unsigned long long), m->stream));   // once: the kernel leaves them zeroed
   }
   if (!m->fit_rec && dev_alloc(&m->fit_rec, (size_t)2 * FP_MAX_BATCH)) return 1;
-  if (!m->fit_io) {
-    FP_HIP_OK(hipHostMalloc((void **)&m->fit_io, 65 * sizeof(PoseFitRec), hipHostMallocCoherent));
-    FP_HIP_OK(hipHostGetDevicePointer((void **)&m->fit_io_dev, m->fit_io, 0));
-  }
+  if (!m->fit_io) FP_HIP_OK(pinned_mapped_alloc(&m->fit_io, &m->fit_io_dev, 65 * sizeof(PoseFitRec), hipHostMallocCoherent));
   g_alloc_epoch++;
   return 0;
 }
@@ -1031,8 +1036,7 @@ fp_model *fp_create_on(int device, const fp_mesh *meshes, int n_meshes, const fl
   // on the first host-frame Track that needs them and grown on demand (ensure_window) [r5] -- a model that is only ever handed device
   // frames, or never tracks, pins no host memory
   if (hipMalloc((void **)&m->frame_dev, 64) != hipSuccess ||
-      hipHostMalloc((void **)&m->frame_pinned, 8 * 64, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void **)&m->frame_pinned_dev, m->frame_pinned, 0) != hipSuccess) {
+      pinned_mapped_alloc(&m->frame_pinned, &m->frame_pinned_dev, 8 * 64, hipHostMallocMapped) != hipSuccess) {
     set_error("[FoundationPose] Failed to allocate the frame record");
     return nullptr;
   }
@@ -1162,8 +1166,7 @@ static int ensure_host_stage(fp_model *m, size_t bytes) {
   if (bytes <= m->host_stage_cap) return 0;
   const size_t cap = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
   uint8_t *stage = nullptr, *stage_dev = nullptr;
-  if (hipHostMalloc((void **)&stage, cap, hipHostMallocMapped) != hipSuccess) { set_error("[FoundationPose] out of pinned host memory for the frame"); return 1; }
-  if (hipHostGetDevicePointer((void **)&stage_dev, stage, 0) != hipSuccess) { (void)hipHostFree(stage); set_error("[FoundationPose] the pinned frame block is not device-mapped"); return 1; }
+  if (pinned_mapped_alloc(&stage, &stage_dev, cap, hipHostMallocMapped) != hipSuccess) { set_error("[FoundationPose] out of pinned, device-mapped host memory for the frame"); return 1; }
   if (m->host_stage) (void)hipHostFree(m->host_stage);
   m->host_stage = stage; m->host_stage_dev = stage_dev; m->host_stage_cap = cap;
   if (!m->host_stage_done) FP_HIP_OK(hipEventCreateWithFlags(&m->host_stage_done, hipEventDisableTiming));
@@ -1194,8 +1197,8 @@ static int ensure_window(fp_model *m, size_t total) {
   FP_HIP_OK(hipStreamSynchronize(m->stream));
   uint8_t *stage = nullptr, *stage_dev = nullptr;
   FrameRef *block = nullptr;
-  if (hipHostMalloc((void **)&stage, cap, hipHostMallocCoherent) != hipSuccess) { set_error("[FoundationPose] out of pinned host memory for the Track window"); return 1; }
-  if (hipHostGetDevicePointer((void **)&stage_dev, stage, 0) != hipSuccess || hipMalloc((void **)&block, cap) != hipSuccess) {
+  if (pinned_mapped_alloc(&stage, &stage_dev, cap, hipHostMallocCoherent) != hipSuccess) { set_error("[FoundationPose] out of pinned host memory for the Track window"); return 1; }
+  if (hipMalloc((void **)&block, cap) != hipSuccess) {
     (void)hipHostFree(stage);
     set_error("[FoundationPose] out of device memory for the Track window");
     return 1;
@@ -1236,19 +1239,19 @@ static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, i
     const size_t o = (size_t)row0 * W, n = (size_t)(row1 - row0) * W;
     const size_t cw = (size_t)(col1 - col0);
     ProfScope ps(&m->prof, m->stream, "h2d_frame", 0, (double)(row1 - row0) * cw * 7);
-    if (n && cw && g_upload_cols && cw * 2 <= (size_t)W) {
-      // the window is less than half the frame wide: a 2-D copy of the rectangle (same device pitch: the kernels index whole frames)
+    if (n && cw && cw * 2 <= (size_t)W) {
+      // the window is less than half the frame wide: only its rectangle is uploaded
       m->frame_partial = true;
       const size_t oc = o + col0, nr = (size_t)(row1 - row0);
       const size_t rgb_bytes = (nr * cw * 3 + 63) & ~(size_t)63, total = 64 + rgb_bytes + nr * cw * 4;
-      if ((g_upload_cols == 1 || g_upload_cols == 3) && ensure_window(m, total) == 0) {
+      if (ensure_window(m, total) == 0) {
         // [r4] The caller's frame is pageable: a 2-D copy from it is staged inside the runtime and holds the calling thread until it
         // is done (two of them: ~48 us of a 260 us Track).  The window is packed here into the model's own pinned block instead (a
         // few hundred short memcpys, ~0.1 MB) TOGETHER with the frame record that describes it, and a small kernel fetches the block
-        // over PCIe (window_fetch_kernel: a copy command of this size costs ~27 us before the graph behind it can start, the kernel
-        // ~6; 2-D copies from pinned memory are no alternative at all: 1.07 ms per Track); crop_body reads the packed window
-        // through the record's pitch and virtual origins.  The caller's buffers are free again when this function returns.  The
-        // pinned block is reused by the next call: a model's Track is waited for (fp_track_wait) before its next submission.
+        // over PCIe (window_fetch_kernel: ~6 us before the graph behind it can start; a copy command of this size ~27 us, 2-D copies
+        // from pinned memory 1.07 ms per Track: both retired, EXPERIMENTS.md); crop_body reads the packed window through the record's
+        // pitch and virtual origins.  The caller's buffers are free again when this function returns.  The pinned block is reused by
+        // the next call: a model's Track is waited for (fp_track_wait) before its next submission.
         uint8_t *dev_block = reinterpret_cast<uint8_t *>(m->frame_dev);
         uint8_t *sr = m->win_stage + 64;
         float *sd = reinterpret_cast<float *>(m->win_stage + 64 + rgb_bytes);
@@ -1266,15 +1269,13 @@ static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, i
         rec.pitch = (int)cw;
         rec.wx0 = col0; rec.wx1 = col1; rec.wy0 = row0; rec.wy1 = row1;
         std::memcpy(m->win_stage, &rec, sizeof(rec));
-        if (g_upload_cols == 3) FP_HIP_OK(hipMemcpyAsync(dev_block, m->win_stage, total, hipMemcpyHostToDevice, m->stream));   // A/B: a copy command
-        else {
-          launch_window_fetch(m->stream, m->win_stage_dev, dev_block, total);
-          FP_HIP_OK(hipGetLastError());
-        }
+        launch_window_fetch(m->stream, m->win_stage_dev, dev_block, total);
+        FP_HIP_OK(hipGetLastError());
         m->frame_pub = rec;
         m->rgb = m->rgb_own; m->depth = m->depth_own;   // (hold nothing of this frame: frame_partial)
         return 0;
       }
+      // the model cannot hold this window (ensure_window): two 2-D copies of the rectangle at the device frame's own pitch
       FP_HIP_OK(hipMemcpy2DAsync(m->rgb_own + oc * 3, (size_t)W * 3, (const uint8_t *)rgb + oc * 3, (size_t)W * 3, cw * 3, nr,
                                  hipMemcpyHostToDevice, m->stream));
       FP_HIP_OK(hipMemcpy2DAsync(m->depth_own + oc, (size_t)W * 4, (const float *)depth + oc, (size_t)W * 4, cw * 4, nr,
@@ -1400,14 +1401,18 @@ static int sample_hypotheses_async(fp_model *m, Target *t, const void *mask, int
   return 0;
 }
 
-// after a synchronisation: the reference's failure modes (foundationpose_sampling.cpp:269,278)
+// the sampler's status word as the reference's failure modes (foundationpose_sampling.cpp:269,278); null: the poses are valid.
+// sampler_status fetches the word and synchronises.
+static const char *sampler_verdict(int st) {
+  return st == 0 ? nullptr : st == 1 ? "[FoundationposeSampling] Mask is all zero."
+       : st == 2 ? "[FoundationposeSampling] No valid value in mask." : "[FoundationposeSampling] sampler did not run";
+}
 static int sampler_status(fp_model *m) {
   int st = 3;
   FP_HIP_OK(hipMemcpyAsync(&st, m->samp_state + 6, 4, hipMemcpyDeviceToHost, m->stream));
   FP_HIP_OK(hipStreamSynchronize(m->stream));
-  FP_CHECK(st != 1, "[FoundationposeSampling] Mask is all zero.");
-  FP_CHECK(st != 2, "[FoundationposeSampling] No valid value in mask.");
-  FP_CHECK(st == 0, "[FoundationposeSampling] sampler did not run");
+  const char *why = sampler_verdict(st);
+  FP_CHECK(!why, why);
   return 0;
 }
 
@@ -1591,11 +1596,22 @@ static int refine_iteration(fp_model *m, Target *t, int N, bool shared_b, const 
   return 0;
 }
 
-int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H,
-                            int W, const char *target_name, int refine_itr, int shard_begin, int shard_count,
-                            float **feat_dev, float **poses_dev) try {
-  SerialGuard serial(m ? m->device : -1);
+// ---- Register: the two halves every Register entry point is made of.  Plain functions: the entry points hold the guard and the
+// exception barrier, and say through the options what is theirs to decide.
+struct RegisterBeginOpts {
+  bool defer_verdict;   // no synchronisation here: the finish that follows on this stream reports the sampler's verdict
+  bool calibration;     // a calibration drives this call (the networks record statistics between their launches): not graphable
+};
+struct RegisterFinishOpts { bool sampler_word; };   // this finish also reports the sampler word of this model (its begin left the verdict to it)
+
+// sampler + refine iterations + score trunk over hypotheses [shard_begin, shard_begin + shard_count) of the grid -> pooled score
+// features / refined poses in the model's buffers.  A failure leaves no pending state, but may leave enqueued work running.
+static int register_begin(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H, int W,
+                          const char *target_name, int refine_itr, int shard_begin, int shard_count, const RegisterBeginOpts &opts,
+                          float **feat_dev, float **poses_dev) {
   RoctxRange range("fp_register_shard_begin (sampler + refine + score trunk)");
+  FP_CHECK(m != nullptr, "[FoundationPose] null model");
+  m->reg_pending = {};
   Target *t = nullptr;
   if (check_frame_args(m, H, W, target_name ? target_name : "", &t)) return 1;
   FP_CHECK(m->refiner && m->scorer, "[FoundationPose] refiner/scorer weights not loaded");
@@ -1605,8 +1621,7 @@ int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, con
            "[FoundationPose] hypothesis shard out of range");
   FP_CHECK(shard_count <= FP_MAX_BATCH, "[FoundationPose] hypothesis shard of " + std::to_string(shard_count) +
            " above the batch limit FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH));
-  const bool graphable = m->use_graphs && !m->prof.on && !m->digests && !m->calibrating && refine_itr >= 1;
-  m->fit_reg_n = 0; m->fit_reg_pending = 0;
+  m->fit_reg_n = 0;
   m->fit_reg_why = m->fit_on ? "the last Register failed" : "the last Register ran with the pose fit off (fp_set_pose_fit)";
   // the pose fit covers a Register whose hypotheses all live on this model: a smaller shard computes none
   const bool fit = m->fit_on && shard_begin == 0 && shard_count == n_all;
@@ -1616,7 +1631,7 @@ int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, con
   const int N = shard_count;
   if (sample_hypotheses_async(m, t, mask, memspace, shard_begin, N)) return 1;
   const size_t half = (size_t)N * FP_NN_IN_IMG_HALFS;
-  if (run_graphed(m, m->rg, t, H, W, refine_itr, N, graphable, [&]() {
+  if (run_graphed(m, m->rg, t, H, W, refine_itr, N, graphable(m, refine_itr) && !opts.calibration, [&]() {
         for (int it = 0; it < refine_itr; it++)
           if (refine_iteration(m, t, N, it == 0 && N > 1)) return 1;  // sampler output: one translation for all hypotheses
         {
@@ -1639,26 +1654,29 @@ int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, con
     return 1;
   if (feat_dev) *feat_dev = m->feat_dev;
   if (poses_dev) *poses_dev = m->poses_dev;
-  if (fit) { m->fit_reg_pending = N; m->fit_reg_tol = fit_tol_n(m->fit_tol_m, t->mesh.diameter); m->fit_reg_diam = t->mesh.diameter; }
-  if (m->defer_begin_sync) return 0;  // fp_register_ex: one synchronisation at the very end
+  if (fit) { m->reg_pending.fit_n = N; m->fit_reg_tol = fit_tol_n(m->fit_tol_m, t->mesh.diameter); m->fit_reg_diam = t->mesh.diameter; }
+  if (opts.defer_verdict) return 0;
   // synchronises: the returned buffers are complete (and the GPU lock may be released); reports the sampler's verdict
   if (sampler_status(m)) {
     set_error(std::string("[FoundationPose] Failed to generate hyp poses!!! ") + g_last_error);
     return 1;
   }
   return 0;
-} FP_CATCH_INT
+}
 
-int fp_register_shard_finish(fp_model *m, const float *all_feat_dev, const float *all_poses_dev, int N_total,
-                             float out_pose[16], int *best_index, float *scores_host) try {
-  SerialGuard serial(m ? m->device : -1);
+// cross-hypothesis head + arg-max over N_total hypotheses (this model's or the gathered ones of every rank) and the call's ONE
+// synchronisation
+static int register_finish(fp_model *m, const float *all_feat_dev, const float *all_poses_dev, int N_total, float out_pose[16],
+                           int *best_index, float *scores_host, const RegisterFinishOpts &opts) {
   FP_CHECK(m && m->scorer && all_feat_dev && all_poses_dev && N_total > 0 && out_pose,
            "[FoundationPose] fp_register_shard_finish: invalid arguments");
   RoctxRange range("fp_register_shard_finish (cross-hypothesis head + arg-max)");
+  const RegisterPending pending = m->reg_pending;
+  m->reg_pending = {};
   // (the records of a begin over all hypotheses belong to this finish when it ranks exactly those, from the model's own buffers)
-  const bool fit = m->fit_reg_pending > 0 && m->fit_reg_pending == N_total && all_poses_dev == m->poses_dev && m->fit_io_dev;
-  if (m->fit_reg_pending > 0 && !fit) m->fit_reg_why = "the last Register was sharded: its finish ranked other hypotheses than its begin fitted";
-  m->fit_reg_pending = 0; m->fit_reg_n = 0;
+  const bool fit = pending.fit_n > 0 && pending.fit_n == N_total && all_poses_dev == m->poses_dev && m->fit_io_dev;
+  if (pending.fit_n > 0 && !fit) m->fit_reg_why = "the last Register was sharded: its finish ranked other hypotheses than its begin fitted";
+  m->fit_reg_n = 0;
   float *scores = m->scores_dev;
   if (N_total > m->cap) {  // gathered hypotheses of all ranks: a persistent buffer, not a malloc/free per Register
     if (N_total > m->scores_all_cap) {
@@ -1670,22 +1688,19 @@ int fp_register_shard_finish(fp_model *m, const float *all_feat_dev, const float
     scores = m->scores_all;
   }
   if (!m->best_pose_dev && dev_alloc(&m->best_pose_dev, 16)) return 1;
-  if (!m->result_pinned) {
-    FP_HIP_OK(hipHostMalloc((void **)&m->result_pinned, 64 * sizeof(int), hipHostMallocMapped));
-    FP_HIP_OK(hipHostGetDevicePointer((void **)&m->result_pinned_dev, m->result_pinned, 0));
-  }
+  if (!m->result_pinned) FP_HIP_OK(pinned_mapped_alloc(&m->result_pinned, &m->result_pinned_dev, 64 * sizeof(int), hipHostMallocMapped));
   int rc = scorer_head(m->stream, &m->prof, m->scorer, m->ws, all_feat_dev, N_total, scores);
   if (!rc) checkpoint(m, 13, scores, (size_t)N_total * 4);
   if (!rc) {
     ProfScope ps(&m->prof, m->stream, "argmax");
     launch_argmax(m->stream, scores, N_total, m->argmax_dev, all_poses_dev, m->best_pose_dev);
   }
-  // ONE synchronisation: winner index, the sampler's status word (when this call also ran the sampler) and the pose
+  // ONE synchronisation: winner index, the sampler's status word (opts.sampler_word) and the pose
   // [r6] written by a kernel into the pinned, device-mapped block: no device -> host copy command in front of the synchronisation
   int *res = m->result_pinned;
   res[0] = -3; res[1] = 3;   // (overwritten by the kernel; what a kernel that never ran would leave is an error, not a stale winner)
   if (!rc) {
-    hipLaunchKernelGGL(fp::publish_result_kernel, dim3(1), dim3(64), 0, m->stream, m->argmax_dev, m->defer_begin_sync ? m->samp_state + 6 : nullptr, m->best_pose_dev, m->result_pinned_dev);
+    hipLaunchKernelGGL(fp::publish_result_kernel, dim3(1), dim3(64), 0, m->stream, m->argmax_dev, opts.sampler_word ? m->samp_state + 6 : nullptr, m->best_pose_dev, m->result_pinned_dev);
     if (hipGetLastError() != hipSuccess) rc = 1;
   }
   if (!rc && fit) {
@@ -1699,9 +1714,7 @@ int fp_register_shard_finish(fp_model *m, const float *all_feat_dev, const float
   if (!rc) {
     // the sampler's verdict first: on failure the caller's pose is left untouched, like the reference, which returns
     // false before it writes out_pose_in_mesh (foundationpose.cpp:196-201)
-    if (res[1] == 1) { set_error("[FoundationPose] Failed to generate hyp poses!!! [FoundationposeSampling] Mask is all zero."); rc = 1; }
-    else if (res[1] == 2) { set_error("[FoundationPose] Failed to generate hyp poses!!! [FoundationposeSampling] No valid value in mask."); rc = 1; }
-    else if (res[1] != 0) { set_error("[FoundationPose] Failed to generate hyp poses!!! sampler did not run"); rc = 1; }
+    if (const char *why = sampler_verdict(res[1])) { set_error(std::string("[FoundationPose] Failed to generate hyp poses!!! ") + why); rc = 1; }
     else if (res[0] == -2) { set_error("[FoundationPose] scores are not finite (a rank of a sharded Register reported a failed shard, or the weights are broken)"); rc = 1; }
   }
   if (!rc) {
@@ -1711,6 +1724,31 @@ int fp_register_shard_finish(fp_model *m, const float *all_feat_dev, const float
   }
   if (rc && g_last_error.empty()) set_error("[FoundationPose] fp_register_shard_finish failed");
   return rc;
+}
+
+// begin + finish back to back on one stream over the whole grid: a single synchronisation, at the end
+static int register_whole(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H, int W,
+                          const char *target_name, int refine_itr, float out_pose[16], bool calibration) {
+  FP_CHECK(m != nullptr, "[FoundationPose] null model");
+  float *feat = nullptr, *poses = nullptr;
+  if (register_begin(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, 0, m->n_hyp(), {/*defer_verdict*/ true, calibration}, &feat, &poses)) {
+    (void)hipStreamSynchronize(m->stream);
+    return 1;
+  }
+  return register_finish(m, feat, poses, m->n_hyp(), out_pose, nullptr, nullptr, {/*sampler_word*/ true});
+}
+
+int fp_register_shard_begin(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H,
+                            int W, const char *target_name, int refine_itr, int shard_begin, int shard_count,
+                            float **feat_dev, float **poses_dev) try {
+  SerialGuard serial(m ? m->device : -1);
+  return register_begin(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, shard_begin, shard_count, RegisterBeginOpts{}, feat_dev, poses_dev);
+} FP_CATCH_INT
+
+int fp_register_shard_finish(fp_model *m, const float *all_feat_dev, const float *all_poses_dev, int N_total,
+                             float out_pose[16], int *best_index, float *scores_host) try {
+  SerialGuard serial(m ? m->device : -1);
+  return register_finish(m, all_feat_dev, all_poses_dev, N_total, out_pose, best_index, scores_host, RegisterFinishOpts{});
 } FP_CATCH_INT
 
 int fp_download(fp_model *m, void *dst_host, const void *src_dev, size_t bytes) try {
@@ -1722,37 +1760,32 @@ int fp_download(fp_model *m, void *dst_host, const void *src_dev, size_t bytes) 
 } FP_CATCH_INT
 
 // Sharded Register without host stalls: everything is enqueued on the model's stream, nothing is allocated or synchronised.
-int fp_register_shard_begin_packed(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H,
-                                   int W, const char *target_name, int refine_itr, int shard_begin, int shard_count,
-                                   float *packed_dev, int rows_per_rank) try {
-  SerialGuard serial(m ? m->device : -1);
+static int register_begin_packed(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H, int W,
+                                 const char *target_name, int refine_itr, int shard_begin, int shard_count, float *packed_dev,
+                                 int rows_per_rank) {
   FP_CHECK(m && packed_dev && rows_per_rank >= shard_count && shard_count >= 0, "[FoundationPose] fp_register_shard_begin_packed: invalid arguments");
   float *feat = nullptr, *poses = nullptr;
+  int rc;
   if (shard_count > 0) {
-    m->defer_begin_sync = true;
-    int rc = fp_register_shard_begin(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, shard_begin, shard_count, &feat, &poses);
-    m->defer_begin_sync = false;
-    if (rc) { (void)hipStreamSynchronize(m->stream); return 1; }
-    m->shard_sampler_pending = true;
+    rc = register_begin(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, shard_begin, shard_count, {/*defer_verdict*/ true, /*calibration*/ false},
+                        &feat, &poses);
   } else {
     // an empty shard still runs the (cheap) sampler, so that a bad mask fails on EVERY rank alike
+    m->reg_pending = {};
     Target *t = nullptr;
     if (check_frame_args(m, H, W, target_name ? target_name : "", &t)) return 1;
     FP_CHECK(mask != nullptr, "[FoundationPose] Register needs a mask");
-    if (upload_frame_async(m, rgb, depth, memspace, H, W) || sample_hypotheses_async(m, t, mask, memspace, 0, 1)) {
-      (void)hipStreamSynchronize(m->stream);
-      return 1;
-    }
-    m->shard_sampler_pending = true;
+    rc = upload_frame_async(m, rgb, depth, memspace, H, W) || sample_hypotheses_async(m, t, mask, memspace, 0, 1);
   }
+  if (rc) { (void)hipStreamSynchronize(m->stream); return 1; }
+  m->reg_pending.sampler = true;
   const int n = rows_per_rank * 528;
   hipLaunchKernelGGL(pack_shard_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, feat, poses, shard_count, rows_per_rank, packed_dev, m->samp_state + 6);
   FP_HIP_OK(hipGetLastError());
   return 0;
-} FP_CATCH_INT
+}
 
-int fp_register_shard_finish_packed(fp_model *m, const float *gathered_dev, int n_total, float out_pose[16], int *best_index) try {
-  SerialGuard serial(m ? m->device : -1);
+static int register_finish_packed(fp_model *m, const float *gathered_dev, int n_total, float out_pose[16], int *best_index) {
   FP_CHECK(m && gathered_dev && n_total > 0 && out_pose, "[FoundationPose] fp_register_shard_finish_packed: invalid arguments");
   if (n_total > m->gath_cap) {
     FP_HIP_OK(hipStreamSynchronize(m->stream));
@@ -1763,12 +1796,20 @@ int fp_register_shard_finish_packed(fp_model *m, const float *gathered_dev, int 
   }
   const int n = n_total * 528;
   hipLaunchKernelGGL(unpack_shards_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, gathered_dev, n_total, m->gath_feat, m->gath_poses);
-  // the sampler's verdict of this rank's begin (if it had a shard) is fetched together with the result
-  m->defer_begin_sync = m->shard_sampler_pending;
-  m->shard_sampler_pending = false;
-  int rc = fp_register_shard_finish(m, m->gath_feat, m->gath_poses, n_total, out_pose, best_index, nullptr);
-  m->defer_begin_sync = false;
-  return rc;
+  // the sampler's verdict of this rank's begin is fetched together with the result
+  return register_finish(m, m->gath_feat, m->gath_poses, n_total, out_pose, best_index, nullptr, {/*sampler_word*/ m->reg_pending.sampler});
+}
+
+int fp_register_shard_begin_packed(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H,
+                                   int W, const char *target_name, int refine_itr, int shard_begin, int shard_count,
+                                   float *packed_dev, int rows_per_rank) try {
+  SerialGuard serial(m ? m->device : -1);
+  return register_begin_packed(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, shard_begin, shard_count, packed_dev, rows_per_rank);
+} FP_CATCH_INT
+
+int fp_register_shard_finish_packed(fp_model *m, const float *gathered_dev, int n_total, float out_pose[16], int *best_index) try {
+  SerialGuard serial(m ? m->device : -1);
+  return register_finish_packed(m, gathered_dev, n_total, out_pose, best_index);
 } FP_CATCH_INT
 
 // ---- native sharded Register: begin -> ONE ncclAllGather (RCCL over xGMI) on the model's stream -> finish.  No torch, no events
@@ -1856,22 +1897,20 @@ int fp_register_sharded(fp_model *m, void *nccl_comm, const void *rgb, const voi
   const size_t need_send = (size_t)per * 528, need_recv = (size_t)world * per * 528;
   if (need_send > m->shard_send_cap || need_recv > m->shard_recv_cap) {
     if (hipStreamSynchronize(m->stream) != hipSuccess) return cannot_join("the model's stream is in an error state");
-    if (need_send > m->shard_send_cap) {
-      dev_free(m->shard_send); m->shard_send_cap = 0;
-      if (hipMalloc((void **)&m->shard_send, need_send * sizeof(float)) != hipSuccess) { m->shard_send = nullptr; return cannot_join("out of device memory for the exchange buffers"); }
-      m->shard_send_cap = need_send;
-    }
-    if (need_recv > m->shard_recv_cap) {
-      dev_free(m->shard_recv); m->shard_recv_cap = 0;
-      if (hipMalloc((void **)&m->shard_recv, need_recv * sizeof(float)) != hipSuccess) { m->shard_recv = nullptr; return cannot_join("out of device memory for the exchange buffers"); }
-      m->shard_recv_cap = need_recv;
-    }
+    auto grow = [](float *&buf, size_t &cap, size_t need) {
+      if (need <= cap) return true;
+      dev_free(buf); cap = 0;
+      if (hipMalloc((void **)&buf, need * sizeof(float)) != hipSuccess) { buf = nullptr; return false; }
+      cap = need;
+      return true;
+    };
+    if (!grow(m->shard_send, m->shard_send_cap, need_send) || !grow(m->shard_recv, m->shard_recv_cap, need_recv))
+      return cannot_join("out of device memory for the exchange buffers");
   }
-  const int rc_begin = fp_register_shard_begin_packed(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, begin, count, m->shard_send, per);
+  const int rc_begin = register_begin_packed(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, begin, count, m->shard_send, per);
   std::string begin_error;
   if (rc_begin) {
     begin_error = g_last_error;
-    m->shard_sampler_pending = false;
     hipLaunchKernelGGL(poison_rows_kernel, dim3((unsigned)((need_send + 255) / 256)), dim3(256), 0, m->stream, m->shard_send, need_send);
   }
   if (world > 1) {
@@ -1889,26 +1928,25 @@ int fp_register_sharded(fp_model *m, void *nccl_comm, const void *rgb, const voi
     set_error(begin_error);
     return 1;
   }
-  return fp_register_shard_finish_packed(m, m->shard_recv, n_total, out_pose, best_index);
+  return register_finish_packed(m, m->shard_recv, n_total, out_pose, best_index);
 } FP_CATCH_INT
 
 int fp_register_ex(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H, int W,
                    const char *target_name, int refine_itr, float out_pose[16]) try {
   SerialGuard serial(m ? m->device : -1);
-  FP_CHECK(m != nullptr, "[FoundationPose] null model");
-  float *feat = nullptr, *poses = nullptr;
-  m->defer_begin_sync = true;  // begin + finish back to back on one stream: a single synchronisation, at the end
-  int rc = fp_register_shard_begin(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, 0, m->n_hyp(), &feat, &poses);
-  if (!rc) rc = fp_register_shard_finish(m, feat, poses, m->n_hyp(), out_pose, nullptr, nullptr);
-  else (void)hipStreamSynchronize(m->stream);
-  m->defer_begin_sync = false;
-  return rc;
+  return register_whole(m, rgb, depth, mask, memspace, H, W, target_name, refine_itr, out_pose, false);
 } FP_CATCH_INT
 
 int fp_register(fp_model *m, const uint8_t *rgb, const float *depth, const uint8_t *mask, int H, int W,
                 const char *target_name, int refine_itr, float out_pose[16]) try {
   return fp_register_ex(m, rgb, depth, mask, FP_HOST, H, W, target_name, refine_itr, out_pose);
 } FP_CATCH_INT
+
+// why a Track that is starting leaves no fit record, unless it succeeds with the option on (fp_last_track_fit reports it)
+static const char *no_track_fit_because(const fp_model *m, int refine_itr) {
+  return !m->fit_on ? "the last Track ran with the pose fit off (fp_set_pose_fit)"
+       : refine_itr <= 0 ? "the last Track ran with refine_itr <= 0: nothing was rendered, so there is no record" : "the last Track failed";
+}
 
 // Track in two halves: everything is ENQUEUED by fp_track_submit (frame upload, the replayed graph); fp_track_wait synchronises the
 // model's stream and hands the pose over.  One host thread can so keep several models (objects) in flight at once.
@@ -1921,11 +1959,9 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
   FP_CHECK(hyp_pose, "[FoundationPose] Track: null pose");
   FP_CHECK(!m->track_pending, "[FoundationPose] fp_track_submit: the previous submission has not been waited for");
   m->fit_track_n = 0;
-  m->fit_track_why = !m->fit_on ? "the last Track ran with the pose fit off (fp_set_pose_fit)"
-                     : refine_itr <= 0 ? "the last Track ran with refine_itr <= 0: nothing was rendered, so there is no record" : "the last Track failed";
+  m->fit_track_why = no_track_fit_because(m, refine_itr);
   const bool fit = m->fit_on && refine_itr >= 1;
   if (fit && ensure_fit(m)) return 1;
-  const bool graphable = m->use_graphs && !m->prof.on && !m->digests && !m->calibrating && refine_itr >= 1;
   // a single refine iteration reads the frame only inside the observed-crop window of the hypothesis (ComputeCropWindowTF,
   // foundationpose_render.cpp:25-70, restated on the host in double with a margin): host frames upload just those rows
   int row0 = 0, row1 = -1, col0 = 0, col1 = -1;
@@ -1963,10 +1999,8 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
     }
   }
   if (upload_frame_async(m, rgb, depth, memspace, H, W, row0, row1, col0, col1)) return 1;
-  if (!m->track_io) {
-    FP_HIP_OK(hipHostMalloc((void **)&m->track_io, 48 * sizeof(float), hipHostMallocCoherent));   // (fine-grained: the done flag is read while the graph is still running)
-    FP_HIP_OK(hipHostGetDevicePointer((void **)&m->track_io_dev, m->track_io, 0));
-  }
+  // (fine-grained: the done flag is read while the graph is still running)
+  if (!m->track_io) FP_HIP_OK(pinned_mapped_alloc(&m->track_io, &m->track_io_dev, 48 * sizeof(float), hipHostMallocCoherent));
   m->track_flag_armed = false;
   if (refine_itr <= 0) {  // no refinement requested: the hypothesis is the answer (the reference's loop runs zero times)
     std::memcpy(m->track_io + 16, hyp_pose, 64);
@@ -1982,7 +2016,7 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
   volatile unsigned *flag = reinterpret_cast<volatile unsigned *>(m->track_io + 32);
   *flag = 0u;
   const bool armed = !m->prof.on && !m->digests && refiner_fuses_pose(m->refiner);
-  if (run_graphed(m, m->tg, t, H, W, refine_itr, 1, graphable, [&]() {
+  if (run_graphed(m, m->tg, t, H, W, refine_itr, 1, graphable(m, refine_itr), [&]() {
         for (int it = 0; it < refine_itr; it++) {
           const bool last = it == refine_itr - 1;
           if (refine_iteration(m, t, 1, false, it == 0 ? m->track_io_dev : nullptr, last ? m->track_io_dev + 16 : nullptr,
@@ -1998,17 +2032,15 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
   return 0;
 }
 
-int fp_track_submit(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W, const float hyp_pose[16],
-                    const char *target_name, int refine_itr) try {
-  SerialGuard serial(m ? m->device : -1);
+static int track_submit(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W, const float hyp_pose[16],
+                        const char *target_name, int refine_itr) {
   const int rc = track_submit_impl(m, rgb, depth, memspace, H, W, hyp_pose, target_name, refine_itr);
   // a failure after the upload was enqueued must not leave H2D copies of the caller's host frame in flight
   if (rc && m && m->stream) (void)hipStreamSynchronize(m->stream);
   return rc;
-} FP_CATCH_INT
+}
 
-int fp_track_wait(fp_model *m, float out_pose[16]) try {
-  SerialGuard serial(m ? m->device : -1);
+static int track_wait(fp_model *m, float out_pose[16]) {
   FP_CHECK(m && out_pose, "[FoundationPose] fp_track_wait: invalid arguments");
   FP_CHECK(m->track_pending, "[FoundationPose] fp_track_wait: nothing was submitted");
   m->track_pending = false;
@@ -2047,6 +2079,17 @@ int fp_track_wait(fp_model *m, float out_pose[16]) try {
   FP_HIP_OK(hipStreamSynchronize(m->stream));
   std::memcpy(out_pose, m->track_io + 16, 64);
   return 0;
+}
+
+int fp_track_submit(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W, const float hyp_pose[16],
+                    const char *target_name, int refine_itr) try {
+  SerialGuard serial(m ? m->device : -1);
+  return track_submit(m, rgb, depth, memspace, H, W, hyp_pose, target_name, refine_itr);
+} FP_CATCH_INT
+
+int fp_track_wait(fp_model *m, float out_pose[16]) try {
+  SerialGuard serial(m ? m->device : -1);
+  return track_wait(m, out_pose);
 } FP_CATCH_INT
 
 // Track of K objects of one frame in ONE batch: the geometry runs per object (its mesh), the refine-net once over all K crops.
@@ -2060,16 +2103,18 @@ int fp_track_multi(fp_model *m, const void *rgb, const void *depth, int memspace
   FP_CHECK(m->refiner, "[FoundationPose] refiner weights not loaded");
   FP_CHECK(!m->track_pending, "[FoundationPose] fp_track_multi: a submitted Track has not been waited for");
   std::vector<Target *> targets(K);
+  std::vector<std::pair<int, int>> groups;   // (first object, count) of every run of consecutive objects with one mesh
   size_t maxV = 0;
   for (int i = 0; i < K; i++) {
     Target *t = nullptr;
     if (check_frame_args(m, H, W, target_names[i] ? target_names[i] : "", &t)) return 1;
     targets[i] = t;
     maxV = std::max(maxV, (size_t)t->mesh.V);
+    if (i > 0 && targets[i - 1] == t) groups.back().second++;
+    else groups.emplace_back(i, 1);
   }
   m->fit_track_n = 0;
-  m->fit_track_why = !m->fit_on ? "the last Track ran with the pose fit off (fp_set_pose_fit)"
-                     : refine_itr <= 0 ? "the last Track ran with refine_itr <= 0: nothing was rendered, so there is no record" : "the last Track failed";
+  m->fit_track_why = no_track_fit_because(m, refine_itr);
   const bool fit = m->fit_on && refine_itr >= 1;
   PoseFitTol fit_tol = {};   // per object: the meshes' diameters differ
   if (fit) {
@@ -2083,41 +2128,28 @@ int fp_track_multi(fp_model *m, const void *rgb, const void *depth, int memspace
     return 0;
   }
   if (ensure_capacity(m, K, maxV)) return 1;
-  if (K > m->multi_io_cap) {
+  if (!m->multi_io) {   // once, for the largest object count
     FP_HIP_OK(hipStreamSynchronize(m->stream));
-    if (m->multi_io) (void)hipHostFree(m->multi_io);
-    m->multi_io = nullptr; m->multi_io_cap = 0;
     g_alloc_epoch++;   // graphs bake the pinned addresses
-    FP_HIP_OK(hipHostMalloc((void **)&m->multi_io, (size_t)2 * 64 * 16 * sizeof(float), hipHostMallocDefault));
-    FP_HIP_OK(hipHostGetDevicePointer((void **)&m->multi_io_dev, m->multi_io, 0));
-    m->multi_io_cap = 64;
+    FP_HIP_OK(pinned_mapped_alloc(&m->multi_io, &m->multi_io_dev, (size_t)2 * 64 * 16 * sizeof(float), hipHostMallocDefault));
   }
   std::memcpy(m->multi_io, hyp_poses, (size_t)K * 64);
-  const bool graphable = m->use_graphs && !m->prof.on && !m->digests && !m->calibrating;
   if (m->mg_sig != targets) { drop_graph(m->mg); m->mg.target = nullptr; m->mg_sig = targets; }
   float *pin_in = m->multi_io_dev, *pin_out = m->multi_io_dev + 64 * 16;
   const size_t IMG = FP_NN_IN_IMG_HALFS;
-  if (run_graphed(m, m->mg, targets[0], H, W, refine_itr, K, graphable, [&]() {
+  if (run_graphed(m, m->mg, targets[0], H, W, refine_itr, K, graphable(m, refine_itr), [&]() {
         for (int it = 0; it < refine_itr; it++) {
-          for (int o = 0; o < K;) {   // groups of consecutive objects with the same mesh
-            int n = 1;
-            while (o + n < K && targets[o + n] == targets[o]) n++;
+          for (const auto &[o, n] : groups)
             if (render_and_crop(m, targets[o], n, 1.2f, nn_mode(m), m->nn_in + (size_t)o * IMG, m->nn_in + (size_t)(K + o) * IMG, nullptr, nullptr, n,
                                 (it == 0 ? pin_in : m->poses_dev) + (size_t)o * 16, m->recs + o))
               return 1;
-            o += n;
-          }
           // one launch over all K objects: object o's crop is image K + o, its threshold its own mesh's
           if (fit && it == refine_itr - 1 && enqueue_pose_fit(m, m->nn_in, m->nn_in + (size_t)K * IMG, K, fit_tol, m->fit_io_dev)) return 1;
           if (refiner_forward(m->stream, &m->prof, m->refiner, m->ws, m->nn_in, K, m->trans_dev, m->rot_dev, 0)) return 1;
-          for (int o = 0; o < K;) {
-            int n = 1;
-            while (o + n < K && targets[o + n] == targets[o]) n++;
+          for (const auto &[o, n] : groups)
             launch_pose_update(m->stream, m->poses_dev + (size_t)o * 16, m->trans_dev + (size_t)o * 3, m->rot_dev + (size_t)o * 3, n,
                                targets[o]->mesh.diameter, it == 0 ? pin_in + (size_t)o * 16 : nullptr,
                                it == refine_itr - 1 ? pin_out + (size_t)o * 16 : nullptr);
-            o += n;
-          }
         }
         return 0;
       }))
@@ -2137,11 +2169,8 @@ int fp_track_ex(fp_model *m, const void *rgb, const void *depth, int memspace, i
   FP_CHECK(out_pose, "[FoundationPose] Track: null pose");
   // an earlier fp_track_submit that is still in flight is the caller's to wait for: refuse without touching it
   FP_CHECK(!m || !m->track_pending, "[FoundationPose] Track: a submitted Track has not been waited for (fp_track_wait)");
-  if (fp_track_submit(m, rgb, depth, memspace, H, W, hyp_pose, target_name, refine_itr)) {
-    if (m) m->track_pending = false;   // this call's own submission failed (fp_track_submit synchronised)
-    return 1;
-  }
-  return fp_track_wait(m, out_pose);
+  if (track_submit(m, rgb, depth, memspace, H, W, hyp_pose, target_name, refine_itr)) return 1;   // (synchronised; nothing is pending)
+  return track_wait(m, out_pose);
 } FP_CATCH_INT
 
 int fp_track(fp_model *m, const uint8_t *rgb, const float *depth, int H, int W, const float hyp_pose[16],
@@ -2263,22 +2292,6 @@ int fp_get_float_model(const fp_model *m) { return m ? (m->fmad ? 1 : 0) : -1; }
 // The record of the precision is replaced only when every step succeeded; a failure restores the previous record (or leaves the
 // precision uncalibrated).  The pose is discarded; the model's precision is unchanged.  ~30 Registers per frame, once per deployment.
 static constexpr int kCalibSlots = 16;   // frame-mean slots a record carries (more frames share slots: frame f -> slot f % 16)
-struct CalibRecord {   // what fp_get_calibration_blob carries for one precision
-  std::vector<float> amax[2], bias_fix[2], tok_fix[2], out_fix[2];
-  std::vector<float> fmeans[2];   // [slots][15][512]
-  int slots = 0;
-  bool valid() const { return !amax[0].empty(); }
-};
-static CalibRecord record_of(const fp_model *m, int precision) {
-  CalibRecord r;
-  for (int k = 0; k < 2; k++) { r.amax[k] = m->calib_amax_q[precision][k]; r.bias_fix[k] = m->calib_bias_fix[precision][k]; r.tok_fix[k] = m->calib_tok_fix[precision][k]; r.out_fix[k] = m->calib_out_fix[precision][k]; r.fmeans[k] = m->calib_fmeans[precision][k]; }
-  r.slots = m->calib_slots[precision];
-  return r;
-}
-static void commit_record(fp_model *m, int precision, const CalibRecord &r) {
-  for (int k = 0; k < 2; k++) { m->calib_amax_q[precision][k] = r.amax[k]; m->calib_bias_fix[precision][k] = r.bias_fix[k]; m->calib_tok_fix[precision][k] = r.tok_fix[k]; m->calib_out_fix[precision][k] = r.out_fix[k]; m->calib_fmeans[precision][k] = r.fmeans[k]; }
-  m->calib_slots[precision] = r.slots;
-}
 // (re-)quantises the LOADED networks of `precision` from a record (weights and corrections)
 static int apply_record(fp_model *m, int precision, const CalibRecord &r) {
   Net *loaded[2] = {m->refiner_p[precision], m->scorer_p[precision]};
@@ -2288,10 +2301,15 @@ static int apply_record(fp_model *m, int precision, const CalibRecord &r) {
   return 0;
 }
 
-static int calibrate_impl(fp_model *m, const std::vector<CalibFrame> &frames, int precision) {
-  FP_CHECK(m != nullptr, "[FoundationPose] null model");
-  FP_CHECK(precision == PREC_FP8 || precision == PREC_INT8, "[FoundationPose] fp_calibrate: precision must be FP_PREC_FP8 or FP_PREC_INT8");
-  FP_CHECK(!m->refiner_path.empty() && !m->scorer_path.empty(), "[FoundationPose] fp_calibrate needs both networks");
+// after a failed apply_record: the previous record goes back onto the precision's loaded networks, or the precision is left
+// uncalibrated (fp_set_precision refuses it until a calibration succeeds)
+static void restore_record(fp_model *m, int precision, const CalibRecord &before) {
+  if (before.valid() && apply_record(m, precision, before) == 0) return;
+  m->calib[precision] = {};
+  for (Net *n : {m->refiner_p[precision], m->scorer_p[precision]}) if (n) net_q8_unready(n);
+}
+
+static int calibrate_impl(fp_model *m, const std::vector<CalibFrame> &frames, int precision) {   // (calibrate_locked checked m and precision)
   FP_CHECK(!frames.empty(), "[FoundationPose] fp_calibrate_finish: no calibration frame was added");
   FP_CHECK(m->refiner_p[precision] && m->scorer_p[precision] && m->refiner_p[PREC_F16] && m->scorer_p[PREC_F16], "[FoundationPose] fp_calibrate: networks not loaded");
   const int prev = m->prec;
@@ -2327,9 +2345,7 @@ static int calibrate_impl(fp_model *m, const std::vector<CalibFrame> &frames, in
     std::vector<double> acc[2] = {std::vector<double>(8, 0.0), std::vector<double>(512, 0.0)};
     int rc = 0;
     for (const CalibFrame &f : frames) {
-      m->calibrating = true;
-      rc = fp_register_ex(m, f.rgb.data(), f.depth.data(), f.mask.data(), FP_HOST, f.H, f.W, f.target.c_str(), 1, pose);
-      m->calibrating = false;
+      rc = register_whole(m, f.rgb.data(), f.depth.data(), f.mask.data(), FP_HOST, f.H, f.W, f.target.c_str(), 1, pose, true);
       if (!rc && out_mean) rc = add_output_means(acc);
       if (rc) break;
     }
@@ -2352,9 +2368,7 @@ static int calibrate_impl(fp_model *m, const std::vector<CalibFrame> &frames, in
     Net *nets[2] = {m->refiner, m->scorer};
     for (size_t f = 0; f < frames.size(); f++) {
       for (Net *n : nets) net_calib_begin(n, m->stream, 1, -1);
-      m->calibrating = true;
-      int rc = fp_register_ex(m, frames[f].rgb.data(), frames[f].depth.data(), frames[f].mask.data(), FP_HOST, frames[f].H, frames[f].W, frames[f].target.c_str(), 1, pose);
-      m->calibrating = false;
+      int rc = register_whole(m, frames[f].rgb.data(), frames[f].depth.data(), frames[f].mask.data(), FP_HOST, frames[f].H, frames[f].W, frames[f].target.c_str(), 1, pose, true);
       if (!rc) rc = add_output_means(acc_out);
       const int slot = (int)(f % (size_t)rec.slots);
       per_slot[slot]++;
@@ -2423,7 +2437,7 @@ static int calibrate_impl(fp_model *m, const std::vector<CalibFrame> &frames, in
   for (int k = 0; k < 2; k++)
     for (const std::vector<float> *v : {&rec.amax[k], &rec.bias_fix[k], &rec.tok_fix[k], &rec.out_fix[k], &rec.fmeans[k]})
       for (float x : *v) FP_CHECK(std::isfinite(x), "[FoundationPose] fp_calibrate: the solved record is not finite (broken weights or frames)");
-  commit_record(m, precision, rec);   // only now: every step succeeded
+  m->calib[precision] = rec;   // only now: every step succeeded
   invalidate_graphs(m);
   return select_precision(m, prev);
 }
@@ -2450,20 +2464,14 @@ static int calibrate_locked(fp_model *m, const std::vector<CalibFrame> &frames, 
   }
   SerialGuard serial(m->device);
   FP_HIP_OK(hipStreamSynchronize(m->stream));
-  const CalibRecord before = record_of(m, precision);
+  const CalibRecord before = m->calib[precision];
   const int rc = calibrate_impl(m, frames, precision);
   if (rc) {   // leave the model usable and the precision's networks consistent with its (previous) record
     const std::string why = g_last_error;
-    m->calibrating = false;
     for (Net *n : {m->refiner_p[precision], m->scorer_p[precision], m->refiner_p[PREC_F16], m->scorer_p[PREC_F16]}) if (n) net_calib_abort(n);
     (void)hipStreamSynchronize(m->stream);
     invalidate_graphs(m);
-    bool restored = before.valid() && apply_record(m, precision, before) == 0;
-    if (!restored) {   // uncalibrated: fp_set_precision refuses the precision until a calibration succeeds
-      for (int k = 0; k < 2; k++) { m->calib_amax_q[precision][k].clear(); m->calib_bias_fix[precision][k].clear(); m->calib_tok_fix[precision][k].clear(); m->calib_out_fix[precision][k].clear(); m->calib_fmeans[precision][k].clear(); }
-      m->calib_slots[precision] = 0;
-      for (Net *n : {m->refiner_p[precision], m->scorer_p[precision]}) if (n) net_q8_unready(n);
-    }
+    restore_record(m, precision, before);
     const bool q8_prev = prev == PREC_FP8 || prev == PREC_INT8;
     (void)select_precision(m, (q8_prev && !m->calibrated(prev)) ? PREC_F16 : prev);
     set_error(why);
@@ -2549,20 +2557,21 @@ static constexpr size_t kCalibSizeV1 = 16 + kCalibFloats * sizeof(float);
 size_t fp_calibration_size(void) { return 16 + (kCalibFloats + kCalibMeanFloats) * sizeof(float); }
 int fp_get_calibration_blob(const fp_model *m, int precision, void *out, size_t capacity) try {
   FP_CHECK(m && out && (precision == PREC_FP8 || precision == PREC_INT8), "[FoundationPose] fp_get_calibration_blob: invalid arguments");
-  FP_CHECK(m->calibrated(precision) && !m->calib_bias_fix[precision][0].empty(), "[FoundationPose] no calibration available for this precision");
+  const CalibRecord &r = m->calib[precision];
+  FP_CHECK(r.valid() && !r.bias_fix[0].empty(), "[FoundationPose] no calibration available for this precision");
   FP_CHECK(capacity >= fp_calibration_size(), "[FoundationPose] fp_get_calibration_blob: buffer too small (fp_calibration_size)");
-  const int slots = m->calib_slots[precision];
+  const int slots = r.slots;
   uint32_t hdr[4] = {kCalibMagic, 2u, (uint32_t)precision, (uint32_t)slots};
   unsigned char *p = (unsigned char *)out;
   std::memcpy(p, hdr, 16); p += 16;
-  for (int k = 0; k < 2; k++) { std::memcpy(p, m->calib_amax_q[precision][k].data(), 15 * 512 * 4); p += 15 * 512 * 4; }
-  for (int k = 0; k < 2; k++) { std::memcpy(p, m->calib_bias_fix[precision][k].data(), 13 * 512 * 4); p += 13 * 512 * 4; }
-  for (int k = 0; k < 2; k++) { std::memcpy(p, m->calib_tok_fix[precision][k].data(), 512 * 4); p += 512 * 4; }
-  for (int k = 0; k < 2; k++) { const size_t n = k == 0 ? 8 : 512; std::memcpy(p, m->calib_out_fix[precision][k].data(), n * 4); p += n * 4; }
+  for (int k = 0; k < 2; k++) { std::memcpy(p, r.amax[k].data(), 15 * 512 * 4); p += 15 * 512 * 4; }
+  for (int k = 0; k < 2; k++) { std::memcpy(p, r.bias_fix[k].data(), 13 * 512 * 4); p += 13 * 512 * 4; }
+  for (int k = 0; k < 2; k++) { std::memcpy(p, r.tok_fix[k].data(), 512 * 4); p += 512 * 4; }
+  for (int k = 0; k < 2; k++) { const size_t n = k == 0 ? 8 : 512; std::memcpy(p, r.out_fix[k].data(), n * 4); p += n * 4; }
   for (int k = 0; k < 2; k++) {
     const size_t n = (size_t)kCalibSlots * 15 * 512, have = (size_t)slots * 15 * 512;
     std::memset(p, 0, n * 4);
-    if (have) std::memcpy(p, m->calib_fmeans[precision][k].data(), have * 4);
+    if (have) std::memcpy(p, r.fmeans[k].data(), have * 4);
     p += n * 4;
   }
   return 0;
@@ -2595,21 +2604,16 @@ int fp_set_calibration_blob(fp_model *m, const void *blob, size_t bytes) try {
   for (int k = 0; k < 2; k++) take(rec.out_fix[k], k == 0 ? 8 : 512);
   rec.slots = slots;
   for (int k = 0; v2 && k < 2; k++) { take(rec.fmeans[k], (size_t)kCalibSlots * 15 * 512); rec.fmeans[k].resize((size_t)slots * 15 * 512); }
-  const CalibRecord before = record_of(m, precision);
+  const CalibRecord before = m->calib[precision];
   if (apply_record(m, precision, rec)) {   // (re-quantises the networks of the precision that are already loaded)
-    // a failure behind the first network leaves it re-quantised to the NEW record while the model still reports the old one: put the
-    // old one back (as calibrate_locked does), or drop the precision's record when that fails too
+    // a failure behind the first network leaves it re-quantised to the NEW record while the model still reports the old one
     const std::string why = fp_last_error();
-    if (!(before.valid() && apply_record(m, precision, before) == 0)) {
-      for (int k = 0; k < 2; k++) { m->calib_amax_q[precision][k].clear(); m->calib_bias_fix[precision][k].clear(); m->calib_tok_fix[precision][k].clear(); m->calib_out_fix[precision][k].clear(); m->calib_fmeans[precision][k].clear(); }
-      m->calib_slots[precision] = 0;
-      for (Net *n : {m->refiner_p[precision], m->scorer_p[precision]}) if (n) net_q8_unready(n);
-    }
+    restore_record(m, precision, before);
     invalidate_graphs(m);
     set_error(why);
     return 1;
   }
-  commit_record(m, precision, rec);
+  m->calib[precision] = rec;
   invalidate_graphs(m);
   return 0;
 } FP_CATCH_INT
@@ -2620,7 +2624,7 @@ int fp_get_calibration(const fp_model *m, float amax_out[32]) try {
   for (int k = 0; k < 2; k++)
     for (int a = 0; a < 16; a++) {
       float v = 0.f;
-      if (a < 15) for (int c = 0; c < 512; c++) v = std::max(v, m->calib_amax_q[pr][k][a * 512 + c]);
+      if (a < 15) for (int c = 0; c < 512; c++) v = std::max(v, m->calib[pr].amax[k][a * 512 + c]);
       amax_out[k * 16 + a] = v;
     }
   return 0;
@@ -2631,22 +2635,16 @@ int fp_set_calibration(fp_model *m, const float amax[32]) try {
   FP_CHECK(m && amax, "[FoundationPose] fp_set_calibration: invalid arguments");
   DeviceScope on_device(m->device);
   FP_HIP_OK(hipStreamSynchronize(m->stream));
+  CalibRecord rec;   // (no frame means: a per-tensor record's weights are rounded to nearest)
   for (int k = 0; k < 2; k++) {
-    std::vector<float> rec((size_t)15 * 512, 0.f);
+    rec.amax[k].assign((size_t)15 * 512, 0.f);
     for (int a = 0; a < 15; a++)
-      for (int c = 0; c < 512; c++) rec[a * 512 + c] = amax[k * 16 + a];
-    for (int pr : {PREC_FP8, PREC_INT8}) {
-      m->calib_amax_q[pr][k] = rec;
-      m->calib_bias_fix[pr][k].assign((size_t)13 * 512, 0.f); m->calib_tok_fix[pr][k].assign(512, 0.f); m->calib_out_fix[pr][k].assign(k == 0 ? 8 : 512, 0.f);
-      m->calib_fmeans[pr][k].clear(); m->calib_slots[pr] = 0;   // (per-tensor records carry no frame means: weights rounded to nearest)
-    }
+      for (int c = 0; c < 512; c++) rec.amax[k][a * 512 + c] = amax[k * 16 + a];
+    rec.bias_fix[k].assign((size_t)13 * 512, 0.f); rec.tok_fix[k].assign(512, 0.f); rec.out_fix[k].assign(k == 0 ? 8 : 512, 0.f);
   }
-  for (int pr : {PREC_FP8, PREC_INT8}) {
-    Net *loaded[2] = {m->refiner_p[pr], m->scorer_p[pr]};
-    for (int k = 0; k < 2; k++)
-      if (loaded[k] && (net_apply_q8(loaded[k], m->calib_amax_q[pr][k].data(), m->calib_bias_fix[pr][k].data(), m->calib_tok_fix[pr][k].data(), true) ||
-                        net_q8_set_out_fix(loaded[k], m->calib_out_fix[pr][k].data()))) return 1;
-  }
+  for (int pr : {PREC_FP8, PREC_INT8}) m->calib[pr] = rec;
+  for (int pr : {PREC_FP8, PREC_INT8})
+    if (apply_record(m, pr, rec)) return 1;
   invalidate_graphs(m);
   return 0;
 } FP_CATCH_INT

@@ -710,3 +710,86 @@ def test_native_sharded_register_world_1(model, syn_mesh, syn_scene):
         np.testing.assert_array_equal(syn.from_colmajor(pose16[None])[0], ref)
     finally:
         comm.close()
+
+
+def test_register_entry_points_interleaved_on_one_model(nets, syn_mesh, syn_scene):
+    """Every Register entry point and a Track in turn on ONE model (42 hypotheses, f16, graphs on): plain Register, the public
+    begin / finish pair, the packed pair, fp_register_sharded at world 1, with a failing call (all-zero mask) of each kind in between.
+    Each successful step runs three times (eager, capture, replay).  No call may leave state behind that changes the next one: every
+    successful Register returns the first one's pose and winner bit for bit, every failure names the sampler's verdict where that
+    protocol reports it (plain Register and the public begin at once, the packed pair in its finish), and the Track equals the same
+    Track on a fresh model."""
+    import torch.distributed as dist
+    from foundationpose_cpp_amd.distributed import HipShardBackend, NativeRcclComm, sharded_register_native
+    sc, name = syn_scene, syn_mesh.name
+    dev = torch.device("cuda", 0)
+    m = FoundationPose(syn_mesh, syn.intrinsics(), nets[0], nets[1])
+    fresh = FoundationPose(syn_mesh, syn.intrinsics(), nets[0], nets[1])
+    comm = NativeRcclComm(dist, dev)
+    try:
+        m.set_inplane_steps(1)
+        n = m.num_hypotheses
+        assert n == 42
+        zero = np.zeros_like(sc.mask)
+        rgb, depth, mask = (torch.from_numpy(x).to(dev) for x in (sc.rgb, sc.depth, sc.mask))
+        be = HipShardBackend(m, dev)
+        packed, gathered = be.buffers(n, 1)
+
+        def packed_pair(mask_dev):
+            be.shard_begin_packed(rgb, depth, mask_dev, 480, 640, name, 1, 0, n, packed, n)
+            be.before_collective(); gathered.copy_(packed); be.after_collective()
+            return be.shard_finish_packed(gathered, n)
+
+        # 1. plain Register
+        A = None
+        for _ in range(3):
+            ok, pose = m.Register(sc.rgb, sc.depth, sc.mask, name)
+            assert ok, m.last_error
+            A = pose if A is None else A
+            np.testing.assert_array_equal(pose, A)
+        # 2. plain Register, all-zero mask
+        ok, _ = m.Register(sc.rgb, sc.depth, zero, name)
+        assert not ok and "Mask is all zero" in m.last_error, m.last_error
+        # 3. the public begin / finish pair: its winner is the winner every later step must name
+        winner = None
+        for _ in range(3):
+            ok, pose, idx, scores, refined, _ = m.register_detailed(sc.rgb, sc.depth, sc.mask, name)
+            assert ok, m.last_error
+            np.testing.assert_array_equal(pose, A)
+            assert 0 <= idx < n
+            np.testing.assert_array_equal(refined[idx], A)
+            winner = idx if winner is None else winner
+            assert idx == winner
+        # 4. public begin, all-zero mask: the begin itself fails
+        assert not m.register_detailed(sc.rgb, sc.depth, zero, name)[0]
+        assert "Mask is all zero" in m.last_error, m.last_error
+        # 5. the packed pair over one shard of 42
+        for _ in range(3):
+            p16, idx = packed_pair(mask)
+            np.testing.assert_array_equal(syn.from_colmajor(p16[None])[0], A)
+            assert idx == winner
+        # 6. packed begin with the all-zero mask succeeds (nothing is synchronised); the finish reports the sampler's verdict
+        with pytest.raises(Exception) as e:
+            packed_pair(torch.zeros_like(mask))
+        assert "Mask is all zero" in str(e.value) and "FoundationposeSampling" in str(e.value), str(e.value)
+        # 7. Track from A
+        ok, want = fresh.Track(sc.rgb, sc.depth, A, name)
+        assert ok, fresh.last_error
+        for _ in range(3):
+            ok, pose = m.Track(sc.rgb, sc.depth, A, name)
+            assert ok, m.last_error
+            np.testing.assert_array_equal(pose, want)
+        # 8. fp_register_sharded, one rank
+        for _ in range(3):
+            p16, idx = sharded_register_native(m, comm, rgb, depth, mask, 480, 640, name)
+            np.testing.assert_array_equal(syn.from_colmajor(p16[None])[0], A)
+            assert idx == winner
+        # 9. plain Register again
+        for _ in range(3):
+            ok, pose = m.Register(sc.rgb, sc.depth, sc.mask, name)
+            assert ok, m.last_error
+            np.testing.assert_array_equal(pose, A)
+    finally:
+        comm.close()
+        m.close()
+        fresh.close()
