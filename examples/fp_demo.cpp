@@ -136,7 +136,9 @@ int main(int argc, char **argv) {
 
   std::unique_ptr<fp_amd::FoundationPose> fpm;
   try {
+    // (the wrapper's constructor hands the vertex colours of a mesh without UVs to the model: fp_set_vertex_colors)
     fpm.reset(new fp_amd::FoundationPose(meshes, K, refiner, scorer, std::max(H, 1080), std::max(W, 1920)));
+    if (meshes[0].color_source == FP_COLOR_VERTEX) std::printf("mesh '%s' has no texture coordinates: rendering its vertex colours\n", name.c_str());
   } catch (const std::exception &e) {
     std::fprintf(stderr, "%s\n", e.what());
     return 1;

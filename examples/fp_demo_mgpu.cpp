@@ -114,6 +114,9 @@ int main(int argc, char **argv) {
     // (fp_create_on makes the device current itself; nothing here calls hipSetDevice)
     models[r] = fp_create_on(devs[r], fp_mesh_view(lm), 1, K, refiner.c_str(), scorer.c_str(), 0, 0);
     if (!models[r] || fp_set_inplane_steps(models[r], hyps / 42)) { rcs[r] = 1; errors[r] = fp_last_error(); }
+    // a mesh without UVs is rendered from its vertex colours (the C ABI keeps fp_mesh unchanged: the colours are handed over here)
+    if (!rcs[r] && fp_mesh_color_source(lm) == FP_COLOR_VERTEX &&
+        fp_set_vertex_colors(models[r], "object", fp_mesh_vertex_colors(lm), fp_mesh_view(lm)->num_vertices)) { rcs[r] = 1; errors[r] = fp_last_error(); }
     bar.wait();
     for (int r2 = 0; r2 < ranks; r2++) if (rcs[r2]) return;   // (every thread sees the same verdict after the barrier)
     for (int it = 0; it < 2 && !rcs[r]; it++)   // eager call, then the captured graph

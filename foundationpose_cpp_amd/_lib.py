@@ -24,6 +24,7 @@ SYMBOLS = [
     "fp_image_read_png", "fp_frame_size", "fp_read_rgb_depth_mask", "fp_read_cam_k", "fp_image_write_png_rgb",
     "fp_draw_bbox3d", "fp_set_precision", "fp_get_precision", "fp_calibrate_fp8", "fp_calibrate", "fp_calibrate_begin", "fp_calibrate_add_frame", "fp_calibrate_finish", "fp_calibrate_abort", "fp_calibrate_frames", "fp_calibration_size", "fp_get_calibration_blob", "fp_set_calibration_blob", "fp_get_calibration", "fp_set_calibration", "fp_set_float_model", "fp_get_float_model", "fp_net_create", "fp_net_destroy", "fp_net_max_batch", "fp_net_blob", "fp_net_infer",
     "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
+    "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
 ]
 
 
@@ -101,6 +102,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.fp_net_max_batch.argtypes = [C.c_void_p]
     L.fp_mesh_view.restype = C.POINTER(FpMesh)
     L.fp_mesh_view.argtypes = [C.c_void_p]
+    L.fp_mesh_vertex_colors.restype = C.c_void_p
+    L.fp_mesh_vertex_colors.argtypes = [C.c_void_p]
     vp, ci, cf, cs = C.c_void_p, C.c_int, C.c_float, C.c_char_p
     sigs = {
         "fp_set_inplane_steps": [vp, ci], "fp_num_hypotheses": [vp],
@@ -131,6 +134,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_get_calibration": [vp, vp], "fp_set_calibration": [vp, vp], "fp_set_float_model": [vp, ci], "fp_get_float_model": [vp],
         "fp_set_pose_fit": [vp, ci, cf], "fp_get_pose_fit": [vp, vp, vp], "fp_last_track_fit": [vp, vp, ci],
         "fp_last_register_fit": [vp, vp, vp, ci], "fp_pose_fit_eval": [vp, cs, vp, ci, cf, cf, vp],
+        "fp_mesh_color_source": [vp], "fp_set_vertex_colors": [vp, cs, vp, ci], "fp_get_color_source": [vp, cs],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

@@ -19,6 +19,7 @@ from .synthetic import Mesh, from_colmajor, to_colmajor
 
 FP_HOST, FP_DEVICE = 0, 1
 FP_PREC_F16, FP_PREC_BF16, FP_PREC_FP8, FP_PREC_INT8 = 0, 1, 2, 3   # include/foundationpose_amd.h
+FP_COLOR_TEXTURE, FP_COLOR_VERTEX = 0, 1
 CROP = 160
 
 
@@ -62,8 +63,10 @@ def _p(a):
 
 def load_mesh(name: str, mesh_file_path: str) -> Mesh:
     """CreateAssimpMeshLoader(name, path) (mesh_loader.hpp:92-93): OBJ + MTL + PNG through the C ABI.
-    Raises FoundationPoseError where the reference throws (empty path, unreadable file, no UVs).
-    Extra attributes: .orient_bounds [4,4], .dimension [3] (GetOrientBounds / GetObjectDimension)."""
+    Raises FoundationPoseError where the reference throws (empty path, unreadable file, neither UVs nor vertex colours).
+    Extra attributes: .orient_bounds [4,4], .dimension [3] (GetOrientBounds / GetObjectDimension).
+    .vertex_colors ([V,3] u8, None when the file has none) and .color_source: FP_COLOR_VERTEX for a file without UVs that carries
+    per-vertex colours (its texcoords are zero and its texture the grey default), FP_COLOR_TEXTURE otherwise."""
     L = _lib.lib()
     h = L.fp_mesh_load_obj(name.encode(), mesh_file_path.encode())
     if not h:
@@ -85,6 +88,10 @@ def load_mesh(name: str, mesh_file_path: str) -> Mesh:
         L.fp_mesh_orient_bounds(h, _p(ob), _p(dim))
         mesh.orient_bounds = from_colmajor(ob)
         mesh.dimension = dim
+        mesh.color_source = L.fp_mesh_color_source(h)
+        cp = L.fp_mesh_vertex_colors(h)
+        if cp:
+            mesh.vertex_colors = arr(cp, C.c_uint8, (nv, 3), np.uint8)
         return mesh
     finally:
         L.fp_mesh_free(h)
@@ -125,6 +132,15 @@ class FoundationPose:
             raise FoundationPoseError(_lib.last_error())
         self._h = C.c_void_p(h)
         self.last_error = ""
+        try:
+            for m in meshes:
+                if m.color_source == FP_COLOR_VERTEX:   # (a file without UVs: load_mesh)
+                    if m.vertex_colors is None:
+                        raise FoundationPoseError(f"[FoundationPose] mesh '{m.name}' has the colour source FP_COLOR_VERTEX but no vertex_colors")
+                    self.set_vertex_colors(m.name, m.vertex_colors)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "_h", None):
@@ -352,6 +368,26 @@ class FoundationPose:
         out = (_lib.FpPoseFit * len(p))()
         self._must(self._L.fp_pose_fit_eval(self._h, target_name.encode(), _p(p), len(p), crop_ratio, tol_m, out))
         return [_fit(r) for r in out]
+
+    # ---- vertex colours (include/foundationpose_amd.h "vertex colours") ----------------------------
+    def set_vertex_colors(self, target_name: str, colors):
+        """colors [V,3] u8 RGB become the colour source of the target's renderings (interpolated per pixel instead of a texture
+        sample); None returns the target to its texture.  Drops the captured graphs like set_pose_fit."""
+        if colors is None:
+            self._must(self._L.fp_set_vertex_colors(self._h, target_name.encode(), None, 0))
+            return
+        c = np.ascontiguousarray(colors, np.uint8)
+        if c.ndim != 2 or c.shape[1] != 3:
+            raise FoundationPoseError("[FoundationPose] set_vertex_colors: colors must be [V,3] u8")
+        self._must(self._L.fp_set_vertex_colors(self._h, target_name.encode(), _p(c), len(c)))
+
+    def color_source(self, target_name: str) -> int:
+        """FP_COLOR_TEXTURE / FP_COLOR_VERTEX of a target"""
+        rc = self._L.fp_get_color_source(self._h, target_name.encode())
+        if rc < 0:
+            self.last_error = _lib.last_error()
+            raise FoundationPoseError(self.last_error)
+        return rc
 
     # ---- float model of the rendering stage (1 = contracted like nvcc -fmad=true, default; 0 = separate roundings) ----
     def set_float_model(self, fmad: int):

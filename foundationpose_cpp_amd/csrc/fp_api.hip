@@ -1101,6 +1101,7 @@ static void destroy_model_impl(fp_model *m) {
   m->prof.reset();
   for (auto &t : m->targets) {
     dev_free(t.mesh.verts); dev_free(t.mesh.normals); dev_free(t.mesh.uvs); dev_free(t.mesh.faces); dev_free(t.mesh.tex);
+    dev_free(t.mesh.vcol);
   }
   dev_free(m->rgb_own); dev_free(m->depth_own); dev_free(m->erode); dev_free(m->bilat); dev_free(m->xyz);
   dev_free(m->recs); dev_free(m->poses_dev); dev_free(m->clip); dev_free(m->attr); dev_free(m->tri_rows); dev_free(m->nn_in);
@@ -2196,6 +2197,37 @@ int fp_get_pose_fit(const fp_model *m, int *on, float *tol_m) try {
   if (on) *on = m->fit_on ? 1 : 0;
   if (tol_m) *tol_m = m->fit_tol_m;
   return 0;
+} FP_CATCH_INT
+
+// ---- vertex colours (DESIGN.md sections 3, 4.1): the target's colour source is its packed colour array when it has one
+int fp_set_vertex_colors(fp_model *m, const char *target_name, const uint8_t *colors, int num_vertices) try {
+  LifeExclusive life;   // destroys the captured graphs: not while another thread is inside a call
+  FP_CHECK(m != nullptr, "[FoundationPose] null model");
+  Target *t = m->find(target_name ? target_name : "");
+  FP_CHECK(t != nullptr, "[FoundationPose] fp_set_vertex_colors: unknown target_name");
+  FP_CHECK(!colors || num_vertices == t->mesh.V, "[FoundationPose] fp_set_vertex_colors: got " + std::to_string(num_vertices) +
+                                                     " colours for a target of " + std::to_string(t->mesh.V) + " vertices");
+  if (!colors && !t->mesh.vcol) return 0;
+  DeviceScope on_device(m->device);
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  invalidate_graphs(m);   // the kernel of the colour source and the array's address are part of the captured bodies
+  if (!colors) { dev_free(t->mesh.vcol); return 0; }
+  std::vector<uint32_t> packed((size_t)t->mesh.V);
+  for (size_t k = 0; k < packed.size(); k++)
+    packed[k] = (uint32_t)colors[k * 3] | (uint32_t)colors[k * 3 + 1] << 8 | (uint32_t)colors[k * 3 + 2] << 16;
+  uint32_t *dev = t->mesh.vcol;
+  if (!dev && dev_alloc(&dev, packed.size())) return 1;
+  if (fp::memcpy_sync(dev, packed.data(), packed.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    if (!t->mesh.vcol) dev_free(dev);   // (a fresh array: the target keeps its texture)
+    FP_CHECK(false, "[FoundationPose] fp_set_vertex_colors: copying the colours to the device failed");
+  }
+  t->mesh.vcol = dev;
+  return 0;
+} FP_CATCH_INT
+int fp_get_color_source(const fp_model *m, const char *target_name) try {
+  Target *t = m ? const_cast<fp_model *>(m)->find(target_name ? target_name : "") : nullptr;
+  if (!t) { set_error(m ? "[FoundationPose] fp_get_color_source: unknown target_name" : "[FoundationPose] null model"); return -1; }
+  return t->mesh.vcol ? FP_COLOR_VERTEX : FP_COLOR_TEXTURE;
 } FP_CATCH_INT
 
 int fp_last_track_fit(fp_model *m, fp_pose_fit *out, int K) try {

@@ -524,12 +524,16 @@ constexpr int TRI_LIST = 8192;   // capacity of the rasteriser's list of triangl
 
 // NT threads per workgroup: 256 normally; 1024 for tiny batches (Track), where the kernel is bound by the latency of the
 // F/NT dependent triangle iterations of each strip rather than by throughput
-template <int MODE, int STRIP_ROWS, int NT, bool FMAD>
+// VCOL: the colour source of the mesh of this launch.  false: the bilinear texture fetch at the interpolated UV;
+// true: the triangle's three packed vertex colours (vcol[v] = r | g << 8 | b << 16, one 4-byte gather per corner) interpolated with the
+// barycentrics like every other attribute -- no UV interpolation and no texel reads.  A template parameter, so that the textured
+// instantiations are the code they were.
+template <int MODE, int STRIP_ROWS, int NT, bool FMAD, bool VCOL = false>
 __global__ __launch_bounds__(NT) void raster_shade_kernel(
     const int32_t *__restrict__ faces, int F, int V, const float *__restrict__ uvs, const uint8_t *__restrict__ tex,
     int TH, int TW, float downscale, const PoseRec *__restrict__ recs, const float4 *__restrict__ clip_all,
     const float4 *__restrict__ attr_all, void *__restrict__ out_all, int32_t *__restrict__ tri_id_dbg,
-    float *__restrict__ rast_dbg, const unsigned *__restrict__ tri_rows_all) {
+    float *__restrict__ rast_dbg, const unsigned *__restrict__ tri_rows_all, const uint32_t *__restrict__ vcol = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned long long *zbuf = reinterpret_cast<unsigned long long *>(smem);
   const int strip = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
@@ -655,6 +659,7 @@ __global__ __launch_bounds__(NT) void raster_shade_kernel(
     int triIdx = (int)color - 1;
     float b0 = 0, b1 = 0, zw = 0, idf = 0;
     float xyz0 = 0, xyz1 = 0, xyz2 = 0, uu = 0, vv = 0, dif = 0;
+    float vc[3] = {0, 0, 0};   // VCOL: the interpolated vertex colour
     if (triIdx >= 0 && triIdx < F) {
       int vi0 = faces[triIdx * 3], vi1 = faces[triIdx * 3 + 1], vi2 = faces[triIdx * 3 + 2];
       float4 p0 = clip[vi0], p1 = clip[vi1], p2 = clip[vi2];
@@ -678,8 +683,17 @@ __global__ __launch_bounds__(NT) void raster_shade_kernel(
       xyz1 = dot3<FMAD>(b0, q0.y, b1, q1.y, b2, q2.y);
       xyz2 = dot3<FMAD>(b0, q0.z, b1, q1.z, b2, q2.z);
       dif = dot3<FMAD>(b0, q0.w, b1, q1.w, b2, q2.w);
-      uu = dot3<FMAD>(b0, uvs[vi0 * 2], b1, uvs[vi1 * 2], b2, uvs[vi2 * 2]);
-      vv = dot3<FMAD>(b0, uvs[vi0 * 2 + 1], b1, uvs[vi1 * 2 + 1], b2, uvs[vi2 * 2 + 1]);
+      if constexpr (VCOL) {
+        const uint32_t c0 = vcol[vi0], c1 = vcol[vi1], c2 = vcol[vi2];
+        const float sc = 1.0f / 255.0f;
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+          vc[c] = dot3<FMAD>(b0, (float)((c0 >> (8 * c)) & 255u) * sc, b1, (float)((c1 >> (8 * c)) & 255u) * sc, b2,
+                             (float)((c2 >> (8 * c)) & 255u) * sc);
+      } else {
+        uu = dot3<FMAD>(b0, uvs[vi0 * 2], b1, uvs[vi1 * 2], b2, uvs[vi2 * 2]);
+        vv = dot3<FMAD>(b0, uvs[vi0 * 2 + 1], b1, uvs[vi1 * 2 + 1], b2, uvs[vi2 * 2 + 1]);
+      }
     }
     if (tri_id_dbg) tri_id_dbg[((size_t)n * CROP + py) * CROP + px] = (int)color;
     if (rast_dbg) {
@@ -688,7 +702,10 @@ __global__ __launch_bounds__(NT) void raster_shade_kernel(
     }
     float o[6];
     float fg = clampf(idf, 0, 1);
-    if (fg > 0.0f) {
+    if (VCOL && fg > 0.0f) {
+      const float shade = mad<FMAD>(dif, 0.5f, 0.8f);
+      for (int c = 0; c < 3; c++) o[c] = clampf(vc[c] * shade * fg, 0.0f, 1.0f);
+    } else if (!VCOL && fg > 0.0f) {
       // bilinear texture fetch, wrap addressing, texel centre u*w - 0.5, texture value = u8 * (1/255)
       float u = uu - floorf(uu), v = vv - floorf(vv);
       u = mad<FMAD>(u, (float)TW, -0.5f); v = mad<FMAD>(v, (float)TH, -0.5f);
@@ -748,7 +765,7 @@ void set_raster_strip_threads(int t) { g_strip_threads = t; }
 static constexpr int g_strip_threads = 0;
 #endif
 
-template <int MODE, int STRIP_ROWS, bool FMAD>
+template <int MODE, int STRIP_ROWS, bool FMAD, bool VCOL>
 static void launch_raster_shade_t(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
                                   const float4 *attr, void *out, int32_t *tri_id_dbg, float *rast_dbg) {
   size_t lds = (size_t)STRIP_ROWS * CROP * sizeof(unsigned long long) + tri_list_lds();
@@ -758,27 +775,27 @@ static void launch_raster_shade_t(hipStream_t s, const DeviceMesh &m, const Pose
   // triangle iterations per strip, not throughput -- 16 waves per strip while two such workgroups per CU hold the whole grid
   // (20 strips x N <= 512), 8 waves up to where 8-row strips are used at all (N < 48).  [r4] tools/profile_shard.py: N = 12: 55 -> 29 us per
   // launch; from N ~ 32 on the launch is bound by the gather rate of the 20x redundant triangle set-up instead (64 us at any width)
-  if (STRIP_ROWS == 8 && MODE != OUT_F32X6 && !tri_id_dbg && !rast_dbg && g_strip_threads != 256) {
+  if constexpr (STRIP_ROWS == 8 && MODE != OUT_F32X6) if (!tri_id_dbg && !rast_dbg && g_strip_threads != 256) {
     if (g_strip_threads == 1024 || (g_strip_threads == 0 && N <= 25)) {
-      hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD>), grid, dim3(1024), lds, s, m.faces, m.F, m.V, m.uvs,
-                         m.tex, m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows);
+      hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD, VCOL>), grid, dim3(1024), lds, s, m.faces, m.F, m.V, m.uvs,
+                         m.tex, m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows, m.vcol);
       return;
     }
     if (g_strip_threads == 512 || (g_strip_threads == 0 && N < 48)) {
-      hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 512, FMAD>), grid, dim3(512), lds, s, m.faces, m.F, m.V, m.uvs,
-                         m.tex, m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows);
+      hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 512, FMAD, VCOL>), grid, dim3(512), lds, s, m.faces, m.F, m.V, m.uvs,
+                         m.tex, m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows, m.vcol);
       return;
     }
   }
   if constexpr (STRIP_ROWS >= 40) {   // (test-build strip heights: z-buffer + list exceed the 64 KB a kernel gets without asking)
     static PerDeviceOnce attr_once;
     attr_once.run([] {
-      (void)hipFuncSetAttribute((const void *)raster_shade_kernel<MODE, STRIP_ROWS, 256, FMAD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      (void)hipFuncSetAttribute((const void *)raster_shade_kernel<MODE, STRIP_ROWS, 256, FMAD, VCOL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)((size_t)STRIP_ROWS * CROP * sizeof(unsigned long long) + (size_t)TRI_LIST * 4 + 16));
     });
   }
-  hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 256, FMAD>), grid, block, lds, s, m.faces, m.F, m.V, m.uvs, m.tex,
-                     m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows);
+  hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 256, FMAD, VCOL>), grid, block, lds, s, m.faces, m.F, m.V, m.uvs, m.tex,
+                     m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows, m.vcol);
 }
 
 #ifdef FP_TEST_HOOKS
@@ -791,7 +808,7 @@ static constexpr int g_strip_rows_override = 0;
 // tall strips with 1024-thread workgroups: every strip walks ALL triangles (setup + cull), so 2 strips of 80 rows do a
 // quarter of the redundant setup of 8 strips of 20 (0.40 -> 0.21 ms per Register at N = 252); 102 KB of LDS = one
 // workgroup per CU, hence 16 waves per workgroup.  A/B codes for set_raster_strip_rows: 1080 / 1040 / 1020
-template <int MODE, int STRIP_ROWS, bool FMAD>
+template <int MODE, int STRIP_ROWS, bool FMAD, bool VCOL>
 static void launch_raster_tall(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
                                const float4 *attr, void *out) {
   const size_t lds_max = (size_t)STRIP_ROWS * CROP * sizeof(unsigned long long) + (size_t)TRI_LIST * 4 + 16;
@@ -799,11 +816,11 @@ static void launch_raster_tall(hipStream_t s, const DeviceMesh &m, const PoseRec
   // once per instantiation and device: opt in to > 64 KB of dynamic LDS
   static PerDeviceOnce attr_once;
   attr_once.run([lds_max] {
-    (void)hipFuncSetAttribute((const void *)raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void *)raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD, VCOL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_max);
   });
-  hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD>), dim3(CROP / STRIP_ROWS, N), dim3(1024), lds, s, m.faces, m.F,
-                     m.V, m.uvs, m.tex, m.TH, m.TW, m.diameter / 2, recs, clip, attr, out, nullptr, nullptr, t_tri_rows);
+  hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD, VCOL>), dim3(CROP / STRIP_ROWS, N), dim3(1024), lds, s, m.faces, m.F,
+                     m.V, m.uvs, m.tex, m.TH, m.TW, m.diameter / 2, recs, clip, attr, out, nullptr, nullptr, t_tri_rows, m.vcol);
 }
 
 // Row ranges pay where a crop is cut into many short strips (Track: 40, small batches: 20 or 8); the two 80-row strips of a full
@@ -812,32 +829,32 @@ static void launch_raster_tall(hipStream_t s, const DeviceMesh &m, const PoseRec
 static int strip_rows_for(int N) { return g_strip_rows_override ? g_strip_rows_override : (N >= 100 ? 1080 : (N >= 48 ? 20 : 8)); }
 bool raster_wants_tri_rows(int N) { return strip_rows_for(N) < 1000 || g_tri_rows_tall; }
 
-template <int MODE, bool FMAD>
+template <int MODE, bool FMAD, bool VCOL>
 static void launch_raster_mode(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
                                const float4 *attr, void *out, int32_t *tri_id_dbg, float *rast_dbg) {
   int rows = strip_rows_for(N);  // (tools/ab_raster_strips.py: 8-row strips win up to ~40 hypotheses)
-  if (rows > 1000 && MODE != OUT_F32X6 && !tri_id_dbg && !rast_dbg) {
-    if (rows == 1080) { launch_raster_tall<MODE, 80, FMAD>(s, m, recs, N, clip, attr, out); return; }
+  if constexpr (MODE != OUT_F32X6) if (rows > 1000 && !tri_id_dbg && !rast_dbg) {
+    if (rows == 1080) { launch_raster_tall<MODE, 80, FMAD, VCOL>(s, m, recs, N, clip, attr, out); return; }
 #ifdef FP_TEST_HOOKS
-    if (rows == 1040) launch_raster_tall<MODE, 40, FMAD>(s, m, recs, N, clip, attr, out);
-    else launch_raster_tall<MODE, 20, FMAD>(s, m, recs, N, clip, attr, out);
+    if (rows == 1040) launch_raster_tall<MODE, 40, FMAD, VCOL>(s, m, recs, N, clip, attr, out);
+    else launch_raster_tall<MODE, 20, FMAD, VCOL>(s, m, recs, N, clip, attr, out);
     return;
 #endif
   }
   if (rows > 1000) rows = 20;
 #ifdef FP_TEST_HOOKS
-  if (rows == 40) { launch_raster_shade_t<MODE, 40, FMAD>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg); return; }
+  if (rows == 40) { launch_raster_shade_t<MODE, 40, FMAD, VCOL>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg); return; }
 #endif
-  if (rows == 20) { launch_raster_shade_t<MODE, 20, FMAD>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg); return; }
+  if (rows == 20) { launch_raster_shade_t<MODE, 20, FMAD, VCOL>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg); return; }
   // one or two hypotheses (Track): 4-row strips with 1024 threads -- the shading pass covers the strip in ONE iteration
   // (640 pixels; 8 rows = 1280 pixels took two, the second a quarter full) and a strip meets half as many triangles
-  if ((rows == 4 || (rows == 8 && N <= 2 && !g_strip_rows_override)) && MODE != OUT_F32X6 && !tri_id_dbg && !rast_dbg) {
+  if constexpr (MODE != OUT_F32X6) if ((rows == 4 || (rows == 8 && N <= 2 && !g_strip_rows_override)) && !tri_id_dbg && !rast_dbg) {
     const size_t lds = (size_t)4 * CROP * sizeof(unsigned long long) + tri_list_lds();
-    hipLaunchKernelGGL((raster_shade_kernel<MODE, 4, 1024, FMAD>), dim3(CROP / 4, N), dim3(1024), lds, s, m.faces, m.F, m.V, m.uvs,
-                       m.tex, m.TH, m.TW, m.diameter / 2, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows);
+    hipLaunchKernelGGL((raster_shade_kernel<MODE, 4, 1024, FMAD, VCOL>), dim3(CROP / 4, N), dim3(1024), lds, s, m.faces, m.F, m.V, m.uvs,
+                       m.tex, m.TH, m.TW, m.diameter / 2, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows, m.vcol);
     return;
   }
-  launch_raster_shade_t<MODE, 8, FMAD>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);
+  launch_raster_shade_t<MODE, 8, FMAD, VCOL>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);
 }
 
 void launch_raster_shade(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
@@ -846,8 +863,11 @@ void launch_raster_shade(hipStream_t s, const DeviceMesh &m, const PoseRec *recs
   t_tri_rows = tri_rows;
 #define FP_RASTER_MODE(MODE)                                                                                      \
   do {                                                                                                            \
-    if (fmad) launch_raster_mode<MODE, true>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);               \
-    else launch_raster_mode<MODE, false>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);                   \
+    if (m.vcol) {                                                                                                 \
+      if (fmad) launch_raster_mode<MODE, true, true>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);       \
+      else launch_raster_mode<MODE, false, true>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);           \
+    } else if (fmad) launch_raster_mode<MODE, true, false>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg); \
+    else launch_raster_mode<MODE, false, false>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);            \
   } while (0)
   if (mode == OUT_F32X6) FP_RASTER_MODE(OUT_F32X6);
   else if (mode == OUT_BF16X8) FP_RASTER_MODE(OUT_BF16X8);

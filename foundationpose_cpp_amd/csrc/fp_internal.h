@@ -137,6 +137,7 @@ struct DeviceMesh {
   float *uvs = nullptr;      // [V,2] (u, 1-v)
   int32_t *faces = nullptr;  // [F,3]
   uint8_t *tex = nullptr;    // [TH,TW,3]
+  uint32_t *vcol = nullptr;  // [V] r | g << 8 | b << 16 (fp_set_vertex_colors); null: the colour source is the texture
 };
 
 enum OutMode { OUT_F32X6 = 0, OUT_F16X8 = 1, OUT_BF16X8 = 2 };  // F32X6: the reference's blob; *X8: the networks' s2d input tensor

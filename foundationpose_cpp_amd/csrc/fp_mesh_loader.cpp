@@ -10,7 +10,11 @@
 //   * UVs are mandatory (throws in the reference :182-185 -> error here); missing/unreadable texture -> 2x2
 //     (100,100,100) (:217-222); texture is returned RGB (imread BGR + cvtColor BGR2RGB, :216,223).
 //   * meshes without normals get area-weighted vertex normals (the reference would dereference a null mNormals).
+//   * new, no counterpart in the reference: per-vertex colours (PLY red/green/blue, OBJ `v x y z r g b`) are read and follow their
+//     position through the de-duplication; a mesh without usable UVs that has them loads with the colour source FP_COLOR_VERTEX
+//     (zero texcoords, the default texture) instead of failing.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -79,12 +83,21 @@ struct Corner { int v, t, n; };
 struct ParsedMesh {
   std::vector<std::array<float, 3>> pos, nrm;
   std::vector<std::array<float, 2>> uv;
+  std::vector<std::array<uint8_t, 3>> col;   // per position; used only when there is one for every position
   std::vector<std::array<Corner, 3>> tris;
   std::string mtllib, usemtl;     // OBJ: the texture is named by the material library
   std::string texture_file;       // PLY: `comment TextureFile <name>` (what assimp turns into the diffuse texture)
 };
 
-// Stanford PLY (ascii / binary_little_endian / binary_big_endian): per-vertex x y z [nx ny nz] [s t | u v | texture_u texture_v],
+// a colour component as the files carry it -> u8: integer types hold 0..255, float types (and OBJ) 0..1
+uint8_t color_u8(double c, bool unit_range) {
+  if (!(c == c)) return 0;
+  if (unit_range) return (uint8_t)std::rint(std::min(std::max((float)c, 0.0f), 1.0f) * 255.0f);
+  return (uint8_t)std::min(std::max(c, 0.0), 255.0);
+}
+
+// Stanford PLY (ascii / binary_little_endian / binary_big_endian): per-vertex x y z [nx ny nz] [s t | u v | texture_u texture_v]
+// [red green blue | diffuse_red diffuse_green diffuse_blue] (alpha is skipped),
 // faces as `property list <T> <T> vertex_indices|vertex_index` (polygons are fanned), optional per-face `texcoord` list (MeshLab's
 // per-wedge UVs), `comment TextureFile <file>`.  The BOP / YCB-V object models come in this form.
 bool parse_ply(const std::string &path, ParsedMesh &out, std::string &err) {
@@ -140,14 +153,18 @@ bool parse_ply(const std::string &path, ParsedMesh &out, std::string &err) {
   for (auto &e : elems) {
     if (e.count > (size_t)1 << 28) { err = "PLY element count out of range"; return false; }
     if (e.name == "vertex") {
-      int ix = -1, iy = -1, iz = -1, inx = -1, iny = -1, inz = -1, iu = -1, iv = -1;
+      int ix = -1, iy = -1, iz = -1, inx = -1, iny = -1, inz = -1, iu = -1, iv = -1, ic[3] = {-1, -1, -1};
       for (size_t k = 0; k < e.props.size(); k++) {
         const std::string &n = e.props[k].name;
         if (e.props[k].list) { err = "PLY: list property on vertices is not supported"; return false; }
         if (n == "x") ix = (int)k; else if (n == "y") iy = (int)k; else if (n == "z") iz = (int)k;
         else if (n == "nx") inx = (int)k; else if (n == "ny") iny = (int)k; else if (n == "nz") inz = (int)k;
         else if (n == "s" || n == "u" || n == "texture_u") iu = (int)k; else if (n == "t" || n == "v" || n == "texture_v") iv = (int)k;
+        else if (n == "red" || n == "diffuse_red") ic[0] = (int)k; else if (n == "green" || n == "diffuse_green") ic[1] = (int)k;
+        else if (n == "blue" || n == "diffuse_blue") ic[2] = (int)k;
       }
+      const bool has_c = ic[0] >= 0 && ic[1] >= 0 && ic[2] >= 0;
+      auto is_float = [](const std::string &t) { return t == "float" || t == "float32" || t == "double" || t == "float64"; };
       if (ix < 0 || iy < 0 || iz < 0) { err = "PLY vertices without x / y / z"; return false; }
       has_n = inx >= 0 && iny >= 0 && inz >= 0;
       has_uv = iu >= 0 && iv >= 0;
@@ -158,6 +175,8 @@ bool parse_ply(const std::string &path, ParsedMesh &out, std::string &err) {
         out.pos.push_back({(float)row[ix], (float)row[iy], (float)row[iz]});
         if (has_n) out.nrm.push_back({(float)row[inx], (float)row[iny], (float)row[inz]});
         if (has_uv) out.uv.push_back({(float)row[iu], (float)row[iv]});
+        if (has_c) out.col.push_back({color_u8(row[ic[0]], is_float(e.props[ic[0]].type)), color_u8(row[ic[1]], is_float(e.props[ic[1]].type)),
+                                      color_u8(row[ic[2]], is_float(e.props[ic[2]].type))});
       }
     } else if (e.name == "face") {
       for (size_t i = 0; i < e.count && !bad; i++) {
@@ -213,6 +232,8 @@ struct fp_loaded_mesh {
   std::vector<float> vertices, normals, texcoords;
   std::vector<uint32_t> faces;
   std::vector<uint8_t> texture;
+  std::vector<uint8_t> colors;   // [V,3] RGB, empty when the file had none
+  int color_source = FP_COLOR_TEXTURE;
   int th = 0, tw = 0;
   float diameter = 0;
   float center[3] = {0, 0, 0};
@@ -246,7 +267,11 @@ static fp_loaded_mesh *fp_mesh_load_obj_impl(const char *name, const char *mesh_
     std::istringstream ss(line);
     std::string tag;
     if (!(ss >> tag) || tag[0] == '#') continue;
-    if (tag == "v") { std::array<float, 3> p{}; ss >> p[0] >> p[1] >> p[2]; pos.push_back(p); }
+    if (tag == "v") {
+      std::array<float, 3> p{}; ss >> p[0] >> p[1] >> p[2]; pos.push_back(p);
+      float c[3];   // the `v x y z r g b` extension, colours in 0..1
+      if (ss >> c[0] >> c[1] >> c[2]) pm.col.push_back({color_u8(c[0], true), color_u8(c[1], true), color_u8(c[2], true)});
+    }
     else if (tag == "vn") { std::array<float, 3> p{}; ss >> p[0] >> p[1] >> p[2]; nrm.push_back(p); }
     else if (tag == "vt") { std::array<float, 2> p{}; ss >> p[0] >> p[1]; uv.push_back(p); }
     else if (tag == "mtllib") { std::getline(ss >> std::ws, mtllib); }
@@ -287,7 +312,13 @@ static fp_loaded_mesh *fp_mesh_load_obj_impl(const char *name, const char *mesh_
       if (c.t < 0 || c.t >= (int)uv.size()) has_uv = false;
       if (c.n < 0 || c.n >= (int)nrm.size()) has_n = false;
     }
-  if (!has_uv) { fp::set_error("[AssimpMeshLoader] Got invalid texturecoords!"); return nullptr; }
+  const bool has_col = !pos.empty() && pm.col.size() == pos.size();   // (an OBJ where only some `v` lines carry colours has none)
+  if (!has_uv && !has_col) { fp::set_error("[AssimpMeshLoader] Got invalid texturecoords!"); return nullptr; }
+  if (!has_uv) {   // colour source = the vertex colours: no texture coordinate takes part in the vertex identity
+    m->color_source = FP_COLOR_VERTEX;
+    for (auto &t : tris)
+      for (auto &c : t) c.t = -1;
+  }
   for (auto &t : tris)
     for (auto &c : t) {
       auto key = std::make_tuple(c.v, c.t, has_n ? c.n : -1);
@@ -297,7 +328,8 @@ static fp_loaded_mesh *fp_mesh_load_obj_impl(const char *name, const char *mesh_
         id = (uint32_t)(m->vertices.size() / 3);
         seen[key] = id;
         for (int k = 0; k < 3; k++) m->vertices.push_back(pos[c.v][k]);
-        for (int k = 0; k < 2; k++) m->texcoords.push_back(uv[c.t][k]);
+        for (int k = 0; k < 2; k++) m->texcoords.push_back(has_uv ? uv[c.t][k] : 0.0f);
+        if (has_col) for (int k = 0; k < 3; k++) m->colors.push_back(pm.col[c.v][k]);
         for (int k = 0; k < 3; k++) m->normals.push_back(has_n ? nrm[c.n][k] : 0.0f);
       } else {
         id = it->second;
@@ -386,6 +418,7 @@ static fp_loaded_mesh *fp_mesh_load_obj_impl(const char *name, const char *mesh_
       if (!tex_path.empty()) tex_path = dirname_of(mesh_file_path) + "/" + tex_path;
     }
     if (is_ply && !pm.texture_file.empty()) tex_path = dirname_of(mesh_file_path) + "/" + pm.texture_file;
+    if (m->color_source == FP_COLOR_VERTEX) tex_path.clear();   // nothing to map a texture with: the default below
     const bool named = !tex_path.empty();
     const bool present = named && std::ifstream(tex_path, std::ios::binary).good();
     std::string why;
@@ -419,6 +452,12 @@ fp_loaded_mesh *fp_mesh_load_obj(const char *name, const char *mesh_file_path) {
 void fp_mesh_free(fp_loaded_mesh *m) { delete m; }
 
 const fp_mesh *fp_mesh_view(const fp_loaded_mesh *m) { return m ? &m->view : nullptr; }
+
+int fp_mesh_color_source(const fp_loaded_mesh *m) {
+  if (!m) { fp::set_error("null mesh"); return -1; }
+  return m->color_source;
+}
+const uint8_t *fp_mesh_vertex_colors(const fp_loaded_mesh *m) { return m && !m->colors.empty() ? m->colors.data() : nullptr; }
 
 int fp_mesh_orient_bounds(const fp_loaded_mesh *m, float orient_bounds[16], float dimension[3]) {
   if (!m) { fp::set_error("null mesh"); return 1; }

@@ -113,8 +113,18 @@ def write_png(path: str, img: np.ndarray) -> None:
 
 
 def write_obj(d: str, mesh, name: str = "textured.obj") -> str:
-    """mesh/ directory: OBJ + MTL + texture PNG in the form fp_mesh_load_obj (and assimp) read"""
+    """mesh/ directory: OBJ + MTL + texture PNG in the form fp_mesh_load_obj (and assimp) read; a mesh whose colour source is its
+    vertex colours is written as one OBJ with `v x y z r g b` lines instead"""
     os.makedirs(d, exist_ok=True)
+    if getattr(mesh, "color_source", 0) == 1 and mesh.vertex_colors is not None:
+        # a vertex-coloured mesh (FP_COLOR_VERTEX): `v x y z r g b` with colours in 0..1, no texture coordinates, no material
+        with open(os.path.join(d, name), "w") as f:
+            f.write("o object\n")
+            f.writelines("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (tuple(p) + tuple(np.asarray(c, np.float64) / 255.0))
+                         for p, c in zip(mesh.vertices, mesh.vertex_colors))
+            f.writelines("vn %.9g %.9g %.9g\n" % tuple(p) for p in mesh.normals)
+            f.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in mesh.faces + 1)
+        return os.path.join(d, name)
     write_png(os.path.join(d, "texture_map.png"), mesh.texture)
     with open(os.path.join(d, "material.mtl"), "w") as f:
         f.write("newmtl material_0\nKd 1 1 1\nmap_Kd texture_map.png\n")

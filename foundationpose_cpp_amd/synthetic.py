@@ -28,6 +28,10 @@ class Mesh:
     texture: np.ndarray       # [TH,TW,3] u8 RGB
     diameter: float = 0.0
     center: np.ndarray | None = None  # AABB centre
+    vertex_colors: np.ndarray | None = None  # [V,3] u8 RGB, or None (files without per-vertex colours)
+    # colour source (include/foundationpose_amd.h FP_COLOR_TEXTURE 0 / FP_COLOR_VERTEX 1): not a field -- set on the instance (load_mesh
+    # does, for files without UVs) to have FoundationPose render the mesh from vertex_colors instead of its texture
+    color_source = 0
 
     def finalize(self) -> "Mesh":
         v = self.vertices.astype(np.float32)

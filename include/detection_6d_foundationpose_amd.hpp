@@ -79,6 +79,8 @@ public:
     for (int c = 0; c < 4; c++)
       for (int r = 0; r < 4; r++) orient_bounds_(r, c) = ob[c * 4 + r];
     dimension_ = Eigen::Vector3f(dim[0], dim[1], dim[2]);
+    color_source_ = fp_mesh_color_source(h);
+    if (const uint8_t *c = fp_mesh_vertex_colors(h)) colors_.assign(c, c + (size_t)m->num_vertices * 3);
     fp_mesh_free(h);
   }
   std::string GetName() const noexcept override { return name_; }
@@ -93,8 +95,14 @@ public:
   const Eigen::Matrix4f &GetOrientBounds() const noexcept override { return orient_bounds_; }
   const Eigen::Vector3f &GetObjectDimension() const noexcept override { return dimension_; }
   const cv::Mat &GetTextureMap() const noexcept override { return texture_; }
+  // new; the reference's loader interface has no colour getter (its loader refuses meshes without UVs): this loader's own members.
+  // FoundationPoseAmd applies the colours of a FP_COLOR_VERTEX mesh itself; the reference-shaped signatures are untouched.
+  int ColorSource() const noexcept { return color_source_; }
+  const std::vector<uint8_t> &VertexColors() const noexcept { return colors_; }   // [V,3] RGB, empty when the file had none
 
 private:
+  int color_source_ = FP_COLOR_TEXTURE;
+  std::vector<uint8_t> colors_;
   std::string name_;
   float diameter_ = 0;
   std::vector<Eigen::Vector3f> vertices_, normals_, uvs_;
@@ -147,6 +155,15 @@ public:
     Eigen::Matrix<float, 3, 3, Eigen::RowMajor> Kr = K;
     h_ = fp_create(cm.data(), (int)cm.size(), Kr.data(), refiner->WeightsPath().c_str(), scorer->WeightsPath().c_str(), max_h, max_w);
     if (!h_) throw std::runtime_error(std::string("[FoundationPose] Failed to Construct FoundationPose, ex : ") + fp_last_error());
+    for (const auto &loader : loaders) {   // meshes without UVs (this shim's own loader reports them) are rendered from their vertex colours
+      const auto *obj = dynamic_cast<const ObjMeshLoader *>(loader.get());
+      if (obj && obj->ColorSource() == FP_COLOR_VERTEX &&
+          fp_set_vertex_colors(h_, obj->GetName().c_str(), obj->VertexColors().data(), (int)(obj->VertexColors().size() / 3))) {
+        const std::string why = fp_last_error();
+        fp_destroy(h_);
+        throw std::runtime_error("[FoundationPose] Failed to Construct FoundationPose, ex : " + why);
+      }
+    }
   }
   ~FoundationPoseAmd() override { fp_destroy(h_); }
 

@@ -74,6 +74,19 @@ void fp_mesh_free(fp_loaded_mesh *mesh);
 const fp_mesh *fp_mesh_view(const fp_loaded_mesh *mesh);
 /* GetOrientBounds() (column-major 4x4: PCA axes | vertex mean) and GetObjectDimension() */
 int fp_mesh_orient_bounds(const fp_loaded_mesh *mesh, float orient_bounds[16], float dimension[3]);
+/* Colour source of a loaded mesh (new; the reference has no counterpart -- its loader refuses a mesh without texture coordinates).
+ * A file with usable UVs is FP_COLOR_TEXTURE: the fp_mesh view is what it always was, whether or not the file also carries colours.
+ * A file without usable UVs but with per-vertex colours -- PLY `red green blue` / `diffuse_red diffuse_green diffuse_blue` (integer types
+ * 0..255, float types 0..1 stored as rint(clamp(c, 0, 1) * 255), alpha skipped), OBJ `v x y z r g b` (0..1) on EVERY `v` line -- loads as
+ * FP_COLOR_VERTEX: the form of the LineMOD / LM-O / T-LESS / HomebrewedDB / ITODD models and of scanner output.  Its fp_mesh view carries
+ * zero texcoords and the 2x2 (100,100,100) default texture, so fp_create takes it as it is and a caller that never hands the colours
+ * over renders a grey object.  A file with neither still fails with the reference's message. */
+#define FP_COLOR_TEXTURE 0
+#define FP_COLOR_VERTEX 1
+int fp_mesh_color_source(const fp_loaded_mesh *mesh);
+/* [num_vertices,3] RGB u8 in the view's vertex order (a colour belongs to its position and follows it through the de-duplication),
+ * valid until fp_mesh_free; NULL when the file had none.  Textured meshes that also carry colours return them too. */
+const uint8_t *fp_mesh_vertex_colors(const fp_loaded_mesh *mesh);
 
 /* ---- construction: CreateFoundationPoseModel (D6F/include/.../foundationpose.hpp:99-105, src/foundationpose.cpp:108-153,448-458).
  * refiner_weights / scorer_weights: paths of packed weight files (tools/pack_weights.py; replaces the TensorRT
@@ -157,6 +170,18 @@ int fp_last_register_fit(fp_model *m, fp_pose_fit *winner, fp_pose_fit *all, int
  * (Track refines at 1.2, Register scores at 1.1), through the same render / crop kernels and the same fit kernel, whether the option
  * is on or off.  Refuses a partially uploaded frame like the other stage operators. */
 int fp_pose_fit_eval(fp_model *m, const char *target_name, const float *poses, int N, float crop_ratio, float tol_m, fp_pose_fit *out);
+
+/* ---- vertex colours: meshes without texture coordinates (new; the reference has no counterpart) ------------------------------
+ * FoundationPose as published renders a mesh without UVs by interpolating its vertex colours.  fp_set_vertex_colors makes
+ * `colors` ([num_vertices,3] RGB u8, host memory, copied; num_vertices must equal the target's vertex count) the colour source of
+ * `target_name`: a foreground pixel of its renderings is then sum_k b_k * (c_k / 255) over the triangle's corners -- the rule every
+ * interpolated attribute follows, in the model's float model -- times the Lambert term, instead of a texture sample (DESIGN.md
+ * section 4.1).  Geometry channels, triangle ids and the crop do not change.  colors == NULL returns the target to its texture.
+ * Works on geometry-only models.  Like fp_set_pose_fit it waits for the model's work and drops the captured graphs; while no target
+ * uses vertex colours nothing is allocated, launched or captured differently.  Errors: unknown target, count mismatch. */
+int fp_set_vertex_colors(fp_model *m, const char *target_name, const uint8_t *colors, int num_vertices);
+/* FP_COLOR_TEXTURE / FP_COLOR_VERTEX, or a negative value on an unknown target */
+int fp_get_color_source(const fp_model *m, const char *target_name);
 
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 

@@ -29,6 +29,10 @@ struct Mesh {  // what BaseMeshLoader's getters return (mesh_loader.hpp:25-61)
   int tex_height = 0, tex_width = 0;
   float diameter = 0;
   float center[3] = {0, 0, 0};
+  // new; the reference has no counterpart: per-vertex colours [V,3] RGB (empty: the file had none) and the colour source
+  // (FP_COLOR_TEXTURE / FP_COLOR_VERTEX: a file without UVs that carries colours; its texcoords are zero, its texture the grey default)
+  std::vector<uint8_t> vertex_colors;
+  int color_source = FP_COLOR_TEXTURE;
 };
 
 // CreateAssimpMeshLoader(name, path) equivalent (mesh_loader.hpp:92-93): OBJ + MTL + PNG; throws like the reference
@@ -46,6 +50,8 @@ inline Mesh LoadObjMesh(const std::string &name, const std::string &mesh_file_pa
   m.texture.assign(v->texture, v->texture + (size_t)v->tex_height * v->tex_width * 3);
   m.tex_height = v->tex_height; m.tex_width = v->tex_width; m.diameter = v->diameter;
   for (int k = 0; k < 3; k++) m.center[k] = v->center[k];
+  m.color_source = fp_mesh_color_source(h);
+  if (const uint8_t *c = fp_mesh_vertex_colors(h)) m.vertex_colors.assign(c, c + (size_t)v->num_vertices * 3);
   fp_mesh_orient_bounds(h, orient_bounds16, dimension3);
   fp_mesh_free(h);
   return m;
@@ -71,6 +77,12 @@ public:
     h_ = fp_create(cm.data(), (int)cm.size(), K, refiner_weights.empty() ? nullptr : refiner_weights.c_str(),
                    scorer_weights.empty() ? nullptr : scorer_weights.c_str(), max_h, max_w);
     if (!h_) throw std::runtime_error(std::string("[FoundationPose] Failed to Construct FoundationPose, ex : ") + fp_last_error());
+    for (const Mesh &m : meshes)   // meshes without UVs are rendered from their vertex colours, with no extra call from the user
+      if (m.color_source == FP_COLOR_VERTEX && fp_set_vertex_colors(h_, m.name.c_str(), m.vertex_colors.data(), (int)(m.vertex_colors.size() / 3))) {
+        const std::string why = fp_last_error();
+        fp_destroy(h_);
+        throw std::runtime_error("[FoundationPose] Failed to Construct FoundationPose, ex : " + why);
+      }
   }
   ~FoundationPose() { fp_destroy(h_); }
   FoundationPose(const FoundationPose &) = delete;
@@ -153,6 +165,11 @@ public:
   // LastTrackFit: one record per tracked object, of the pose the last refine iteration STARTED from (one frame late with refine_itr 1);
   // LastRegisterFit: the returned pose's record (all: every hypothesis'); PoseFit: any poses on the uploaded frame (fp_upload_frame)
   bool SetPoseFit(bool on, float tol_m = 0.005f) { return ok(fp_set_pose_fit(h_, on ? 1 : 0, tol_m)); }
+  // vertex colours (new; the reference has no counterpart): colors = [V,3] RGB u8 of the target, nullptr = back to its texture
+  bool SetVertexColors(const std::string &target_name, const uint8_t *colors, int num_vertices) {
+    return ok(fp_set_vertex_colors(h_, target_name.c_str(), colors, num_vertices));
+  }
+  int ColorSource(const std::string &target_name) const { return fp_get_color_source(h_, target_name.c_str()); }
   bool LastTrackFit(std::vector<fp_pose_fit> &out, size_t objects = 1) {
     out.resize(objects);
     return ok(fp_last_track_fit(h_, out.data(), (int)objects));
