@@ -200,14 +200,8 @@ void roctx_push(const char *name) { if (roctx_api().push) (void)roctx_api().push
 void roctx_pop() { if (roctx_api().pop) (void)roctx_api().pop(); }
 #ifdef FP_TEST_HOOKS
 static int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;   // A/B (fpt_set_calib_opts): steps of the 8-bit calibration
-static int g_vertex_crop = 1;   // A/B (fpt_set_vertex_crop): Track's crop warp (and, unless 2, the triangles' row ranges) inside the vertex launch
-static int g_tri_rows_all_batches = 0;   // A/B (fpt_set_tri_rows(2)): size the buffer for large batches too
-static int g_tri_rows = 1;      // A/B (fpt_set_tri_rows): per-triangle row ranges, so that a strip of the rasteriser skips the triangles that miss it
 #else
 static constexpr int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;
-static constexpr int g_vertex_crop = 1;
-static constexpr int g_tri_rows = 1;
-static constexpr int g_tri_rows_all_batches = 0;
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -564,9 +558,8 @@ static int ensure_capacity(fp_model *m, int N, size_t V) {
     if (dev_alloc(&m->attr, (size_t)m->cap * V)) return 1;
     m->vert_cap = (size_t)m->cap * V;
   }
-  // row ranges: for the largest mesh of the model (any target may be rendered) and for the batch sizes that are rendered in short
-  // strips (raster_wants_tri_rows: below 100 hypotheses; a larger batch falls back to the full walk when the buffer is too small)
-  const size_t tri_need = (size_t)(g_tri_rows_all_batches ? m->cap : std::min(m->cap, 99)) * m->max_faces;
+  // row ranges: for the largest mesh of the model (any target may be rendered) and for the batch sizes plan_render uses them at
+  const size_t tri_need = (size_t)std::min(m->cap, RENDER_TRI_ROWS_MAX_N) * m->max_faces;
   if (V > 0 && tri_need > m->tri_cap) {
     g_alloc_epoch++;
     dev_free(m->tri_rows);
@@ -596,7 +589,8 @@ static int check_frame_args(fp_model *m, int H, int W, const char *target_name, 
   return 0;
 }
 
-// render + crop for N poses already in m->poses_dev; writes the fp16 network input (both halves) or fp32 blobs
+// render + crop for N poses already in m->poses_dev; writes the fp16 network input (both halves) or fp32 blobs.  WHAT is launched
+// is plan_render's decision (fp_geometry.hip); this function builds the query and runs the plan's steps
 // n_crop: number of observed crops to produce (N, or 1 when every hypothesis shares the same translation)
 static int render_and_crop(fp_model *m, Target *t, int N, float crop_ratio, OutMode mode, void *out_a, void *out_b,
                            int32_t *dbg_tri, float *dbg_rast, int n_crop = -1, const float *poses_src = nullptr, PoseRec *recs = nullptr) {
@@ -604,38 +598,39 @@ static int render_and_crop(fp_model *m, Target *t, int N, float crop_ratio, OutM
   if (!recs) recs = m->recs;   // (fp_track_multi: the records of one object group inside the batch)
   hipStream_t s = m->stream;
   const size_t out_bytes = (mode == OUT_F32X6 ? 24.0 : 16.0) * FP_CROP_HW * FP_CROP_HW;  // both 2-byte modes: 16 B per pixel
-  if (!out_a) {
-    ProfScope ps(&m->prof, s, "pose_setup");
-    launch_pose_setup(s, poses_src ? poses_src : m->poses_dev, N, m->K, m->H, m->W, crop_ratio, t->mesh.diameter, recs);
+  const float *poses = poses_src ? poses_src : m->poses_dev;
+  const DeviceMesh &mesh = t->mesh;
+  RenderQuery q;
+  q.N = N; q.mode = mode; q.out_a = out_a != nullptr; q.out_b = out_b != nullptr; q.taps = dbg_tri || dbg_rast; q.prof = m->prof.on;
+  q.F = mesh.F; q.tri_cap = m->tri_rows ? m->tri_cap : 0;
+  const RenderPlan plan = plan_render(q);
+  unsigned *const rows = plan.row_ranges != ROW_RANGES_NONE ? m->tri_rows : nullptr;
+  switch (plan.front) {
+    case FRONT_SETUP: {
+      ProfScope ps(&m->prof, s, "pose_setup");
+      launch_pose_setup(s, poses, N, m->K, m->H, m->W, crop_ratio, mesh.diameter, recs);
+    } break;
+    case FRONT_SETUP_VERTEX: {   // pose set-up (crop window, bounding box, projection) is computed inside the vertex kernel: one launch less per render
+      ProfScope ps(&m->prof, s, "vertex", 0, (double)N * mesh.V * 32.0 + mesh.V * 24.0);
+      launch_setup_vertex(s, mesh, poses, N, m->K, m->H, m->W, crop_ratio, mesh.diameter, recs, m->clip, m->attr, m->fmad);
+    } break;
+    case FRONT_SETUP_VERTEX_CROP:   // tiny batches (Track): set-up + vertex stage + crop warp + the triangles' row ranges as ONE launch
+      launch_setup_vertex_crop(s, mesh, poses, N, m->K, m->H, m->W, crop_ratio, mesh.diameter, recs, m->clip, m->attr, m->fmad, m->frame_dev,
+                               n_crop, mode, out_b, plan.row_ranges == ROW_RANGES_BY_FRONT ? rows : nullptr);
+      break;
   }
-  unsigned *const rows_small = g_tri_rows && m->tri_rows && raster_wants_tri_rows(N) && (size_t)N * t->mesh.F <= m->tri_cap ? m->tri_rows : nullptr;
-  if (out_a && out_b && N <= 4 && !m->prof.on && !dbg_tri && !dbg_rast && g_vertex_crop &&
-      launch_setup_vertex_crop(s, t->mesh, poses_src ? poses_src : m->poses_dev, N, m->K, m->H, m->W, crop_ratio, t->mesh.diameter, recs, m->clip,
-                               m->attr, m->fmad, m->frame_dev, n_crop, mode, out_b, g_vertex_crop == 2 ? nullptr : rows_small)) {
-    // tiny batches (Track): set-up + vertex stage + crop warp + the triangles' row ranges were ONE launch; the rasteriser follows
-    unsigned *rows = rows_small;
-    if (rows && g_vertex_crop == 2) launch_tri_rows(s, t->mesh, N, m->clip, rows);   // A/B: the row ranges as their own launch
-    launch_raster_shade(s, t->mesh, recs, N, m->clip, m->attr, mode, out_a, nullptr, nullptr, m->fmad, rows);
-    FP_HIP_OK(hipGetLastError());
-    return 0;
+  if (plan.row_ranges == ROW_RANGES_OWN_LAUNCH) {
+    ProfScope ps(&m->prof, s, "tri_rows", 0, (double)N * mesh.F * (12.0 + 48.0 + 4.0));
+    launch_tri_rows(s, mesh, N, m->clip, rows);
   }
-  if (out_a) {
-    {   // pose set-up (crop window, bounding box, projection) is computed inside the vertex kernel: one launch less per render
-      ProfScope ps(&m->prof, s, "vertex", 0, (double)N * t->mesh.V * 32.0 + t->mesh.V * 24.0);
-      launch_setup_vertex(s, t->mesh, poses_src ? poses_src : m->poses_dev, N, m->K, m->H, m->W, crop_ratio, t->mesh.diameter, recs,
-                          m->clip, m->attr, m->fmad);
-    }
-    unsigned *rows = g_tri_rows && m->tri_rows && raster_wants_tri_rows(N) && (size_t)N * t->mesh.F <= m->tri_cap ? m->tri_rows : nullptr;
-    if (rows) {
-      ProfScope ps(&m->prof, s, "tri_rows", 0, (double)N * t->mesh.F * (12.0 + 48.0 + 4.0));
-      launch_tri_rows(s, t->mesh, N, m->clip, rows);
-    }
-    ProfScope ps(&m->prof, s, "raster_shade", 0, (double)N * (out_bytes + t->mesh.V * 32.0 + t->mesh.F * 12.0));
-    launch_raster_shade(s, t->mesh, recs, N, m->clip, m->attr, mode, out_a, dbg_tri, dbg_rast, m->fmad, rows);
+  if (plan.front != FRONT_SETUP) {
+    ProfScope ps(&m->prof, s, "raster_shade", 0, (double)N * (out_bytes + mesh.V * 32.0 + mesh.F * 12.0));
+    FP_CHECK(launch_raster_shade(s, plan, mesh, recs, N, m->clip, m->attr, mode, out_a, dbg_tri, dbg_rast, m->fmad, rows),
+             "[FoundationPose] internal error: no rasteriser instantiation for the render plan");
   }
-  if (out_b) {
+  if (plan.crop_launch) {
     ProfScope ps(&m->prof, s, "crop_warp", 0, (double)n_crop * out_bytes);
-    launch_crop(s, m->frame_dev, m->H, m->W, m->K, recs, n_crop, t->mesh.diameter, mode, out_b);
+    launch_crop(s, m->frame_dev, m->H, m->W, m->K, recs, n_crop, mesh.diameter, mode, out_b);
   }
   FP_HIP_OK(hipGetLastError());
   return 0;
@@ -790,8 +785,6 @@ extern "C" {
 
 #ifdef FP_TEST_HOOKS
 void fpt_set_calib_opts(int sweeps, int tok, int out) { g_calib_sweeps = sweeps; g_calib_tok = tok; g_calib_out = out; }
-void fpt_set_vertex_crop(int v) { g_vertex_crop = v; }
-void fpt_set_tri_rows(int v) { g_tri_rows = v != 0; g_tri_rows_all_batches = v == 2; }
 // A/B hook: hipGraph replay of the Track / Register bodies on or off for one model
 int fpt_model_use_graphs(fp_model *m, int on) {
   m->use_graphs = on != 0;

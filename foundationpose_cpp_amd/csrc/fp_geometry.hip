@@ -23,6 +23,7 @@
 
 #include "fp_internal.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace fp {
 
@@ -32,7 +33,7 @@ namespace fp {
 #define CR_DEPTH_MAX (0xFFFFFFFFu - (2200u << 3))
 
 static constexpr int CROP = FP_CROP_HW;
-// rows of the 160-row viewport owned by one workgroup: 20 (8 strips/hypothesis) for large batches, 8 (20 strips) when
+// rows of the 160-row viewport owned by one workgroup: 4 / 8 / 20 / 80 by batch size (plan_render below) -- short strips when
 // the batch alone cannot fill the chip (Track: N = 1).  The shading pass is a chain of dependent loads per pixel, so
 // its latency is hidden by workgroup count, not by work per thread.
 
@@ -748,131 +749,99 @@ __global__ __launch_bounds__(NT) void raster_shade_kernel(
   }
 }
 
-// the row ranges of the launch in progress (launch_raster_shade sets it; the launchers below are plain host code of the same call)
-static thread_local const unsigned *t_tri_rows = nullptr;
-static size_t tri_list_lds() { return t_tri_rows ? (size_t)TRI_LIST * 4 + 16 : 0; }
-
+// ---- the render + crop schedule ----------------------------------------------------------------------------------------------
+// A/B switches (fpt_set_tri_rows / fpt_set_raster_strip_threads / fpt_set_vertex_crop): an object of the test build only, read by
+// plan_render alone; the product plans with the defaults
+struct RenderOverride {
+  int tri_rows = 1;      // 0: no row ranges, every strip walks every triangle
+  int threads = 0;       // 256 / 512 / 1024: threads per workgroup of the product path's 8-row strips; 0: by batch size
+  int vertex_crop = 1;   // 0: no fused front launch; 2: fused, but the row ranges as their own tri_rows_kernel launch
+};
 #ifdef FP_TEST_HOOKS
-static int g_tri_rows_tall = 0;  // A/B (test build): row ranges for the tall strips of large batches too
-void set_tri_rows_tall(int v) { g_tri_rows_tall = v; }
-#else
-static constexpr int g_tri_rows_tall = 0;
-#endif
-#ifdef FP_TEST_HOOKS
-static int g_strip_threads = 0;  // A/B (test build): threads per 8-row strip workgroup for small batches, 0 = by batch size
-void set_raster_strip_threads(int t) { g_strip_threads = t; }
-#else
-static constexpr int g_strip_threads = 0;
+static RenderOverride g_render_override;
 #endif
 
-template <int MODE, int STRIP_ROWS, bool FMAD, bool VCOL>
-static void launch_raster_shade_t(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
-                                  const float4 *attr, void *out, int32_t *tri_id_dbg, float *rast_dbg) {
-  size_t lds = (size_t)STRIP_ROWS * CROP * sizeof(unsigned long long) + tri_list_lds();
-  dim3 grid(CROP / STRIP_ROWS, N), block(256);
-  float downscale = m.diameter / 2;
-  // small batches (a few objects, a 32-hypothesis shard of a strong-scaled Register): the launch is a latency chain of F / NT dependent
-  // triangle iterations per strip, not throughput -- 16 waves per strip while two such workgroups per CU hold the whole grid
-  // (20 strips x N <= 512), 8 waves up to where 8-row strips are used at all (N < 48).  [r4] tools/profile_shard.py: N = 12: 55 -> 29 us per
-  // launch; from N ~ 32 on the launch is bound by the gather rate of the 20x redundant triangle set-up instead (64 us at any width)
-  if constexpr (STRIP_ROWS == 8 && MODE != OUT_F32X6) if (!tri_id_dbg && !rast_dbg && g_strip_threads != 256) {
-    if (g_strip_threads == 1024 || (g_strip_threads == 0 && N <= 25)) {
-      hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD, VCOL>), grid, dim3(1024), lds, s, m.faces, m.F, m.V, m.uvs,
-                         m.tex, m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows, m.vcol);
-      return;
-    }
-    if (g_strip_threads == 512 || (g_strip_threads == 0 && N < 48)) {
-      hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 512, FMAD, VCOL>), grid, dim3(512), lds, s, m.faces, m.F, m.V, m.uvs,
-                         m.tex, m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows, m.vcol);
-      return;
-    }
-  }
-  if constexpr (STRIP_ROWS >= 40) {   // (test-build strip heights: z-buffer + list exceed the 64 KB a kernel gets without asking)
-    static PerDeviceOnce attr_once;
-    attr_once.run([] {
-      (void)hipFuncSetAttribute((const void *)raster_shade_kernel<MODE, STRIP_ROWS, 256, FMAD, VCOL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((size_t)STRIP_ROWS * CROP * sizeof(unsigned long long) + (size_t)TRI_LIST * 4 + 16));
-    });
-  }
-  hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 256, FMAD, VCOL>), grid, block, lds, s, m.faces, m.F, m.V, m.uvs, m.tex,
-                     m.TH, m.TW, downscale, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows, m.vcol);
-}
-
-#ifdef FP_TEST_HOOKS
-static int g_strip_rows_override = 0;  // A/B: tools/ab_raster_strips.py (test build only)
-void set_raster_strip_rows(int r) { g_strip_rows_override = r; }
-#else
-static constexpr int g_strip_rows_override = 0;
-#endif
-
-// tall strips with 1024-thread workgroups: every strip walks ALL triangles (setup + cull), so 2 strips of 80 rows do a
-// quarter of the redundant setup of 8 strips of 20 (0.40 -> 0.21 ms per Register at N = 252); 102 KB of LDS = one
-// workgroup per CU, hence 16 waves per workgroup.  A/B codes for set_raster_strip_rows: 1080 / 1040 / 1020
-template <int MODE, int STRIP_ROWS, bool FMAD, bool VCOL>
-static void launch_raster_tall(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
-                               const float4 *attr, void *out) {
-  const size_t lds_max = (size_t)STRIP_ROWS * CROP * sizeof(unsigned long long) + (size_t)TRI_LIST * 4 + 16;
-  size_t lds = (size_t)STRIP_ROWS * CROP * sizeof(unsigned long long) + tri_list_lds();
-  // once per instantiation and device: opt in to > 64 KB of dynamic LDS
-  static PerDeviceOnce attr_once;
-  attr_once.run([lds_max] {
-    (void)hipFuncSetAttribute((const void *)raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD, VCOL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_max);
-  });
-  hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, 1024, FMAD, VCOL>), dim3(CROP / STRIP_ROWS, N), dim3(1024), lds, s, m.faces, m.F,
-                     m.V, m.uvs, m.tex, m.TH, m.TW, m.diameter / 2, recs, clip, attr, out, nullptr, nullptr, t_tri_rows, m.vcol);
-}
-
+// Small batches (a few objects, a 32-hypothesis shard of a strong-scaled Register): the rasteriser is a latency chain of F / NT
+// dependent triangle iterations per strip, not throughput.  One or two hypotheses (Track): 4-row strips with 1024 threads -- the
+// shading pass covers the strip in ONE iteration (640 pixels; 8 rows = 1280 pixels took two, the second a quarter full) and a strip
+// meets half as many triangles.  8-row strips: 16 waves while two such workgroups per CU hold the whole grid (20 strips x N <= 512),
+// 8 waves up to where 8-row strips are used at all; [r4] tools/profile_shard.py: N = 12: 55 -> 29 us per launch; from N ~ 32 on the
+// launch is bound by the gather rate of the 20x redundant triangle set-up instead (64 us at any width).  Full Register batches:
+// every strip walks ALL triangles (set-up + cull), so 2 strips of 80 rows do a quarter of the redundant set-up of 8 strips of 20
+// (0.40 -> 0.21 ms per Register at N = 252); 102 KB of LDS = one workgroup per CU, hence 16 waves per workgroup.
 // Row ranges pay where a crop is cut into many short strips (Track: 40, small batches: 20 or 8); the two 80-row strips of a full
 // Register batch meet half of the triangles each, and the extra launch + list passes cost what the skipped set-ups save
 // (tools/mesh_size_sweep.py: N = 252, 20 k triangles, 412 -> 396 us of rasteriser + the range kernel).
-static int strip_rows_for(int N) { return g_strip_rows_override ? g_strip_rows_override : (N >= 100 ? 1080 : (N >= 48 ? 20 : 8)); }
-bool raster_wants_tri_rows(int N) { return strip_rows_for(N) < 1000 || g_tri_rows_tall; }
-
-template <int MODE, bool FMAD, bool VCOL>
-static void launch_raster_mode(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
-                               const float4 *attr, void *out, int32_t *tri_id_dbg, float *rast_dbg) {
-  int rows = strip_rows_for(N);  // (tools/ab_raster_strips.py: 8-row strips win up to ~40 hypotheses)
-  if constexpr (MODE != OUT_F32X6) if (rows > 1000 && !tri_id_dbg && !rast_dbg) {
-    if (rows == 1080) { launch_raster_tall<MODE, 80, FMAD, VCOL>(s, m, recs, N, clip, attr, out); return; }
+// The wide workgroups and the fused front launch exist for the product path only: a 2-byte output mode without debug taps.
+RenderPlan plan_render(const RenderQuery &q) {
 #ifdef FP_TEST_HOOKS
-    if (rows == 1040) launch_raster_tall<MODE, 40, FMAD, VCOL>(s, m, recs, N, clip, attr, out);
-    else launch_raster_tall<MODE, 20, FMAD, VCOL>(s, m, recs, N, clip, attr, out);
-    return;
+  const RenderOverride ov = g_render_override;
+#else
+  constexpr RenderOverride ov{};
 #endif
+  const bool product_path = q.mode != OUT_F32X6 && !q.taps;
+  RenderPlan p{};
+  p.front = !q.out_a ? FRONT_SETUP
+            : q.out_b && q.N <= RENDER_FUSED_FRONT_MAX_N && product_path && !q.prof && ov.vertex_crop ? FRONT_SETUP_VERTEX_CROP
+                                                                                                        : FRONT_SETUP_VERTEX;
+  const bool ranges = ov.tri_rows && q.out_a && q.N <= RENDER_TRI_ROWS_MAX_N && q.F > 0 && (size_t)q.N * (size_t)q.F <= q.tri_cap;
+  p.row_ranges = !ranges ? ROW_RANGES_NONE : p.front == FRONT_SETUP_VERTEX_CROP && ov.vertex_crop != 2 ? ROW_RANGES_BY_FRONT : ROW_RANGES_OWN_LAUNCH;
+  p.crop_launch = q.out_b && p.front != FRONT_SETUP_VERTEX_CROP;
+  if (product_path && q.N > RENDER_TRI_ROWS_MAX_N) { p.strip_rows = 80; p.threads = 1024; }
+  else if (q.N > RENDER_ROWS8_MAX_N) { p.strip_rows = 20; p.threads = 256; }
+  else if (product_path && q.N <= RENDER_ROWS4_MAX_N) { p.strip_rows = 4; p.threads = 1024; }
+  else {
+    p.strip_rows = 8;
+    p.threads = !product_path ? 256 : ov.threads ? ov.threads : q.N <= RENDER_NT1024_MAX_N ? 1024 : 512;
   }
-  if (rows > 1000) rows = 20;
-#ifdef FP_TEST_HOOKS
-  if (rows == 40) { launch_raster_shade_t<MODE, 40, FMAD, VCOL>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg); return; }
-#endif
-  if (rows == 20) { launch_raster_shade_t<MODE, 20, FMAD, VCOL>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg); return; }
-  // one or two hypotheses (Track): 4-row strips with 1024 threads -- the shading pass covers the strip in ONE iteration
-  // (640 pixels; 8 rows = 1280 pixels took two, the second a quarter full) and a strip meets half as many triangles
-  if constexpr (MODE != OUT_F32X6) if ((rows == 4 || (rows == 8 && N <= 2 && !g_strip_rows_override)) && !tri_id_dbg && !rast_dbg) {
-    const size_t lds = (size_t)4 * CROP * sizeof(unsigned long long) + tri_list_lds();
-    hipLaunchKernelGGL((raster_shade_kernel<MODE, 4, 1024, FMAD, VCOL>), dim3(CROP / 4, N), dim3(1024), lds, s, m.faces, m.F, m.V, m.uvs,
-                       m.tex, m.TH, m.TW, m.diameter / 2, recs, clip, attr, out, tri_id_dbg, rast_dbg, t_tri_rows, m.vcol);
-    return;
-  }
-  launch_raster_shade_t<MODE, 8, FMAD, VCOL>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);
+  const int zbuf = p.strip_rows * CROP * (int)sizeof(unsigned long long), list = TRI_LIST * 4 + 16;
+  p.lds = zbuf + (ranges ? list : 0);
+  p.lds_optin = zbuf + list > 64 * 1024;   // (per instantiation, whichever way this launch uses it)
+  return p;
 }
 
-void launch_raster_shade(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
+template <int MODE, int STRIP_ROWS, int NT, bool FMAD, bool VCOL>
+static void launch_raster_instance(hipStream_t s, const RenderPlan &plan, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
+                                   const float4 *attr, void *out, int32_t *tri_id_dbg, float *rast_dbg, const unsigned *tri_rows) {
+  constexpr int LDS_MAX = STRIP_ROWS * CROP * (int)sizeof(unsigned long long) + TRI_LIST * 4 + 16;
+  if constexpr (LDS_MAX > 64 * 1024) {   // once per instantiation and device: opt in to > 64 KB of dynamic LDS
+    static PerDeviceOnce attr_once;
+    attr_once.run([] {
+      (void)hipFuncSetAttribute((const void *)raster_shade_kernel<MODE, STRIP_ROWS, NT, FMAD, VCOL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    });
+  }
+  hipLaunchKernelGGL((raster_shade_kernel<MODE, STRIP_ROWS, NT, FMAD, VCOL>), dim3(CROP / STRIP_ROWS, N), dim3(NT), (size_t)plan.lds, s, m.faces, m.F,
+                     m.V, m.uvs, m.tex, m.TH, m.TW, m.diameter / 2, recs, clip, attr, out, tri_id_dbg, rast_dbg, tri_rows, m.vcol);
+}
+
+// THE table of rasteriser instantiations, (strip rows, threads): every output mode has the first line, the 2-byte modes the second too
+#define FP_RASTER_SHAPES_ANY_MODE(X) X(8, 256) X(20, 256)
+#define FP_RASTER_SHAPES_2_BYTE(X) X(4, 1024) X(8, 1024) X(8, 512) X(80, 1024)
+template <class F> static bool with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+bool launch_raster_shade(hipStream_t s, const RenderPlan &plan, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
                          const float4 *attr, OutMode mode, void *out, int32_t *tri_id_dbg, float *rast_dbg, bool fmad,
                          const unsigned *tri_rows) {
-  t_tri_rows = tri_rows;
-#define FP_RASTER_MODE(MODE)                                                                                      \
-  do {                                                                                                            \
-    if (m.vcol) {                                                                                                 \
-      if (fmad) launch_raster_mode<MODE, true, true>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);       \
-      else launch_raster_mode<MODE, false, true>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);           \
-    } else if (fmad) launch_raster_mode<MODE, true, false>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg); \
-    else launch_raster_mode<MODE, false, false>(s, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg);            \
-  } while (0)
-  if (mode == OUT_F32X6) FP_RASTER_MODE(OUT_F32X6);
-  else if (mode == OUT_BF16X8) FP_RASTER_MODE(OUT_BF16X8);
-  else FP_RASTER_MODE(OUT_F16X8);
-#undef FP_RASTER_MODE
+  auto with_mode = [&](auto mode_c) {
+    return with_bool(fmad, [&](auto fmad_c) {
+      return with_bool(m.vcol != nullptr, [&](auto vcol_c) {
+        constexpr int MODE = decltype(mode_c)::value;
+#define FP_RASTER_SHAPE(ROWS, NT)                                                                                                     \
+  if (plan.strip_rows == ROWS && plan.threads == NT) {                                                                                \
+    launch_raster_instance<MODE, ROWS, NT, decltype(fmad_c)::value, decltype(vcol_c)::value>(s, plan, m, recs, N, clip, attr, out, tri_id_dbg, rast_dbg, \
+                                                                                              tri_rows);                              \
+    return true;                                                                                                                      \
+  }
+        FP_RASTER_SHAPES_ANY_MODE(FP_RASTER_SHAPE)
+        if constexpr (MODE != OUT_F32X6) { FP_RASTER_SHAPES_2_BYTE(FP_RASTER_SHAPE) }
+#undef FP_RASTER_SHAPE
+        return false;
+      });
+    });
+  };
+  if (mode == OUT_F32X6) return with_mode(std::integral_constant<int, OUT_F32X6>{});
+  if (mode == OUT_BF16X8) return with_mode(std::integral_constant<int, OUT_BF16X8>{});
+  return with_mode(std::integral_constant<int, OUT_F16X8>{});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1119,11 +1088,10 @@ __global__ __launch_bounds__(256) void vertex_crop_kernel(const float *__restric
   crop_body<MODE>(frame, sa.img_h, sa.img_w, sa.K.k[0], sa.K.k[4], sa.K.k[2], sa.K.k[5], own, sa.diameter / 2, out_b, n, i);
 }
 
-// returns false when the combination is not instantiated (fp32 blobs): the caller then launches the two kernels
-bool launch_setup_vertex_crop(hipStream_t s, const DeviceMesh &m, const float *poses_dev, int N, const float *K9_host, int img_h, int img_w,
+// 2-byte output modes only: plan_render asks for this launch in no other
+void launch_setup_vertex_crop(hipStream_t s, const DeviceMesh &m, const float *poses_dev, int N, const float *K9_host, int img_h, int img_w,
                               float crop_ratio, float diameter, PoseRec *recs, float4 *clip, float4 *attr, bool fmad, const FrameRef *frame,
                               int n_crop, OutMode mode, void *out_b, unsigned *tri_rows) {
-  if (mode == OUT_F32X6) return false;
   PoseSetupArgs sa;
   sa.poses = poses_dev;
   for (int i = 0; i < 9; i++) sa.K.k[i] = K9_host[i];
@@ -1135,7 +1103,6 @@ bool launch_setup_vertex_crop(hipStream_t s, const DeviceMesh &m, const float *p
   if (mode == OUT_BF16X8) { if (fmad) FP_VC(true, OUT_BF16X8); else FP_VC(false, OUT_BF16X8); }
   else { if (fmad) FP_VC(true, OUT_F16X8); else FP_VC(false, OUT_F16X8); }
 #undef FP_VC
-  return true;
 }
 
 void launch_crop(hipStream_t s, const FrameRef *frame, int H, int W, const float *K, const PoseRec *recs,
@@ -1404,3 +1371,24 @@ void launch_pose_fit(hipStream_t s, const void *img_a, size_t a_stride_halfs, co
 }
 
 }  // namespace fp
+
+#ifdef FP_TEST_HOOKS
+extern "C" {
+void fpt_set_tri_rows(int v) { fp::g_render_override.tri_rows = v != 0; }
+void fpt_set_raster_strip_threads(int t) { fp::g_render_override.threads = t == 256 || t == 512 || t == 1024 ? t : 0; }
+void fpt_set_vertex_crop(int v) { fp::g_render_override.vertex_crop = v; }
+// HOST-ONLY (no HIP call: runs without a GPU, tests/test_render_plan_cpu.py): the plans of n render_and_crop calls under the current
+// switches.  query8 [n][8] = {N, mode (OutMode), out_a, out_b, taps, prof, F, capacity of the row-range buffer in entries}
+// -> plan7 [n][7] = {front (RenderFront), row_ranges (RowRanges), strip_rows, threads, lds, lds_optin, crop_launch}
+void fpt_plan_render(const long long *query8, int *plan7, long long n) {
+  for (long long i = 0; i < n; i++, query8 += 8, plan7 += 7) {
+    fp::RenderQuery q;
+    q.N = (int)query8[0]; q.mode = (fp::OutMode)query8[1]; q.out_a = query8[2] != 0; q.out_b = query8[3] != 0; q.taps = query8[4] != 0;
+    q.prof = query8[5] != 0; q.F = (int)query8[6]; q.tri_cap = (size_t)query8[7];
+    const fp::RenderPlan p = fp::plan_render(q);
+    const int f[7] = {p.front, p.row_ranges, p.strip_rows, p.threads, p.lds, p.lds_optin ? 1 : 0, p.crop_launch ? 1 : 0};
+    for (int k = 0; k < 7; k++) plan7[k] = f[k];
+  }
+}
+}
+#endif

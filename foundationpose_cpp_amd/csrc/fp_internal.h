@@ -192,22 +192,46 @@ __device__ __forceinline__ void pose_update_one(float *poses, const float *__res
 }
 #endif
 struct FrameRef;
-// tiny batches: the same + the observed-crop warp of hypotheses [0, n_crop) in ONE launch (false: not available for this output mode);
-// tri_rows non-null: the launch also leaves the [N, F] row ranges launch_tri_rows would compute from its clip coordinates
-bool launch_setup_vertex_crop(hipStream_t s, const DeviceMesh &m, const float *poses_dev, int N, const float *K9_host, int img_h, int img_w,
+// tiny batches: the same + the observed-crop warp of hypotheses [0, n_crop) in ONE launch, 2-byte output modes only (plan_render asks
+// for it in no other); tri_rows non-null: the launch also leaves the [N, F] row ranges launch_tri_rows would compute from its clip coordinates
+void launch_setup_vertex_crop(hipStream_t s, const DeviceMesh &m, const float *poses_dev, int N, const float *K9_host, int img_h, int img_w,
                               float crop_ratio, float diameter, PoseRec *recs, float4 *clip, float4 *attr, bool fmad, const FrameRef *frame,
                               int n_crop, OutMode mode, void *out_b, unsigned *tri_rows);
-// tri_rows: [N, F] row ranges from launch_tri_rows of the same clip coordinates (a strip then skips the triangles that miss it), or null
+// [N, F] row ranges of the triangles of these clip coordinates (a strip of the rasteriser then skips the triangles that miss it)
 void launch_tri_rows(hipStream_t s, const DeviceMesh &m, int N, const float4 *clip, unsigned *rows);
-bool raster_wants_tri_rows(int N);   // false for batches that are rendered in two tall strips per crop
-void launch_raster_shade(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
+
+// The render + crop schedule: which kernels one render_and_crop call (fp_api.hip) launches and in which shape is
+// plan_render's decision alone -- a pure host function (no HIP call; the test build's fpt_plan_render asks it without a GPU,
+// tests/test_render_plan_cpu.py), like plan_conv of fp_nn.hip.  The thresholds, each the LARGEST batch of its row of the table:
+constexpr int RENDER_FUSED_FRONT_MAX_N = 4;   // set-up + vertex stage + crop warp (+ row ranges) as one launch (Track)
+constexpr int RENDER_ROWS4_MAX_N = 2;         // 4-row strips of 1024 threads
+constexpr int RENDER_NT1024_MAX_N = 25;       // 8-row strips of 1024 threads
+constexpr int RENDER_ROWS8_MAX_N = 47;        // 8-row strips (of 512 threads); above: 20-row strips of 256 threads
+constexpr int RENDER_TRI_ROWS_MAX_N = 99;     // row ranges; above: two 80-row strips of 1024 threads that walk every triangle
+struct RenderQuery {
+  int N = 0;
+  OutMode mode = OUT_F16X8;
+  bool out_a = false, out_b = false;   // a rendered / an observed output is wanted
+  bool taps = false;                   // debug taps (triangle ids, rasteriser output) are attached
+  bool prof = false;                   // the profiler is on: every stage is its own, bracketed launch
+  int F = 0;                           // triangles of the target
+  size_t tri_cap = 0;                  // entries of the model's row-range buffer, 0: none
+};
+enum RenderFront { FRONT_SETUP = 0, FRONT_SETUP_VERTEX = 1, FRONT_SETUP_VERTEX_CROP = 2 };   // pose set-up alone (crop without render) | + vertex stage | + crop warp
+enum RowRanges { ROW_RANGES_NONE = 0, ROW_RANGES_BY_FRONT = 1, ROW_RANGES_OWN_LAUNCH = 2 };    // BY_FRONT: written by the fused front launch
+struct RenderPlan {
+  RenderFront front;
+  RowRanges row_ranges;
+  int strip_rows, threads;   // the rasteriser's instantiation (meaningless after FRONT_SETUP: nothing is rendered)
+  int lds;                   // its dynamic LDS: the strip's z-buffer (+ the triangle list with row ranges)
+  bool lds_optin;            // the instantiation needs the > 64 KB opt-in
+  bool crop_launch;          // crop_kernel as its own launch
+};
+RenderPlan plan_render(const RenderQuery &q);
+// the rasteriser instantiation the plan names; tri_rows non-null exactly when plan.row_ranges says so.  false: no such instantiation
+bool launch_raster_shade(hipStream_t s, const RenderPlan &plan, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
                          const float4 *attr, OutMode mode, void *out, int32_t *tri_id_dbg, float *rast_dbg, bool fmad,
-                         const unsigned *tri_rows = nullptr);
-#ifdef FP_TEST_HOOKS
-void set_raster_strip_rows(int rows);  // 0 = automatic (A/B hook)
-void set_tri_rows_tall(int v);
-void set_raster_strip_threads(int threads);  // 0 = by batch size; 256 / 512 / 1024 (A/B hook, 8-row strips)
-#endif
+                         const unsigned *tri_rows);
 // the frame a replayed hipGraph reads: kernels inside graphs take the frame through this device-resident record, so a caller's
 // device frame is used in place (no copy into model-owned buffers) and the graph stays valid when the pointers change
 // how the kernels of a (replayed) graph find the current frame.  Whole frames: pitch = 0 (rows are W pixels apart), window = all.

@@ -174,9 +174,6 @@ void fpt_set_i8_stream(int v) { fp::g_i8_stream = v; }
 void fpt_set_q8_blocks(int v) { fp::g_q8_blocks = v & fp::Q8_BLOCKS_ALL; }   // [r6] stage mask of 8-bit networks loaded from now on (tools/q8_blocks.py)
 void fpt_set_conv_ablate(int v) { fp::g_conv_ablate = v; }
 void fpt_set_splitk_ablate(int v) { fp::g_splitk_ablate = v; }
-void fpt_set_raster_strip_rows(int r) { fp::set_raster_strip_rows(r); }
-void fpt_set_raster_strip_threads(int t) { fp::set_raster_strip_threads(t); }
-void fpt_set_tri_rows_tall(int v) { fp::set_tri_rows_tall(v); }
 
 // clock probe: allocate room for `blocks` records, run convs, then read back mean shader MHz and mean main-loop cycles
 int fpt_clk_probe(int blocks, double *mhz_out, double *loop_cycles_out) {

@@ -172,7 +172,7 @@ def _register_case(tl, model, mesh, om, scene, hyp, begin, count, dt, subset=Non
 
 @pytest.mark.parametrize("dt", DTS, ids=NAME.get)
 def test_register_252_both_passes(tl, model, syn_mesh, om, syn_scene, hyp, dt):
-    """the headline: 80-row strips of 1024 threads (launch_raster_tall), no row ranges, crop_kernel in the packed mode"""
+    """the headline: 80-row strips of 1024 threads, no row ranges, crop_kernel in the packed mode"""
     model.set_precision(PREC[dt])
     try:
         _report(_register_case(tl, model, syn_mesh, om, syn_scene, hyp, 0, 252, dt))
@@ -180,7 +180,7 @@ def test_register_252_both_passes(tl, model, syn_mesh, om, syn_scene, hyp, dt):
         model.set_precision(FP_PREC_F16)
 
 
-# every switch of strip_rows_for / launch_raster_shade_t / render_and_crop, on both sides: 4- vs 8-row strips (2 | 3), the fused
+# every switch of plan_render (fp_geometry.hip), on both sides: 4- vs 8-row strips (2 | 3), the fused
 # vertex_crop_kernel vs separate launches (4 | 5), 1024 vs 512 threads (25 | 26), 512 vs 256 threads and 8 vs 20 rows (47 | 48), 20 vs 80 rows
 # and with vs without row ranges (99 | 100); slices from the middle of the grid, three of them ending at hypothesis 252
 SWITCH_SLICES = [(251, 1), (100, 2), (7, 3), (130, 4), (61, 5), (200, 25), (226, 26), (33, 47), (150, 48), (11, 99), (152, 100)]
