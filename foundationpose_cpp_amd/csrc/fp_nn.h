@@ -56,7 +56,7 @@ void nn_scratch_free(NNScratch *);
 // debug (cross-model corruption checks): the activation arena and the f32 side buffer
 void nn_scratch_debug_info(const NNScratch *, const void **buf, size_t *bytes, const void **f32, size_t *f32_bytes);
 #ifdef FP_TEST_HOOKS
-// test build: fill every interior of the 2-byte activation arena (borders and the zero-initialised counters stay), the split-K
+// test build: fill every interior of the 2-byte activation arena (the zero borders stay), the split-K
 // partials, the f32 side buffer and the cross-attention scratch with a poison pattern -- kind 0: quiet NaN, 1: the largest finite
 // value with alternating sign.  dt = the arena's element type (DT_F16 / DT_BF16).
 int nn_scratch_poison(NNScratch *, int dt, int kind, hipStream_t s);

@@ -52,6 +52,7 @@
 #include <atomic>
 #include <memory>
 #include <thread>
+#include <utility>
 
 namespace fp {
 
@@ -289,8 +290,11 @@ struct Net {
   ConvLayer a0, a1, ra[2][2];        // encodeA
   ConvLayer rb[2][2], b2, rc[2][2];  // encodeAB
   EncLayer trans, rot;               // refiner
-  // the two heads' Linear layers stored back to back ([2][Cout][K], [2][Cout]) for the one-launch small-batch path
-  ConvLayer g_in_proj, g_out_proj, g_lin1, g_lin2;
+  // the two heads' QKV projections stored back to back ([2][Cout][K], [2][Cout]) for Track's grouped launch
+  ConvLayer g_in_proj;
+#ifdef FP_TEST_HOOKS
+  ConvLayer g_out_proj, g_lin1, g_lin2;   // the same for the Linear layers of Track's launch chain (TAIL_GROUPED_CHAIN, test build)
+#endif
   MHA att, att_cross;                // scorer
   LinearF32 score_lin;
   unsigned char *pe = nullptr;       // [400,512], act_dt
@@ -843,6 +847,25 @@ static bool make_mha(Net *net, const std::map<std::string, HostTensor> &m, const
          make_linear_f32(net, m, prefix + ".out_proj.weight", prefix + ".out_proj.bias", EMBED, EMBED, &a->out_proj_f32, err);
 }
 
+// What the schedule behind the trunk (plan_heads) takes for granted of a loaded network: qkv_tile_kernel and the one-launch encoder tail
+// (enc_tail_kernel) read 512-wide Linear layers from their step-major copies in the token path's element type, and the refiner's read-outs
+// are Linear(512, 3).  The product has no other form to fall back on (the launch chains exist in the test build only), so a network that
+// does not fit fails to load, with an error that says so.  With this loader the check can never fire: make_linear_conv / make_linear_f32
+// fix every shape, the heads are built in the 2-byte type `adt`, and finish_layer makes the step-major copy of every 2-byte Linear layer.
+static bool check_head_layouts(const Net *net, std::string *err) {
+  const int dt = net->act_dt;
+  const auto lin = [&](const ConvLayer &L, int Cout) { return L.wstep && L.Cin == EMBED && L.Cout == Cout && L.dt == dt; };
+  bool ok = dt == DT_F16 || dt == DT_BF16;
+  if (net->scorer) {
+    ok = ok && lin(net->att.in_proj, 3 * EMBED);
+  } else {
+    for (const EncLayer *L : {&net->trans, &net->rot})
+      ok = ok && lin(L->att.in_proj, 3 * EMBED) && lin(L->att.out_proj, EMBED) && lin(L->lin1, EMBED) && lin(L->lin2, EMBED) && L->head.in == EMBED && L->head.out == 3;
+  }
+  if (!ok) *err = "the transformer layers do not fit qkv_tile_kernel / the one-launch encoder tail (512-wide 2-byte Linear layers with a step-major copy, Linear(512,3) read-outs): no other schedule exists in this build";
+  return ok;
+}
+
 static Net *net_load_impl(const char *path, bool is_scorer, int prec, std::string *err) {
   std::map<std::string, HostTensor> m;
   if (!read_fpw(path, m, err)) return nullptr;
@@ -879,16 +902,18 @@ static Net *net_load_impl(const char *path, bool is_scorer, int prec, std::strin
            make_linear_f32(net.get(), m, p1 + ".weight", p1 + ".bias", 3, EMBED, &heads[i]->head, err);
     }
     if (ok) {
-      ok = make_grouped(net.get(), net->trans.att.in_proj, net->rot.att.in_proj, &net->g_in_proj) &&
-           make_grouped(net.get(), net->trans.att.out_proj, net->rot.att.out_proj, &net->g_out_proj) &&
-           make_grouped(net.get(), net->trans.lin1, net->rot.lin1, &net->g_lin1) &&
-           make_grouped(net.get(), net->trans.lin2, net->rot.lin2, &net->g_lin2);
+      ok = make_grouped(net.get(), net->trans.att.in_proj, net->rot.att.in_proj, &net->g_in_proj);
+#ifdef FP_TEST_HOOKS
+      ok = ok && make_grouped(net.get(), net->trans.att.out_proj, net->rot.att.out_proj, &net->g_out_proj) &&
+           make_grouped(net.get(), net->trans.lin1, net->rot.lin1, &net->g_lin1) && make_grouped(net.get(), net->trans.lin2, net->rot.lin2, &net->g_lin2);
+#endif
       if (!ok) *err = "could not build the grouped head weights";
     }
   } else if (ok) {
     ok = make_mha(net.get(), m, "att", adt, &net->att, err) && make_mha(net.get(), m, "att_cross", adt, &net->att_cross, err) &&
          make_linear_f32(net.get(), m, "linear.weight", "linear.bias", 1, EMBED, &net->score_lin, err);
   }
+  ok = ok && check_head_layouts(net.get(), err);
   if (ok) {
     // PositionalEmbedding(d_model=512, max_len=400): pe[t,2i]=sin(t*w_i), pe[t,2i+1]=cos(t*w_i), w_i=exp(-2i*ln(1e4)/512)
     std::vector<float> pe((size_t)400 * EMBED);
@@ -1185,6 +1210,16 @@ void nn_scratch_debug_info(const NNScratch *w, const void **buf, size_t *bytes, 
   *f32 = w->f32; *f32_bytes = (size_t)w->cap * EMBED * sizeof(float);
 }
 
+// f32 side buffer: [cap][512] pooled features and, in the test build, the [2][LN_PMEAN_PARTS][512] partial column sums of
+// layernorm_pmean_kernel (Track's launch chain cuts a 400-token sequence into LN_PMEAN_PARTS runs of LN_PMEAN_ROWS rows)
+static constexpr int LN_PMEAN_PARTS = 16, LN_PMEAN_ROWS = 25;
+#ifdef FP_TEST_HOOKS
+static constexpr size_t F32_PSUMS = (size_t)2 * LN_PMEAN_PARTS * EMBED;
+static float *pmean_sums(const NNScratch *ws) { return ws->f32 + (size_t)ws->cap * EMBED; }
+#else
+static constexpr size_t F32_PSUMS = 0;
+#endif
+
 static int ensure_scratch(NNScratch *ws, int N, hipStream_t s) {
   if (N <= ws->cap) return 0;
   if (ws->buf) (void)hipFree(ws->buf);
@@ -1193,9 +1228,7 @@ static int ensure_scratch(NNScratch *ws, int N, hipStream_t s) {
   int cap = std::max(N, 8);
   g_alloc_epoch++;
   FP_HIP_OK(hipMalloc((void **)&ws->buf, (size_t)cap * per_hyp_bytes(ws)));
-  // [cap][512] pooled features + the arrival counter of token_mean_pose_kernel + [2][16][512] partial sums of layernorm_pmean_kernel (Track)
-  FP_HIP_OK(hipMalloc((void **)&ws->f32, ((size_t)cap * EMBED + 16 + 2 * 16 * EMBED) * sizeof(float)));
-  FP_HIP_OK(hipMemsetAsync(ws->f32 + (size_t)cap * EMBED, 0, 16 * sizeof(float), s));
+  FP_HIP_OK(hipMalloc((void **)&ws->f32, ((size_t)cap * EMBED + F32_PSUMS) * sizeof(float)));
   // the zero borders are written here once and never again: every producer stores interiors only, and the arena is
   // carved by CAPACITY (not by the current N), so an image slot's border never moves
   FP_HIP_OK(hipMemsetAsync(ws->buf, 0, (size_t)cap * PER_HYP, s));
@@ -1250,16 +1283,17 @@ static constexpr unsigned long long *g_clk_probe = nullptr;
 FP_HOOK g_conv_variant = 0;    // 0 default; 7 force / 8 disable the resident-halo kernels; 3 = 256x128 ping-pong everywhere; 5 = 256x256 rounds without
                                // the halo kernels
 FP_HOOK g_conv_ablate = 0;     // timing-only ablations (wrong results) of conv_big_pp_kernel / conv_halo_kernel
-FP_HOOK g_fuse_pose = 1;       // Track: 1 = both Linear(512,3) heads + RefinePostProcess in one kernel (small_linear2_pose_kernel), 0 = two kernels, 2 = A/B: the token mean in that kernel too (token_mean_pose_kernel, last-arriver; not faster)
-FP_HOOK g_ln_pmean = 1;        // [r5] Track: LayerNorm 2 + partial token sums in one launch (layernorm_pmean_kernel) instead of layernorm + token_mean
-FP_HOOK g_qkv_ablate = 0;      // timing-only ablations of qkv_tile_kernel (test build, wrong results)
 FP_HOOK g_splitk_ablate = 0;   // test build, wrong results: conv_splitk_reduce_kernel sums all slices but the last (the float64 checks must fail)
-FP_HOOK g_qkv_tile = 1;        // [r5] QKV projections of Register (N > 1) on qkv_tile_kernel (80-token tiles resident in LDS) instead of gemm_k32_kernel
-FP_HOOK g_enc_tail = 1;        // [r5] Register (N > 1): out_proj + LayerNorm 1 + FFN + LayerNorm 2 + token sums of BOTH heads as one launch (enc_tail_kernel) instead of five per head
 FP_HOOK g_i8_stream = 0;       // test build A/B: 1 = INT8 networks with an 8-bit residual stream (run_trunk_i8; faster, but its common-mode error is frame-specific: DESIGN.md section 4.4)
 FP_HOOK g_smallm = 1;          // small problems (Track, a few objects) on conv_smallx_kernel: K split over the waves of a workgroup, no split-K slabs / reduce launch
                                // (0 = off, 2 = for every size, 3 = its first version, conv_smallm_kernel)
-FP_HOOK g_att_variant = 1;     // 1 = attention32_kernel (8 = without the XCD remap); round-1 kernel: 2 remap + 16-B stores, 3 no XCD remap, 5 remap + 2-B stores, 7 neither
+// the five switches of the schedule behind the trunk: read by heads_override() alone, decided on by plan_heads alone (HeadsOverride)
+FP_HOOK g_enc_tail = 1;        // [r5] out_proj + LayerNorm 1 + FFN + LayerNorm 2 + token sums of BOTH refiner heads as one launch (enc_tail_kernel); 0 = the launch
+                               // chains (test build only: the float64-tapped reference)
+FP_HOOK g_ln_pmean = 1;        // [r5] Track's launch chain: LayerNorm 2 + partial token sums in one launch (layernorm_pmean_kernel) instead of layernorm + token_mean
+FP_HOOK g_fuse_pose = 1;       // Track: 1 = the read-out kernel applies RefinePostProcess too (one launch less), 0 = the caller launches pose_update
+FP_HOOK g_qkv_ablate = 0;      // timing-only ablations of qkv_tile_kernel (test build, wrong results)
+FP_HOOK g_att_variant = 1;     // a row of ATT_VARIANTS: 1 = attention32_kernel / attention32_skv_kernel as shipped, 8 = without the XCD remap, 16.. = timing ablations
 
 // Thresholds of the convolution schedule (plan_conv).  They were A/B switches until their experiments settled (EXPERIMENTS.md).
 static constexpr int SPLITK_TARGET = 128;   // workgroups a split-K launch aims for (96-128 best, 256 is 6 % slower)
@@ -1519,6 +1553,170 @@ static int plan_conv(const ConvProblem &q, ConvPlan *plan) {
     add(CK_SPLITK_REDUCE, "conv_splitk_reduce_kernel", M, (int)((octs + 255) / 256), 256, 0).post = q.post;
   }
   return finish();
+}
+
+// =================================================================================================
+// the schedule behind the trunk: QKV projection, attention, encoder tail, token pooling, read-out
+// =================================================================================================
+// plan_heads decides what runs behind the token tensor of the refiner (both heads), of the scorer's feature pass and of its cross-attention
+// head; refiner_forward, scorer_features and scorer_head build the query and execute the plan.  Like plan_conv it is plain host arithmetic
+// on the pass, the batch and the element type: it makes no HIP call, reads no global, and can be asked without a GPU (fpt_plan_heads,
+// tests/test_heads_plan_cpu.py).  The Linear layers inside a form go through run_conv / plan_conv as before; their schedule is not
+// restated here.  The shapes the forms rely on (512-wide Linear layers with a step-major copy, Linear(512, 3) read-outs) are what the loader
+// builds for every network it accepts (check_head_layouts).
+
+// Thresholds of this schedule, each measured in its round (EXPERIMENTS.md).
+static constexpr int SEQ_TOKENS = 400;            // tokens per hypothesis (the 20 x 20 map of the trunk)
+static_assert(LN_PMEAN_PARTS * LN_PMEAN_ROWS == SEQ_TOKENS, "layernorm_pmean_kernel's partition covers a sequence");
+static constexpr int QKV_TILE_TOKENS = 80;        // qkv_tile_kernel: tokens per workgroup, resident in LDS (a sequence = 5 tiles)
+static constexpr int QKV_TILE_MIN_ROWS = 800;     // ... from two sequences on (one sequence alone is a scorer batch of 1: too few workgroups)
+static constexpr int ATT_QROWS = 128;             // attention32_kernel: query rows per workgroup (4 waves x 32)
+static constexpr int ATT_SKV_QROWS = 32;          // attention32_skv_kernel: query rows per workgroup, its 4 waves split the keys
+static constexpr int ATT_SKV_MAX_WGS = 64;        // the split-key kernel takes over when attention32_kernel's grid would have at most this many
+static constexpr int ATT_SKV_MIN_T = 32;          // workgroups (a small grid of long latency chains) and the sequence is longer than one key block
+static constexpr int TRACK_GROUP_PITCH = 512;     // Track: rows between the two heads' sequences in the grouped launches (400 padded to the 128-row tile)
+static constexpr int ENC_TAIL_TOKENS_1 = 16, ENC_TAIL_TOKENS_5 = 80;   // enc_tail_kernel<., 1> / <., 5>: tokens per workgroup
+static constexpr int LN_MEAN_MIN_N = 96;          // per-head chain: layernorm_mean_kernel (one workgroup per sequence) from this many sequences on; below it
+                                                  // is a serial chain (26 us at N = 32 against 9 + 9 for layernorm + token_mean)
+// dynamic LDS bytes
+static constexpr int LDS_QKV_TILE = 16 * QKV_TILE_TOKENS * 64;
+static constexpr int LDS_ATT_SKV = 4 * 2 * (32 * 256 + 8 * 1056);      // per wave: two buffers of a K tile + 8 V sub-tiles
+static constexpr int LDS_ENC_TAIL_1 = 16 * ENC_TAIL_TOKENS_1 * 64 + 2 * 8 * ENC_TAIL_TOKENS_1 * 4;              // tile + LayerNorm exchanges
+static constexpr int LDS_ENC_TAIL_5 = 16 * ENC_TAIL_TOKENS_5 * 64 + 2 * 8 * ENC_TAIL_TOKENS_5 * 4 + 4 * 8192;   // ... + the two parked x1 fragments
+// Settled the other way and retired (EXPERIMENTS.md, "Heads schedule in one plan"): the round-1 attention_kernel; 8 waves per workgroup and
+// the lazy running maximum in attention32_kernel (their instantiations; the template keeps the two parameters); the token mean inside
+// Track's read-out launch (token_mean_pose_kernel); the switch that put the QKV projection of N > 1 back on the Linear schedule.
+
+enum HeadsPass { HP_REFINER = 0, HP_SCORER_FEATURES = 1, HP_SCORER_HEAD = 2 };
+enum QkvForm { QKV_LINEAR = 0, QKV_TILE = 1, QKV_GROUPED = 2 };   // the Linear schedule (plan_conv) / qkv_tile_kernel / Track's grouped Linear of both heads
+enum AttKernel { ATT_32 = 0, ATT_32_SKV = 1 };
+// enc_tail_kernel<., 1> / <., 5> in one launch, or (test build) Track's grouped five-launch chain / the chain per head; none in the scorer
+enum TailForm { TAIL_NONE = 0, TAIL_ONE_1 = 1, TAIL_ONE_5 = 2, TAIL_GROUPED_CHAIN = 3, TAIL_HEAD_CHAIN = 4 };
+// the tail's partial dot products / layernorm_pmean_kernel / layernorm_mean_kernel / layernorm_kernel + token_mean_kernel / token_mean_kernel alone (scorer)
+enum PoolForm { POOL_TAIL_PDOT = 0, POOL_LN_PMEAN = 1, POOL_LN_MEAN = 2, POOL_LN_TOKEN_MEAN = 3, POOL_TOKEN_MEAN = 4 };
+enum ReadoutKernel { RO_ENC_HEADS = 0, RO_SMALL_LINEAR2_POSE = 1, RO_SMALL_LINEAR2 = 2, RO_SMALL_LINEAR = 3 };
+
+// The switches of the test build (fpt_set_enc_tail ...).  Only plan_heads reads them; the product passes the defaults.
+struct HeadsOverride {
+  int enc_tail = 1;      // 0: the refiner's encoder tail as launch chains
+  int ln_pmean = 1;      // Track's chain: 0 = layernorm + token_mean instead of layernorm_pmean_kernel
+  int fuse_pose = 1;     // 0: never fuse RefinePostProcess into the read-out
+  int qkv_ablate = 0;    // timing ablation of qkv_tile_kernel (f16; 1, 2, 3, 4, 7)
+  int att_variant = 1;   // id of a row of ATT_VARIANTS
+};
+
+// The instantiations of attention32_kernel: row 0 is the product's, the others exist in the test build only (timing, wrong results from
+// row 2 on).  The launcher builds its kernel table from these rows (launch_attention); plan_attention picks the row.
+struct AttVariant {
+  int id;        // fpt_set_att_variant / fpt_attention_bench
+  bool remap;    // the XCD remap of the grid
+  int ablate;    // ABL bits: 1 no staging after the first tile, 2 no softmax, 4 no PV, 8 no QK, 16 no prefetch distance, 32 no LDS stores
+};
+static constexpr AttVariant ATT_VARIANTS[] = {{1, true, 0},  {8, false, 0},  {16, true, 16}, {17, true, 1}, {18, true, 2},  {19, true, 32},
+                                              {20, true, 4}, {22, true, 6}, {24, true, 8},  {30, true, 14}, {31, true, 15}};
+#ifdef FP_TEST_HOOKS
+static constexpr int N_ATT_VARIANTS = (int)(sizeof(ATT_VARIANTS) / sizeof(ATT_VARIANTS[0]));
+#else
+static constexpr int N_ATT_VARIANTS = 1;   // the product instantiates row 0 alone
+#endif
+
+struct HeadsQuery {
+  int pass = HP_REFINER;
+  int N = 1;                 // hypotheses (the scorer head: of all shards together)
+  int dt = DT_F16;           // element type of the token path (DT_F16 / DT_BF16)
+  bool fuse_offer = false;   // the caller offers a PoseUpdateFuse
+  HeadsOverride ov;
+};
+
+struct AttLaunch {
+  int kernel = ATT_32;       // AttKernel
+  int variant = 0;           // row of ATT_VARIANTS (attention32_kernel; the split-key kernel has the product's form only)
+  int B = 0, T = 0, pitch = 0;   // sequences, tokens per sequence, rows between the first tokens of consecutive sequences
+  int nq = 0;                // query tiles per sequence and head
+  unsigned grid = 0;
+  int block = 256, lds = 0;  // threads per workgroup, dynamic LDS bytes
+};
+
+struct HeadsPlan {
+  int qkv = QKV_LINEAR;      // QkvForm
+  int qkv_ablate = 0;        // test build: the qkv_tile_kernel ablation instantiated (0 = the real kernel)
+  unsigned qkv_grid = 0;     // qkv_tile_kernel: workgroups (512 threads)
+  int qkv_lds = 0;
+  AttLaunch att;
+  int tail = TAIL_NONE;      // TailForm
+  int tail_tiles = 0;        // enc_tail_kernel: tiles per head (the grid is both heads')
+  unsigned tail_grid = 0;
+  int tail_lds = 0;
+  int pool = POOL_TOKEN_MEAN;      // PoolForm
+  int readout = RO_SMALL_LINEAR;   // ReadoutKernel
+  bool fuse_pose = false;    // RefinePostProcess runs inside the read-out kernel
+};
+
+// self- or cross-attention over B sequences of T tokens
+static AttLaunch plan_attention(int B, int T, int pitch, const HeadsOverride &ov) {
+  AttLaunch a;
+  a.B = B; a.T = T; a.pitch = pitch;
+  for (int i = 0; i < N_ATT_VARIANTS; i++)
+    if (ATT_VARIANTS[i].id == ov.att_variant) a.variant = i;   // (a retired or unknown id: the product's row)
+  a.nq = (T + ATT_QROWS - 1) / ATT_QROWS;
+  a.grid = (unsigned)(a.nq * HEADS * B);
+  // a small grid of long latency chains (Track: 2 sequences; the cross-attention: one): split the keys over the waves instead
+  if (a.variant == 0 && a.nq * HEADS * B <= ATT_SKV_MAX_WGS && T > ATT_SKV_MIN_T) {
+    a.kernel = ATT_32_SKV;
+    a.nq = (T + ATT_SKV_QROWS - 1) / ATT_SKV_QROWS;
+    a.grid = (unsigned)(a.nq * HEADS * B);
+    a.lds = LDS_ATT_SKV;
+  }
+  return a;
+}
+
+static int plan_heads(const HeadsQuery &q, HeadsPlan *plan) {
+  *plan = HeadsPlan{};
+  FP_CHECK(q.dt == DT_F16 || q.dt == DT_BF16, "plan_heads: the transformer part runs on 2-byte elements");
+  FP_CHECK(q.pass >= HP_REFINER && q.pass <= HP_SCORER_HEAD && q.N >= 1, "plan_heads: invalid query");
+  const HeadsOverride &ov = q.ov;
+  const int N = q.N;
+  if (q.pass == HP_SCORER_HEAD) {   // cross-attention: the N hypotheses are ONE sequence; Linear layers in front and behind, Linear(512, 1) in f32
+    plan->att = plan_attention(1, N, N, ov);
+    return 0;
+  }
+  FP_CHECK(N <= MAX_BATCH, "plan_heads: batch outside 1..FP_MAX_BATCH");
+  const bool refiner = q.pass == HP_REFINER;
+  const bool track = refiner && N == 1;         // both heads in ONE launch per layer: Track is bound by its dependent launches, not by work
+  const bool chain = refiner && !ov.enc_tail;
+  const int rows = N * SEQ_TOKENS;
+  if (track) {
+    plan->qkv = QKV_GROUPED;
+  } else if (!chain && rows % QKV_TILE_TOKENS == 0 && rows >= QKV_TILE_MIN_ROWS) {
+    plan->qkv = QKV_TILE;
+    plan->qkv_grid = (unsigned)(rows / QKV_TILE_TOKENS);
+    plan->qkv_lds = LDS_QKV_TILE;
+    const int a = ov.qkv_ablate;
+    plan->qkv_ablate = (q.dt == DT_F16 && (a == 1 || a == 2 || a == 3 || a == 4 || a == 7)) ? a : 0;
+  }
+  plan->att = track ? plan_attention(2, SEQ_TOKENS, TRACK_GROUP_PITCH, ov) : plan_attention(N, SEQ_TOKENS, SEQ_TOKENS, ov);
+  if (!refiner) return 0;   // scorer features: token mean, then out_proj as a 512 x 512 GEMV in f32 (out_proj is affine: it commutes with the mean)
+  if (!chain) {
+    // [r5] everything row-wise behind the attention -- out_proj, LayerNorm 1, FFN, LayerNorm 2 and each tile's share of the read-out -- as ONE
+    // launch for both heads, and one small launch that adds the shares up
+    const int tok = track ? ENC_TAIL_TOKENS_1 : ENC_TAIL_TOKENS_5;
+    plan->tail = track ? TAIL_ONE_1 : TAIL_ONE_5;
+    plan->tail_tiles = rows / tok;
+    plan->tail_grid = (unsigned)(2 * plan->tail_tiles);
+    plan->tail_lds = track ? LDS_ENC_TAIL_1 : LDS_ENC_TAIL_5;
+    plan->pool = POOL_TAIL_PDOT;
+    plan->readout = RO_ENC_HEADS;
+    plan->fuse_pose = track && q.fuse_offer && ov.fuse_pose;
+  } else if (track) {
+    plan->tail = TAIL_GROUPED_CHAIN;
+    plan->pool = ov.ln_pmean ? POOL_LN_PMEAN : POOL_LN_TOKEN_MEAN;
+    plan->fuse_pose = q.fuse_offer && ov.fuse_pose;
+    plan->readout = plan->fuse_pose ? RO_SMALL_LINEAR2_POSE : RO_SMALL_LINEAR2;
+  } else {
+    plan->tail = TAIL_HEAD_CHAIN;
+    plan->pool = N >= LN_MEAN_MIN_N ? POOL_LN_MEAN : POOL_LN_TOKEN_MEAN;
+  }
+  return 0;
 }
 
 // Activation taps (test build only; tests/test_layers_gpu.py): an armed tap copies the tensor a producer just wrote -- borders
@@ -1918,96 +2116,63 @@ static int run_gemm(const Ctx &c, const char *tag, const ConvLayer &L, const voi
   return run_conv(c, tag, L, ai, rows, 1, 1, 0, ao, 0, relu, res ? &ar : nullptr, 0, 0, grp);
 }
 
-// the QKV projection of `rows` tokens ([rows][512] -> [rows][1536]); rows % 80 == 0 and N > 1: qkv_tile_kernel, else the Linear schedule
-static int run_qkv(const Ctx &c, const ConvLayer &L, const void *x, int rows, void *qkv) {
-  if (g_qkv_tile && rows % 80 == 0 && rows >= 800 && L.wstep && L.Cin == EMBED && L.Cout == 3 * EMBED && (L.dt == DT_F16 || L.dt == DT_BF16)) {
-    NetScope ps(c, "gemm_qkv/qkv_tile_kernel", 2.0 * rows * EMBED * 3.0 * EMBED, (double)rows * EMBED * 2.0 * 4.0);
-    QkvTileParams q{(const unsigned char *)x, L.wstep, L.bias, (unsigned char *)qkv, rows / 80};
-#ifdef FP_TEST_HOOKS
-    if (g_qkv_ablate == 1) { FP_LAUNCH((qkv_tile_kernel<DT_F16, 1>), dim3((unsigned)q.tiles), dim3(512), 16 * 80 * 64, c.s, q); return 0; }
-    if (g_qkv_ablate == 2) { FP_LAUNCH((qkv_tile_kernel<DT_F16, 2>), dim3((unsigned)q.tiles), dim3(512), 16 * 80 * 64, c.s, q); return 0; }
-    if (g_qkv_ablate == 3) { FP_LAUNCH((qkv_tile_kernel<DT_F16, 3>), dim3((unsigned)q.tiles), dim3(512), 16 * 80 * 64, c.s, q); return 0; }
-    if (g_qkv_ablate == 4) { FP_LAUNCH((qkv_tile_kernel<DT_F16, 4>), dim3((unsigned)q.tiles), dim3(512), 16 * 80 * 64, c.s, q); return 0; }
-    if (g_qkv_ablate == 7) { FP_LAUNCH((qkv_tile_kernel<DT_F16, 7>), dim3((unsigned)q.tiles), dim3(512), 16 * 80 * 64, c.s, q); return 0; }
-#endif
-    if (L.dt == DT_BF16) FP_LAUNCH((qkv_tile_kernel<DT_BF16>), dim3((unsigned)q.tiles), dim3(512), 16 * 80 * 64, c.s, q);
-    else FP_LAUNCH((qkv_tile_kernel<DT_F16>), dim3((unsigned)q.tiles), dim3(512), 16 * 80 * 64, c.s, q);
-    return 0;
-  }
-  return run_gemm(c, "gemm_qkv", L, x, rows, qkv, false);
+// f16 / bf16 dispatch of the transformer part: f(tag) with tag.value = DT_F16 or DT_BF16 as a constant, tag's E = the element type
+template <int DT>
+struct DtTag {
+  static constexpr int value = DT;
+  using E = typename ElemT<DT>::t;
+};
+template <typename F>
+static void with_dt(int dt, F &&f) {
+  if (dt == DT_BF16) f(DtTag<DT_BF16>{});
+  else f(DtTag<DT_F16>{});
 }
 
-template <int DT>
-static void launch_attention(const Ctx &c, const void *qkv, void *out, int B, int T, int tstride, int ld) {
-  using E = typename ElemT<DT>::t;
-  const E *q = (const E *)qkv;
-  E *o = (E *)out;
+static HeadsOverride heads_override() {   // the test build's switches; the defaults in the product, where they are constants
+  HeadsOverride ov;
+  ov.enc_tail = g_enc_tail; ov.ln_pmean = g_ln_pmean; ov.fuse_pose = g_fuse_pose; ov.qkv_ablate = g_qkv_ablate; ov.att_variant = g_att_variant;
+  return ov;
+}
+
+// the QKV projection of `rows` tokens ([rows][512] -> [rows][1536]) in the form the plan chose: qkv_tile_kernel or the Linear schedule
+static int run_qkv(const Ctx &c, const HeadsPlan &hp, const ConvLayer &L, const void *x, int rows, void *qkv) {
+  if (hp.qkv != QKV_TILE) return run_gemm(c, "gemm_qkv", L, x, rows, qkv, false);
+  NetScope ps(c, "gemm_qkv/qkv_tile_kernel", 2.0 * rows * EMBED * 3.0 * EMBED, (double)rows * EMBED * 2.0 * 4.0);
+  const QkvTileParams q{(const unsigned char *)x, L.wstep, L.bias, (unsigned char *)qkv, (int)hp.qkv_grid};
+  const dim3 grid(hp.qkv_grid), blk(512);
 #ifdef FP_TEST_HOOKS
-  if (g_att_variant != 1) {  // the round-1 kernel (64 query rows per workgroup), kept in the test build for A/B
-    const int nq = (T + 63) / 64;
-    dim3 grid((unsigned)(nq * HEADS * B)), blk(256);
-    if (g_att_variant == 3) FP_LAUNCH_RAW((attention_kernel<64, false, true, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
-    else if (g_att_variant == 5) FP_LAUNCH_RAW((attention_kernel<64, true, false, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
-    else if (g_att_variant == 7) FP_LAUNCH_RAW((attention_kernel<64, false, false, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
-    else if (g_att_variant == 9)  // 8 waves = 256 query rows per workgroup (K/V staged half as often; 9 % slower: the two waves of a SIMD run in lockstep)
-      FP_LAUNCH_RAW((attention32_kernel<true, DT, 0, 8>), dim3((unsigned)(((T + 255) / 256) * HEADS * B)), dim3(512), 0, c.s, q, o, T, (T + 255) / 256, tstride, ld);
-    else if (g_att_variant == 10) FP_LAUNCH_RAW((attention32_kernel<true, DT, 64>), dim3((unsigned)(((T + 127) / 128) * HEADS * B)), blk, 0, c.s, q, o, T, (T + 127) / 128, tstride, ld);
-    else if (g_att_variant == 8) FP_LAUNCH_RAW((attention32_kernel<false, DT>), dim3((unsigned)(((T + 127) / 128) * HEADS * B)), blk, 0, c.s, q, o, T, (T + 127) / 128, tstride, ld);
-    else if (g_att_variant >= 16 && g_att_variant < 32) {
-      const dim3 g32((unsigned)(((T + 127) / 128) * HEADS * B));
-      const int nq32 = (T + 127) / 128;
-      switch (g_att_variant - 16) {
-        case 1: FP_LAUNCH_RAW((attention32_kernel<true, DT, 1>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 2: FP_LAUNCH_RAW((attention32_kernel<true, DT, 2>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 4: FP_LAUNCH_RAW((attention32_kernel<true, DT, 4>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 8: FP_LAUNCH_RAW((attention32_kernel<true, DT, 8>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 6: FP_LAUNCH_RAW((attention32_kernel<true, DT, 6>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 14: FP_LAUNCH_RAW((attention32_kernel<true, DT, 14>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 15: FP_LAUNCH_RAW((attention32_kernel<true, DT, 15>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 0: FP_LAUNCH_RAW((attention32_kernel<true, DT, 16>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        case 3: FP_LAUNCH_RAW((attention32_kernel<true, DT, 32>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-        default: FP_LAUNCH_RAW((attention32_kernel<true, DT, 0>), g32, blk, 0, c.s, q, o, T, nq32, tstride, ld); break;
-      }
-    }
-    else FP_LAUNCH_RAW((attention_kernel<64, true, true, DT>), grid, blk, 0, c.s, q, o, T, nq, tstride);
-    return;
+  switch (hp.qkv_ablate) {
+    case 1: FP_LAUNCH((qkv_tile_kernel<DT_F16, 1>), grid, blk, hp.qkv_lds, c.s, q); return 0;
+    case 2: FP_LAUNCH((qkv_tile_kernel<DT_F16, 2>), grid, blk, hp.qkv_lds, c.s, q); return 0;
+    case 3: FP_LAUNCH((qkv_tile_kernel<DT_F16, 3>), grid, blk, hp.qkv_lds, c.s, q); return 0;
+    case 4: FP_LAUNCH((qkv_tile_kernel<DT_F16, 4>), grid, blk, hp.qkv_lds, c.s, q); return 0;
+    case 7: FP_LAUNCH((qkv_tile_kernel<DT_F16, 7>), grid, blk, hp.qkv_lds, c.s, q); return 0;
+    default: break;
   }
 #endif
-  const int nq = (T + 127) / 128;
-  if (nq * HEADS * B <= 64 && T > 32) {  // a small grid of long latency chains: split the keys over the waves instead
-    const int nq32 = (T + 31) / 32;
-    FP_LAUNCH((attention32_skv_kernel<true, DT>), dim3((unsigned)(nq32 * HEADS * B)), dim3(256), 4 * 2 * (32 * 256 + 8 * 1056), c.s, q, o, T, nq32, tstride, ld);
-    return;
-  }
-  FP_LAUNCH_RAW((attention32_kernel<true, DT>), dim3((unsigned)(nq * HEADS * B)), dim3(256), 0, c.s, q, o, T, nq, tstride, ld);
-}
-static int run_attention(const Ctx &c, int dt, const void *qkv, void *out, int B, int T, int tstride = 0, int ld = 3 * EMBED) {
-  if (tstride == 0) tstride = T;
-  double flops = 4.0 * (double)B * HEADS * (double)T * T * HDIM;
-  NetScope ps(c, "attention", flops, (double)B * T * (1536 + 512) * 2.0);
-  if (dt == DT_BF16) launch_attention<DT_BF16>(c, qkv, out, B, T, tstride, ld);
-  else launch_attention<DT_F16>(c, qkv, out, B, T, tstride, ld);
+  with_dt(L.dt, [&](auto t) { FP_LAUNCH((qkv_tile_kernel<decltype(t)::value>), grid, blk, hp.qkv_lds, c.s, q); });
   return 0;
 }
 
-static void run_layernorm(const Ctx &c, int dt, const void *x, const LNParams &ln, void *y, size_t rows, const LNParams *ln1 = nullptr,
-                          size_t split_row = 0) {
-  NetScope ps(c, "layernorm", 0, (double)rows * EMBED * 4.0);
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  const float *g1 = ln1 ? ln1->g : ln.g, *b1 = ln1 ? ln1->b : ln.b;
-  const size_t sr = ln1 ? split_row : rows;
-  if (dt == DT_BF16) FP_LAUNCH_RAW(layernorm_kernel<DT_BF16>, grid, dim3(256), 0, c.s, (const __bf16 *)x, ln.g, ln.b, (__bf16 *)y, rows, g1, b1, sr);
-  else FP_LAUNCH_RAW(layernorm_kernel<DT_F16>, grid, dim3(256), 0, c.s, (const _Float16 *)x, ln.g, ln.b, (_Float16 *)y, rows, g1, b1, sr);
+// attention32_kernel's instantiations, one per row of ATT_VARIANTS (the product: row 0 alone)
+template <int DT, size_t... I>
+static void launch_attention32(const Ctx &c, const AttLaunch &a, const typename ElemT<DT>::t *q, typename ElemT<DT>::t *o, int ld, std::index_sequence<I...>) {
+  const auto launch = [&](auto row) {
+    constexpr AttVariant V = ATT_VARIANTS[decltype(row)::value];
+    FP_LAUNCH_RAW((attention32_kernel<V.remap, DT, V.ablate>), dim3(a.grid), dim3(a.block), a.lds, c.s, q, o, a.T, a.nq, a.pitch, ld);
+  };
+  ((a.variant == (int)I ? launch(std::integral_constant<size_t, I>{}) : (void)0), ...);
 }
-
-static void run_layernorm_mean(const Ctx &c, int dt, const void *x, const LNParams &ln, float *out, int B, int T, int tstride = 0,
-                               const LNParams *ln1 = nullptr, int split_b = 0) {
-  NetScope ps(c, "layernorm_mean", 0, (double)B * T * EMBED * 2.0);
-  const float *g1 = ln1 ? ln1->g : ln.g, *b1 = ln1 ? ln1->b : ln.b;
-  const int sb = ln1 ? split_b : B;
-  if (tstride == 0) tstride = T;
-  if (dt == DT_BF16) FP_LAUNCH_RAW(layernorm_mean_kernel<DT_BF16>, dim3(B), dim3(1024), 0, c.s, (const __bf16 *)x, ln.g, ln.b, g1, b1, sb, out, T, tstride);
-  else FP_LAUNCH_RAW(layernorm_mean_kernel<DT_F16>, dim3(B), dim3(1024), 0, c.s, (const _Float16 *)x, ln.g, ln.b, g1, b1, sb, out, T, tstride);
+static int run_attention(const Ctx &c, int dt, const AttLaunch &a, const void *qkv, void *out, int ld = 3 * EMBED) {
+  double flops = 4.0 * (double)a.B * HEADS * (double)a.T * a.T * HDIM;
+  NetScope ps(c, "attention", flops, (double)a.B * a.T * (1536 + 512) * 2.0);
+  with_dt(dt, [&](auto t) {
+    constexpr int DT = decltype(t)::value;
+    using E = typename decltype(t)::E;
+    if (a.kernel == ATT_32_SKV) FP_LAUNCH((attention32_skv_kernel<true, DT>), dim3(a.grid), dim3(a.block), a.lds, c.s, (const E *)qkv, (E *)out, a.T, a.nq, a.pitch, ld);
+    else launch_attention32<DT>(c, a, (const E *)qkv, (E *)out, ld, std::make_index_sequence<N_ATT_VARIANTS>{});
+  });
+  return 0;
 }
 
 static void run_small_linear(const Ctx &c, const float *x, const LinearF32 &L, float *y, int B) {
@@ -2018,9 +2183,33 @@ static void run_small_linear(const Ctx &c, const float *x, const LinearF32 &L, f
 
 static void run_token_mean(const Ctx &c, int dt, const void *x, float *out, int B, int T, int tstride = 0) {
   NetScope ps(c, "token_mean", 0, (double)B * T * EMBED * 2.0);
-  if (dt == DT_BF16) FP_LAUNCH_RAW(token_mean_kernel<DT_BF16>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)x, out, T, tstride ? tstride : T);
-  else FP_LAUNCH_RAW(token_mean_kernel<DT_F16>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)x, out, T, tstride ? tstride : T);
+  with_dt(dt, [&](auto t) {
+    using E = typename decltype(t)::E;
+    FP_LAUNCH_RAW(token_mean_kernel<decltype(t)::value>, dim3(B, EMBED / 64), dim3(256), 0, c.s, (const E *)x, out, T, tstride ? tstride : T);
+  });
 }
+
+#ifdef FP_TEST_HOOKS   // launchers of the chain forms' kernels (fp_nn_small_kernels.inc)
+static void run_layernorm(const Ctx &c, int dt, const void *x, const LNParams &ln, void *y, size_t rows, const LNParams *ln1 = nullptr,
+                          size_t split_row = 0) {
+  NetScope ps(c, "layernorm", 0, (double)rows * EMBED * 4.0);
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  const float *g1 = ln1 ? ln1->g : ln.g, *b1 = ln1 ? ln1->b : ln.b;
+  const size_t sr = ln1 ? split_row : rows;
+  with_dt(dt, [&](auto t) {
+    using E = typename decltype(t)::E;
+    FP_LAUNCH_RAW(layernorm_kernel<decltype(t)::value>, grid, dim3(256), 0, c.s, (const E *)x, ln.g, ln.b, (E *)y, rows, g1, b1, sr);
+  });
+}
+
+static void run_layernorm_mean(const Ctx &c, int dt, const void *x, const LNParams &ln, float *out, int B, int T) {
+  NetScope ps(c, "layernorm_mean", 0, (double)B * T * EMBED * 2.0);
+  with_dt(dt, [&](auto t) {
+    using E = typename decltype(t)::E;
+    FP_LAUNCH_RAW(layernorm_mean_kernel<decltype(t)::value>, dim3(B), dim3(1024), 0, c.s, (const E *)x, ln.g, ln.b, ln.g, ln.b, B, out, T, T);
+  });
+}
+#endif
 
 // calibration statistics of a trunk activation [pixels incl. the zero border][C]: per channel |max| (optional) and the sum of the
 // values -- 8-bit tensors de-quantised with their per-channel scale (DT_I8: (stored ^ 0x80) * scale).  Border pixels hold 0 and
@@ -2143,9 +2332,7 @@ int nn_scratch_poison(NNScratch *ws, int dt, int kind, hipStream_t s) {
     }
     for (unsigned char *t : {a.tokens, a.att, a.y1, a.y2}) fill16(t, cap, 400, 1, 0, EMBED);
     fill16(a.qkv, cap, 400, 1, 0, 3 * EMBED);
-    // f32 side buffer: the pooled rows and the partial sums of layernorm_pmean_kernel; NOT the 16 zero-initialised arrival counters
-    fill32(ws->f32, cap * EMBED);
-    fill32(ws->f32 + cap * EMBED + 16, 2 * 16 * EMBED);
+    fill32(ws->f32, cap * EMBED + F32_PSUMS);   // the pooled rows and the partial sums of layernorm_pmean_kernel
   }
   fill32(ws->splitk, ws->splitk_cap);
   if (ws->head_buf) fill16(ws->head_buf, (size_t)ws->head_cap * 5, 1, 1, 0, EMBED);
@@ -2429,9 +2616,180 @@ static int run_trunk(const Ctx &c, const Arena &a, const void *nn_in, int N, int
   return 0;
 }
 
-bool refiner_fuses_pose(const Net *net) {
-  return net && !net->scorer && g_fuse_pose && net->trans.head.out == 3 && net->rot.head.out == 3;
+static HeadsQuery heads_query(int pass, int N, int dt, bool fuse_offer) {
+  HeadsQuery q;
+  q.pass = pass; q.N = N; q.dt = dt; q.fuse_offer = fuse_offer;
+  q.ov = heads_override();
+  return q;
 }
+
+bool refiner_fuses_pose(const Net *net) {
+  HeadsPlan hp;
+  return net && !net->scorer && plan_heads(heads_query(HP_REFINER, 1, net->act_dt, true), &hp) == 0 && hp.fuse_pose;
+}
+
+// Track: the QKV projection and the self-attention of BOTH heads as one grouped launch each.  Rows [0,400) = translation head, [512,912) =
+// rotation head (groups padded to the 128-row tile; the rows in between carry don't-care values that no valid row ever reads: every op
+// behind the trunk is row-wise, attention is per sequence).  The attention outputs land in a.att at the same pitch.
+static int track_qkv_attention(const Ctx &c, const HeadsPlan &hp, const Arena &a) {
+  const int G = hp.att.pitch;
+  const ConvGroup g_x{G, true, true};
+  if (run_gemm(c, "gemm_qkv", c.net->g_in_proj, a.tokens, 2 * G, a.qkv, false, nullptr, &g_x)) return 1;
+  FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv, (size_t)SEQ_TOKENS * 3 * EMBED * 2);
+  FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv + (size_t)G * 3 * EMBED * 2, (size_t)SEQ_TOKENS * 3 * EMBED * 2);
+  if (run_attention(c, c.net->act_dt, hp.att, a.qkv, a.att)) return 1;
+  FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_ATT, a.att, (size_t)SEQ_TOKENS * EMBED * 2);
+  FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_ATT, a.att + (size_t)G * EMBED * 2, (size_t)SEQ_TOKENS * EMBED * 2);
+  return 0;
+}
+
+static EncTailParams enc_tail_params(const Net *net, const void *x, const void *att_trans, const void *att_rot, float *pdot, int tiles) {
+  EncTailParams q{};
+  q.x = (const unsigned char *)x;
+  q.pdot = pdot;
+  q.tiles = tiles;
+  q.head_out = net->trans.head.out;
+  const EncLayer *heads[2] = {&net->trans, &net->rot};
+  const void *att[2] = {att_trans, att_rot};
+  for (int i = 0; i < 2; i++) {
+    const EncLayer &L = *heads[i];
+    q.att[i] = (const unsigned char *)att[i];
+    q.w[i][0] = L.att.out_proj.wstep; q.w[i][1] = L.lin1.wstep; q.w[i][2] = L.lin2.wstep;
+    q.bias[i][0] = L.att.out_proj.bias; q.bias[i][1] = L.lin1.bias; q.bias[i][2] = L.lin2.bias;
+    q.ln_g[i][0] = L.ln1.g; q.ln_b[i][0] = L.ln1.b; q.ln_g[i][1] = L.ln2.g; q.ln_b[i][1] = L.ln2.b;
+    q.head_w[i] = L.head.w;
+  }
+  return q;
+}
+
+// The refiner heads of the product (TAIL_ONE_1 / TAIL_ONE_5): QKV projection + self-attention per head (Track: grouped), then ONE launch for
+// everything row-wise behind them (enc_tail_kernel, fp_nn_enc_kernels.inc: five dependent launches per head before, 33 us of Track's 202 us
+// graph) and one for the token mean + Linear(512,3) of both heads, which at Track also applies RefinePostProcess when the plan says so
+static int heads_one_launch(const Ctx &c, const HeadsPlan &hp, const Arena &a, int N, float *trans_dev, float *rot_dev, const PoseUpdateFuse *fuse) {
+  const Net *net = c.net;
+  const int dt = net->act_dt;
+  const size_t rows = (size_t)N * SEQ_TOKENS;
+  const unsigned char *att[2] = {a.att, a.y1};
+  if (hp.qkv == QKV_GROUPED) {
+    if (track_qkv_attention(c, hp, a)) return 1;
+    att[1] = a.att + (size_t)hp.att.pitch * EMBED * 2;
+  } else {
+    const EncLayer *heads[2] = {&net->trans, &net->rot};
+    unsigned char *att_out[2] = {a.att, a.y1};
+    for (int i = 0; i < 2; i++) {
+      if (run_qkv(c, hp, heads[i]->att.in_proj, a.tokens, (int)rows, a.qkv)) return 1;
+      FP_TAP_IMGS(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv, (size_t)SEQ_TOKENS * 3 * EMBED * 2, N, N);
+      if (run_attention(c, dt, hp.att, a.qkv, att_out[i])) return 1;
+      FP_TAP_IMGS(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_ATT, att_out[i], (size_t)SEQ_TOKENS * EMBED * 2, N, N);
+    }
+  }
+  float *const pdot = reinterpret_cast<float *>(a.y2);   // [2][tiles][4] f32
+  {
+    NetScope ps(c, "enc_tail", 2.0 * 3.0 * 2.0 * (double)rows * EMBED * EMBED, 2.0 * 2.0 * (double)rows * EMBED * 2.0);
+    const EncTailParams q = enc_tail_params(net, a.tokens, att[0], att[1], pdot, hp.tail_tiles);
+    with_dt(dt, [&](auto t) {
+      constexpr int DT = decltype(t)::value;
+      if (hp.tail == TAIL_ONE_1) FP_LAUNCH((enc_tail_kernel<DT, 1>), dim3(hp.tail_grid), dim3(512), hp.tail_lds, c.s, q);
+      else FP_LAUNCH((enc_tail_kernel<DT, 5>), dim3(hp.tail_grid), dim3(512), hp.tail_lds, c.s, q);
+    });
+  }
+  FP_TAP(c, TAP_PDOT, pdot, (size_t)2 * hp.tail_tiles * 4 * sizeof(float));
+  {
+    NetScope ps(c, "small_linear", 2.0 * 2 * N * net->trans.head.out * EMBED, 0);
+    const EncHeadsParams p{pdot, {net->trans.head.b, net->rot.head.b}, {trans_dev, rot_dev}, N, hp.tail_tiles / N, net->trans.head.out, (float)SEQ_TOKENS};
+    FP_LAUNCH_RAW(enc_heads_kernel, dim3((unsigned)N), dim3(64), 0, c.s, p, hp.fuse_pose ? *fuse : PoseUpdateFuse{}, hp.fuse_pose ? 1 : 0);
+  }
+  return 0;
+}
+
+#ifdef FP_TEST_HOOKS
+// The launch-chain forms of the refiner heads (HeadsOverride::enc_tail = 0): what the product ran until round 5, kept in the test build as
+// the reference whose every intermediate tensor can be tapped and checked in float64 (tests/test_layers_gpu.py).
+
+// Track (TAIL_GROUPED_CHAIN): out_proj, LayerNorm 1, FFN1, FFN2, LayerNorm 2 + pooling as grouped launches over both heads
+static int heads_grouped_chain(const Ctx &c, const HeadsPlan &hp, const Arena &a, NNScratch *ws, float *trans_dev, float *rot_dev, const PoseUpdateFuse *fuse) {
+  const Net *net = c.net;
+  const int dt = net->act_dt, G = hp.att.pitch;
+  const EncLayer &T0 = net->trans, &R0 = net->rot;
+  const void *x = a.tokens;
+  const ConvGroup g_in{G, false, true}, g_own{G, false, false};
+  if (track_qkv_attention(c, hp, a)) return 1;
+  const size_t hb = (size_t)SEQ_TOKENS * EMBED * 2, ho = (size_t)G * EMBED * 2;   // (taps: a head's 400 rows, the second head's offset)
+  if (run_gemm(c, "gemm_512", net->g_out_proj, a.att, 2 * G, a.y1, false, x, &g_in)) return 1;   // + residual x (shared)
+  FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_Y1, a.y1, hb);
+  FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_Y1, a.y1 + ho, hb);
+  run_layernorm(c, dt, a.y1, T0.ln1, a.y2, 2 * G, &R0.ln1, G);
+  FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_X1, a.y2, hb);
+  FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_X1, a.y2 + ho, hb);
+  if (run_gemm(c, "gemm_512", net->g_lin1, a.y2, 2 * G, a.y1, true, nullptr, &g_own)) return 1;
+  FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_HID, a.y1, hb);
+  FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_HID, a.y1 + ho, hb);
+  if (run_gemm(c, "gemm_512", net->g_lin2, a.y1, 2 * G, a.att, false, a.y2, &g_own)) return 1;   // + residual x1
+  FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_Y2, a.att, hb);
+  FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_Y2, a.att + ho, hb);
+  // LayerNorm 2 feeds nothing but the token mean.  [r5] ONE launch: 2 x 16 workgroups normalise 25 rows each and leave partial column sums,
+  // which the heads kernel adds up (layernorm_pmean_kernel).  Before: LayerNorm over 800 workgroup-rows + a 16-workgroup mean, two
+  // dependent launches (11 us; the one-workgroup-per-sequence fused kernel of Register is a 20 us serial chain at two sequences)
+  const bool pmean = hp.pool == POOL_LN_PMEAN;
+  float *const psums = pmean_sums(ws);   // [2][LN_PMEAN_PARTS][512]
+  if (pmean) {
+    NetScope ps(c, "layernorm_pmean", 0, 2.0 * SEQ_TOKENS * EMBED * 2.0);
+    with_dt(dt, [&](auto t) {
+      using E = typename decltype(t)::E;
+      FP_LAUNCH_RAW(layernorm_pmean_kernel<decltype(t)::value>, dim3(2, LN_PMEAN_PARTS), dim3(256), 0, c.s, (const E *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1,
+                    psums, SEQ_TOKENS, G, LN_PMEAN_ROWS);
+    });
+    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_POOL, psums, (size_t)LN_PMEAN_PARTS * EMBED * sizeof(float));   // (partial column sums: 16 x 25 rows)
+    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_POOL, psums + LN_PMEAN_PARTS * EMBED, (size_t)LN_PMEAN_PARTS * EMBED * sizeof(float));
+  } else {
+    run_layernorm(c, dt, a.att, T0.ln2, a.y1, 2 * G, &R0.ln2, G);
+    run_token_mean(c, dt, a.y1, ws->f32, 2, SEQ_TOKENS, G);
+  }
+  NetScope ps(c, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
+  SmallLinear2 sl{{pmean ? psums : ws->f32, pmean ? psums + LN_PMEAN_PARTS * EMBED : ws->f32 + EMBED}, {T0.head.w, R0.head.w}, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}};
+  if (pmean) { sl.parts = LN_PMEAN_PARTS; sl.tokens = (float)SEQ_TOKENS; }
+  if (hp.readout == RO_SMALL_LINEAR2_POSE) FP_LAUNCH_RAW(small_linear2_pose_kernel, dim3(1), dim3(1024), 0, c.s, sl, T0.head.in, *fuse);
+  else FP_LAUNCH_RAW(small_linear2_kernel, dim3((unsigned)((T0.head.out + 3) / 4), 2), dim3(256), 0, c.s, sl, 1, T0.head.out, T0.head.in);
+  return 0;
+}
+
+// N > 1 (TAIL_HEAD_CHAIN): the post-norm TransformerEncoderLayer of each head as launches, x1 = LN1(x + SA(x)); x2 = LN2(x1 + W2 relu(W1 x1))
+static int heads_per_head_chain(const Ctx &c, const HeadsPlan &hp, const Arena &a, NNScratch *ws, int N, float *trans_dev, float *rot_dev) {
+  const Net *net = c.net;
+  const int dt = net->act_dt;
+  const void *x = a.tokens;
+  const size_t rows = (size_t)N * SEQ_TOKENS;
+  const EncLayer *heads[2] = {&net->trans, &net->rot};
+  float *outs[2] = {trans_dev, rot_dev};
+  for (int i = 0; i < 2; i++) {
+    const EncLayer &L = *heads[i];
+    const int tp = TAP_HEAD + i * TAP_HEAD_STRIDE;
+    const size_t tb1 = (size_t)SEQ_TOKENS * EMBED * 2;   // (taps: one hypothesis' 400 rows)
+    if (run_qkv(c, hp, L.att.in_proj, x, (int)rows, a.qkv)) return 1;
+    FP_TAP_IMGS(c, tp + TAP_H_QKV, a.qkv, 3 * tb1, N, N);
+    if (run_attention(c, dt, hp.att, a.qkv, a.att)) return 1;
+    FP_TAP_IMGS(c, tp + TAP_H_ATT, a.att, tb1, N, N);
+    if (run_gemm(c, "gemm_512", L.att.out_proj, a.att, (int)rows, a.y1, false, x)) return 1;  // + residual x
+    FP_TAP_IMGS(c, tp + TAP_H_Y1, a.y1, tb1, N, N);
+    run_layernorm(c, dt, a.y1, L.ln1, a.y2, rows);                                           // x1 = y2
+    FP_TAP_IMGS(c, tp + TAP_H_X1, a.y2, tb1, N, N);
+    if (run_gemm(c, "gemm_512", L.lin1, a.y2, (int)rows, a.y1, true)) return 1;
+    FP_TAP_IMGS(c, tp + TAP_H_HID, a.y1, tb1, N, N);
+    if (run_gemm(c, "gemm_512", L.lin2, a.y1, (int)rows, a.att, false, a.y2)) return 1;       // + residual x1
+    FP_TAP_IMGS(c, tp + TAP_H_Y2, a.att, tb1, N, N);
+    if (hp.pool == POOL_LN_MEAN) run_layernorm_mean(c, dt, a.att, L.ln2, ws->f32, N, SEQ_TOKENS);
+    else {
+      run_layernorm(c, dt, a.att, L.ln2, a.y1, rows);
+      FP_TAP_IMGS(c, tp + TAP_H_LN2, a.y1, tb1, N, N);
+      run_token_mean(c, dt, a.y1, ws->f32, N, SEQ_TOKENS);
+    }
+    FP_TAP(c, tp + TAP_H_POOL, ws->f32, (size_t)N * EMBED * sizeof(float));
+    run_small_linear(c, ws->f32, L.head, outs[i], N);  // Linear(512,3) commutes with the token mean
+  }
+  return 0;
+}
+#endif
+
 int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, const void *nn_in, int N,
                     float *trans_dev, float *rot_dev, int shared_b, const PoseUpdateFuse *fuse, bool *fused_out) {
   if (fused_out) *fused_out = false;
@@ -2442,197 +2800,25 @@ int refiner_forward(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
   Ctx c{s, prof, net, ws};
   const Arena a = carve(ws);
   if (run_trunk(c, a, nn_in, N, shared_b ? 1 : N)) return 1;
-  const int dt = net->act_dt;
-  const void *x = a.tokens;
-  const size_t rows = (size_t)N * 400;
-  const EncLayer *heads[2] = {&net->trans, &net->rot};
-  float *outs[2] = {trans_dev, rot_dev};
-  const auto tail_ok = [&](const EncLayer &L) {
-    return L.att.out_proj.wstep && L.lin1.wstep && L.lin2.wstep && L.head.in == EMBED && L.head.out <= 3 && L.att.out_proj.Cin == EMBED && L.lin1.Cin == EMBED &&
-           L.lin1.Cout == EMBED && L.lin2.Cin == EMBED && L.lin2.Cout == EMBED && L.att.out_proj.dt == dt && L.lin1.dt == dt && L.lin2.dt == dt;
-  };
-  if (N == 1) {
-    // Track: both heads in ONE launch per layer (Track is bound by its ~65 dependent launches, not by work).  Rows
-    // [0,400) = translation head, [512,912) = rotation head (groups padded to the 128-row tile; the rows in between
-    // carry don't-care values that no valid row ever reads: every op here is row-wise, attention is per sequence).
-    const int G = 512;
-    ConvGroup g_x{G, true, true}, g_in{G, false, true}, g_own{G, false, false};
-    const EncLayer &T0 = net->trans, &R0 = net->rot;
-    if (run_gemm(c, "gemm_qkv", net->g_in_proj, x, 2 * G, a.qkv, false, nullptr, &g_x)) return 1;
-    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv, (size_t)400 * 3 * EMBED * 2);
-    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv + (size_t)G * 3 * EMBED * 2, (size_t)400 * 3 * EMBED * 2);
-    if (run_attention(c, dt, a.qkv, a.att, 2, 400, G)) return 1;
-    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_ATT, a.att, (size_t)400 * EMBED * 2);
-    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_ATT, a.att + (size_t)G * EMBED * 2, (size_t)400 * EMBED * 2);
-    if (g_enc_tail && (dt == DT_F16 || dt == DT_BF16) && tail_ok(T0) && tail_ok(R0) && T0.head.out == 3 && R0.head.out == 3
+  HeadsPlan hp;
+  if (plan_heads(heads_query(HP_REFINER, N, net->act_dt, fuse != nullptr), &hp)) return 1;
+  switch (hp.tail) {
+    case TAIL_ONE_1:
+    case TAIL_ONE_5:
+      if (heads_one_launch(c, hp, a, N, trans_dev, rot_dev, fuse)) return 1;
+      break;
 #ifdef FP_TEST_HOOKS
-        && g_fuse_pose != 2
+    case TAIL_GROUPED_CHAIN:
+      if (heads_grouped_chain(c, hp, a, ws, trans_dev, rot_dev, fuse)) return 1;
+      break;
+    case TAIL_HEAD_CHAIN:
+      if (heads_per_head_chain(c, hp, a, ws, N, trans_dev, rot_dev)) return 1;
+      break;
 #endif
-    ) {
-      // [r5] everything row-wise behind the attention as ONE launch of 2 x 25 sixteen-token tiles (enc_tail_kernel<., 1>) instead of
-      // out_proj, LayerNorm 1, FFN1, FFN2, LayerNorm 2 + partial sums (five dependent launches, 33 us of the 202 us graph)
-      float *const pdot = reinterpret_cast<float *>(a.y2);   // [2][25][4]
-      {
-        NetScope ps(c, "enc_tail", 2.0 * 3.0 * 2.0 * 400.0 * EMBED * EMBED, 2.0 * 2.0 * 400.0 * EMBED * 2.0);
-        EncTailParams q{};
-        q.x = (const unsigned char *)x;
-        q.pdot = pdot;
-        q.tiles = 25;
-        q.head_out = 3;
-        const EncLayer *hl[2] = {&T0, &R0};
-        for (int i = 0; i < 2; i++) {
-          const EncLayer &L = *hl[i];
-          q.att[i] = (const unsigned char *)a.att + (size_t)i * G * EMBED * 2;
-          q.w[i][0] = L.att.out_proj.wstep; q.w[i][1] = L.lin1.wstep; q.w[i][2] = L.lin2.wstep;
-          q.bias[i][0] = L.att.out_proj.bias; q.bias[i][1] = L.lin1.bias; q.bias[i][2] = L.lin2.bias;
-          q.ln_g[i][0] = L.ln1.g; q.ln_b[i][0] = L.ln1.b; q.ln_g[i][1] = L.ln2.g; q.ln_b[i][1] = L.ln2.b;
-          q.head_w[i] = L.head.w;
-        }
-        constexpr unsigned kLds = 16 * 16 * 64 + 2 * 8 * 16 * 4;
-        if (dt == DT_BF16) FP_LAUNCH((enc_tail_kernel<DT_BF16, 1>), dim3(50), dim3(512), kLds, c.s, q);
-        else FP_LAUNCH((enc_tail_kernel<DT_F16, 1>), dim3(50), dim3(512), kLds, c.s, q);
-      }
-      FP_TAP(c, TAP_PDOT, pdot, (size_t)2 * 25 * 4 * sizeof(float));
-      {
-        NetScope ps(c, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
-        EncHeadsParams hp{pdot, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}, 1, 25, 3, 400.f};
-        const bool do_fuse = fuse && g_fuse_pose;
-        FP_LAUNCH_RAW(enc_heads_kernel, dim3(1), dim3(64), 0, c.s, hp, do_fuse ? *fuse : PoseUpdateFuse{}, do_fuse ? 1 : 0);
-        if (do_fuse && fused_out) *fused_out = true;
-      }
-      FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
-      FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
-      FP_HIP_OK(hipGetLastError());
-      return 0;
-    }
-    [[maybe_unused]] const size_t hb = (size_t)400 * EMBED * 2, ho = (size_t)G * EMBED * 2;   // (taps: a head's 400 rows, the second head's offset)
-    if (run_gemm(c, "gemm_512", net->g_out_proj, a.att, 2 * G, a.y1, false, x, &g_in)) return 1;   // + residual x (shared)
-    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_Y1, a.y1, hb);
-    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_Y1, a.y1 + ho, hb);
-    run_layernorm(c, dt, a.y1, T0.ln1, a.y2, 2 * G, &R0.ln1, G);
-    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_X1, a.y2, hb);
-    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_X1, a.y2 + ho, hb);
-    if (run_gemm(c, "gemm_512", net->g_lin1, a.y2, 2 * G, a.y1, true, nullptr, &g_own)) return 1;
-    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_HID, a.y1, hb);
-    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_HID, a.y1 + ho, hb);
-    if (run_gemm(c, "gemm_512", net->g_lin2, a.y1, 2 * G, a.att, false, a.y2, &g_own)) return 1;   // + residual x1
-    FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_Y2, a.att, hb);
-    FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_Y2, a.att + ho, hb);
-    // LayerNorm 2 feeds nothing but the token mean.  [r5] ONE launch: 2 x 16 workgroups normalise 25 rows each and leave partial column sums,
-    // which the heads kernel adds up (layernorm_pmean_kernel).  Before: LayerNorm over 800 workgroup-rows + a 16-workgroup mean, two
-    // dependent launches (11 us; the one-workgroup-per-sequence fused kernel of Register is a 20 us serial chain at two sequences)
-    constexpr int kParts = 16, kRowsPerPart = 25;
-    float *const psums = ws->f32 + (size_t)ws->cap * EMBED + 16;   // [2][kParts][512]
-    const bool pmean = g_ln_pmean != 0
-#ifdef FP_TEST_HOOKS
-                       && g_fuse_pose != 2
-#endif
-        ;
-    if (pmean) {
-      NetScope ps(c, "layernorm_pmean", 0, 2.0 * 400 * EMBED * 2.0);
-      if (dt == DT_BF16) FP_LAUNCH_RAW(layernorm_pmean_kernel<DT_BF16>, dim3(2, kParts), dim3(256), 0, c.s, (const __bf16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
-      else FP_LAUNCH_RAW(layernorm_pmean_kernel<DT_F16>, dim3(2, kParts), dim3(256), 0, c.s, (const _Float16 *)a.att, T0.ln2.g, T0.ln2.b, R0.ln2.g, R0.ln2.b, 1, psums, 400, G, kRowsPerPart);
-      FP_TAP(c, TAP_HEAD + 0 * TAP_HEAD_STRIDE + TAP_H_POOL, psums, (size_t)kParts * EMBED * sizeof(float));   // (partial column sums: kParts x 25 rows)
-      FP_TAP(c, TAP_HEAD + 1 * TAP_HEAD_STRIDE + TAP_H_POOL, psums + kParts * EMBED, (size_t)kParts * EMBED * sizeof(float));
-    } else run_layernorm(c, dt, a.att, T0.ln2, a.y1, 2 * G, &R0.ln2, G);
-#ifdef FP_TEST_HOOKS
-    if (fuse && g_fuse_pose == 2 && T0.head.out == 3 && R0.head.out == 3 && T0.head.in == EMBED) {
-      // A/B (test build): token mean + both heads + RefinePostProcess as one launch whose last workgroup runs the heads -- measured
-      // no faster than the two launches (14.0 us against 6.0 + 6.6 in the replayed graph: the release / acquire pair and the 16
-      // same-address atomics across XCDs cost what the launch did), DESIGN.md section 8
-      NetScope ps(c, "token_mean", 0, 2.0 * 400 * EMBED * 2.0);
-      SmallLinear2 sl{{ws->f32, ws->f32 + EMBED}, {T0.head.w, R0.head.w}, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}};
-      unsigned *arrivals = reinterpret_cast<unsigned *>(ws->f32 + (size_t)ws->cap * EMBED);
-      if (dt == DT_BF16) FP_LAUNCH_RAW(token_mean_pose_kernel<DT_BF16>, dim3(2, EMBED / 64), dim3(384), 0, c.s, (const __bf16 *)a.y1, ws->f32, 400, G, arrivals, sl, T0.head.in, *fuse);
-      else FP_LAUNCH_RAW(token_mean_pose_kernel<DT_F16>, dim3(2, EMBED / 64), dim3(384), 0, c.s, (const _Float16 *)a.y1, ws->f32, 400, G, arrivals, sl, T0.head.in, *fuse);
-      if (fused_out) *fused_out = true;
-      FP_HIP_OK(hipGetLastError());
-      return 0;
-    }
-#endif
-    if (!pmean) run_token_mean(c, dt, a.y1, ws->f32, 2, 400, G);
-    {
-      NetScope ps(c, "small_linear", 2.0 * 2 * T0.head.out * T0.head.in, 0);
-      SmallLinear2 a{{pmean ? psums : ws->f32, pmean ? psums + kParts * EMBED : ws->f32 + EMBED}, {T0.head.w, R0.head.w}, {T0.head.b, R0.head.b}, {trans_dev, rot_dev}};
-      if (pmean) { a.parts = kParts; a.tokens = 400.f; }
-      if (fuse && g_fuse_pose && T0.head.out == 3 && R0.head.out == 3) {
-        FP_LAUNCH_RAW(small_linear2_pose_kernel, dim3(1), dim3(1024), 0, c.s, a, T0.head.in, *fuse);
-        if (fused_out) *fused_out = true;
-      } else
-        FP_LAUNCH_RAW(small_linear2_kernel, dim3((unsigned)((T0.head.out + 3) / 4), 2), dim3(256), 0, c.s, a, 1, T0.head.out, T0.head.in);
-    }
-    FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
-    FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
-    FP_HIP_OK(hipGetLastError());
-    return 0;
+    default:
+      FP_CHECK(false, "refiner_forward: the launch-chain forms of the heads exist in the test build only");
   }
-  if (g_enc_tail && N > 1 && (dt == DT_F16 || dt == DT_BF16) && tail_ok(net->trans) && tail_ok(net->rot) && net->trans.head.out == net->rot.head.out) {
-    // [r5] both heads: QKV projection + self-attention per head (the attention outputs in a.att / a.y1), then ONE launch for everything
-    // row-wise behind them (enc_tail_kernel, fp_nn_enc_kernels.inc) and one for the token mean + Linear(512,3) of both heads
-    void *att_out[2] = {a.att, a.y1};
-    for (int i = 0; i < 2; i++) {
-      if (run_qkv(c, heads[i]->att.in_proj, x, (int)rows, a.qkv)) return 1;
-      FP_TAP_IMGS(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_QKV, a.qkv, (size_t)400 * 3 * EMBED * 2, N, N);
-      if (run_attention(c, dt, a.qkv, att_out[i], N, 400)) return 1;
-      FP_TAP_IMGS(c, TAP_HEAD + i * TAP_HEAD_STRIDE + TAP_H_ATT, att_out[i], (size_t)400 * EMBED * 2, N, N);
-    }
-    float *const pdot = reinterpret_cast<float *>(a.y2);   // [2][N * 5][4] f32
-    {
-      NetScope ps(c, "enc_tail", 2.0 * 3.0 * 2.0 * (double)rows * EMBED * EMBED, 2.0 * 2.0 * (double)rows * EMBED * 2.0);
-      EncTailParams q{};
-      q.x = (const unsigned char *)x;
-      q.pdot = pdot;
-      q.tiles = N * 5;
-      q.head_out = net->trans.head.out;
-      for (int i = 0; i < 2; i++) {
-        const EncLayer &L = *heads[i];
-        q.att[i] = (const unsigned char *)att_out[i];
-        q.w[i][0] = L.att.out_proj.wstep; q.w[i][1] = L.lin1.wstep; q.w[i][2] = L.lin2.wstep;
-        q.bias[i][0] = L.att.out_proj.bias; q.bias[i][1] = L.lin1.bias; q.bias[i][2] = L.lin2.bias;
-        q.ln_g[i][0] = L.ln1.g; q.ln_b[i][0] = L.ln1.b; q.ln_g[i][1] = L.ln2.g; q.ln_b[i][1] = L.ln2.b;
-        q.head_w[i] = L.head.w;
-      }
-      constexpr unsigned kLds = 16 * 80 * 64 + 2 * 8 * 80 * 4 + 4 * 8192;   // tile + LayerNorm exchanges + the two parked x1 fragments
-      if (dt == DT_BF16) FP_LAUNCH((enc_tail_kernel<DT_BF16, 5>), dim3((unsigned)(2 * q.tiles)), dim3(512), kLds, c.s, q);
-      else FP_LAUNCH((enc_tail_kernel<DT_F16, 5>), dim3((unsigned)(2 * q.tiles)), dim3(512), kLds, c.s, q);
-    }
-    FP_TAP(c, TAP_PDOT, pdot, (size_t)2 * N * 5 * 4 * sizeof(float));
-    {
-      NetScope ps(c, "small_linear", 2.0 * 2 * N * net->trans.head.out * EMBED, 0);
-      EncHeadsParams hp{pdot, {net->trans.head.b, net->rot.head.b}, {trans_dev, rot_dev}, N, 5, net->trans.head.out, 400.f};
-      FP_LAUNCH_RAW(enc_heads_kernel, dim3((unsigned)N), dim3(64), 0, c.s, hp, PoseUpdateFuse{}, 0);
-    }
-    FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
-    FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
-    FP_HIP_OK(hipGetLastError());
-    return 0;
-  }
-  for (int i = 0; i < 2; i++) {
-    const EncLayer &L = *heads[i];
-    // post-norm TransformerEncoderLayer: x1 = LN1(x + SA(x)); x2 = LN2(x1 + W2 relu(W1 x1))
-    [[maybe_unused]] const int tp = TAP_HEAD + i * TAP_HEAD_STRIDE;
-    [[maybe_unused]] const size_t tb1 = (size_t)400 * EMBED * 2;   // (taps: one hypothesis' 400 rows)
-    if (run_gemm(c, "gemm_qkv", L.att.in_proj, x, (int)rows, a.qkv, false)) return 1;
-    FP_TAP_IMGS(c, tp + TAP_H_QKV, a.qkv, 3 * tb1, N, N);
-    if (run_attention(c, dt, a.qkv, a.att, N, 400)) return 1;
-    FP_TAP_IMGS(c, tp + TAP_H_ATT, a.att, tb1, N, N);
-    if (run_gemm(c, "gemm_512", L.att.out_proj, a.att, (int)rows, a.y1, false, x)) return 1;  // + residual x
-    FP_TAP_IMGS(c, tp + TAP_H_Y1, a.y1, tb1, N, N);
-    run_layernorm(c, dt, a.y1, L.ln1, a.y2, rows);                                           // x1 = y2
-    FP_TAP_IMGS(c, tp + TAP_H_X1, a.y2, tb1, N, N);
-    if (run_gemm(c, "gemm_512", L.lin1, a.y2, (int)rows, a.y1, true)) return 1;
-    FP_TAP_IMGS(c, tp + TAP_H_HID, a.y1, tb1, N, N);
-    if (run_gemm(c, "gemm_512", L.lin2, a.y1, (int)rows, a.att, false, a.y2)) return 1;       // + residual x1
-    FP_TAP_IMGS(c, tp + TAP_H_Y2, a.att, tb1, N, N);
-    if (N >= 96) run_layernorm_mean(c, dt, a.att, L.ln2, ws->f32, N, 400);
-    else {  // few sequences: one workgroup per sequence is a serial chain (26 us at N = 32 against 9 + 9 for the two-kernel form)
-      run_layernorm(c, dt, a.att, L.ln2, a.y1, rows);
-      FP_TAP_IMGS(c, tp + TAP_H_LN2, a.y1, tb1, N, N);
-      run_token_mean(c, dt, a.y1, ws->f32, N, 400);
-    }
-    FP_TAP(c, tp + TAP_H_POOL, ws->f32, (size_t)N * EMBED * sizeof(float));
-    run_small_linear(c, ws->f32, L.head, outs[i], N);  // Linear(512,3) commutes with the token mean
-  }
+  if (fused_out) *fused_out = hp.fuse_pose;
   FP_TAP(c, TAP_TRANS, trans_dev, (size_t)N * 3 * sizeof(float));
   FP_TAP(c, TAP_ROT, rot_dev, (size_t)N * 3 * sizeof(float));
   FP_HIP_OK(hipGetLastError());
@@ -2647,13 +2833,15 @@ int scorer_features(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws
   Ctx c{s, prof, net, ws};
   const Arena a = carve(ws);
   if (run_trunk(c, a, nn_in, N, N)) return 1;
-  const size_t rows = (size_t)N * 400;
-  if (run_qkv(c, net->att.in_proj, a.tokens, (int)rows, a.qkv)) return 1;
-  FP_TAP_IMGS(c, TAP_HEAD + TAP_H_QKV, a.qkv, (size_t)400 * 3 * EMBED * 2, N, N);
-  if (run_attention(c, net->act_dt, a.qkv, a.att, N, 400)) return 1;
-  FP_TAP_IMGS(c, TAP_HEAD + TAP_H_ATT, a.att, (size_t)400 * EMBED * 2, N, N);
+  HeadsPlan hp;
+  if (plan_heads(heads_query(HP_SCORER_FEATURES, N, net->act_dt, false), &hp)) return 1;
+  const size_t rows = (size_t)N * SEQ_TOKENS;
+  if (run_qkv(c, hp, net->att.in_proj, a.tokens, (int)rows, a.qkv)) return 1;
+  FP_TAP_IMGS(c, TAP_HEAD + TAP_H_QKV, a.qkv, (size_t)SEQ_TOKENS * 3 * EMBED * 2, N, N);
+  if (run_attention(c, net->act_dt, hp.att, a.qkv, a.att)) return 1;
+  FP_TAP_IMGS(c, TAP_HEAD + TAP_H_ATT, a.att, (size_t)SEQ_TOKENS * EMBED * 2, N, N);
   // feature = mean_t(out_proj(att)) = out_proj(mean_t(att))  (out_proj is affine) -> 512x512 GEMV per hypothesis
-  run_token_mean(c, net->act_dt, a.att, ws->f32, N, 400);
+  run_token_mean(c, net->act_dt, a.att, ws->f32, N, SEQ_TOKENS);
   FP_TAP(c, TAP_HEAD + TAP_H_POOL, ws->f32, (size_t)N * EMBED * sizeof(float));
   run_small_linear(c, ws->f32, net->att.out_proj_f32, feat_dev, N);
   FP_TAP(c, TAP_FEAT, feat_dev, (size_t)N * EMBED * sizeof(float));
@@ -2666,6 +2854,8 @@ int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, co
   if (ensure_head_scratch(ws, n_total)) return 1;
   Ctx c{s, prof, net, ws};
   const int N = n_total, dt = net->act_dt;
+  HeadsPlan hp;
+  if (plan_heads(heads_query(HP_SCORER_HEAD, N, dt, false), &hp)) return 1;
   unsigned char *p = ws->head_buf;
   unsigned char *xf = p; p += (size_t)N * EMBED * 2;
   unsigned char *qkv = p; p += (size_t)N * 3 * EMBED * 2;
@@ -2675,14 +2865,13 @@ int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, co
     NetScope ps(c, "cast", 0, (double)N * EMBED * 6.0);
     size_t n = (size_t)N * EMBED;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (dt == DT_BF16) FP_LAUNCH_RAW(cast_f32_kernel<DT_BF16>, grid, dim3(256), 0, c.s, feats_dev, (__bf16 *)xf, n);
-    else FP_LAUNCH_RAW(cast_f32_kernel<DT_F16>, grid, dim3(256), 0, c.s, feats_dev, (_Float16 *)xf, n);
+    with_dt(dt, [&](auto t) { FP_LAUNCH_RAW(cast_f32_kernel<decltype(t)::value>, grid, dim3(256), 0, c.s, feats_dev, (typename decltype(t)::E *)xf, n); });
   }
   FP_TAP(c, TAP_XF, xf, (size_t)N * EMBED * 2);
   // att_cross: sequence = the N hypotheses, batch 1
   if (run_gemm(c, "gemm_cross", net->att_cross.in_proj, xf, N, qkv, false)) return 1;
   FP_TAP(c, TAP_XQKV, qkv, (size_t)N * 3 * EMBED * 2);
-  if (run_attention(c, dt, qkv, att, 1, N)) return 1;
+  if (run_attention(c, dt, hp.att, qkv, att)) return 1;
   FP_TAP(c, TAP_XATT, att, (size_t)N * EMBED * 2);
   // out_proj through the same MFMA GEMM (M = N rows), then Linear(512,1) in f32
   if (run_gemm(c, "gemm_cross", net->att_cross.out_proj, att, N, xf, false)) return 1;
@@ -2690,8 +2879,7 @@ int scorer_head(hipStream_t s, Profiler *prof, const Net *net, NNScratch *ws, co
   {
     // Linear(512,1) on 2-byte rows: widen to f32 first (token_mean with T = 1 is a plain copy of each row)
     NetScope ps(c, "score_linear", 2.0 * N * EMBED, 0);
-    if (dt == DT_BF16) FP_LAUNCH_RAW(token_mean_kernel<DT_BF16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const __bf16 *)xf, o32, 1, 1);
-    else FP_LAUNCH_RAW(token_mean_kernel<DT_F16>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const _Float16 *)xf, o32, 1, 1);
+    with_dt(dt, [&](auto t) { FP_LAUNCH_RAW(token_mean_kernel<decltype(t)::value>, dim3(N, EMBED / 64), dim3(256), 0, c.s, (const typename decltype(t)::E *)xf, o32, 1, 1); });
   }
   FP_TAP(c, TAP_O32, o32, (size_t)N * EMBED * sizeof(float));
   run_small_linear(c, o32, net->score_lin, scores_dev, N);

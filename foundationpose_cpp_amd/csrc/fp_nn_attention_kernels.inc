@@ -6,166 +6,10 @@
 // attention: out[b,t,h*128+d] = softmax_k(q.k/sqrt(128)) v,  qkv = [B,T,1536] (q|k|v, heads contiguous inside each)
 // =================================================================================================
 
-// (a 64-key-block variant of this kernel measured 6 % slower inside Register and was dropped)
-// ATT_QROWS query rows per workgroup (64 = 4 waves, one per SIMD; 80-row / 5-wave tiles cover 400 tokens exactly but
-// measured 12 % slower: two waves of a workgroup share a SIMD).  The 1-D grid is remapped so the query
-// tiles of one (image, head) run on the SAME XCD and share its L2 copy of K/V (a (qt,h,b) grid spread them over all 8
-// XCDs: rocprofv3 FETCH_SIZE showed 1.16 GB fetched per launch for 0.31 GB of QKV).
-template <int ATT_QROWS, bool REMAP, bool PERM, int DT>
-__global__ __launch_bounds__(ATT_QROWS * 4, 2) void attention_kernel(const typename ElemT<DT>::t *__restrict__ qkv, typename ElemT<DT>::t *__restrict__ out, int T, int nq,
-                                                                 int tstride /* rows between the first tokens of consecutive sequences */) {
-  constexpr int KS = 136;  // K tile row stride (halfs): 128 + 8 pad
-  constexpr int VS = 40;   // V^T tile row stride (halfs): 32 keys + 8 pad
-  using E = typename ElemT<DT>::t;
-  using E8 = typename ElemT<DT>::v8;
-  using E4 = typename ElemT<DT>::v4;
-  __shared__ __attribute__((aligned(16))) E Ks[32 * KS];
-  __shared__ __attribute__((aligned(16))) E Vt[HDIM * VS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int logical;
-  {
-    const int nblk = gridDim.x, bi = blockIdx.x;
-    const int xcd = bi & 7, within = bi >> 3, q = nblk >> 3, r = nblk & 7;
-    logical = REMAP ? (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within : bi;
-  }
-  const int qt = logical % nq, h = (logical / nq) % HEADS, b = logical / (nq * HEADS);
-  const int g = lane >> 4, li = lane & 15;
-  const size_t rowstride = 3 * EMBED;
-  const E *base = qkv + (size_t)b * tstride * rowstride;
-  const int q_row = qt * ATT_QROWS + wave * 16 + li;
-  const int q_ld = min(q_row, T - 1);
-  E8 qf[4];
-#pragma unroll
-  for (int ds = 0; ds < 4; ds++)
-    qf[ds] = *reinterpret_cast<const E8 *>(base + (size_t)q_ld * rowstride + h * HDIM + ds * 32 + g * 8);
-
-  f4 o[8];
-#pragma unroll
-  for (int dt = 0; dt < 8; dt++) o[dt] = (f4){0.f, 0.f, 0.f, 0.f};
-  float m_run = -INFINITY, l_run = 0.f;
-  const float sl2e = 0.08838834764831845f * 1.4426950408889634f;  // 1/sqrt(128) * log2(e)
-
-  const int nkb = (T + 31) / 32;
-  // staging roles.  K: thread -> (key = idx>>4, 16-B chunk = idx&15): coalesced 256-B rows.  V: thread -> (key = idx&31,
-  // chunk = idx>>5) so the 2-byte transposed LDS writes of one instruction cover 32 consecutive keys of one d row
-  // (bank-conflict free; the previous key-major mapping was a 16-way conflict on every ds_write_b16).
-  // (the first 4 waves stage; wave 4 only computes)
-  E8 kreg[2], vreg[2];
-  auto load_tile = [&](int kb) {
-    if (ATT_QROWS > 64 && tid >= 256) return;
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      int idx = tid + j * 256;
-      int krow = min(kb * 32 + (idx >> 4), T - 1);
-      kreg[j] = *reinterpret_cast<const E8 *>(base + (size_t)krow * rowstride + EMBED + h * HDIM + (idx & 15) * 8);
-      int vrow = min(kb * 32 + (idx & 31), T - 1);
-      vreg[j] = *reinterpret_cast<const E8 *>(base + (size_t)vrow * rowstride + 2 * EMBED + h * HDIM + (idx >> 5) * 8);
-    }
-  };
-  load_tile(0);
-  for (int kb = 0; kb < nkb; kb++) {
-    if (ATT_QROWS <= 64 || tid < 256) {
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        int idx = tid + j * 256;
-        *reinterpret_cast<E8 *>(&Ks[(idx >> 4) * KS + (idx & 15) * 8]) = kreg[j];
-        int key = idx & 31, chunk = idx >> 5;
-        // V^T row e*16 + chunk holds d = chunk*8 + e, so MFMA column li of tile dt is d = li*8 + dt and a lane ends up
-        // owning 8 consecutive d (one 16-byte output store per query row)
-#pragma unroll
-        for (int e = 0; e < 8; e++) Vt[(PERM ? e * 16 + chunk : chunk * 8 + e) * VS + key] = vreg[j][e];
-      }
-    }
-    __syncthreads();
-    if (kb + 1 < nkb) load_tile(kb + 1);  // next tile's global loads fly under this tile's MFMAs
-    // S^T tiles: st[kt][r] = S[key = kt*16 + g*4 + r][q = li]
-    f4 st[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; kt++) {
-      st[kt] = (f4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ds = 0; ds < 4; ds++) {
-        E8 kf = *reinterpret_cast<const E8 *>(&Ks[(kt * 16 + li) * KS + ds * 32 + g * 8]);
-        st[kt] = mfma32<DT>(__builtin_bit_cast(i4, kf), __builtin_bit_cast(i4, qf[ds]), st[kt]);
-      }
-    }
-    // softmax in base 2 on the RAW scores: p = exp2(s*c - m*c), c = scale*log2(e) -- one fma + one v_exp per score; the
-    // running maximum m is kept unscaled.  Keys past T exist only in the last block (wave-uniform branch).
-    if (kb == nkb - 1 && (T & 31)) {
-#pragma unroll
-      for (int kt = 0; kt < 2; kt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          if (kb * 32 + kt * 16 + g * 4 + r >= T) st[kt][r] = -INFINITY;
-    }
-    float mx = fmaxf(fmaxf(fmaxf(st[0][0], st[0][1]), fmaxf(st[0][2], st[0][3])),
-                     fmaxf(fmaxf(st[1][0], st[1][1]), fmaxf(st[1][2], st[1][3])));
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx);
-    const float mc = m_new * sl2e;
-    const float alpha = __builtin_amdgcn_exp2f(m_run * sl2e - mc);  // m_run = -inf on the first block -> 0
-    float psum = 0.f;
-    E8 pf;
-#pragma unroll
-    for (int kt = 0; kt < 2; kt++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(st[kt][r], sl2e, -mc));
-        psum += pv;
-        pf[kt * 4 + r] = (E)pv;
-      }
-    psum += __shfl_xor(psum, 16);
-    psum += __shfl_xor(psum, 32);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
-    // rescale O rows (row q' = g*4 + r lives in lanes with li == q') -- only when some row's running maximum moved:
-    // after the first key blocks alpha is exactly 1 for every row most of the time, and the 32 multiplies + 4 shuffles
-    // per block made this kernel VALU-bound (x * 1.0f is exact, so skipping it changes nothing)
-    const bool rescale = __any(alpha != 1.0f);
-    if (rescale) {
-      float ar[4];
-#pragma unroll
-      for (int r = 0; r < 4; r++) ar[r] = __shfl(alpha, g * 4 + r);
-#pragma unroll
-      for (int dt = 0; dt < 8; dt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) o[dt][r] *= ar[r];
-    }
-#pragma unroll
-    for (int dt = 0; dt < 8; dt++) {
-      // V^T fragment: col li of tile dt is d = li*8 + dt; k-slots 0..3 -> keys g*4.., 4..7 -> keys 16+g*4..
-      E4 v0 = *reinterpret_cast<const E4 *>(&Vt[(dt * 16 + li) * VS + g * 4]);
-      E4 v1 = *reinterpret_cast<const E4 *>(&Vt[(dt * 16 + li) * VS + 16 + g * 4]);
-      E8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-      o[dt] = mfma32<DT>(__builtin_bit_cast(i4, pf), __builtin_bit_cast(i4, vf), o[dt]);
-    }
-    __syncthreads();
-  }
-  float lr[4];
-#pragma unroll
-  for (int r = 0; r < 4; r++) lr[r] = 1.0f / __shfl(l_run, g * 4 + r);
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    int row = qt * ATT_QROWS + wave * 16 + g * 4 + r;
-    if (row >= T) continue;
-    if (PERM) {
-      E8 ov;
-#pragma unroll
-      for (int dt = 0; dt < 8; dt++) ov[dt] = (E)(o[dt][r] * lr[r]);
-      *reinterpret_cast<E8 *>(out + ((size_t)b * tstride + row) * EMBED + h * HDIM + li * 8) = ov;
-    } else {
-      E *dst = out + ((size_t)b * tstride + row) * EMBED + h * HDIM + li;
-#pragma unroll
-      for (int dt = 0; dt < 8; dt++) dst[dt * 16] = (E)(o[dt][r] * lr[r]);
-    }
-  }
-}
-
 // -------------------------------------------------------------------------------------------------
-// attention32_kernel [r2]: the kernel above is LDS-bandwidth-bound -- a wave owns ONE 16-row query tile, so every 32-key
-// block costs it the whole K and V tile (16 KB of fragment reads) for 16 MFMAs, 2.4x what the LDS delivers at the MFMA
-// rate, plus sixteen 2-byte transposing LDS writes per thread.  Here:
+// attention32_kernel [r2]: the round-1 kernel (attention_kernel, retired; EXPERIMENTS.md) was LDS-bandwidth-bound -- a wave owned ONE
+// 16-row query tile, so every 32-key block cost it the whole K and V tile (16 KB of fragment reads) for 16 MFMAs, 2.4x what the LDS
+// delivers at the MFMA rate, plus sixteen 2-byte transposing LDS writes per thread.  Here:
 //   * a wave owns 32 query rows (two 16-row tiles): every K / V fragment feeds two MFMAs (LDS bytes per MFMA halved),
 //     a workgroup = 4 waves = 128 query rows (4 workgroups per 400-token sequence and head instead of 7: K/V staged 4x);
 //   * O is accumulated TRANSPOSED, O^T[d][q] = V^T P^T: a lane owns one query in S^T and in O^T alike, so the online-softmax
@@ -202,7 +46,10 @@ __device__ __forceinline__ float rows_sum(float x) {
   auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
-template <bool REMAP, int DT, int ABL = 0, int NW = 4>  // NW waves = NW * 32 query rows per workgroup; ABL (timing ablations, wrong results): 1 no staging after the first tile, 2 no softmax, 4 no PV, 8 no QK
+// NW waves = NW * 32 query rows per workgroup; ABL (timing ablations, wrong results): 1 no staging after the first tile, 2 no softmax, 4 no PV,
+// 8 no QK.  Nothing instantiates NW != 4 (8 waves: 9 % slower, the two waves of a SIMD run in lockstep) or ABL & 64 (below) any more; the two
+// stay in the signature because the product instantiations compile to other code without either (four v_mov move by one slot each).
+template <bool REMAP, int DT, int ABL = 0, int NW = 4>
 __global__ __launch_bounds__(NW * 64, 2) void attention32_kernel(const typename ElemT<DT>::t *__restrict__ qkv, typename ElemT<DT>::t *__restrict__ out, int T, int nq,
                                                              int tstride /* rows between the first tokens of consecutive sequences */,
                                                              int qkv_ld /* elements between consecutive qkv rows (>= 1536) */) {
@@ -368,11 +215,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attention32_kernel(const typename 
         float mx = vmax_f32(vmax_f32(vmax_f32(st[qi][0][0], st[qi][0][1]), vmax_f32(st[qi][0][2], st[qi][0][3])),
                             vmax_f32(vmax_f32(st[qi][1][0], st[qi][1][1]), vmax_f32(st[qi][1][2], st[qi][1][3])));
         mx = rows_max(mx);
-        // (ABL 64, test build: a LAZY reference -- it only moves when the block maximum exceeds it by more than 2^8, which skips most of
-        // the 64-multiply rescales of O^T: 213 -> 204 us per launch.  Not shipped: mathematically the same, but a row whose threshold
+        // (ABL 64, no longer instantiated: a LAZY reference -- it only moves when the block maximum exceeds it by more than 2^8, which skips
+        // most of the 64-multiply rescales of O^T: 213 -> 204 us per launch.  Not shipped: mathematically the same, but a row whose threshold
         // decision flips under a 1e-3 perturbation of its inputs gets a different f16 rounding of ALL its P values, and the score-net's
-        // pooled feature then moves by up to 1.3x the between-hypothesis spread between a shard of 32 and the full batch
-        // (tools/ab_shard_att.py); with the exact running maximum the rounding pattern is shared and the two agree to 0.12x.)
+        // pooled feature then moves by up to 1.3x the between-hypothesis spread between a shard of 32 and the full batch;
+        // with the exact running maximum the rounding pattern is shared and the two agree to 0.12x.)
         const float m_new = (ABL & 64) ? ((mx * sl2e > m_run[qi] * sl2e + 8.0f) ? mx : m_run[qi]) : vmax_f32(m_run[qi], mx);
         const float mc = m_new * sl2e;
         const float alpha = __builtin_amdgcn_exp2f(m_run[qi] * sl2e - mc);  // m_run = -inf on the first block -> 0

@@ -23,36 +23,6 @@ __global__ void add_pos_embed_kernel(typename ElemT<DT>::t *__restrict__ x, cons
   reinterpret_cast<E8 *>(x)[i] = r;
 }
 
-// y = LayerNorm(x) over 512 channels, eps 1e-5; one wave per row
-// rows >= split_row use (gamma1, beta1): the refiner's two heads normalised in one launch
-template <int DT>
-__global__ __launch_bounds__(256) void layernorm_kernel(const typename ElemT<DT>::t *__restrict__ x, const float *__restrict__ gamma0,
-                                                        const float *__restrict__ beta0, typename ElemT<DT>::t *__restrict__ y, size_t rows,
-                                                        const float *__restrict__ gamma1, const float *__restrict__ beta1,
-                                                        size_t split_row) {
-  size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  int lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const float *gamma = row >= split_row ? gamma1 : gamma0, *beta = row >= split_row ? beta1 : beta0;
-  using E8 = typename ElemT<DT>::v8;
-  E8 v = reinterpret_cast<const E8 *>(x + row * EMBED)[lane];
-  float f[8], s = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; e++) { f[e] = (float)v[e]; s += f[e]; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  float mean = s * (1.0f / EMBED), q = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; e++) { f[e] -= mean; q += f[e] * f[e]; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-  float rstd = rsqrtf(q * (1.0f / EMBED) + 1e-5f);
-  E8 r;
-#pragma unroll
-  for (int e = 0; e < 8; e++) r[e] = (typename ElemT<DT>::t)(f[e] * rstd * gamma[lane * 8 + e] + beta[lane * 8 + e]);
-  reinterpret_cast<E8 *>(y + row * EMBED)[lane] = r;
-}
-
 // out[b,c] = mean_t x[b,t,c]  (f32 out).  Deterministic (no atomics: the arg-max over near-tied scores must not depend
 // on summation order).  block = (b, 64-channel group); a lane loads 8 channels (16 B) of one token, so a wave covers 8
 // tokens per load and walks the sequence in strides of 32 tokens (13 dependent steps for T = 400 instead of 100: at
@@ -85,6 +55,79 @@ __global__ __launch_bounds__(256) void token_mean_kernel(const typename ElemT<DT
   }
   __syncthreads();
   if (wave == 0) out[(size_t)b * EMBED + cg * 64 + lane] = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (float)T;
+}
+
+// y[b,o] = bias[o] + sum_c x[b,c] W[o,c]   (f32).  One wave per (output o, block of 8 rows b): the weight row lives in registers
+// (C = 512: 8 floats per lane) and is reused for the 8 rows, so W is read B/8 times instead of B times (the 512x512 out_proj of
+// the score-net at N = 252: 130 MB -> 16 MB of L2 reads); the summation order of a (b, o) pair is the same as one wave per output.
+__global__ __launch_bounds__(256) void small_linear_kernel(const float *__restrict__ x, const float *__restrict__ W,
+                                                           const float *__restrict__ bias, float *__restrict__ y, int B,
+                                                           int O, int C) {
+  const int nbb = (B + 7) / 8;
+  size_t widx = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  int lane = threadIdx.x & 63;
+  if (widx >= (size_t)nbb * O) return;
+  const int bb = (int)(widx / O), o = (int)(widx - (size_t)bb * O);
+  const int b0 = bb * 8, nb = min(8, B - b0);
+  if (C == 512) {
+    float w[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = W[(size_t)o * C + lane + 64 * j];
+    for (int i = 0; i < nb; i++) {
+      const float *xr = x + (size_t)(b0 + i) * C;
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; j++) s += xr[lane + 64 * j] * w[j];
+#pragma unroll
+      for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k);
+      if (lane == 0) y[(size_t)(b0 + i) * O + o] = s + bias[o];
+    }
+    return;
+  }
+  for (int i = 0; i < nb; i++) {
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += x[(size_t)(b0 + i) * C + c] * W[(size_t)o * C + c];
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k);
+    if (lane == 0) y[(size_t)(b0 + i) * O + o] = s + bias[o];
+  }
+}
+
+#ifdef FP_TEST_HOOKS
+// -------------------------------------------------------------------------------------------------
+// Kernels of the launch-chain forms of the refiner heads (plan_heads: TAIL_GROUPED_CHAIN / TAIL_HEAD_CHAIN).  The chains are the
+// float64-tapped reference of the test build (tests/test_layers_gpu.py); the product runs enc_tail_kernel + enc_heads_kernel and
+// does not carry them.
+// -------------------------------------------------------------------------------------------------
+
+// y = LayerNorm(x) over 512 channels, eps 1e-5; one wave per row
+// rows >= split_row use (gamma1, beta1): the refiner's two heads normalised in one launch
+template <int DT>
+__global__ __launch_bounds__(256) void layernorm_kernel(const typename ElemT<DT>::t *__restrict__ x, const float *__restrict__ gamma0,
+                                                        const float *__restrict__ beta0, typename ElemT<DT>::t *__restrict__ y, size_t rows,
+                                                        const float *__restrict__ gamma1, const float *__restrict__ beta1,
+                                                        size_t split_row) {
+  size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float *gamma = row >= split_row ? gamma1 : gamma0, *beta = row >= split_row ? beta1 : beta0;
+  using E8 = typename ElemT<DT>::v8;
+  E8 v = reinterpret_cast<const E8 *>(x + row * EMBED)[lane];
+  float f[8], s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; e++) { f[e] = (float)v[e]; s += f[e]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  float mean = s * (1.0f / EMBED), q = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; e++) { f[e] -= mean; q += f[e] * f[e]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+  float rstd = rsqrtf(q * (1.0f / EMBED) + 1e-5f);
+  E8 r;
+#pragma unroll
+  for (int e = 0; e < 8; e++) r[e] = (typename ElemT<DT>::t)(f[e] * rstd * gamma[lane * 8 + e] + beta[lane * 8 + e]);
+  reinterpret_cast<E8 *>(y + row * EMBED)[lane] = r;
 }
 
 // Track [r5]: LayerNorm + PARTIAL token sums for a handful of sequences -- layernorm_kernel + token_mean_kernel were two dependent
@@ -193,42 +236,6 @@ __global__ __launch_bounds__(1024) void layernorm_mean_kernel(const typename Ele
   }
 }
 
-// y[b,o] = bias[o] + sum_c x[b,c] W[o,c]   (f32).  One wave per (output o, block of 8 rows b): the weight row lives in registers
-// (C = 512: 8 floats per lane) and is reused for the 8 rows, so W is read B/8 times instead of B times (the 512x512 out_proj of
-// the score-net at N = 252: 130 MB -> 16 MB of L2 reads); the summation order of a (b, o) pair is the same as one wave per output.
-__global__ __launch_bounds__(256) void small_linear_kernel(const float *__restrict__ x, const float *__restrict__ W,
-                                                           const float *__restrict__ bias, float *__restrict__ y, int B,
-                                                           int O, int C) {
-  const int nbb = (B + 7) / 8;
-  size_t widx = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  int lane = threadIdx.x & 63;
-  if (widx >= (size_t)nbb * O) return;
-  const int bb = (int)(widx / O), o = (int)(widx - (size_t)bb * O);
-  const int b0 = bb * 8, nb = min(8, B - b0);
-  if (C == 512) {
-    float w[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = W[(size_t)o * C + lane + 64 * j];
-    for (int i = 0; i < nb; i++) {
-      const float *xr = x + (size_t)(b0 + i) * C;
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; j++) s += xr[lane + 64 * j] * w[j];
-#pragma unroll
-      for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k);
-      if (lane == 0) y[(size_t)(b0 + i) * O + o] = s + bias[o];
-    }
-    return;
-  }
-  for (int i = 0; i < nb; i++) {
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += x[(size_t)(b0 + i) * C + c] * W[(size_t)o * C + c];
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k);
-    if (lane == 0) y[(size_t)(b0 + i) * O + o] = s + bias[o];
-  }
-}
-
 // the same for two independent layers of equal shape in ONE launch (blockIdx.y picks the layer): the refiner's two heads at Track
 // parts > 0 [r5]: x[h] is not the token mean but `parts` partial COLUMN SUMS [parts][C] of layernorm_pmean_kernel; the mean of
 // channel c is (p0 + p1 + ... in this fixed order) / tokens (B == 1: Track)
@@ -262,9 +269,6 @@ __global__ __launch_bounds__(256) void small_linear2_kernel(const SmallLinear2 a
   if (lane == 0) a.y[h][widx] = s + a.bias[h][o];
 }
 
-// cat[i][:, :, C:2C] = cat[0][:, :, C:2C] for i in 1..N-1 (bordered [N,HP,WP,2C] tensor, interior pixels only); CB = bytes
-// of C channels.  Used when every hypothesis shares one observed crop (Register's first refine iteration: the sampler
-// gives all 252 poses the same translation, foundationpose_sampling.cpp:388-391, so transf_input is identical for all of them).
 // Track's last kernel: both Linear(512,3) heads (waves 0..5: one output each, the same summation as small_linear2_kernel) and, once
 // they are stored, RefinePostProcess of the one hypothesis (pose_update_one) -- small_linear2_kernel + pose_update_kernel in one launch
 __global__ __launch_bounds__(1024) void small_linear2_pose_kernel(const SmallLinear2 a, int C, const PoseUpdateFuse f) {
@@ -299,76 +303,11 @@ __global__ __launch_bounds__(1024) void small_linear2_pose_kernel(const SmallLin
     if (f.done_flag) __hip_atomic_store(f.done_flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
+#endif  // FP_TEST_HOOKS
 
-#ifdef FP_TEST_HOOKS
-// [r4] A/B of the test build (fpt_set_fuse_pose(2)), measured no faster than the two launches it replaces -- Track's last TWO kernels
-// in one launch.  The 16 workgroups are token_mean_kernel's (waves 0..3: the same loads, the same
-// summation order, the same store); each then releases its 64 means and counts itself in, and the workgroup that arrives LAST runs
-// small_linear2_pose_kernel's body on the 1024 means (read at agent scope: they were written by workgroups of other XCDs) -- both
-// heads, RefinePostProcess, the completion flag.  It also clears the counter for the next launch / graph replay.  One dependent
-// launch less per Track, but the release / acquire pair and 16 same-address atomics across XCDs cost as much as the launch did
-// (14.0 us in the replayed graph against 6.0 + 6.6; tools/ab_track.py: 254.1 vs 254.3 us per call).
-template <int DT>
-__global__ __launch_bounds__(384) void token_mean_pose_kernel(const typename ElemT<DT>::t *__restrict__ x, float *out, int T, int tstride,
-                                                              unsigned *arrivals, const SmallLinear2 a, int C, const PoseUpdateFuse f) {
-  using E8 = typename ElemT<DT>::v8;
-  __shared__ float part[4][64];
-  __shared__ float head_out[6];
-  __shared__ unsigned is_last;
-  const int b = blockIdx.x, cg = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int slot = lane >> 3, c8 = (lane & 7) * 8;
-  if (wave < 4) {
-    const typename ElemT<DT>::t *src = x + (size_t)b * tstride * EMBED + cg * 64 + c8;
-    float s[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) s[e] = 0.f;
-    for (int t = wave * 8 + slot; t < T; t += 32) {
-      E8 v = *reinterpret_cast<const E8 *>(src + (size_t)t * EMBED);
-#pragma unroll
-      for (int e = 0; e < 8; e++) s[e] += (float)v[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      s[e] += __shfl_xor(s[e], 8);
-      s[e] += __shfl_xor(s[e], 16);
-      s[e] += __shfl_xor(s[e], 32);
-    }
-    if (slot == 0) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) part[wave][c8 + e] = s[e];
-    }
-  }
-  __syncthreads();
-  if (wave == 0) {
-    out[(size_t)b * EMBED + cg * 64 + lane] = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (float)T;
-    __threadfence();   // release this workgroup's means to the device before it is counted
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    is_last = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * gridDim.y - 1 ? 1u : 0u;
-  __syncthreads();
-  if (!is_last) return;
-  __threadfence();
-  const int h = wave / 3, o = wave - h * 3;
-  const float *xm = a.x[h], *W = a.W[h];
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += __hip_atomic_load(xm + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * W[(size_t)o * C + c];
-#pragma unroll
-  for (int k = 32; k > 0; k >>= 1) s += __shfl_xor(s, k);
-  if (lane == 0) {
-    const float y = s + a.bias[h][o];
-    a.y[h][o] = y;
-    head_out[wave] = y;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(arrivals, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    pose_update_one(f.poses, head_out, head_out + 3, 0, f.diameter, f.poses_in ? f.poses_in : f.poses, f.extra_out);
-    if (f.done_flag) __hip_atomic_store(f.done_flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-#endif
-
+// cat[i][:, :, C:2C] = cat[0][:, :, C:2C] for i in 1..N-1 (bordered [N,HP,WP,2C] tensor, interior pixels only); CB = bytes
+// of C channels.  Used when every hypothesis shares one observed crop (Register's first refine iteration: the sampler
+// gives all 252 poses the same translation, foundationpose_sampling.cpp:388-391, so transf_input is identical for all of them).
 __global__ void broadcast_b_kernel(unsigned char *__restrict__ cat, int N, int HP, int WP, int H, int W, int pad, int CB) {
   const int chunks = CB / 16;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

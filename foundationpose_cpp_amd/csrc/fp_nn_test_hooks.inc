@@ -127,7 +127,6 @@ void fpt_set_q8_headroom(float v) { fp::g_q8_headroom = v; }
 void fpt_set_q8_wq(int wclip, int efr, int imgbias) { fp::g_q8_wclip = wclip; fp::g_q8_efr = efr; fp::g_q8_imgbias = imgbias; }
 void fpt_set_ln_pmean(int v) { fp::g_ln_pmean = v; }
 void fpt_set_enc_tail(int v) { fp::g_enc_tail = v; }
-void fpt_set_qkv_tile(int v) { fp::g_qkv_tile = v; }
 void fpt_set_qkv_ablate(int v) { fp::g_qkv_ablate = v; }
 // HOST-ONLY (no HIP call: runs without a GPU, tests/test_quantiser_cpu.py): the INT8 weight quantiser of fp_nn.hip on rows [Cout][taps][Cin]
 // with the activation scales s_in [Cin] folded in and (m_int != null) the calibration frames' mean integer activations [J][Cin]:
@@ -168,6 +167,22 @@ int fpt_plan_conv(const int *shape10, int dt, int odt, int flags, int split_imgs
   }
   if (post_fused) *post_fused = plan.post_fused ? 1 : 0;
   return plan.n;
+}
+// HOST-ONLY (no HIP call: runs without a GPU, tests/test_heads_plan_cpu.py): what plan_heads chooses behind the trunk under the current
+// switches.  pass: 0 refiner, 1 scorer features, 2 scorer head (fp_nn.hip HeadsPass); dt: DT_F16 / DT_BF16; fuse_offer: the caller offers a
+// PoseUpdateFuse.  fields18 = {qkv form, qkv ablation, qkv grid, qkv LDS bytes, attention kernel, XCD remap, attention ablation bits, B, T,
+// pitch, query tiles, attention grid, attention block, attention LDS bytes, tail form, pooling form, read-out kernel, pose fused} (the enums
+// of fp_nn.hip) and tail3 = {tiles per head, grid, LDS bytes} of enc_tail_kernel.  Returns 0, or 1 when the query is refused.
+int fpt_plan_heads(int pass, int N, int dt, int fuse_offer, int *fields18, int *tail3) {
+  fp::HeadsPlan p;
+  if (fp::plan_heads(fp::heads_query(pass, N, dt, fuse_offer != 0), &p)) return 1;
+  const fp::AttVariant &v = fp::ATT_VARIANTS[p.att.variant];
+  const int f[18] = {p.qkv, p.qkv_ablate, (int)p.qkv_grid, p.qkv_lds, p.att.kernel, v.remap ? 1 : 0, v.ablate, p.att.B, p.att.T,
+                     p.att.pitch, p.att.nq, (int)p.att.grid, p.att.block, p.att.lds, p.tail, p.pool, p.readout, p.fuse_pose ? 1 : 0};
+  std::memcpy(fields18, f, sizeof(f));
+  const int t[3] = {p.tail_tiles, (int)p.tail_grid, p.tail_lds};
+  std::memcpy(tail3, t, sizeof(t));
+  return 0;
 }
 void fpt_set_conv_variant(int v) { fp::g_conv_variant = v; }
 void fpt_set_i8_stream(int v) { fp::g_i8_stream = v; }
@@ -497,7 +512,7 @@ int fpt_attention_dt(const float *qkv, int B, int T, float *out, int dt) {
   auto hq = encode(qkv, nq, dt, 1.f);
   FP_HIP_OK(fp::memcpy_sync(dq.p, hq.data(), nq * 2, hipMemcpyHostToDevice));
   Ctx c{nullptr, nullptr, nullptr};
-  if (run_attention(c, dt, dq.p, dout.p, B, T)) return 1;
+  if (run_attention(c, dt, plan_attention(B, T, T, heads_override()), dq.p, dout.p)) return 1;
   FP_HIP_OK(hipDeviceSynchronize());
   std::vector<unsigned char> ho(no * 2);
   FP_HIP_OK(fp::memcpy_sync(ho.data(), dout.p, no * 2, hipMemcpyDeviceToHost));
@@ -681,19 +696,19 @@ float fpt_attention_bench(int B, int T, int iters, int variant) {
   for (size_t i = 0; i < nq; i++) { st = st * 1664525u + 1013904223u; hq[i] = __float2half(((st >> 8) & 0xffff) / 65536.0f - 0.5f); }
   if (fp::memcpy_sync(dq.p, hq.data(), nq * 2, hipMemcpyHostToDevice) != hipSuccess) return -1.f;
   Ctx c{nullptr, nullptr, nullptr};
-  int saved = g_att_variant;
-  g_att_variant = variant;
+  HeadsOverride ov;
+  ov.att_variant = variant;   // (a row of ATT_VARIANTS; any other id times the shipped kernel)
+  const AttLaunch att = plan_attention(B, T, T, ov);
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.f;
-  for (int i = 0; i < 3; i++) run_attention(c, DT_F16, dq.p, dout.p, B, T, 0, ld);
+  for (int i = 0; i < 3; i++) run_attention(c, DT_F16, att, dq.p, dout.p, ld);
   (void)hipEventRecord(e0, nullptr);
-  for (int i = 0; i < iters; i++) run_attention(c, DT_F16, dq.p, dout.p, B, T, 0, ld);
+  for (int i = 0; i < iters; i++) run_attention(c, DT_F16, att, dq.p, dout.p, ld);
   (void)hipEventRecord(e1, nullptr);
   float ms = -1.f;
   if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -(float)iters;
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  g_att_variant = saved;
   return ms / iters;
 }
 

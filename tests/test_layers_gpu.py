@@ -60,6 +60,7 @@ def tl():
     L.fpt_launch_log_get.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
     L.fpt_launch_log_get_all.argtypes = [C.POINTER(C.c_int), C.c_char_p, C.c_int, C.c_int]
     L.fpt_plan_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.fpt_plan_heads.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     yield L
     L.fpt_tap_clear()
     if TABLE:
@@ -806,6 +807,76 @@ def test_plan_equals_reality(tl, model, crops, disc_nets, syn_mesh, scene):
                 _same_launches(f"fp_net_infer scorer={scorer} batch={batch}", real, _plan(tl, model, PLAN_SCORER if scorer else PLAN_REFINER, batch))
         finally:
             tl.fp_net_destroy(n)
+
+
+# fp_nn.hip: QkvForm, TailForm, PoolForm of fpt_plan_heads (fields18[0], [14], [15])
+QKV_LINEAR, QKV_TILE, QKV_GROUPED = 0, 1, 2
+TAIL_NONE, TAIL_ONE_1, TAIL_ONE_5, TAIL_GROUPED_CHAIN, TAIL_HEAD_CHAIN = range(5)
+POOL_TAIL_PDOT, POOL_LN_PMEAN, POOL_LN_MEAN, POOL_LN_TOKEN_MEAN, POOL_TOKEN_MEAN = range(5)
+
+
+def _heads_plan(tl, kind, N, offer=0):
+    f, t = (C.c_int * 18)(), (C.c_int * 3)()
+    assert tl.fpt_plan_heads(kind, N, LR.F16, offer, f, t) == 0
+    return dict(qkv=f[0], tail=f[14], pool=f[15])
+
+
+def _head_launches(recs):
+    """the launches behind the trunk as the log names them: a Linear layer is its tag (one entry however many steps its plan_conv schedule
+    takes), the QKV projection says whether qkv_tile_kernel ran it"""
+    last = max(i for i, r in enumerate(recs) if r["tag"] == "conv_512" or r["kernel"] == "add_pos_embed")
+    out = []
+    for r in recs[last + 1:]:
+        if r["kernel"] == "conv_splitk_reduce_kernel" or r["m_begin"] > 0:
+            continue
+        if r["tag"] == "gemm_qkv":
+            out.append("qkv:tile" if r["kernel"] == "qkv_tile_kernel" else "qkv:linear")
+        else:
+            out.append(r["tag"] or r["kernel"])
+    return out
+
+
+def _launches_of_plan(kind, p):
+    """what the forms of a HeadsPlan launch, in order"""
+    qkv = "qkv:tile" if p["qkv"] == QKV_TILE else "qkv:linear"
+    pool = {POOL_LN_PMEAN: ["layernorm_pmean"], POOL_LN_MEAN: ["layernorm_mean"], POOL_LN_TOKEN_MEAN: ["layernorm", "token_mean"],
+            POOL_TOKEN_MEAN: ["token_mean"], POOL_TAIL_PDOT: []}[p["pool"]]
+    chain = ["gemm_512", "layernorm", "gemm_512", "gemm_512"]
+    if kind == PLAN_SCORER_FEATURES:
+        return [qkv, "attention"] + pool + ["small_linear"]
+    if p["tail"] in (TAIL_ONE_1, TAIL_ONE_5):
+        return [qkv, "attention"] * (1 if p["qkv"] == QKV_GROUPED else 2) + ["enc_tail", "small_linear"]
+    if p["tail"] == TAIL_GROUPED_CHAIN:
+        return [qkv, "attention"] + chain + pool + ["small_linear"]
+    assert p["tail"] == TAIL_HEAD_CHAIN
+    return ([qkv, "attention"] + chain + pool + ["small_linear"]) * 2
+
+
+SCORER_HEAD_LAUNCHES = ["cast", "gemm_cross", "attention", "gemm_cross", "score_linear", "small_linear"]
+
+
+def test_the_pure_heads_plan_is_what_launches(tl, model):
+    """fpt_plan_heads (host arithmetic alone, tests/test_heads_plan_cpu.py holds it to its table) against the launch log of a plan-only
+    forward pass (fpt_plan_forward, which test_plan_equals_reality ties to the real calls): the records behind the trunk are the forms the
+    pure plan names, at every N where a form changes -- and under enc_tail = 0 at the boundary of layernorm_mean"""
+    _set_prec(model, FP_PREC_F16)
+    for N in (1, 2, 4, 5, 95, 96, 252):
+        p = _heads_plan(tl, 0, N)
+        assert p["tail"] == (TAIL_ONE_1 if N == 1 else TAIL_ONE_5) and p["qkv"] == (QKV_GROUPED if N == 1 else QKV_TILE)
+        assert _head_launches(_plan(tl, model, PLAN_REFINER, N)) == _launches_of_plan(PLAN_REFINER, p), N
+    tl.fpt_set_enc_tail(0)
+    try:
+        for N in (1, 95, 96):
+            p = _heads_plan(tl, 0, N)
+            assert p["tail"] == (TAIL_GROUPED_CHAIN if N == 1 else TAIL_HEAD_CHAIN)
+            assert p["pool"] == (POOL_LN_PMEAN if N == 1 else POOL_LN_MEAN if N >= 96 else POOL_LN_TOKEN_MEAN)
+            assert _head_launches(_plan(tl, model, PLAN_REFINER, N)) == _launches_of_plan(PLAN_REFINER, p), N
+    finally:
+        tl.fpt_set_enc_tail(1)
+    for N in (4, 5, 32, 33, 2048, 2049):
+        p = _heads_plan(tl, 1, N)
+        assert _heads_plan(tl, 2, N) == dict(qkv=QKV_LINEAR, tail=TAIL_NONE, pool=POOL_TOKEN_MEAN)
+        assert _head_launches(_plan(tl, model, PLAN_SCORER, N)) == _launches_of_plan(PLAN_SCORER_FEATURES, p) + SCORER_HEAD_LAUNCHES, N
 
 
 def _register_shard_stages(tl, model, disc_nets, syn_mesh, scene, begin, count, prec):

@@ -490,8 +490,8 @@ hyp = syn.perturb_pose(scene.gt_pose)
 for vc in (0, 1, 2):            # 2: fused vertex + crop launch, the triangles' row ranges as their own launch
     # et 1: the encoder tail of both heads as one launch (enc_tail_kernel<., 1>, the product); et 0: out_proj, LayerNorm, FFN1, FFN2 as launches, then
     # pm 1: LayerNorm 2 + partial token sums in one launch (the product until round 5's last session), 0: layernorm + token_mean
-    # fu 1: heads + RefinePostProcess in one launch (the product), 2: the token mean in that launch too (A/B; exists for et 0 / pm 0 only)
-    for et, pm, fu in ((1, 1, 0), (1, 1, 1), (0, 1, 0), (0, 1, 1), (0, 0, 0), (0, 0, 1), (0, 0, 2)):
+    # fu 1: heads + RefinePostProcess in one launch (the product), 0: RefinePostProcess as its own launch
+    for et, pm, fu in ((1, 1, 0), (1, 1, 1), (0, 1, 0), (0, 1, 1), (0, 0, 0), (0, 0, 1)):
         L.fpt_set_vertex_crop(vc); L.fpt_set_fuse_pose(fu); L.fpt_set_ln_pmean(pm); L.fpt_set_enc_tail(et)
         m = FoundationPose(mesh, scene.K, rp, sp)
         poses = []
@@ -507,7 +507,7 @@ for vc in (0, 1, 2):            # 2: fused vertex + crop launch, the triangles' 
 @pytest.mark.gpu
 def test_track_launch_fusions_do_not_change_a_bit(tmp_path):
     """Track's fused launches (pose set-up + vertex stage + crop warp + the triangles' row ranges in one kernel; both Linear(512,3) heads
-    + RefinePostProcess in one kernel; the A/B form whose last workgroup also ran the token mean) against the separate kernels they
+    + RefinePostProcess in one kernel) against the separate kernels they
     replace, in the test build where every form exists: every pose of an eager call, a graph capture, a replay and a two-iteration
     Track is bit-identical within each form of the encoder tail -- the LayerNorm-2 + partial-sums launch [r5] adds the 400 rows
     in another (fixed) order than layernorm + token_mean, and the one-launch tail (enc_tail_kernel, the product) sums inside its LayerNorms
@@ -520,7 +520,7 @@ def test_track_launch_fusions_do_not_change_a_bit(tmp_path):
     res = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l.split() for l in res.stdout.splitlines() if l.startswith("POSES")]
-    assert len(lines) == 21
+    assert len(lines) == 18
     forms = {}
     for l in lines:
         forms.setdefault(l[2][0], set()).add(l[3])      # "e": encoder tail in one launch, "1" / "0": the launch chain with / without the fused LayerNorm 2

@@ -1,6 +1,6 @@
 """A/B of a library test hook inside the real Register pipeline (N = 252), same process / same box.
 
-    python tools/ab_pipeline.py fpt_set_att_variant 7 1 7 1
+    python tools/ab_pipeline.py fpt_set_att_variant 8 1 8 1
     python tools/ab_pipeline.py fpt_set_conv_ablate 0 16 0 16        # 16 = no streaming stores
 """
 import os, sys, tempfile
