@@ -4,6 +4,7 @@
     python examples/demo_sequence.py --data test_data/mustard0 --refiner refiner.fpw --scorer scorer.fpw --out out
     python examples/demo_sequence.py --synthetic 8 --out out      # seeded synthetic sequence + synthetic weights
     python examples/demo_sequence.py --synthetic 8 --fit 5        # + pose-fit columns (tolerance 5 mm) and a LOST? marker per frame
+    python examples/demo_sequence.py --synthetic 8 --depth-filter # the networks see bilateral(erode(depth)), like FoundationPose as published
 """
 import argparse
 import os
@@ -18,7 +19,7 @@ from foundationpose_cpp_amd import FoundationPose, _lib, dataset as D, load_mesh
 from foundationpose_cpp_amd.synthetic import to_colmajor  # noqa: E402
 
 
-def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, fit_mm=None, lost_below=0.5):
+def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, fit_mm=None, lost_below=0.5, depth_filter=False):
     """fit_mm: pose-fit tolerance in millimetres (None = off: the log is the plain pose log).  With it every log line also carries
     n_model and the inlier / front / behind shares of the model, and LOST? when the inlier share is under lost_below.  Track's record
     describes the pose the frame STARTED from (the previous frame's answer) against this frame's depth."""
@@ -27,6 +28,8 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
     model = FoundationPose(mesh, seq.K, refiner, scorer, max_input_image_height=max(seq.H, 1080), max_input_image_width=max(seq.W, 1920))
     if fit_mm is not None:
         model.set_pose_fit(True, fit_mm * 1e-3)
+    if depth_filter:
+        model.set_depth_filter(True)
     os.makedirs(out, exist_ok=True)
     poses = []
     with open(os.path.join(out, "poses.txt"), "w") as log:
@@ -73,6 +76,8 @@ def main():
     ap.add_argument("--fit", type=float, nargs="?", const=5.0, default=None, metavar="TOL_MM",
                     help="log the pose fit per frame (tolerance in mm, default 5) and mark frames whose inlier share is under --lost-below")
     ap.add_argument("--lost-below", type=float, default=0.5, metavar="SHARE")
+    ap.add_argument("--depth-filter", action="store_true",
+                    help="Register and Track read bilateral(erode(depth)) instead of the raw depth (FoundationPose as published); default off")
     ap.add_argument("--synthetic", type=int, metavar="N", help="write and use an N-frame synthetic sequence + synthetic weights")
     a = ap.parse_args()
     if a.synthetic:
@@ -83,7 +88,7 @@ def main():
         W.pack_synthetic("refiner", a.refiner)
         W.pack_synthetic("scorer", a.scorer)
         print("synthetic sequence:", a.data, "(synthetic weights: poses are not meaningful, only reproducible)")
-    run(a.data, a.refiner, a.scorer, a.out, a.name, a.refine_itr, a.plots, a.fit, a.lost_below)
+    run(a.data, a.refiner, a.scorer, a.out, a.name, a.refine_itr, a.plots, a.fit, a.lost_below, a.depth_filter)
     print("wrote", os.path.join(a.out, "poses.txt"))
 
 

@@ -114,7 +114,7 @@ int main(int argc, char **argv) {
   const int reps = std::atoi(arg(argc, argv, "--reps", mode == "speed_track" ? "5000" : "50"));
   if (root.empty() || refiner.empty() || scorer.empty()) {
     std::fprintf(stderr, "usage: fp_demo --data DIR --refiner R.fpw --scorer S.fpw [--mesh M.obj] [--out DIR] "
-                         "[--mode test|speed_register|speed_track] [--reps N] [--refine-itr N] [--plots] [--fit [TOL_MM]] [--lost-below SHARE]\n");
+                         "[--mode test|speed_register|speed_track] [--reps N] [--refine-itr N] [--plots] [--fit [TOL_MM]] [--lost-below SHARE] [--depth-filter]\n");
     return 2;
   }
   float K[9];
@@ -150,6 +150,8 @@ int main(int argc, char **argv) {
   const float fit_mm = fit && fit_arg[0] != '-' ? (float)std::atof(fit_arg) : 5.0f;
   const double lost_below = std::atof(arg(argc, argv, "--lost-below", "0.5"));
   if (fit && !fpm->SetPoseFit(true, fit_mm * 1e-3f)) { std::fprintf(stderr, "%s\n", fpm->last_error().c_str()); return 1; }
+  // --depth-filter: Register and Track read bilateral(erode(depth)) instead of the raw depth, like FoundationPose as published (default off)
+  if (flag(argc, argv, "--depth-filter") && !fpm->SetDepthFilter(true)) { std::fprintf(stderr, "%s\n", fpm->last_error().c_str()); return 1; }
   Frame f0;
   if (!read_frame(root, ids[0], H, W, true, f0)) { std::fprintf(stderr, "%s\n", fp_last_error()); return 1; }
   const fp_amd::ImageU8 rgb0{f0.rgb.data(), H, W, 3}, mask0{f0.mask.data(), H, W, 1};

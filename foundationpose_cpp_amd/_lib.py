@@ -25,6 +25,7 @@ SYMBOLS = [
     "fp_draw_bbox3d", "fp_set_precision", "fp_get_precision", "fp_calibrate_fp8", "fp_calibrate", "fp_calibrate_begin", "fp_calibrate_add_frame", "fp_calibrate_finish", "fp_calibrate_abort", "fp_calibrate_frames", "fp_calibration_size", "fp_get_calibration_blob", "fp_set_calibration_blob", "fp_get_calibration", "fp_set_calibration", "fp_set_float_model", "fp_get_float_model", "fp_net_create", "fp_net_destroy", "fp_net_max_batch", "fp_net_blob", "fp_net_infer",
     "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
+    "fp_set_depth_filter", "fp_get_depth_filter",
 ]
 
 
@@ -135,6 +136,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_set_pose_fit": [vp, ci, cf], "fp_get_pose_fit": [vp, vp, vp], "fp_last_track_fit": [vp, vp, ci],
         "fp_last_register_fit": [vp, vp, vp, ci], "fp_pose_fit_eval": [vp, cs, vp, ci, cf, cf, vp],
         "fp_mesh_color_source": [vp], "fp_set_vertex_colors": [vp, cs, vp, ci], "fp_get_color_source": [vp, cs],
+        "fp_set_depth_filter": [vp, ci], "fp_get_depth_filter": [vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

@@ -369,6 +369,17 @@ class FoundationPose:
         self._must(self._L.fp_pose_fit_eval(self._h, target_name.encode(), _p(p), len(p), crop_ratio, tol_m, out))
         return [_fit(r) for r in out]
 
+    # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
+    def set_depth_filter(self, on: bool):
+        """Register, Track and the stage operators read bilateral(erode(depth)) instead of the depth itself, like FoundationPose as
+        published (default off).  Depth below 0.1 m reads as missing then.  Drops the captured graphs like set_pose_fit."""
+        self._must(self._L.fp_set_depth_filter(self._h, 1 if on else 0))
+
+    def depth_filter(self) -> bool:
+        on = self._L.fp_get_depth_filter(self._h)
+        self._must(1 if on < 0 else 0)
+        return bool(on)
+
     # ---- vertex colours (include/foundationpose_amd.h "vertex colours") ----------------------------
     def set_vertex_colors(self, target_name: str, colors):
         """colors [V,3] u8 RGB become the colour source of the target's renderings (interpolated per pixel instead of a texture

@@ -492,6 +492,10 @@ struct fp_model {
   int fit_reg_n = 0, fit_reg_index = -1;   // records of the last Register in fit_rec (0: none) and its winner
   float fit_reg_tol = 0, fit_reg_diam = 0;
 
+  // depth filter (fp_set_depth_filter): the crops read D' = bilateral(erode(depth)) out of `bilat` through the frame
+  // record.  No buffer of its own: Register's sampler leaves the whole frame's D' there anyway, Track fills its window of it.
+  bool dfilt_on = false;
+
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
   // into a hipGraph and replayed.  The graph bakes buffer addresses, so it is keyed by g_alloc_epoch.
   // (Register's ~110 launches are replayed the same way: inter-kernel gaps are ~4 % of a 12 ms Register.)
@@ -636,8 +640,10 @@ static int render_and_crop(fp_model *m, Target *t, int N, float crop_ratio, OutM
   return 0;
 }
 
-static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W, int row0 = 0, int row1 = -1, int col0 = 0, int col1 = -1);
+static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W, int row0 = 0, int row1 = -1, int col0 = 0, int col1 = -1,
+                              const TrackWindow *filt = nullptr);
 static int set_rotation_grid(fp_model *m, int steps);
+static int publish_record(fp_model *m, const FrameRef &want);
 
 static void drop_graph(fp_model::GraphSlot &g) {
   if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -889,6 +895,29 @@ long long fpt_read_buffer(fp_model *m, int which, void *dst, long long max_bytes
   return (long long)b;
 }
 
+// the fused depth filter (depth_filter_rect_kernel) on [x0, x1) x [y0, y1) of the uploaded frame -> out_host, the rectangle's D' row by
+// row ((y1 - y0) * (x1 - x0) floats; the rectangle is clamped to the frame first).  The kernel writes into `erode`, which is filled with
+// NaN before: a pixel of the rectangle it did not write comes back as NaN.  The model's frame record is put back afterwards.
+int fpt_depth_filter_rect(fp_model *m, int x0, int y0, int x1, int y1, float *out_host) try {
+  FP_CHECK(m && out_host && m->depth && !m->frame_partial, "[FoundationPose] fpt_depth_filter_rect: no whole frame uploaded");
+  SerialGuard serial(m->device);
+  x0 = std::max(x0, 0); y0 = std::max(y0, 0); x1 = std::min(x1, m->W); y1 = std::min(y1, m->H);
+  FP_CHECK(x1 > x0 && y1 > y0, "[FoundationPose] fpt_depth_filter_rect: empty rectangle");
+  const FrameRef before = m->frame_pub;
+  FrameRef r{};
+  r.rgb = m->rgb; r.depth = m->erode; r.raw = m->depth;
+  r.wx0 = x0; r.wy0 = y0; r.wx1 = x1; r.wy1 = y1; r.ux1 = m->W; r.uy1 = m->H;
+  FP_HIP_OK(hipMemsetAsync(m->erode, 0xff, (size_t)m->H * m->W * 4, m->stream));
+  if (publish_record(m, r)) return 1;
+  launch_depth_filter_rect(m->stream, m->frame_dev, m->H, m->W);
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipMemcpy2DAsync(out_host, (size_t)(x1 - x0) * 4, m->erode + (size_t)y0 * m->W + x0, (size_t)m->W * 4, (size_t)(x1 - x0) * 4, (size_t)(y1 - y0),
+                             hipMemcpyDeviceToHost, m->stream));
+  if (before.rgb && publish_record(m, before)) return 1;
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  return 0;
+} FP_CATCH_INT
+
 #endif  // FP_TEST_HOOKS
 
 const char *fp_last_error(void) { return g_last_error.c_str(); }
@@ -1024,7 +1053,6 @@ fp_model *fp_create_on(int device, const fp_mesh *meshes, int n_meshes, const fl
   if (max_w > 0) m->max_w = max_w;
   // non-blocking: no implicit synchronisation with the legacy null stream (other models' threads, the caller's framework)
   if (stream_acquire(&m->stream) != hipSuccess) { set_error("[FoundationPose] Failed to create stream"); return nullptr; }
-  static_assert(sizeof(FrameRef) <= 64, "the packed window starts 64 bytes into the frame block");
   // the frame record's device block [FrameRef, padded to 64 bytes | packed window]: the window part and its pinned twin are allocated
   // on the first host-frame Track that needs them and grown on demand (ensure_window) [r5] -- a model that is only ever handed device
   // frames, or never tracks, pins no host memory
@@ -1170,6 +1198,7 @@ static int stage_fetch(fp_model *m, void *dst_dev, const void *src_host, size_t 
   FP_CHECK(stage_off % 16 == 0 && stage_off + bytes <= m->host_stage_cap && ((uintptr_t)dst_dev & 15) == 0, "[FoundationPose] internal: misaligned staged upload");
   std::memcpy(m->host_stage + stage_off, src_host, bytes);
   const unsigned blocks = (unsigned)std::min<size_t>(1024, (bytes / 16 + 255) / 256 + 1);
+  FP_GEOM_LOG("staged_upload");
   hipLaunchKernelGGL(fp::staged_upload_kernel, dim3(blocks), dim3(256), 0, m->stream, m->host_stage_dev + stage_off, (unsigned char *)dst_dev, bytes);
   FP_HIP_OK(hipGetLastError());
   return 0;
@@ -1205,7 +1234,30 @@ static int ensure_window(fp_model *m, size_t total) {
   return 0;
 }
 
-static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W, int row0, int row1, int col0, int col1) {
+// the frame record of the model's current frame read whole: with the depth filter on the crops read `bilat`, which the caller fills
+static FrameRef whole_frame_record(const fp_model *m) {
+  FrameRef r{};   // no pitch, no window
+  r.rgb = m->rgb; r.depth = m->depth;
+  if (m->dfilt_on) { r.depth = m->bilat; r.raw = m->depth; r.ux1 = m->W; r.uy1 = m->H; }
+  return r;
+}
+// makes `want` the record the kernels read, unless it is already
+static int publish_record(fp_model *m, const FrameRef &want) {
+  if (same_record(m->frame_pub, want)) return 0;
+  // (a ring of pinned records: the asynchronous shard entry points return before the copy has run)
+  const unsigned k = m->frame_pub_count++ & 7;
+  FrameRef *slot = reinterpret_cast<FrameRef *>(m->frame_pinned + 64 * k);
+  *slot = want;
+  launch_window_fetch(m->stream, m->frame_pinned_dev + 64 * k, m->frame_dev, 64);   // [r6] 64 bytes by a kernel, not a copy command
+  FP_HIP_OK(hipGetLastError());
+  m->frame_pub = want;
+  return 0;
+}
+
+// filt (depth filter on, Track): the rectangle of the frame the call's depth_filter_rect launch fills and the crops may read; the rows /
+// columns uploaded hold every pixel within the filter's reach of it.  Null: the whole frame.
+static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W, int row0, int row1, int col0, int col1,
+                              const TrackWindow *filt) {
   Target *t = nullptr;
   if (check_frame_args(m, H, W, nullptr, &t)) return 1;
   FP_CHECK(rgb && depth, "[FoundationPose] Got INVALID rgb/depth ptr");
@@ -1224,6 +1276,7 @@ static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, i
     m->rgb = (const uint8_t *)rgb;
     m->depth = (const float *)depth;
     m->frame_partial = false;
+    row0 = 0; row1 = H; col0 = 0; col1 = W;
   } else {
     if (row1 < 0 || row1 > H) row1 = H;
     row0 = std::max(0, std::min(row0, row1));
@@ -1262,6 +1315,14 @@ static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, i
         rec.depth = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(dev_block) + 64 + rgb_bytes - (uintptr_t)(org * 4));
         rec.pitch = (int)cw;
         rec.wx0 = col0; rec.wx1 = col1; rec.wy0 = row0; rec.wy1 = row1;
+        if (m->dfilt_on) {
+          // the packed depth is the filter's input; its output goes to `bilat` under the same pitch and virtual origin, and the crops
+          // read that inside the filtered rectangle alone
+          rec.raw = rec.depth;
+          rec.ux0 = col0; rec.ux1 = col1; rec.uy0 = row0; rec.uy1 = row1;
+          rec.depth = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(m->bilat) - (uintptr_t)(org * 4));
+          if (filt) { rec.wx0 = filt->col0; rec.wx1 = filt->col1; rec.wy0 = filt->row0; rec.wy1 = filt->row1; }
+        }
         std::memcpy(m->win_stage, &rec, sizeof(rec));
         launch_window_fetch(m->stream, m->win_stage_dev, dev_block, total);
         FP_HIP_OK(hipGetLastError());
@@ -1289,17 +1350,21 @@ static int upload_frame_async(fp_model *m, const void *rgb, const void *depth, i
     m->rgb = m->rgb_own;
     m->depth = m->depth_own;
   }
-  if (m->frame_pub.rgb != m->rgb || m->frame_pub.depth != m->depth) {
-    // (a ring of pinned records: the asynchronous shard entry points return before the copy has run)
-    const unsigned k = m->frame_pub_count++ & 7;
-    FrameRef *slot = reinterpret_cast<FrameRef *>(m->frame_pinned + 64 * k);
-    *slot = FrameRef{};   // whole frame: no pitch, no window
-    slot->rgb = m->rgb; slot->depth = m->depth;
-    launch_window_fetch(m->stream, m->frame_pinned_dev + 64 * k, m->frame_dev, 64);   // [r6] 64 bytes by a kernel, not a copy command
-    FP_HIP_OK(hipGetLastError());
-    m->frame_pub = *slot;
+  FrameRef want = whole_frame_record(m);
+  if (m->dfilt_on) {
+    // the unfiltered depth exists where this call put it (a device frame: everywhere)
+    want.ux0 = col0; want.ux1 = col1; want.uy0 = row0; want.uy1 = row1;
+    if (filt) { want.wx0 = filt->col0; want.wx1 = filt->col1; want.wy0 = filt->row0; want.wy1 = filt->row1; }
   }
-  return 0;
+  return publish_record(m, want);
+}
+
+// stage operators on the uploaded frame: with the depth filter on they read D' of the whole frame (the last call may have been a Track,
+// which fills its window of `bilat` alone, or the option may have been switched since the upload)
+static int run_depth_filters(fp_model *m);
+static int stage_frame(fp_model *m) {
+  if (m->dfilt_on && run_depth_filters(m)) return 1;
+  return publish_record(m, whole_frame_record(m));
 }
 
 int fp_upload_frame(fp_model *m, const void *rgb, const void *depth, int memspace, int H, int W) try {
@@ -1315,7 +1380,8 @@ int fp_get_xyz_map(fp_model *m, float *xyz_host) try {
   FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
   size_t px = (size_t)m->H * m->W;
   if (!m->xyz && dev_alloc(&m->xyz, m->frame_cap * 3)) return 1;
-  launch_depth_to_xyz(m->stream, m->depth, m->H, m->W, m->K, m->xyz);
+  if (m->dfilt_on && run_depth_filters(m)) return 1;   // the map of D': what the networks see
+  launch_depth_to_xyz(m->stream, m->dfilt_on ? m->bilat : m->depth, m->H, m->W, m->K, m->xyz);
   FP_HIP_OK(hipMemcpyAsync(xyz_host, m->xyz, px * 12, hipMemcpyDeviceToHost, m->stream));
   FP_HIP_OK(hipStreamSynchronize(m->stream));
   return 0;
@@ -1445,7 +1511,7 @@ int fp_render_and_transform(fp_model *m, const char *target_name, const float *p
   FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
   Target *t = m->find(target_name ? target_name : "");
   FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
-  if (upload_poses(m, t, poses, N)) return 1;
+  if (stage_frame(m) || upload_poses(m, t, poses, N)) return 1;
   const size_t bytes = (size_t)N * FP_CROP_HW * FP_CROP_HW * 6 * sizeof(float);
   float *a = render_out, *b = transf_out;
   if (out_memspace == FP_HOST) {
@@ -1936,6 +2002,12 @@ int fp_register(fp_model *m, const uint8_t *rgb, const float *depth, const uint8
   return fp_register_ex(m, rgb, depth, mask, FP_HOST, H, W, target_name, refine_itr, out_pose);
 } FP_CATCH_INT
 
+// Track with the depth filter on: D' on the rectangle the frame record names, before anything reads it
+static void enqueue_depth_filter(fp_model *m) {
+  ProfScope ps(&m->prof, m->stream, "depth_filter_rect");
+  launch_depth_filter_rect(m->stream, m->frame_dev, m->H, m->W);
+}
+
 // why a Track that is starting leaves no fit record, unless it succeeds with the option on (fp_last_track_fit reports it)
 static const char *no_track_fit_because(const fp_model *m, int refine_itr) {
   return !m->fit_on ? "the last Track ran with the pose fit off (fp_set_pose_fit)"
@@ -1958,41 +2030,20 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
   if (fit && ensure_fit(m)) return 1;
   // a single refine iteration reads the frame only inside the observed-crop window of the hypothesis (ComputeCropWindowTF,
   // foundationpose_render.cpp:25-70, restated on the host in double with a margin): host frames upload just those rows
+  // (plan_track_window; with the depth filter on, a device frame is read inside the same window, and a host frame uploads the
+  // window grown by the filter's reach of 4 pixels: erode 2 + bilateral 2)
   int row0 = 0, row1 = -1, col0 = 0, col1 = -1;
-  if (memspace != FP_DEVICE && refine_itr == 1) {
-    const double r = (double)t->mesh.diameter * 1.2 / 2, tx = hyp_pose[12], ty = hyp_pose[13], tz = hyp_pose[14];
-    auto proj_v = [&](double x, double y, double z) {
-      const double q1 = m->K[3] * x + m->K[4] * y + m->K[5] * z, q2 = m->K[6] * x + m->K[7] * y + m->K[8] * z;
-      return q1 / q2;
-    };
-    auto proj_u = [&](double x, double y, double z) {
-      const double q0 = m->K[0] * x + m->K[1] * y + m->K[2] * z, q2 = m->K[6] * x + m->K[7] * y + m->K[8] * z;
-      return q0 / q2;
-    };
-    if (tz > 1e-6) {
-      const double v0 = proj_v(tx, ty, tz);
-      double rad = 0;
-      const double offs[4][2] = {{r, 0}, {-r, 0}, {0, r}, {0, -r}};
-      for (auto &o : offs) rad = std::max(rad, std::fabs(proj_v(tx + o[0], ty + o[1], tz) - v0));
-      // far outside [-H, 2H] (tiny tz, huge translation) the casts below would overflow: such a window either misses the frame
-      // (decided in double) or the whole frame is uploaded
-      if (std::isfinite(v0) && std::isfinite(rad) && rad < 4.0 * H) {
-        if (v0 + rad + 5 <= 0 || v0 - rad - 4 >= H) { row0 = 0; row1 = 0; }   // window outside the frame: nothing is read
-        else if (v0 > -(double)H && v0 < 2.0 * H) {
-          row0 = (int)std::floor(v0 - rad) - 4;
-          row1 = (int)std::ceil(v0 + rad) + 5;
-          // the window is a square of the same radius around (u0, v0): its columns, with the same margin
-          const double u0 = proj_u(tx, ty, tz);
-          if (std::isfinite(u0) && u0 > -(double)W && u0 < 2.0 * W) {
-            col0 = (int)std::floor(u0 - rad) - 4;
-            col1 = (int)std::ceil(u0 + rad) + 5;
-            if (col1 <= 0 || col0 >= W) { col0 = 0; col1 = -1; }   // (a window beside the frame: keep whole rows)
-          }
-        }
-      }
+  TrackWindow filt = {TRACK_WINDOW_WHOLE, 0, H, 0, W};
+  if (refine_itr == 1 && (memspace != FP_DEVICE || m->dfilt_on)) {
+    filt = plan_track_window(m->K, t->mesh.diameter, hyp_pose, H, W, 0);
+    const TrackWindow up = m->dfilt_on ? plan_track_window(m->K, t->mesh.diameter, hyp_pose, H, W, 4) : filt;
+    if (up.kind == TRACK_WINDOW_OUTSIDE) { row0 = 0; row1 = 0; }
+    else if (up.kind != TRACK_WINDOW_WHOLE) {
+      row0 = up.row0; row1 = up.row1;
+      if (up.kind == TRACK_WINDOW_RECT) { col0 = up.col0; col1 = up.col1; }
     }
   }
-  if (upload_frame_async(m, rgb, depth, memspace, H, W, row0, row1, col0, col1)) return 1;
+  if (upload_frame_async(m, rgb, depth, memspace, H, W, row0, row1, col0, col1, m->dfilt_on && filt.kind != TRACK_WINDOW_WHOLE ? &filt : nullptr)) return 1;
   // (fine-grained: the done flag is read while the graph is still running)
   if (!m->track_io) FP_HIP_OK(pinned_mapped_alloc(&m->track_io, &m->track_io_dev, 48 * sizeof(float), hipHostMallocCoherent));
   m->track_flag_armed = false;
@@ -2011,6 +2062,7 @@ static int track_submit_impl(fp_model *m, const void *rgb, const void *depth, in
   *flag = 0u;
   const bool armed = !m->prof.on && !m->digests && refiner_fuses_pose(m->refiner);
   if (run_graphed(m, m->tg, t, H, W, refine_itr, 1, graphable(m, refine_itr), [&]() {
+        if (m->dfilt_on) enqueue_depth_filter(m);   // the rectangle comes from the frame record: the captured launch serves every pose
         for (int it = 0; it < refine_itr; it++) {
           const bool last = it == refine_itr - 1;
           if (refine_iteration(m, t, 1, false, it == 0 ? m->track_io_dev : nullptr, last ? m->track_io_dev + 16 : nullptr,
@@ -2132,6 +2184,7 @@ int fp_track_multi(fp_model *m, const void *rgb, const void *depth, int memspace
   float *pin_in = m->multi_io_dev, *pin_out = m->multi_io_dev + 64 * 16;
   const size_t IMG = FP_NN_IN_IMG_HALFS;
   if (run_graphed(m, m->mg, targets[0], H, W, refine_itr, K, graphable(m, refine_itr), [&]() {
+        if (m->dfilt_on) enqueue_depth_filter(m);   // (the whole frame)
         for (int it = 0; it < refine_itr; it++) {
           for (const auto &[o, n] : groups)
             if (render_and_crop(m, targets[o], n, 1.2f, nn_mode(m), m->nn_in + (size_t)o * IMG, m->nn_in + (size_t)(K + o) * IMG, nullptr, nullptr, n,
@@ -2191,6 +2244,22 @@ int fp_get_pose_fit(const fp_model *m, int *on, float *tol_m) try {
   if (tol_m) *tol_m = m->fit_tol_m;
   return 0;
 } FP_CATCH_INT
+
+// ---- depth filter
+int fp_set_depth_filter(fp_model *m, int on) try {
+  LifeExclusive life;   // destroys the captured graphs: not while another thread is inside a call
+  FP_CHECK(m != nullptr, "[FoundationPose] null model");
+  DeviceScope on_device(m->device);
+  if ((on != 0) == m->dfilt_on) return 0;
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  m->dfilt_on = on != 0;
+  invalidate_graphs(m);   // the filter launch is part of the captured Track bodies
+  return 0;
+} FP_CATCH_INT
+int fp_get_depth_filter(const fp_model *m) {
+  if (!m) { set_error("[FoundationPose] null model"); return -1; }
+  return m->dfilt_on ? 1 : 0;
+}
 
 // ---- vertex colours (DESIGN.md sections 3, 4.1): the target's colour source is its packed colour array when it has one
 int fp_set_vertex_colors(fp_model *m, const char *target_name, const uint8_t *colors, int num_vertices) try {
@@ -2259,7 +2328,7 @@ int fp_pose_fit_eval(fp_model *m, const char *target_name, const float *poses, i
   FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
   Target *t = m->find(target_name ? target_name : "");
   FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
-  if (ensure_fit(m) || upload_poses(m, t, poses, N)) return 1;
+  if (ensure_fit(m) || stage_frame(m) || upload_poses(m, t, poses, N)) return 1;
   const size_t half = (size_t)N * FP_NN_IN_IMG_HALFS;
   if (render_and_crop(m, t, N, crop_ratio, nn_mode(m), m->nn_in, m->nn_in + half, nullptr, nullptr)) return 1;
   const float tol_n = fit_tol_n(tol_m, t->mesh.diameter);

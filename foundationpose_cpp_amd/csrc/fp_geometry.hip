@@ -175,6 +175,7 @@ __global__ void pose_setup_kernel(const float *__restrict__ poses, int N, K9 K, 
 
 void launch_pose_setup(hipStream_t s, const float *poses_dev, int N, const float *K9_host, int img_h, int img_w,
                        float crop_ratio, float diameter, PoseRec *recs) {
+  FP_GEOM_LOG("pose_setup");
   K9 K;
   for (int i = 0; i < 9; i++) K.k[i] = K9_host[i];
   hipLaunchKernelGGL(pose_setup_kernel, dim3((N + 63) / 64), dim3(64), 0, s, poses_dev, N, K, img_h, img_w,
@@ -270,6 +271,7 @@ __global__ void vertex_kernel(const float *__restrict__ verts, const float *__re
 float4 *g_vertex_dbg = nullptr;  // race hunt (tools/dbg_concurrent3.py): launches with N == 64 fill it
 #endif
 void launch_vertex(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int N, float4 *clip, float4 *attr, bool fmad) {
+  FP_GEOM_LOG("vertex");
   float4 *dbg = nullptr;
 #ifdef FP_TEST_HOOKS
   if (g_vertex_dbg && N == 64) dbg = g_vertex_dbg;
@@ -283,6 +285,7 @@ void launch_vertex(hipStream_t s, const DeviceMesh &m, const PoseRec *recs, int 
 // pose set-up + vertex stage in one launch: recs[0..N) are WRITTEN here (by the thread of vertex 0 of each hypothesis)
 void launch_setup_vertex(hipStream_t s, const DeviceMesh &m, const float *poses_dev, int N, const float *K9_host, int img_h, int img_w,
                          float crop_ratio, float diameter, PoseRec *recs, float4 *clip, float4 *attr, bool fmad) {
+  FP_GEOM_LOG("setup_vertex");
   PoseSetupArgs sa;
   sa.poses = poses_dev;
   for (int i = 0; i < 9; i++) sa.K.k[i] = K9_host[i];
@@ -518,6 +521,7 @@ __global__ __launch_bounds__(256) void tri_rows_kernel(const int32_t *__restrict
   rows_all[(size_t)n * F + f] = out;
 }
 void launch_tri_rows(hipStream_t s, const DeviceMesh &m, int N, const float4 *clip, unsigned *rows) {
+  FP_GEOM_LOG("tri_rows");
   if (m.F <= 0 || N <= 0) return;
   hipLaunchKernelGGL(tri_rows_kernel, dim3((m.F + 255) / 256, N), dim3(256), 0, s, m.faces, m.F, m.V, clip, rows);
 }
@@ -822,6 +826,7 @@ template <class F> static bool with_bool(bool b, F &&f) { return b ? f(std::true
 bool launch_raster_shade(hipStream_t s, const RenderPlan &plan, const DeviceMesh &m, const PoseRec *recs, int N, const float4 *clip,
                          const float4 *attr, OutMode mode, void *out, int32_t *tri_id_dbg, float *rast_dbg, bool fmad,
                          const unsigned *tri_rows) {
+  FP_GEOM_LOG("raster_shade");
   auto with_mode = [&](auto mode_c) {
     return with_bool(fmad, [&](auto fmad_c) {
       return with_bool(m.vcol != nullptr, [&](auto vcol_c) {
@@ -964,6 +969,7 @@ __global__ __launch_bounds__(1024) void sampler_pose_kernel(int *__restrict__ st
 
 void launch_sampler(hipStream_t s, const float *filtered_depth, const uint8_t *mask_dev, int H, int W, float min_depth,
                     const float *K9_host, const float *grid_dev, int first, int N, int *state, float *vals, float *poses) {
+  FP_GEOM_LOG("sampler");
   // `state` was initialised when it was allocated and every sampler_pose_kernel launch resets it for the next frame
   hipLaunchKernelGGL(sampler_scan_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, filtered_depth, mask_dev, H, W, min_depth,
                      state, vals);
@@ -1092,6 +1098,7 @@ __global__ __launch_bounds__(256) void vertex_crop_kernel(const float *__restric
 void launch_setup_vertex_crop(hipStream_t s, const DeviceMesh &m, const float *poses_dev, int N, const float *K9_host, int img_h, int img_w,
                               float crop_ratio, float diameter, PoseRec *recs, float4 *clip, float4 *attr, bool fmad, const FrameRef *frame,
                               int n_crop, OutMode mode, void *out_b, unsigned *tri_rows) {
+  FP_GEOM_LOG("setup_vertex_crop");
   PoseSetupArgs sa;
   sa.poses = poses_dev;
   for (int i = 0; i < 9; i++) sa.K.k[i] = K9_host[i];
@@ -1107,6 +1114,7 @@ void launch_setup_vertex_crop(hipStream_t s, const DeviceMesh &m, const float *p
 
 void launch_crop(hipStream_t s, const FrameRef *frame, int H, int W, const float *K, const PoseRec *recs,
                  int N, float diameter, OutMode mode, void *out) {
+  FP_GEOM_LOG("crop");
   dim3 grid((CROP * CROP + 255) / 256, N), block(256);
   float downscale = diameter / 2;
   if (mode == OUT_F32X6)
@@ -1142,59 +1150,63 @@ __global__ __launch_bounds__(256) void window_fetch_kernel(const uint4 *__restri
   for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) dst[i] = src_host[i];
 }
 void launch_window_fetch(hipStream_t s, const void *src_host_mapped, void *dst, size_t bytes) {
+  FP_GEOM_LOG("window_fetch");
   const unsigned n16 = (unsigned)((bytes + 15) / 16);
   const unsigned blocks = std::min(256u, (n16 + 255) / 256);
   hipLaunchKernelGGL(window_fetch_kernel, dim3(blocks), dim3(256), 0, s, (const uint4 *)src_host_mapped, (uint4 *)dst, n16);
 }
 
 void launch_depth_to_xyz(hipStream_t s, const float *depth, int H, int W, const float *K, float *xyz) {
+  FP_GEOM_LOG("depth_to_xyz");
   hipLaunchKernelGGL(depth_to_xyz_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, depth, H, W, K[0], K[4], K[2],
                      K[5], xyz);
 }
 
-__global__ void erode_kernel(const float *__restrict__ depth, float *__restrict__ out, int H, int W) {
+// erode_depth / bilateral_filter_depth of ONE pixel (w, h) of an H x W frame; tap(u, v) returns the input at a pixel inside the frame
+// (a neighbour outside the frame is skipped by its coordinates, never read).  The whole-frame kernels and the fused rectangle kernel
+// below call these same two functions, so their results are equal bit for bit (this file is built with -ffp-contract=off): u outer,
+// v inner, the same expf.
+template <class Tap>
+__device__ __forceinline__ float erode_px(int w, int h, int H, int W, Tap tap) {
   const int radius = 2;
   const float depth_diff_thres = 0.001f, ratio_thres = 0.8f, zfar = 100.0f;
-  int w = blockIdx.x * blockDim.x + threadIdx.x, h = blockIdx.y * blockDim.y + threadIdx.y;
-  if (w >= W || h >= H) return;
-  float d_ori = depth[h * W + w];
-  if (d_ori < 0.1f || d_ori >= zfar) { out[h * W + w] = 0.0f; return; }
+  float d_ori = tap(w, h);
+  if (d_ori < 0.1f || d_ori >= zfar) return 0.0f;
   float bad = 0.0f, total = 0.0f;
   for (int u = w - radius; u <= w + radius; u++) {
     if (u < 0 || u >= W) continue;
     for (int v = h - radius; v <= h + radius; v++) {
       if (v < 0 || v >= H) continue;
-      float cur = depth[v * W + u];
+      float cur = tap(u, v);
       total += 1.0f;
       if (cur < 0.1f || cur >= zfar || fabsf(cur - d_ori) > depth_diff_thres) bad += 1.0f;
     }
   }
-  out[h * W + w] = ((bad / total) > ratio_thres) ? 0.0f : d_ori;
+  return ((bad / total) > ratio_thres) ? 0.0f : d_ori;
 }
 
-__global__ void bilateral_kernel(const float *__restrict__ depth, float *__restrict__ out, int H, int W) {
+template <class Tap>
+__device__ __forceinline__ float bilateral_px(int w, int h, int H, int W, Tap tap) {
   const int radius = 2;
   const float zfar = 100.0f, sigmaD = 2.0f, sigmaR = 100000.0f;
-  int w = blockIdx.x * blockDim.x + threadIdx.x, h = blockIdx.y * blockDim.y + threadIdx.y;
-  if (w >= W || h >= H) return;
   float mean = 0.0f;
   int nvalid = 0;
   for (int u = w - radius; u <= w + radius; u++) {
     if (u < 0 || u >= W) continue;
     for (int v = h - radius; v <= h + radius; v++) {
       if (v < 0 || v >= H) continue;
-      float cur = depth[v * W + u];
+      float cur = tap(u, v);
       if (cur >= 0.1f && cur < zfar) { nvalid++; mean += cur; }
     }
   }
-  if (nvalid == 0) { out[h * W + w] = 0.0f; return; }
+  if (nvalid == 0) return 0.0f;
   mean /= (float)nvalid;
-  float dc = depth[h * W + w], sw = 0.0f, sum = 0.0f;
+  float dc = tap(w, h), sw = 0.0f, sum = 0.0f;
   for (int u = w - radius; u <= w + radius; u++) {
     if (u < 0 || u >= W) continue;
     for (int v = h - radius; v <= h + radius; v++) {
       if (v < 0 || v >= H) continue;
-      float cur = depth[v * W + u];
+      float cur = tap(u, v);
       if (cur >= 0.1f && cur < zfar && fabsf(cur - mean) < 0.01f) {
         float wgt = expf(-((float)((u - w) * (u - w) + (v - h) * (v - h))) / (2.0f * sigmaD * sigmaD) -
                          (dc - cur) * (dc - cur) / (2.0f * sigmaR * sigmaR));
@@ -1203,13 +1215,79 @@ __global__ void bilateral_kernel(const float *__restrict__ depth, float *__restr
       }
     }
   }
-  out[h * W + w] = (sw > 0.0f && nvalid > 0) ? sum / sw : 0.0f;
+  return (sw > 0.0f && nvalid > 0) ? sum / sw : 0.0f;
+}
+
+__global__ void erode_kernel(const float *__restrict__ depth, float *__restrict__ out, int H, int W) {
+  int w = blockIdx.x * blockDim.x + threadIdx.x, h = blockIdx.y * blockDim.y + threadIdx.y;
+  if (w >= W || h >= H) return;
+  out[h * W + w] = erode_px(w, h, H, W, [&](int u, int v) { return depth[v * W + u]; });
+}
+
+__global__ void bilateral_kernel(const float *__restrict__ depth, float *__restrict__ out, int H, int W) {
+  int w = blockIdx.x * blockDim.x + threadIdx.x, h = blockIdx.y * blockDim.y + threadIdx.y;
+  if (w >= W || h >= H) return;
+  out[h * W + w] = bilateral_px(w, h, H, W, [&](int u, int v) { return depth[v * W + u]; });
+}
+
+// The depth filter of a Track (fp_set_depth_filter): D' = bilateral(erode(raw)) on the rectangle the frame
+// record names, in one launch.  A workgroup walks tiles of 32 x 16 output pixels: it stages the tile plus a 4-pixel apron of raw depth
+// in LDS (40 x 24 floats: every raw pixel is fetched from memory once per tile), erodes the tile plus a 2-pixel apron into LDS
+// (36 x 20) and writes the bilateral of the tile; the 25 + 25 + 25 taps of a pixel come from LDS, 6.6 KB per workgroup.  Rows of
+// 40 / 36 floats read at consecutive lanes: no bank conflicts worth a padding column.  The rectangle, both addresses and the pitch
+// are read from the record, and the grid is fixed by the frame size (tiles are strided over it), so a captured launch serves every
+// rectangle of that frame size.  A staged pixel outside the frame is never used (erode_px / bilateral_px skip it by its coordinates);
+// one inside the frame but outside [ux0, ux1) x [uy0, uy1) would be a host-side error and reads 0 instead of foreign memory.
+__global__ __launch_bounds__(256) void depth_filter_rect_kernel(const FrameRef *__restrict__ frame, int H, int W) {
+  constexpr int TW = DEPTH_FILTER_TILE_W, TH = DEPTH_FILTER_TILE_H, RW = TW + 8, RH = TH + 8, EW = TW + 4, EH = TH + 4;
+  __shared__ float raw_s[RH * RW];
+  __shared__ float ero_s[EH * EW];
+  const float *__restrict__ raw = frame->raw;
+  float *__restrict__ out = const_cast<float *>(frame->depth);
+  const int P = frame->pitch > 0 ? frame->pitch : W;
+  const int x0 = max(frame->wx0, 0), y0 = max(frame->wy0, 0), x1 = min(frame->wx1, W), y1 = min(frame->wy1, H);
+  const int ux0 = frame->ux0, uy0 = frame->uy0, ux1 = frame->ux1, uy1 = frame->uy1;
+  if (raw == nullptr || out == nullptr || x1 <= x0 || y1 <= y0) return;   // (uniform: no barrier is skipped by part of a workgroup)
+  const int tiles_x = (x1 - x0 + TW - 1) / TW, tiles = tiles_x * ((y1 - y0 + TH - 1) / TH);
+  const int tid = threadIdx.x;
+  for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int ty = t / tiles_x, bx = x0 + (t - ty * tiles_x) * TW, by = y0 + ty * TH;
+    for (int i = tid; i < RH * RW; i += 256) {
+      const int ry = i / RW, gx = bx - 4 + (i - ry * RW), gy = by - 4 + ry;
+      float v = 0.0f;
+      if (gx >= 0 && gx < W && gy >= 0 && gy < H && gx >= ux0 && gx < ux1 && gy >= uy0 && gy < uy1) v = raw[(long long)gy * P + gx];
+      raw_s[i] = v;
+    }
+    __syncthreads();
+    for (int i = tid; i < EH * EW; i += 256) {
+      const int ey = i / EW, gx = bx - 2 + (i - ey * EW), gy = by - 2 + ey;
+      float v = 0.0f;
+      if (gx >= 0 && gx < W && gy >= 0 && gy < H)
+        v = erode_px(gx, gy, H, W, [&](int u, int vv) { return raw_s[(vv - (by - 4)) * RW + (u - (bx - 4))]; });
+      ero_s[i] = v;
+    }
+    __syncthreads();
+    for (int i = tid; i < TH * TW; i += 256) {
+      const int oy = i / TW, gx = bx + (i - oy * TW), gy = by + oy;
+      if (gx < x1 && gy < y1)
+        out[(long long)gy * P + gx] = bilateral_px(gx, gy, H, W, [&](int u, int vv) { return ero_s[(vv - (by - 2)) * EW + (u - (bx - 2))]; });
+    }
+    __syncthreads();   // the next tile overwrites both arrays
+  }
+}
+
+void launch_depth_filter_rect(hipStream_t s, const FrameRef *frame_dev, int H, int W) {
+  FP_GEOM_LOG("depth_filter_rect");
+  const int tiles = ((W + DEPTH_FILTER_TILE_W - 1) / DEPTH_FILTER_TILE_W) * ((H + DEPTH_FILTER_TILE_H - 1) / DEPTH_FILTER_TILE_H);
+  hipLaunchKernelGGL(depth_filter_rect_kernel, dim3(std::min(256, std::max(1, tiles))), dim3(256), 0, s, frame_dev, H, W);
 }
 
 void launch_erode(hipStream_t s, const float *depth, float *out, int H, int W) {
+  FP_GEOM_LOG("erode");
   hipLaunchKernelGGL(erode_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, s, depth, out, H, W);
 }
 void launch_bilateral(hipStream_t s, const float *depth, float *out, int H, int W) {
+  FP_GEOM_LOG("bilateral");
   hipLaunchKernelGGL(bilateral_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, s, depth, out, H, W);
 }
 
@@ -1226,6 +1304,7 @@ __global__ void pose_update_kernel(float *poses, const float *__restrict__ trans
 
 void launch_pose_update(hipStream_t s, float *poses, const float *trans, const float *rot, int N, float diameter, const float *poses_in,
                         float *extra_out) {
+  FP_GEOM_LOG("pose_update");
   hipLaunchKernelGGL(pose_update_kernel, dim3((N + 63) / 64), dim3(64), 0, s, poses, trans, rot, N, diameter, poses_in ? poses_in : poses,
                      extra_out);
 }
@@ -1264,6 +1343,7 @@ __global__ void argmax_kernel(const float *__restrict__ scores, int N, int *__re
 }
 
 void launch_argmax(hipStream_t s, const float *scores, int N, int *index_dev, const float *poses, float *best_pose_dev) {
+  FP_GEOM_LOG("argmax");
   hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(256), 0, s, scores, N, index_dev, poses, best_pose_dev);
 }
 
@@ -1280,6 +1360,7 @@ __global__ void pack_f32x6_kernel(const float *__restrict__ in, uint4 *__restric
 }
 
 void launch_pack_f32x6(hipStream_t s, const float *in, void *out, size_t pixels, OutMode mode) {
+  FP_GEOM_LOG("pack_f32x6");
   const dim3 grid((unsigned)((pixels + 255) / 256));
   if (mode == OUT_BF16X8) hipLaunchKernelGGL(pack_f32x6_kernel<OUT_BF16X8>, grid, dim3(256), 0, s, in, reinterpret_cast<uint4 *>(out), pixels);
   else hipLaunchKernelGGL(pack_f32x6_kernel<OUT_F16X8>, grid, dim3(256), 0, s, in, reinterpret_cast<uint4 *>(out), pixels);
@@ -1364,10 +1445,50 @@ int pose_fit_split(int N) {
 }
 void launch_pose_fit(hipStream_t s, const void *img_a, size_t a_stride_halfs, const void *img_b, size_t b_stride_halfs, int N,
                      const PoseFitTol &tol, OutMode mode, unsigned long long *acc, PoseFitRec *out) {
+  FP_GEOM_LOG("pose_fit");
   const dim3 grid(pose_fit_split(N), N);
   const uint4 *a = reinterpret_cast<const uint4 *>(img_a), *b = reinterpret_cast<const uint4 *>(img_b);
   if (mode == OUT_BF16X8) hipLaunchKernelGGL(pose_fit_kernel<OUT_BF16X8>, grid, dim3(256), 0, s, a, a_stride_halfs / 8, b, b_stride_halfs / 8, tol, acc, out);
   else hipLaunchKernelGGL(pose_fit_kernel<OUT_F16X8>, grid, dim3(256), 0, s, a, a_stride_halfs / 8, b, b_stride_halfs / 8, tol, acc, out);
+}
+
+
+TrackWindow plan_track_window(const float K[9], float diameter, const float pose[16], int H, int W, int reach) {
+  TrackWindow out = {TRACK_WINDOW_WHOLE, 0, H, 0, W};
+  const double r = (double)diameter * 1.2 / 2, tx = pose[12], ty = pose[13], tz = pose[14];
+  auto proj_v = [&](double x, double y, double z) {
+    const double q1 = K[3] * x + K[4] * y + K[5] * z, q2 = K[6] * x + K[7] * y + K[8] * z;
+    return q1 / q2;
+  };
+  auto proj_u = [&](double x, double y, double z) {
+    const double q0 = K[0] * x + K[1] * y + K[2] * z, q2 = K[6] * x + K[7] * y + K[8] * z;
+    return q0 / q2;
+  };
+  if (!(tz > 1e-6)) return out;
+  const double v0 = proj_v(tx, ty, tz);
+  double rad = 0;
+  const double offs[4][2] = {{r, 0}, {-r, 0}, {0, r}, {0, -r}};
+  for (auto &o : offs) rad = std::max(rad, std::fabs(proj_v(tx + o[0], ty + o[1], tz) - v0));
+  // far outside [-H, 2H] (tiny tz, huge translation) the casts below would overflow: such a window either misses the frame
+  // (decided in double) or the whole frame is taken
+  if (!(std::isfinite(v0) && std::isfinite(rad) && rad < 4.0 * H)) return out;
+  if (v0 + rad + 5 <= 0 || v0 - rad - 4 >= H) return TrackWindow{TRACK_WINDOW_OUTSIDE, 0, 0, 0, 0};   // nothing is read
+  if (!(v0 > -(double)H && v0 < 2.0 * H)) return out;
+  int row0 = (int)std::floor(v0 - rad) - 4, row1 = (int)std::ceil(v0 + rad) + 5, col0 = 0, col1 = W;
+  out.kind = TRACK_WINDOW_ROWS;
+  // the window is a square of the same radius around (u0, v0): its columns, with the same margin
+  const double u0 = proj_u(tx, ty, tz);
+  if (std::isfinite(u0) && u0 > -(double)W && u0 < 2.0 * W) {
+    const int c0 = (int)std::floor(u0 - rad) - 4, c1 = (int)std::ceil(u0 + rad) + 5;
+    if (!(c1 <= 0 || c0 >= W)) { out.kind = TRACK_WINDOW_RECT; col0 = c0 - reach; col1 = c1 + reach; }   // (a window beside the frame: keep whole rows)
+  }
+  row0 -= reach; row1 += reach;
+  if (row1 < 0 || row1 > H) row1 = H;
+  row0 = std::max(0, std::min(row0, row1));
+  if (col1 < 0 || col1 > W) col1 = W;
+  col0 = std::max(0, std::min(col0, col1));
+  out.row0 = row0; out.row1 = row1; out.col0 = col0; out.col1 = col1;
+  return out;
 }
 
 }  // namespace fp

@@ -117,6 +117,15 @@ struct ProfScope {
 // geometry kernels (fp_geometry.hip)
 // ---------------------------------------------------------------------------------------------
 
+// test build: the launch log of fp_nn.hip (fpt_launch_log_*) armed with 2 also records every launch outside the networks -- frame
+// upload, record publication, depth filters, sampler, render, crop, pose fit -- with net = -1, for tests that count a call's launches
+#ifdef FP_TEST_HOOKS
+void log_geometry_launch(const char *name);
+#define FP_GEOM_LOG(name) fp::log_geometry_launch(name)
+#else
+#define FP_GEOM_LOG(name) ((void)0)
+#endif
+
 // Per-hypothesis record produced by the pose-setup kernel; everything the reference computes on the host per
 // pose (ComputeCropWindowTF, ConstructBBox2D, ProjectMatrixFromIntrinsics, foundationpose_render.cpp:25-186,590).
 struct PoseRec {
@@ -242,7 +251,32 @@ struct FrameRef {
   const float *depth;
   int pitch = 0;
   int wx0 = 0, wy0 = 0, wx1 = 0x7fffffff, wy1 = 0x7fffffff;
+  // depth filter (fp_set_depth_filter; unused while the option is off): `depth` is then a model-owned buffer
+  // that depth_filter_rect_kernel fills inside [wx0, wx1) x [wy0, wy1) from the unfiltered depth `raw`, which is addressed like
+  // `depth` (same pitch, same virtual origin) and exists inside [ux0, ux1) x [uy0, uy1)
+  const float *raw = nullptr;
+  int ux0 = 0, uy0 = 0, ux1 = 0, uy1 = 0;
 };
+static_assert(sizeof(FrameRef) <= 64, "a frame record is one 64-byte slot of the record ring and the head of the window block");
+inline bool same_record(const FrameRef &a, const FrameRef &b) {
+  return a.rgb == b.rgb && a.depth == b.depth && a.pitch == b.pitch && a.wx0 == b.wx0 && a.wy0 == b.wy0 && a.wx1 == b.wx1 && a.wy1 == b.wy1 &&
+         a.raw == b.raw && a.ux0 == b.ux0 && a.uy0 == b.uy0 && a.ux1 == b.ux1 && a.uy1 == b.uy1;
+}
+// The window of the frame a Track with one refine iteration reads (DESIGN.md sections 4.2, 4.7): ComputeCropWindowTF
+// (foundationpose_render.cpp:25-70) restated on the host in double with a margin, grown by `reach` pixels on every side (the depth
+// filter reads 4 pixels around every pixel the crop may read) and clamped to the frame.  A pure host function like plan_render
+// (the test build's fpt_plan_track_window asks it without a GPU); WHICH outcome it is never depends on reach.
+enum TrackWindowKind { TRACK_WINDOW_WHOLE = 0, TRACK_WINDOW_OUTSIDE = 1, TRACK_WINDOW_ROWS = 2, TRACK_WINDOW_RECT = 3 };
+struct TrackWindow {
+  TrackWindowKind kind;        // WHOLE: no estimate, the whole frame | OUTSIDE: the crop window misses the frame, nothing is read
+  int row0, row1, col0, col1;  // ROWS: rows [row0, row1) of every column | RECT: those rows of columns [col0, col1)
+};
+TrackWindow plan_track_window(const float K[9], float diameter, const float pose[16], int H, int W, int reach);
+// depth filter of a rectangle in ONE launch: D' = bilateral(erode(raw)) inside the record's window (clamped to the frame), written to
+// the record's `depth` -- the same values, bit for bit, as launch_erode + launch_bilateral give there.  Every argument that changes
+// with the pose comes from the record in device memory: the launch may be captured and replayed for any window of an H x W frame.
+constexpr int DEPTH_FILTER_TILE_W = 32, DEPTH_FILTER_TILE_H = 16;
+void launch_depth_filter_rect(hipStream_t s, const FrameRef *frame_dev, int H, int W);
 void launch_crop(hipStream_t s, const FrameRef *frame_dev, int H, int W, const float *K9_host,
                  const PoseRec *recs, int N, float diameter, OutMode mode, void *out);
 void launch_depth_to_xyz(hipStream_t s, const float *depth, int H, int W, const float *K9_host, float *xyz);

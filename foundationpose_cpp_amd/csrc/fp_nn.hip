@@ -1768,8 +1768,14 @@ struct LaunchRec {
   int pe;               // the launch adds the positional table in its epilogue
   char name[80];        // "tag/kernel" as the profiler names it
 };
-static bool g_launch_log_on = false;
+static int g_launch_log_on = 0;   // 1: the networks' launches, 2: also the launches outside the networks (log_geometry_launch)
 static std::vector<LaunchRec> g_launch_log;
+void log_geometry_launch(const char *name) {
+  if (g_launch_log_on != 2) return;
+  LaunchRec r{-1, -1, 0, 0, 0, 1, 0, {}};
+  std::snprintf(r.name, sizeof(r.name), "%s", name);
+  g_launch_log.push_back(r);
+}
 // Plan-only mode (fpt_plan_forward): the host side of a forward pass runs and the launch log records what it would launch, but no
 // network kernel is issued -- FP_LAUNCH / FP_LAUNCH_RAW do nothing.  The schedule is decided exactly as in a real call.
 static bool g_plan_only = false;

@@ -99,7 +99,7 @@ int fpt_tap_window(int img0, int nimg) {
 // out as ints {net, prec, side, m_begin, M, ksplit, pe} and its "tag/kernel" name (name_cap bytes, NUL-terminated)
 void fpt_launch_log_arm(int on) {
   if (on) fp::g_launch_log.clear();
-  fp::g_launch_log_on = on != 0;
+  fp::g_launch_log_on = on == 2 ? 2 : on != 0;   // 2: with the launches outside the networks (net = -1)
 }
 int fpt_launch_log_count() { return (int)fp::g_launch_log.size(); }
 int fpt_launch_log_get(int i, int *fields7, char *name, int name_cap) {
@@ -184,6 +184,16 @@ int fpt_plan_heads(int pass, int N, int dt, int fuse_offer, int *fields18, int *
   std::memcpy(tail3, t, sizeof(t));
   return 0;
 }
+// HOST-ONLY (no HIP call: runs without a GPU, tests/test_depth_filter_cpu.py): plan_track_window (fp_geometry.hip) of n poses.
+// K9 row-major intrinsics, poses16 [n][16] column-major -> out5 [n][5] = {kind (TrackWindowKind), row0, row1, col0, col1}
+void fpt_plan_track_window(const float *K9, float diameter, const float *poses16, int H, int W, int reach, int *out5, int n) {
+  for (int i = 0; i < n; i++) {
+    const fp::TrackWindow w = fp::plan_track_window(K9, diameter, poses16 + (size_t)i * 16, H, W, reach);
+    const int f[5] = {w.kind, w.row0, w.row1, w.col0, w.col1};
+    for (int k = 0; k < 5; k++) out5[(size_t)i * 5 + k] = f[k];
+  }
+}
+void fpt_depth_filter_tile(int *tile_w, int *tile_h) { *tile_w = fp::DEPTH_FILTER_TILE_W; *tile_h = fp::DEPTH_FILTER_TILE_H; }
 void fpt_set_conv_variant(int v) { fp::g_conv_variant = v; }
 void fpt_set_i8_stream(int v) { fp::g_i8_stream = v; }
 void fpt_set_q8_blocks(int v) { fp::g_q8_blocks = v & fp::Q8_BLOCKS_ALL; }   // [r6] stage mask of 8-bit networks loaded from now on (tools/q8_blocks.py)

@@ -186,6 +186,10 @@ public:
   // the C-ABI handle: options the reference does not have (fp_set_precision, fp_calibrate_fp8, fp_set_float_model, the hypothesis-
   // shard entry points ...) are reached through it: `auto *amd = dynamic_cast<detection_6d::FoundationPoseAmd *>(model.get());`
   fp_model *handle() { return h_; }
+  // depth filter (new; foundationpose_amd.h "depth filter"): Register and Track read bilateral(erode(depth)) like FoundationPose as
+  // published; default off = the reference's behaviour
+  bool SetDepthFilter(bool on) { return fp_set_depth_filter(h_, on ? 1 : 0) == 0; }
+  bool DepthFilter() const { return fp_get_depth_filter(h_) == 1; }
 
 private:
   fp_model *h_ = nullptr;

@@ -142,7 +142,8 @@ int fp_track_ex(fp_model *m, const void *rgb, const void *depth, int memspace, i
  * 0 (no valid depth, outside the frame and more than two diameters away all read 0).  With d = observed z - rendered z (one f32
  * subtraction) and tol_n = (float)tol_m / ((float)diameter / 2), an observed pixel is an INLIER when |d| <= tol_n, in FRONT when
  * d < -tol_n (something nearer than the model: an occluder) and BEHIND when d > tol_n (the surface is not where the model says).
- * The record is bit-reproducible: the same frame and pose give the same record on every call. */
+ * The record is bit-reproducible: the same frame and pose give the same record on every call.  It is computed from the crops the
+ * networks are fed: with fp_set_depth_filter on, the observed z is that of the filtered depth. */
 typedef struct fp_pose_fit {
   int32_t n_model, n_observed, n_inlier, n_front, n_behind; /* n_observed == n_inlier + n_front + n_behind */
   int32_t reserved;
@@ -182,6 +183,25 @@ int fp_pose_fit_eval(fp_model *m, const char *target_name, const float *poses, i
 int fp_set_vertex_colors(fp_model *m, const char *target_name, const uint8_t *colors, int num_vertices);
 /* FP_COLOR_TEXTURE / FP_COLOR_VERTEX, or a negative value on an unknown target */
 int fp_get_color_source(const fp_model *m, const char *target_name);
+
+/* ---- depth filter: what FoundationPose as published feeds its networks (new; the reference filters for the sampler only) -----
+ * Default off: exactly the behaviour without the option.  With the option on, every depth value a crop or warp reads is taken from
+ * D' = bilateral(erode(D)) of the current frame instead of D: erode with radius 2, difference 0.001 m, ratio 0.8, zfar 100; bilateral
+ * with radius 2, sigmaD 2, sigmaR 1e5 and |d - mean| < 0.01 -- the sampler's constants, so D' is the array fp_filter_depth returns as
+ * bilateral_out, frame borders included (a neighbour outside the frame is skipped, not read as zero).  The caller's depth is never
+ * modified, FP_DEVICE frames included.  RGB, the rendered half, triangle ids and the crop window transform do not change.
+ * Applies to fp_register / _ex / _shard_begin / _shard_begin_packed / _sharded, fp_track / _ex / _submit / _multi, the Registers of
+ * the 8-bit calibration (which then collect their statistics on filtered input: calibrate with the option set as it will be served)
+ * and the stage operators on an uploaded frame: fp_render_and_transform, fp_pose_fit_eval and fp_get_xyz_map (the map of D', which
+ * is what the networks see).  fp_filter_depth and fp_get_hyp_poses do not change.  The pose fit reads the crops the networks are
+ * fed, so its records follow the option.
+ * Erode zeroes depth below 0.1 m (not 0.001 m): with the option on, an object nearer than 10 cm has no observed geometry.
+ * Register reuses the D' its sampler computes anyway; a Track with refine_itr == 1 filters only its crop window, in one kernel
+ * (DESIGN.md section 4.7).  Works on geometry-only models.  Like fp_set_pose_fit it waits for the model's work and drops the captured
+ * graphs; while the option is off nothing is allocated, launched or captured differently. */
+int fp_set_depth_filter(fp_model *m, int on);
+/* 1 / 0, or a negative value on a null model */
+int fp_get_depth_filter(const fp_model *m);
 
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 

@@ -165,6 +165,10 @@ public:
   // LastTrackFit: one record per tracked object, of the pose the last refine iteration STARTED from (one frame late with refine_itr 1);
   // LastRegisterFit: the returned pose's record (all: every hypothesis'); PoseFit: any poses on the uploaded frame (fp_upload_frame)
   bool SetPoseFit(bool on, float tol_m = 0.005f) { return ok(fp_set_pose_fit(h_, on ? 1 : 0, tol_m)); }
+  // depth filter (foundationpose_amd.h "depth filter"): Register, Track and the stage operators read bilateral(erode(depth)) instead
+  // of the depth itself, like FoundationPose as published; default off
+  bool SetDepthFilter(bool on) { return ok(fp_set_depth_filter(h_, on ? 1 : 0)); }
+  bool DepthFilter() const { return fp_get_depth_filter(h_) == 1; }
   // vertex colours (new; the reference has no counterpart): colors = [V,3] RGB u8 of the target, nullptr = back to its texture
   bool SetVertexColors(const std::string &target_name, const uint8_t *colors, int num_vertices) {
     return ok(fp_set_vertex_colors(h_, target_name.c_str(), colors, num_vertices));
