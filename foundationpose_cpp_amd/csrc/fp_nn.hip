@@ -1652,21 +1652,27 @@ struct HeadsPlan {
   bool fuse_pose = false;    // RefinePostProcess runs inside the read-out kernel
 };
 
+// the launch of ONE of the two kernels over B sequences of T tokens: query tiles, grid, dynamic LDS.  The only copy of this arithmetic:
+// plan_attention chooses between two of these, the test build's fpt_attention_raw forces either.
+static AttLaunch attention_launch(int kernel, int variant, int B, int T, int pitch) {
+  AttLaunch a;
+  a.kernel = kernel; a.variant = variant;
+  a.B = B; a.T = T; a.pitch = pitch;
+  const int qrows = kernel == ATT_32_SKV ? ATT_SKV_QROWS : ATT_QROWS;
+  a.nq = (T + qrows - 1) / qrows;
+  a.grid = (unsigned)(a.nq * HEADS * B);
+  a.lds = kernel == ATT_32_SKV ? LDS_ATT_SKV : 0;
+  return a;
+}
+
 // self- or cross-attention over B sequences of T tokens
 static AttLaunch plan_attention(int B, int T, int pitch, const HeadsOverride &ov) {
-  AttLaunch a;
-  a.B = B; a.T = T; a.pitch = pitch;
+  int variant = 0;
   for (int i = 0; i < N_ATT_VARIANTS; i++)
-    if (ATT_VARIANTS[i].id == ov.att_variant) a.variant = i;   // (a retired or unknown id: the product's row)
-  a.nq = (T + ATT_QROWS - 1) / ATT_QROWS;
-  a.grid = (unsigned)(a.nq * HEADS * B);
+    if (ATT_VARIANTS[i].id == ov.att_variant) variant = i;   // (a retired or unknown id: the product's row)
+  const AttLaunch a = attention_launch(ATT_32, variant, B, T, pitch);
   // a small grid of long latency chains (Track: 2 sequences; the cross-attention: one): split the keys over the waves instead
-  if (a.variant == 0 && a.nq * HEADS * B <= ATT_SKV_MAX_WGS && T > ATT_SKV_MIN_T) {
-    a.kernel = ATT_32_SKV;
-    a.nq = (T + ATT_SKV_QROWS - 1) / ATT_SKV_QROWS;
-    a.grid = (unsigned)(a.nq * HEADS * B);
-    a.lds = LDS_ATT_SKV;
-  }
+  if (variant == 0 && a.grid <= (unsigned)ATT_SKV_MAX_WGS && T > ATT_SKV_MIN_T) return attention_launch(ATT_32_SKV, 0, B, T, pitch);
   return a;
 }
 

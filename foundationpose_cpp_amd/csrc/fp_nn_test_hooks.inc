@@ -531,6 +531,45 @@ int fpt_attention_dt(const float *qkv, int B, int T, float *out, int dt) {
 }
 int fpt_attention(const float *qkv, int B, int T, float *out) { return fpt_attention_dt(qkv, B, T, out, fp::DT_F16); }
 
+// The attention kernels on raw element patterns (tests/test_attention_gpu.py): qkv_bits [B * pitch][1536] and out_bits [B * pitch][512] are
+// 2-byte patterns of dt (DT_F16 / DT_BF16).  out_bits is uploaded before the launch and downloaded after it, so what the caller put where
+// the kernel does not write (rows T..pitch-1 of a sequence) comes back as it went in.  kernel: -1 = what plan_attention chooses with the
+// product's defaults, 0 / 1 = attention32_kernel / attention32_skv_kernel forced, in the product's instantiation and with the launch
+// arithmetic of the plan (attention_launch).  info3 = {kernel that ran, query tiles, grid}.  Both device buffers carry ATT_RAW_GUARD guard
+// rows in front and behind: quiet NaNs around the input, a canary around the output.  Returns 0, 1 on failure (fp_last_error), 2 when an
+// output guard row changed, 3 when an input guard row changed.
+static constexpr int ATT_RAW_GUARD = 128;
+int fpt_attention_raw(const uint16_t *qkv_bits, int B, int T, int pitch, int dt, int kernel, uint16_t *out_bits, int *info3) {
+  using namespace fp;
+  FP_CHECK(qkv_bits && out_bits && info3, "fpt_attention_raw: null argument");
+  FP_CHECK(dt == DT_F16 || dt == DT_BF16, "fpt_attention_raw: the attention kernels run on 2-byte elements");
+  FP_CHECK(kernel >= -1 && kernel <= ATT_32_SKV, "fpt_attention_raw: kernel is -1 (planned), 0 (attention32_kernel) or 1 (attention32_skv_kernel)");
+  FP_CHECK(B >= 1 && T >= 1 && pitch >= T && (long long)B * pitch <= (1 << 22), "fpt_attention_raw: invalid shape");
+  const AttLaunch a = kernel < 0 ? plan_attention(B, T, pitch, HeadsOverride{}) : attention_launch(kernel, 0, B, T, pitch);
+  const size_t G = ATT_RAW_GUARD, rows = (size_t)B * pitch;
+  const uint16_t qnan = dt == DT_BF16 ? 0x7FC0 : 0x7E00, canary = 0xA5C3;
+  std::vector<uint16_t> hq((rows + 2 * G) * 1536, qnan), ho((rows + 2 * G) * 512, canary);
+  std::memcpy(hq.data() + G * 1536, qkv_bits, rows * 1536 * 2);
+  std::memcpy(ho.data() + G * 512, out_bits, rows * 512 * 2);
+  DevBuf<uint16_t> dq(hq.size()), dout(ho.size());
+  FP_CHECK(dq.p && dout.p, "fpt_attention_raw: allocation failed");
+  FP_HIP_OK(fp::memcpy_sync(dq.p, hq.data(), hq.size() * 2, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dout.p, ho.data(), ho.size() * 2, hipMemcpyHostToDevice));
+  Ctx c{nullptr, nullptr, nullptr};
+  if (run_attention(c, dt, a, dq.p + G * 1536, dout.p + G * 512)) return 1;
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipDeviceSynchronize());
+  std::vector<uint16_t> hq2(hq.size());
+  FP_HIP_OK(fp::memcpy_sync(hq2.data(), dq.p, hq2.size() * 2, hipMemcpyDeviceToHost));
+  FP_HIP_OK(fp::memcpy_sync(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost));
+  std::memcpy(out_bits, ho.data() + G * 512, rows * 512 * 2);
+  info3[0] = a.kernel; info3[1] = a.nq; info3[2] = (int)a.grid;
+  for (size_t i = 0; i < G * 512; i++)
+    if (ho[i] != canary || ho[(G + rows) * 512 + i] != canary) { fp::set_error("fpt_attention_raw: the kernel wrote outside its output rows"); return 2; }
+  if (hq2 != hq) { fp::set_error("fpt_attention_raw: the input buffer changed"); return 3; }
+  return 0;
+}
+
 
 // concurrency stress: `nthreads` host threads, each with its own stream and buffers, run the same convolution `iters`
 // times and compare every result bit-for-bit with their first one (device-side).  Returns the number of mismatching

@@ -42,6 +42,23 @@ def ulp(t, dt):
     return torch.exp2(e - MANT[dt])
 
 
+BIAS_ULP = 0.05   # mean signed error of a stage, in ulps (truncation instead of RNE would be ~0.5)
+
+
+def stage_error(got, ref, acc, dt, pre=None, second_rounding=None):
+    """a stage stored in the element type against its UNROUNDED float64 reference: -> (worst |got - ref| / bound over the elements, mean
+    signed error in ulps of |ref| + acc), bound = 0.5 ulp(|ref| + acc) + acc.  pre: the reference before a ReLU (where it is below -acc
+    the output must be exactly 0); second_rounding: a value that was rounded once more on the way (adds its half ulp)."""
+    bound = 0.5 * ulp(ref.abs() + acc, dt) + acc
+    if second_rounding is not None:      # ref = rnd(c + pe) with c itself rounded first
+        bound = bound + 0.5 * ulp(second_rounding.abs() + acc, dt)
+    if pre is not None:
+        bound = torch.where(pre <= -acc, torch.zeros_like(bound), bound)
+    err = (got - ref).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+    return float(ratio.max()), float(((got - ref) / ulp(ref.abs() + acc, dt)).mean())
+
+
 def pos_table():
     """PositionalEmbedding(512, 400) in f32, as the library's host code builds it"""
     t = np.arange(400, dtype=np.float32)[:, None]
@@ -169,11 +186,12 @@ def linear(w: Weights, wname, bname, x, res=None, relu=False, out_dt="same", f32
     return rnd(y, dt), C_ACC * a
 
 
-def sdpa(qkv, dt, per=32, round_out=True):
+def sdpa(qkv, dt, per=32, round_out=True, q_per=None):
     """multi-head attention core of qkv [B, T, 1536] (q | k | v, 4 heads of 128) -> (ref, acc) [B, T, 512].
     acc: P is rounded to the element type before the PV product (relative 2u on numerator and denominator) and the scores carry the
     f32 accumulation error C_ACC * scale * sum|q k| (relative on p) -- (2u + 2 C_ACC scale max_j sum|q k_j|) * sum_j p_j |v_j|, plus the
-    PV accumulation."""
+    PV accumulation.  q_per: queries per pass (a softmax row needs every key but no other query: the [q_per, T] score tiles bound the
+    memory of a long sequence)."""
     B, T, _ = qkv.shape
     u = 0.0 if dt is None else UNIT[dt]
     scale = 1.0 / math.sqrt(EMBED // HEADS)
@@ -181,16 +199,19 @@ def sdpa(qkv, dt, per=32, round_out=True):
     acc = torch.empty_like(out)
     for sl in _chunks(B, per):
         x = qkv[sl].to(torch.float64).reshape(-1, T, 3, HEADS, EMBED // HEADS).permute(2, 0, 3, 1, 4)   # [3, b, h, T, d]
-        q, k, v = x[0], x[1], x[2]
-        s = (q @ k.transpose(-1, -2)) * scale
-        sa = (q.abs() @ k.abs().transpose(-1, -2)) * scale
-        p = torch.softmax(s, -1)
-        o = p @ v
-        pv = p @ v.abs()
-        rel = 2 * u + 2 * C_ACC * sa.amax(-1, keepdim=True)
-        a = rel * pv + C_ACC * pv
-        out[sl] = o.permute(0, 2, 1, 3).reshape(-1, T, EMBED)
-        acc[sl] = a.permute(0, 2, 1, 3).reshape(-1, T, EMBED)
+        k, v = x[1], x[2]
+        kt, kat, va = k.transpose(-1, -2), k.abs().transpose(-1, -2), v.abs()
+        for qs in _chunks(T, q_per or T):
+            q = x[0][:, :, qs]
+            s = (q @ kt) * scale
+            sa = (q.abs() @ kat) * scale
+            p = torch.softmax(s, -1)
+            o = p @ v
+            pv = p @ va
+            rel = 2 * u + 2 * C_ACC * sa.amax(-1, keepdim=True)
+            a = rel * pv + C_ACC * pv
+            out[sl, qs] = o.permute(0, 2, 1, 3).reshape(-1, o.shape[2], EMBED)
+            acc[sl, qs] = a.permute(0, 2, 1, 3).reshape(-1, o.shape[2], EMBED)
     return (rnd(out, dt) if round_out else out), acc
 
 

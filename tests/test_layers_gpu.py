@@ -37,7 +37,7 @@ TAP_PDOT, TAP_TRANS, TAP_ROT, TAP_FEAT = 32, 33, 34, 35
 TAP_XF, TAP_XQKV, TAP_XATT, TAP_XOUT, TAP_O32, TAP_SCORES, TAP_PE = 36, 37, 38, 39, 40, 41, 42
 H_QKV, H_ATT, H_Y1, H_X1, H_HID, H_Y2, H_POOL, H_LN2 = range(8)
 PDOT_U = 4      # pdot: error <= PDOT_U unit roundoffs of the element type, relative to the spread of the reference over tiles
-BIAS_ULP = 0.05
+BIAS_ULP = LR.BIAS_ULP
 DEV = "cuda"
 TABLE = []
 FAILS = []   # stage failures of the running test: every stage is checked, then _flush() reports them all by name
@@ -185,15 +185,7 @@ def _tapped(tl, kind, N, NB2, five, dt, call, win=None, head=True):
 
 def _compare(case, stage, got, ref, acc, dt, pre=None, second_rounding=None, record=True):
     """per-element bound + bias; returns (worst err / bound, mean error in ulps)"""
-    bound = 0.5 * LR.ulp(ref.abs() + acc, dt) + acc
-    if second_rounding is not None:      # ref = rnd(c + pe) with c itself rounded first
-        bound = bound + 0.5 * LR.ulp(second_rounding.abs() + acc, dt)
-    if pre is not None:
-        bound = torch.where(pre <= -acc, torch.zeros_like(bound), bound)
-    err = (got - ref).abs()
-    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    worst = float(ratio.max())
-    bias = float(((got - ref) / LR.ulp(ref.abs() + acc, dt)).mean())
+    worst, bias = LR.stage_error(got, ref, acc, dt, pre=pre, second_rounding=second_rounding)
     if record:
         TABLE.append((case, stage, worst, bias))
     return worst, bias
