@@ -5,6 +5,7 @@
     python examples/demo_sequence.py --synthetic 8 --out out      # seeded synthetic sequence + synthetic weights
     python examples/demo_sequence.py --synthetic 8 --fit 5        # + pose-fit columns (tolerance 5 mm) and a LOST? marker per frame
     python examples/demo_sequence.py --synthetic 8 --depth-filter # the networks see bilateral(erode(depth)), like FoundationPose as published
+    python examples/demo_sequence.py --synthetic 8 --render       # + <id>_render.png beside every box plot: the model's visible pixels, flat-shaded over the frame
 """
 import argparse
 import os
@@ -19,10 +20,12 @@ from foundationpose_cpp_amd import FoundationPose, _lib, dataset as D, load_mesh
 from foundationpose_cpp_amd.synthetic import to_colmajor  # noqa: E402
 
 
-def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, fit_mm=None, lost_below=0.5, depth_filter=False):
+def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, fit_mm=None, lost_below=0.5, depth_filter=False, render=False):
     """fit_mm: pose-fit tolerance in millimetres (None = off: the log is the plain pose log).  With it every log line also carries
     n_model and the inlier / front / behind shares of the model, and LOST? when the inlier share is under lost_below.  Track's record
-    describes the pose the frame STARTED from (the previous frame's answer) against this frame's depth."""
+    describes the pose the frame STARTED from (the previous frame's answer) against this frame's depth.
+    render: beside every <id>_plot.png also write <id>_render.png, the overlay of fp_render_pose at the frame's pose (a silhouette shows
+    a rotation about the object's long axis that the 12-edge box cannot)."""
     seq = D.Sequence(data)
     mesh = load_mesh(name, seq.mesh_path())
     model = FoundationPose(mesh, seq.K, refiner, scorer, max_input_image_height=max(seq.H, 1080), max_input_image_width=max(seq.W, 1920))
@@ -33,7 +36,7 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
     os.makedirs(out, exist_ok=True)
     poses = []
     with open(os.path.join(out, "poses.txt"), "w") as log:
-        def emit(i, pose, rgb, plot, fit=None):
+        def emit(i, pose, rgb, depth, plot, fit=None):
             tail = ""
             if fit is not None:
                 tail = " fit %d %.4f %.4f %.4f" % (fit.n_model, fit.inlier_share, fit.front_share, fit.behind_share)
@@ -41,6 +44,10 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
                     tail += " LOST?"
                     print(f"{seq.ids[i]}: LOST? inliers {fit.inlier_share:.2f} front {fit.front_share:.2f} behind {fit.behind_share:.2f} of {fit.n_model} model pixels")
             log.write(seq.ids[i] + "".join(" %.9g" % v for v in to_colmajor(pose[None])[0]) + tail + "\n")
+            if plot and render:
+                model.upload_frame(rgb, depth)      # (a Track from a host frame uploaded only its crop window)
+                over = model.render_pose(name, pose, want=("overlay",))["overlay"]
+                _lib.lib().fp_image_write_png_rgb(os.path.join(out, seq.ids[i] + "_render.png").encode(), over.ctypes.data, seq.H, seq.W)
             if plot:
                 img = D.draw_bbox3d(rgb, seq.K, D.convert_pose_mesh2bbox(pose, mesh), mesh.dimension)
                 _lib.lib().fp_image_write_png_rgb(os.path.join(out, seq.ids[i] + "_plot.png").encode(), img.ctypes.data, seq.H, seq.W)
@@ -48,7 +55,7 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
         ok, pose = model.Register(rgb, depth, mask, name, refine_itr)
         if not ok:
             raise SystemExit(model.last_error)
-        emit(0, pose, rgb, True, model.last_register_fit() if fit_mm is not None else None)
+        emit(0, pose, rgb, depth, True, model.last_register_fit() if fit_mm is not None else None)
         poses.append(pose)
         t0 = time.perf_counter()
         for i in range(1, len(seq)):
@@ -56,7 +63,7 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
             ok, pose = model.Track(rgb, depth, pose, name, refine_itr)
             if not ok:
                 raise SystemExit(model.last_error)
-            emit(i, pose, rgb, plots or i + 1 == len(seq), model.last_track_fit()[0] if fit_mm is not None and refine_itr >= 1 else None)
+            emit(i, pose, rgb, depth, plots or i + 1 == len(seq), model.last_track_fit()[0] if fit_mm is not None and refine_itr >= 1 else None)
             poses.append(pose)
         if len(seq) > 1:
             print(f"tracked {len(seq) - 1} frames, {(len(seq) - 1) / (time.perf_counter() - t0):.1f} fps including PNG decode")
@@ -78,6 +85,8 @@ def main():
     ap.add_argument("--lost-below", type=float, default=0.5, metavar="SHARE")
     ap.add_argument("--depth-filter", action="store_true",
                     help="Register and Track read bilateral(erode(depth)) instead of the raw depth (FoundationPose as published); default off")
+    ap.add_argument("--render", action="store_true",
+                    help="beside every <id>_plot.png write <id>_render.png: the model at the frame's pose, its visible pixels flat-shaded over the frame; default off")
     ap.add_argument("--synthetic", type=int, metavar="N", help="write and use an N-frame synthetic sequence + synthetic weights")
     a = ap.parse_args()
     if a.synthetic:
@@ -88,7 +97,7 @@ def main():
         W.pack_synthetic("refiner", a.refiner)
         W.pack_synthetic("scorer", a.scorer)
         print("synthetic sequence:", a.data, "(synthetic weights: poses are not meaningful, only reproducible)")
-    run(a.data, a.refiner, a.scorer, a.out, a.name, a.refine_itr, a.plots, a.fit, a.lost_below, a.depth_filter)
+    run(a.data, a.refiner, a.scorer, a.out, a.name, a.refine_itr, a.plots, a.fit, a.lost_below, a.depth_filter, a.render)
     print("wrote", os.path.join(a.out, "poses.txt"))
 
 

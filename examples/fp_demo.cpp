@@ -6,6 +6,7 @@
 // FPSCounter; `speed_track` (:132-158) = Register once, 5000 x Track.  Instead of cv::imshow / an mp4 it writes
 //   <out>/poses.txt          one line per frame: id + the 16 column-major floats (a numeric log the reference lacks)
 //   <out>/<id>_plot.png      rgb with the green oriented-bounding-box overlay (first / last frame, or all with --plots)
+//   <out>/<id>_render.png    with --render, beside every plot: the model at the frame's pose, its visible pixels flat-shaded over the rgb
 //
 // build:  g++ -std=c++17 -Iinclude examples/fp_demo.cpp -o fp_demo -Lfoundationpose_cpp_amd -lfoundationpose_amd
 //             -Wl,-rpath,$PWD/foundationpose_cpp_amd -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib
@@ -114,7 +115,7 @@ int main(int argc, char **argv) {
   const int reps = std::atoi(arg(argc, argv, "--reps", mode == "speed_track" ? "5000" : "50"));
   if (root.empty() || refiner.empty() || scorer.empty()) {
     std::fprintf(stderr, "usage: fp_demo --data DIR --refiner R.fpw --scorer S.fpw [--mesh M.obj] [--out DIR] "
-                         "[--mode test|speed_register|speed_track] [--reps N] [--refine-itr N] [--plots] [--fit [TOL_MM]] [--lost-below SHARE] [--depth-filter]\n");
+                         "[--mode test|speed_register|speed_track] [--reps N] [--refine-itr N] [--plots] [--fit [TOL_MM]] [--lost-below SHARE] [--depth-filter] [--render]\n");
     return 2;
   }
   float K[9];
@@ -189,6 +190,10 @@ int main(int argc, char **argv) {
   FILE *log = std::fopen((out + "/poses.txt").c_str(), "w");
   if (!log) { std::fprintf(stderr, "cannot write %s/poses.txt\n", out.c_str()); return 1; }
   const bool all_plots = flag(argc, argv, "--plots");
+  // --render: beside every plot, fp_render_pose's overlay of the frame's pose (default off).  A Track from a host frame uploads only
+  // its crop window, so the frame is uploaded whole first; the overlay is made before the box is drawn into the rgb.
+  const bool render = flag(argc, argv, "--render");
+  std::vector<uint8_t> overlay;
   auto emit = [&](const std::string &id, const fp_amd::Pose &p, Frame &f, bool plot, const fp_pose_fit *r) {
     std::fprintf(log, "%s", id.c_str());
     for (float v : p) std::fprintf(log, " %.9g", v);
@@ -198,6 +203,14 @@ int main(int argc, char **argv) {
       if (in < lost_below) std::printf("%s: LOST? inliers %.2f front %.2f behind %.2f of %d model pixels\n", id.c_str(), in, r->n_front / n, r->n_behind / n, r->n_model);
     }
     std::fprintf(log, "\n");
+    if (plot && render) {
+      overlay.resize((size_t)H * W * 3);
+      fp_frame_render want = {};
+      want.overlay = overlay.data();
+      if (fp_upload_frame(fpm->handle(), f.rgb.data(), f.depth.data(), FP_HOST, H, W) || !fpm->RenderPose(name, p, want))
+        std::fprintf(stderr, "%s: no render: %s\n", id.c_str(), fp_last_error());
+      else fp_image_write_png_rgb((out + "/" + id + "_render.png").c_str(), overlay.data(), H, W);
+    }
     if (plot) {
       fp_amd::Pose box = pose_mesh2bbox(p, meshes[0].center, ob);
       fp_draw_bbox3d(f.rgb.data(), H, W, K, box.data(), dim);

@@ -26,6 +26,7 @@ SYMBOLS = [
     "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
     "fp_set_depth_filter", "fp_get_depth_filter",
+    "fp_render_pose",
 ]
 
 
@@ -34,6 +35,12 @@ class FpPoseFit(C.Structure):
     _fields_ = [("n_model", C.c_int32), ("n_observed", C.c_int32), ("n_inlier", C.c_int32), ("n_front", C.c_int32),
                 ("n_behind", C.c_int32), ("reserved", C.c_int32), ("sum_dz_q20", C.c_int64), ("mean_dz_m", C.c_float),
                 ("tol_n", C.c_float)]
+
+
+class FpFrameRender(C.Structure):
+    """fp_frame_render of include/foundationpose_amd.h: every pointer optional, all in the call's memspace"""
+    _fields_ = [("model_depth", C.c_void_p), ("model_mask", C.c_void_p), ("visible_mask", C.c_void_p), ("tri_id", C.c_void_p),
+                ("overlay", C.c_void_p)]
 
 
 class FpMesh(C.Structure):
@@ -137,6 +144,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_last_register_fit": [vp, vp, vp, ci], "fp_pose_fit_eval": [vp, cs, vp, ci, cf, cf, vp],
         "fp_mesh_color_source": [vp], "fp_set_vertex_colors": [vp, cs, vp, ci], "fp_get_color_source": [vp, cs],
         "fp_set_depth_filter": [vp, ci], "fp_get_depth_filter": [vp],
+        "fp_render_pose": [vp, cs, vp, cf, vp, ci],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

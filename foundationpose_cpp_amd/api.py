@@ -249,6 +249,7 @@ class FoundationPose:
         if rgb.shape[:2] != depth.shape or (mask is not None and mask.shape != depth.shape):
             self.last_error = "[FoundationPose] Got rgb/depth/mask with different size!"
             return None, None, None
+        self._hw = depth.shape   # (the size of the frame the call hands to the library: render_pose sizes its outputs by it)
         return rgb, depth, mask
 
     # ---- stage-level operators -------------------------------------------------------------------
@@ -368,6 +369,29 @@ class FoundationPose:
         out = (_lib.FpPoseFit * len(p))()
         self._must(self._L.fp_pose_fit_eval(self._h, target_name.encode(), _p(p), len(p), crop_ratio, tol_m, out))
         return [_fit(r) for r in out]
+
+    # ---- a pose at frame resolution (include/foundationpose_amd.h "a pose at frame resolution") ----
+    RENDER_OUTPUTS = {"model_depth": (np.float32, ()), "model_mask": (np.uint8, ()), "visible_mask": (np.uint8, ()),
+                      "tri_id": (np.int32, ()), "overlay": (np.uint8, (3,))}
+
+    def render_pose(self, target_name: str, pose, tol_m: float = 0.005,
+                    want=("model_depth", "model_mask", "visible_mask", "tri_id", "overlay")) -> dict:
+        """fp_render_pose: the target under `pose` ([4,4], what Register / Track return) rasterised at the size of the uploaded frame
+        -> {name: array} for the names in `want`: model_depth [H,W] f32 (0 = background), model_mask / visible_mask [H,W] u8 (255 / 0),
+        tri_id [H,W] i32 (triangle + 1), overlay [H,W,3] u8.  A model pixel is visible unless the RAW observed depth is valid and more
+        than tol_m in front of it.  Raises FoundationPoseError for a pose that would need clipping (a vertex nearer than 1 cm)."""
+        hw = getattr(self, "_hw", None)
+        if hw is None:
+            self.last_error = "[FoundationPose] fp_render_pose: no frame uploaded"
+            raise FoundationPoseError(self.last_error)
+        unknown = [n for n in want if n not in self.RENDER_OUTPUTS]
+        if unknown:
+            raise FoundationPoseError(f"[FoundationPose] render_pose: unknown outputs {unknown}")
+        out = {n: np.zeros(tuple(hw) + self.RENDER_OUTPUTS[n][1], self.RENDER_OUTPUTS[n][0]) for n in want}
+        rec = _lib.FpFrameRender(**{n: _p(a) for n, a in out.items()})
+        p = to_colmajor(np.asarray(pose, np.float32).reshape(4, 4))
+        self._must(self._L.fp_render_pose(self._h, target_name.encode(), _p(p), tol_m, C.byref(rec), FP_HOST))
+        return out
 
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):

@@ -496,6 +496,14 @@ struct fp_model {
   // record.  No buffer of its own: Register's sampler leaves the whole frame's D' there anyway, Track fills its window of it.
   bool dfilt_on = false;
 
+  // frame-resolution rendering (fp_render_pose).  Nothing below is allocated before the first call; no captured
+  // graph reads any of it, so growing it never touches the allocation epoch.
+  int4 *fr_snap = nullptr;      // [fr_vert_cap] {xi, yi, bits(z), 0}
+  float4 *fr_cam = nullptr;     // [fr_vert_cap] camera-space vertices
+  int *fr_flag = nullptr;       // the vertex pass's refusal word
+  uint8_t *fr_out = nullptr;    // FP_HOST outputs are rendered here first: [depth | tri_id | overlay | model_mask | visible_mask] of fr_out_px pixels
+  size_t fr_vert_cap = 0, fr_out_px = 0;
+
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
   // into a hipGraph and replayed.  The graph bakes buffer addresses, so it is keyed by g_alloc_epoch.
   // (Register's ~110 launches are replayed the same way: inter-kernel gaps are ~4 % of a 12 ms Register.)
@@ -832,6 +840,20 @@ int fpt_plan_forward(fp_model *m, int kind, int N, int shared_b) try {
 // bit 0: graphs still enabled (a failed capture disables them), bit 1: Track graph instantiated, bit 2: Register graph
 int fpt_model_graph_state(fp_model *m) { return (m->use_graphs ? 1 : 0) | (m->tg.exec ? 2 : 0) | (m->rg.exec ? 4 : 0); }
 
+// fp_render_pose's host-side screen bound without a GPU (tests/test_frame_render_bound_cpu.py): tiles [tx0, tx1] x [ty0, ty1] of an H x W frame
+// for a column-major pose, row-major K and a vertex-norm bound
+int fpt_frame_tile_bound(const float pose[16], const float K[9], double radius, int H, int W, int out4[4]) {
+  FramePose P;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) P.r[r * 3 + c] = pose[c * 4 + r];
+    P.t[r] = pose[12 + r];
+  }
+  P.fx = K[0]; P.cx = K[2]; P.fy = K[4]; P.cy = K[5];
+  const FrameTileBound b = frame_tile_bound(P, radius, H, W);
+  out4[0] = b.tx0; out4[1] = b.ty0; out4[2] = b.tx1; out4[3] = b.ty1;
+  return 0;
+}
+
 // debug: enable the stage digests and read them back (16 slots; zeroed by every read)
 int fpt_digests(fp_model *m, unsigned long long out[16]) {
   if (!m->digests) {
@@ -1082,6 +1104,10 @@ fp_model *fp_create_on(int device, const fp_mesh *meshes, int n_meshes, const fl
       uv[(size_t)k * 2] = src.texcoords[(size_t)k * 2];
       uv[(size_t)k * 2 + 1] = 1 - src.texcoords[(size_t)k * 2 + 1];
     }
+    double norm2 = 0;
+    for (int k = 0; k < d.V; k++)
+      norm2 = std::max(norm2, (double)v[(size_t)k * 3] * v[(size_t)k * 3] + (double)v[(size_t)k * 3 + 1] * v[(size_t)k * 3 + 1] + (double)v[(size_t)k * 3 + 2] * v[(size_t)k * 3 + 2]);
+    d.max_norm = (float)(std::sqrt(norm2) * (1.0 + 1e-6));   // (rounded up: fp_render_pose's screen bound must contain every vertex)
     std::vector<int32_t> f((size_t)d.F * 3);
     for (size_t k = 0; k < f.size(); k++) f[k] = (int32_t)src.faces[k];
     bool ok = !dev_alloc(&d.verts, v.size()) && !dev_alloc(&d.normals, v.size()) && !dev_alloc(&d.uvs, uv.size()) &&
@@ -1140,6 +1166,7 @@ static void destroy_model_impl(fp_model *m) {
   dev_free(m->grid_dev); dev_free(m->samp_state); dev_free(m->samp_vals); dev_free(m->mask_dev);
   if (m->digests) (void)hipFree(m->digests);
   dev_free(m->fit_acc); dev_free(m->fit_rec);
+  dev_free(m->fr_snap); dev_free(m->fr_cam); dev_free(m->fr_flag); dev_free(m->fr_out);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
@@ -1154,6 +1181,8 @@ void fp_destroy(fp_model *m) {
   destroy_model_impl(m);
 }
 
+static_assert(FP_RENDER_SNAP_MAX == fp::FRAME_RENDER_SNAP_MAX && FP_RENDER_NEAR_M == fp::FRAME_RENDER_NEAR,
+              "include/foundationpose_amd.h: the refusal constants of fp_render_pose are those of fp_internal.h");
 static_assert(FP_MAX_BATCH == fp::MAX_BATCH && 42 * FP_MAX_INPLANE_STEPS <= FP_MAX_BATCH && 42 * (FP_MAX_INPLANE_STEPS + 1) > FP_MAX_BATCH,
               "include/foundationpose_amd.h: the batch limit is fp_nn.h MAX_BATCH");
 int fp_set_inplane_steps(fp_model *m, int steps) try {
@@ -2338,6 +2367,85 @@ int fp_pose_fit_eval(fp_model *m, const char *target_name, const float *poses, i
   FP_HIP_OK(hipMemcpyAsync(recs.data(), recs_dev, recs.size() * sizeof(PoseFitRec), hipMemcpyDeviceToHost, m->stream));
   FP_HIP_OK(hipStreamSynchronize(m->stream));
   for (int i = 0; i < N; i++) fit_record(out + i, recs[(size_t)i], tol_n, t->mesh.diameter);
+  return 0;
+} FP_CATCH_INT
+
+// ---- frame-resolution rendering of one pose
+static size_t fr_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], float tol_m, const fp_frame_render *out, int memspace) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && pose && out, "[FoundationPose] fp_render_pose: invalid arguments");
+  FP_CHECK(memspace == FP_HOST || memspace == FP_DEVICE, "[FoundationPose] fp_render_pose: memspace must be FP_HOST or FP_DEVICE");
+  FP_CHECK(out->model_depth || out->model_mask || out->visible_mask || out->tri_id || out->overlay, "[FoundationPose] fp_render_pose: no output requested");
+  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_render_pose: tol_m must be finite and >= 0 (metres)");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_render_pose: a submitted Track has not been waited for (fp_track_wait)");
+  FP_CHECK(m->depth != nullptr && m->rgb != nullptr && m->H > 0, "[FoundationPose] fp_render_pose: no frame uploaded");
+  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  Target *t = m->find(target_name ? target_name : "");
+  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  const DeviceMesh &mesh = t->mesh;
+  const int H = m->H, W = m->W;
+  const size_t px = (size_t)H * W;
+  hipStream_t s = m->stream;
+  if ((size_t)mesh.V > m->fr_vert_cap) {
+    FP_HIP_OK(hipStreamSynchronize(s));
+    dev_free(m->fr_snap); dev_free(m->fr_cam);
+    m->fr_vert_cap = 0;
+    if (dev_alloc(&m->fr_snap, (size_t)mesh.V) || dev_alloc(&m->fr_cam, (size_t)mesh.V)) return 1;
+    m->fr_vert_cap = (size_t)mesh.V;
+  }
+  if (!m->fr_flag && dev_alloc(&m->fr_flag, 1)) return 1;
+  FramePose P;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) P.r[r * 3 + c] = pose[c * 4 + r];
+    P.t[r] = pose[12 + r];
+  }
+  P.fx = m->K[0]; P.cx = m->K[2]; P.fy = m->K[4]; P.cy = m->K[5];
+  // (a) vertex pass + the refusal word: a pose that needs a clipper, or leaves the exact integer range, gives an error, not a picture
+  FP_HIP_OK(hipMemsetAsync(m->fr_flag, 0, sizeof(int), s));
+  {
+    ProfScope ps(&m->prof, s, "frame_vertex", 0, (double)mesh.V * (12.0 + 32.0));
+    launch_frame_vertex(s, mesh, P, m->fr_snap, m->fr_cam, m->fr_flag);
+    FP_HIP_OK(hipGetLastError());
+  }
+  int flag = 0;
+  FP_HIP_OK(hipMemcpyAsync(&flag, m->fr_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  FP_HIP_OK(hipStreamSynchronize(s));
+  FP_CHECK(!(flag & FRAME_RENDER_FLAG_NEAR), "[FoundationPose] fp_render_pose: pose refused: a vertex lies nearer than FP_RENDER_NEAR_M (0.01 m) to the camera plane, or behind it (there is no clipper)");
+  FP_CHECK(!(flag & FRAME_RENDER_FLAG_RANGE), "[FoundationPose] fp_render_pose: pose refused: a vertex projects beyond FP_RENDER_SNAP_MAX sixteenths of a pixel (the exact range of the edge functions)");
+  // (b) raster + resolve, straight into the caller's device memory or into the model's staging block
+  FrameRenderOut o = {out->model_depth, out->model_mask, out->visible_mask, out->tri_id, out->overlay};
+  const size_t off_tri = fr_align(px * 4), off_ovl = off_tri + fr_align(px * 4), off_mask = off_ovl + fr_align(px * 3), off_vis = off_mask + fr_align(px);
+  if (memspace == FP_HOST) {
+    if (px > m->fr_out_px) {
+      dev_free(m->fr_out);
+      m->fr_out_px = 0;
+      if (dev_alloc(&m->fr_out, off_vis + fr_align(px))) return 1;
+      m->fr_out_px = px;
+    }
+    // (offsets are those of THIS frame size: a smaller frame than the block was sized for uses its front)
+    o.depth = out->model_depth ? reinterpret_cast<float *>(m->fr_out) : nullptr;
+    o.tri = out->tri_id ? reinterpret_cast<int32_t *>(m->fr_out + off_tri) : nullptr;
+    o.overlay = out->overlay ? m->fr_out + off_ovl : nullptr;
+    o.mask = out->model_mask ? m->fr_out + off_mask : nullptr;
+    o.vis = out->visible_mask ? m->fr_out + off_vis : nullptr;
+  }
+  const FrameTileBound bound = frame_tile_bound(P, (double)mesh.max_norm, H, W);
+  {
+    const double wr = (o.depth ? 4.0 : 0.0) + (o.tri ? 4.0 : 0.0) + (o.overlay ? 3.0 : 0.0) + (o.mask ? 1.0 : 0.0) + (o.vis ? 1.0 : 0.0);
+    const double rd = (o.overlay ? 3.0 : 0.0) + (o.vis || o.overlay ? 4.0 : 0.0);
+    ProfScope ps(&m->prof, s, "frame_raster", 0, (double)px * (wr + rd));
+    launch_frame_raster(s, mesh, m->fr_snap, m->fr_cam, m->rgb, m->depth, H, W, bound, tol_m, o);
+    FP_HIP_OK(hipGetLastError());
+  }
+  if (memspace == FP_HOST) {
+    if (out->model_depth) FP_HIP_OK(hipMemcpyAsync(out->model_depth, o.depth, px * 4, hipMemcpyDeviceToHost, s));
+    if (out->tri_id) FP_HIP_OK(hipMemcpyAsync(out->tri_id, o.tri, px * 4, hipMemcpyDeviceToHost, s));
+    if (out->overlay) FP_HIP_OK(hipMemcpyAsync(out->overlay, o.overlay, px * 3, hipMemcpyDeviceToHost, s));
+    if (out->model_mask) FP_HIP_OK(hipMemcpyAsync(out->model_mask, o.mask, px, hipMemcpyDeviceToHost, s));
+    if (out->visible_mask) FP_HIP_OK(hipMemcpyAsync(out->visible_mask, o.vis, px, hipMemcpyDeviceToHost, s));
+  }
+  FP_HIP_OK(hipStreamSynchronize(s));
   return 0;
 } FP_CATCH_INT
 

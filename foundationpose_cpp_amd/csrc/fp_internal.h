@@ -141,6 +141,7 @@ struct DeviceMesh {
   int V = 0, F = 0, TH = 0, TW = 0;
   float diameter = 0;
   float center[3] = {0, 0, 0};
+  float max_norm = 0;        // largest vertex norm of the centred mesh (the screen bound of fp_render_pose)
   float *verts = nullptr;    // [V,3] centred
   float *normals = nullptr;  // [V,3]
   float *uvs = nullptr;      // [V,2] (u, 1-v)
@@ -313,6 +314,33 @@ struct PoseFitRec {   // the integer part of fp_pose_fit (include/foundationpose
 int pose_fit_split(int N);   // workgroups per hypothesis
 void launch_pose_fit(hipStream_t s, const void *img_a, size_t a_stride, const void *img_b, size_t b_stride, int N, const PoseFitTol &tol,
                      OutMode mode, unsigned long long *acc, PoseFitRec *out);
+
+// frame-resolution rendering of one pose (fp_render_pose; fp_frame_render.hip)
+constexpr float FRAME_RENDER_NEAR = 0.01f;          // = FP_RENDER_NEAR_M: a vertex with z below it refuses the pose (there is no clipper)
+constexpr int FRAME_RENDER_SNAP_MAX = 1 << 26;      // = FP_RENDER_SNAP_MAX: largest |snapped coordinate| (1/16 px); edge functions stay below 2^56
+constexpr int FRAME_RENDER_FLAG_NEAR = 1, FRAME_RENDER_FLAG_RANGE = 2;
+constexpr int FRAME_RENDER_TILE = 32, FRAME_RENDER_THREADS = 256;   // a 32 x 32 px tile per workgroup: 8 KB of 64-bit keys in LDS
+constexpr int FRAME_RENDER_TINT_R = 40, FRAME_RENDER_TINT_G = 220, FRAME_RENDER_TINT_B = 120;
+struct FramePose {
+  float r[9];   // linear part, ROW-major
+  float t[3];
+  float fx, fy, cx, cy;
+};
+struct FrameRenderOut {   // device pointers, null = not wanted
+  float *depth;
+  uint8_t *mask, *vis;
+  int32_t *tri;
+  uint8_t *overlay;
+};
+struct FrameTileBound {
+  int tx0, ty0, tx1, ty1;   // tiles [tx0, tx1] x [ty0, ty1] walk the triangles, the others write background
+};
+// pure host function: the conservative screen bound of the object, in tiles
+FrameTileBound frame_tile_bound(const FramePose &pose, double radius, int H, int W);
+// snap [V] = {xi, yi, bits(z), 0}, cam [V] = {x, y, z, 0}; *flag must be zero on entry
+void launch_frame_vertex(hipStream_t s, const DeviceMesh &m, const FramePose &pose, int4 *snap, float4 *cam, int *flag);
+void launch_frame_raster(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const uint8_t *rgb, const float *depth,
+                         int H, int W, const FrameTileBound &bound, float tol_m, const FrameRenderOut &out);
 
 // host helpers (fp_host.cpp part of fp_api.hip)
 std::vector<float> make_rotation_grid(int min_views, int inplane_steps);

@@ -203,6 +203,37 @@ int fp_set_depth_filter(fp_model *m, int on);
 /* 1 / 0, or a negative value on a null model */
 int fp_get_depth_filter(const fp_model *m);
 
+/* ---- a pose at frame resolution: which pixels of this frame are the object? (new; the reference has no counterpart) ------------
+ * fp_render_pose rasterises `target_name` under `pose` (centred-mesh -> camera, column-major: what Register and Track return) at the
+ * size of the uploaded frame (fp_upload_frame, or whatever the last Register / device-frame Track left) with the model's K, and
+ * compares it per pixel with the observed depth.  Geometry only: no texture, no vertex colours, no anti-aliasing.  Rules (DESIGN.md
+ * section 4.8; every f32 operation separately rounded, independent of fp_set_float_model): vertices are projected and snapped to
+ * 1/16 px; the sample point of pixel (c, r) is the image point (c, r) of K -- the convention of the xyz map, NOT c + 0.5; coverage is
+ * decided by 64-bit integer edge functions with a top-left fill rule, both windings drawn; depth is perspective-correct; the nearest
+ * triangle wins and at equal depth the lower index.  The result is bit-reproducible and independent of thread order.
+ * With D the observed depth at the pixel, a model pixel is OCCLUDED when !(D < 0.001f) && D < z - tol_m (one f32 subtraction) and
+ * VISIBLE otherwise: missing depth counts as visible.  tol_m must be finite and >= 0.
+ * D is always the RAW uploaded depth, whether fp_set_depth_filter is on or off.
+ * There is no clipper: a pose with any vertex at z < FP_RENDER_NEAR_M (1 cm; the depth VALIDITY threshold of the frame is 0.001 m), or
+ * with a vertex that projects beyond FP_RENDER_SNAP_MAX sixteenths of a pixel (the range that keeps the edge functions exact), is
+ * refused with an error before anything is rasterised.
+ * Every output pointer is optional (NULL = not wanted; all NULL is an error) and lives in `memspace`.  FP_DEVICE outputs are written
+ * by the kernel directly -- visible_mask can go straight into fp_register_ex as the mask of a re-Register;
+ * FP_HOST outputs are copied on the model's stream, followed by one synchronisation.  H and W are the uploaded frame's.
+ * Works on geometry-only models; refuses a partially uploaded frame like the other stage operators.  Register, Track, their captured
+ * graphs and every existing kernel are untouched: the call's buffers are its own, allocated at its first use. */
+#define FP_RENDER_NEAR_M 0.01f
+#define FP_RENDER_SNAP_MAX 67108864 /* 2^26 */
+typedef struct fp_frame_render {      /* every pointer optional (NULL = not wanted); all in the call's memspace */
+  float   *model_depth;   /* [H,W]   camera z of the nearest model surface, metres; 0 = background            */
+  uint8_t *model_mask;    /* [H,W]   255 where the model covers the pixel, else 0                             */
+  uint8_t *visible_mask;  /* [H,W]   255 where it does and nothing observed is in front of it, else 0         */
+  int32_t *tri_id;        /* [H,W]   triangle index + 1, 0 = background (tests / debugging)                   */
+  uint8_t *overlay;       /* [H,W,3] the uploaded rgb with the visible model pixels drawn flat-shaded over it */
+} fp_frame_render;
+int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], float tol_m,
+                   const fp_frame_render *out, int memspace);
+
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 
 /* UploadDataToDevice + convert_depth_to_xyz_map (src/foundationpose.cpp:267-315, src/foundationpose_utils.cu:3-32). */

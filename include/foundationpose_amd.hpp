@@ -187,6 +187,13 @@ public:
     out.resize(poses.size());
     return ok(fp_pose_fit_eval(h_, target_name.c_str(), poses.empty() ? nullptr : poses[0].data(), (int)poses.size(), crop_ratio, tol_m, out.data()));
   }
+  // a pose at frame resolution (foundationpose_amd.h "a pose at frame resolution"): the target under `pose` rasterised at the size of
+  // the uploaded frame (fp_upload_frame, a Register or a device-frame Track); every pointer of `out` is optional and lives in `memspace`.
+  // FP_DEVICE: the kernel writes the caller's buffers directly -- out.visible_mask is the mask of the next fp_register_ex.
+  // A pose that would need clipping (a vertex nearer than FP_RENDER_NEAR_M) is refused: false + last_error().
+  bool RenderPose(const std::string &target_name, const Pose &pose, const fp_frame_render &out, float tol_m = 0.005f, int memspace = FP_HOST) {
+    return ok(fp_render_pose(h_, target_name.c_str(), pose.data(), tol_m, &out, memspace));
+  }
 
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
