@@ -1997,6 +1997,10 @@ static int ensure_splitk(const Ctx &c, size_t need, float **slab) {
 }
 
 using ConvLaunch = int (*)(const Ctx &, const ConvStep &, const ConvParams &);
+#ifdef FP_TEST_HOOKS
+static ConvPlan g_last_conv_plan;   // the plan and the kernels' ODT of the last run_conv call of this process (single-threaded test hooks)
+static int g_last_conv_odt = -1;
+#endif
 
 // post / post_fused: a positional table the layer may add to its output (see ConvParams::post); *post_fused tells the
 // caller whether the plan did (otherwise the caller launches add_pos_embed_kernel)
@@ -2109,6 +2113,9 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
   ConvPlan plan;
   if (plan_conv(q, &plan)) return 1;
   if (post_fused) *post_fused = plan.post_fused;
+#ifdef FP_TEST_HOOKS
+  g_last_conv_plan = plan; g_last_conv_odt = odt;   // (fpt_conv_q8_raw reports the plan that ran: this one, not a second plan_conv call)
+#endif
   for (int i = 0; i < plan.n; i++) {
     const ConvStep &st = plan.step[i];
     p.m_begin = st.m_begin; p.M = st.M;
@@ -2261,6 +2268,16 @@ __global__ __launch_bounds__(256) void chan_stats_kernel(const unsigned char *__
     if (sacc[e] != 0.f) atomicAdd(reinterpret_cast<unsigned long long *>(sum + cg * 8 + e), (unsigned long long)__double2ll_rn((double)sacc[e] * 1048576.0));
   }
 }
+// the launch of chan_stats_kernel on a tensor [pixels][C] of element type dt (calib_record; fpt_chan_stats_raw); returns the grid
+static unsigned launch_chan_stats(hipStream_t s, int dt, const unsigned char *x, size_t pixels, int C, const float *scale, float *amax, long long *sum) {
+  const int groups = C / 8;
+  const dim3 grid((unsigned)((size_t)1024 * groups / 256)), blk(256);   // 1024 pixel lanes per channel group
+  if (dt == DT_BF16) FP_LAUNCH_RAW(chan_stats_kernel<DT_BF16>, grid, blk, 0, s, x, pixels, C, scale, amax, sum);
+  else if (dt == DT_FP8) FP_LAUNCH_RAW(chan_stats_kernel<DT_FP8>, grid, blk, 0, s, x, pixels, C, scale, amax, sum);
+  else if (dt == DT_I8) FP_LAUNCH_RAW(chan_stats_kernel<DT_I8>, grid, blk, 0, s, x, pixels, C, scale, amax, sum);
+  else FP_LAUNCH_RAW(chan_stats_kernel<DT_F16>, grid, blk, 0, s, x, pixels, C, scale, amax, sum);
+  return grid.x;
+}
 // act_id: trunk activation (0..14); dt / scale describe the tensor at `buf`
 static void calib_record(const Ctx &c, int act_id, const void *buf, size_t pixels, int C, int dt, const float *scale = nullptr) {
   if (!c.net->calib_mode || (c.net->calib_only >= 0 && c.net->calib_only != act_id)) return;
@@ -2273,13 +2290,7 @@ static void calib_record(const Ctx &c, int act_id, const void *buf, size_t pixel
   }
   float *amax = c.net->calib_mode == 1 ? c.net->calib_amax + act_id * 512 : nullptr;
   long long *sum = c.net->calib_sum + act_id * 512;
-  const unsigned char *x = (const unsigned char *)buf;
-  const int groups = C / 8;
-  const dim3 grid((unsigned)((size_t)1024 * groups / 256)), blk(256);   // 1024 pixel lanes per channel group
-  if (dt == DT_BF16) FP_LAUNCH_RAW(chan_stats_kernel<DT_BF16>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
-  else if (dt == DT_FP8) FP_LAUNCH_RAW(chan_stats_kernel<DT_FP8>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
-  else if (dt == DT_I8) FP_LAUNCH_RAW(chan_stats_kernel<DT_I8>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
-  else FP_LAUNCH_RAW(chan_stats_kernel<DT_F16>, grid, blk, 0, c.s, x, pixels, C, scale, amax, sum);
+  launch_chan_stats(c.s, dt, (const unsigned char *)buf, pixels, C, scale, amax, sum);
 }
 
 // arena carve (by capacity, see ensure_scratch)
@@ -2431,6 +2442,32 @@ static int run_trunk_i8(const Ctx &c, const Arena &a, const void *nn_in, int N, 
   return 0;
 }
 #endif
+// the launch of q8_img_bias_fused_kernel for layer L on its 8-bit input xq [NBi, HW + 2, HW + 2, Cin] (run_trunk_q8; fpt_q8_img_bias_raw).
+// lattice: the sums run over the even rows x even columns of the padded image (HW + 2 is even): (HW/2 + 1)^2 lattice points, (HW/2)^2
+// of them interior; otherwise over every pixel
+static unsigned launch_q8_img_bias_fused(hipStream_t s, const ConvLayer &L, const unsigned char *xq, int NBi, int HW, bool lattice, float *out) {
+  const int wp2 = lattice ? (HW + 2) / 2 : 0;
+  const dim3 grid((NBi + Q8_BIAS_IMGS - 1) / Q8_BIAS_IMGS);
+  FP_LAUNCH_RAW(q8_img_bias_fused_kernel, grid, dim3(1024), 0, s, xq, wp2 ? wp2 * wp2 : (HW + 2) * (HW + 2), L.tmat_t, L.cscale,
+                     L.bias, wp2 ? 1.f / (float)((HW / 2) * (HW / 2)) : 1.f / (float)(HW * HW), L.Cin, L.Cout, out, wp2, (HW + 2) * (HW + 2), NBi);
+  return grid.x;
+}
+#ifdef FP_TEST_HOOKS
+// the three-launch form of the same (A/B, test build): sums [NBi][Cin] must be zero on entry and are left zero
+static void launch_q8_img_bias_3(hipStream_t s, const ConvLayer &L, const unsigned char *xq, int NBi, int HW, int *sums, float *out) {
+  FP_LAUNCH_RAW(q8_img_sum_kernel, dim3(NBi, HW == 40 ? 6 : 2), dim3(256), 0, s, xq, (HW + 2) * (HW + 2), L.Cin, sums);
+  FP_LAUNCH_RAW(q8_img_bias_kernel, dim3(NBi, L.Cout / 64), dim3(256), 0, s, sums, L.tmat_t, L.cscale, L.bias, 1.f / (float)(HW * HW), L.Cin, L.Cout, out);
+  (void)hipMemsetAsync(sums, 0, (size_t)NBi * L.Cin * sizeof(int), s);
+}
+#endif
+// the launch of q8_copy_kernel: the 8-bit copy (type q) of the bordered f16 tensor x16 [imgs, HW + 2, HW + 2, Cc] (run_trunk_q8; fpt_q8_copy_raw)
+static unsigned launch_q8_copy(hipStream_t s, int q, const void *x16, void *xq, const float *oinv, int imgs, int HW, int Cc) {
+  const size_t octs = (size_t)imgs * HW * HW * (Cc / 8);
+  const dim3 grid((unsigned)((octs + 255) / 256));
+  if (q == DT_FP8) FP_LAUNCH_RAW(q8_copy_kernel<DT_FP8>, grid, dim3(256), 0, s, (const _Float16 *)x16, (unsigned char *)xq, oinv, HW + 2, HW + 2, 1, Cc, octs);
+  else FP_LAUNCH_RAW(q8_copy_kernel<DT_I8>, grid, dim3(256), 0, s, (const _Float16 *)x16, (unsigned char *)xq, oinv, HW + 2, HW + 2, 1, Cc, octs);
+  return grid.x;
+}
 static int run_trunk_q8(const Ctx &c, const Arena &a, const void *nn_in, int N, int n_b) {
   const Net *net = c.net;
 #ifdef FP_TEST_HOOKS
@@ -2452,16 +2489,11 @@ static int run_trunk_q8(const Ctx &c, const Arena &a, const void *nn_in, int N, 
     NetScope ps(c, "q8_img_bias", 0, (double)NBi * (HW + 2) * (HW + 2) * L.Cin);
 #ifdef FP_TEST_HOOKS
     if (g_q8_imgbias == 2) {   // A/B (test build): the three-launch form (sliced integer-atomic sums, 64-channel bias blocks, clear)
-      FP_LAUNCH_RAW(q8_img_sum_kernel, dim3(NBi, HW == 40 ? 6 : 2), dim3(256), 0, c.s, (const unsigned char *)xq, (HW + 2) * (HW + 2), L.Cin, c.ws->img_sum);
-      FP_LAUNCH_RAW(q8_img_bias_kernel, dim3(NBi, L.Cout / 64), dim3(256), 0, c.s, c.ws->img_sum, L.tmat_t, L.cscale, L.bias, 1.f / (float)(HW * HW), L.Cin, L.Cout, c.ws->img_bias);
-      (void)hipMemsetAsync(c.ws->img_sum, 0, (size_t)NBi * L.Cin * sizeof(int), c.s);
+      launch_q8_img_bias_3(c.s, L, (const unsigned char *)xq, NBi, HW, c.ws->img_sum, c.ws->img_bias);
     } else
 #endif
     {
-      // even rows x even columns of the padded image (HW + 2 is even): (HW/2 + 1)^2 lattice points, (HW/2)^2 of them interior
-      const int wp2 = g_q8_imgbias == 3 ? 0 : (HW + 2) / 2;
-      FP_LAUNCH_RAW(q8_img_bias_fused_kernel, dim3((NBi + Q8_BIAS_IMGS - 1) / Q8_BIAS_IMGS), dim3(1024), 0, c.s, (const unsigned char *)xq, wp2 ? wp2 * wp2 : (HW + 2) * (HW + 2), L.tmat_t, L.cscale,
-                         L.bias, wp2 ? 1.f / (float)((HW / 2) * (HW / 2)) : 1.f / (float)(HW * HW), L.Cin, L.Cout, c.ws->img_bias, wp2, (HW + 2) * (HW + 2), NBi);
+      launch_q8_img_bias_fused(c.s, L, (const unsigned char *)xq, NBi, HW, g_q8_imgbias != 3, c.ws->img_bias);
     }
     return c.ws->img_bias;
   };
@@ -2476,10 +2508,7 @@ static int run_trunk_q8(const Ctx &c, const Arena &a, const void *nn_in, int N, 
   float *const *scd = net->act_scale_dev;
   auto qcopy = [&](const void *x16, void *xq, int imgs, int HW, int Cc, int act) {
     NetScope ps(c, "q8_copy", 0, (double)imgs * HW * HW * Cc * 3.0);
-    const size_t octs = (size_t)imgs * HW * HW * (Cc / 8);
-    const dim3 grid((unsigned)((octs + 255) / 256));
-    if (q == DT_FP8) FP_LAUNCH_RAW(q8_copy_kernel<DT_FP8>, grid, dim3(256), 0, c.s, (const _Float16 *)x16, (unsigned char *)xq, oinv[act], HW + 2, HW + 2, 1, Cc, octs);
-    else FP_LAUNCH_RAW(q8_copy_kernel<DT_I8>, grid, dim3(256), 0, c.s, (const _Float16 *)x16, (unsigned char *)xq, oinv[act], HW + 2, HW + 2, 1, Cc, octs);
+    launch_q8_copy(c.s, q, x16, xq, oinv[act], imgs, HW, Cc);
   };
   // first conv of a residual block (no skip operand): 8-bit -> 8-bit with the consumer's scales folded in, or plain f16
   auto first = [&](const char *tag, const ConvLayer &L, bool on, const Act &x16, const Act &xq, int NB, int HW, const Act &y16, const Act &yq, int act, size_t P, int Cc) -> int {

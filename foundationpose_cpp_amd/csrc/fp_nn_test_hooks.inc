@@ -143,6 +143,21 @@ int fpt_quantise_i8(const float *rows, int Cout, int ntaps, int Cin, const float
   std::memcpy(tmat_t_out, tm.data(), tm.size() * sizeof(float));
   return 0;
 }
+// HOST-ONLY (no HIP call: runs without a GPU, tests/q8_conv_cases.py): the weight codes and row scales quantise_q8 gives an 8-bit layer of
+// element type dt (DT_FP8 / DT_I8) without calibration means, as fpt_conv_q8_raw's apply_q8_layer call does: rows [Cout][taps][Cin] f32,
+// s_in [Cin] -> q [Cout][taps][Cin] (e4m3 bits / int8), sw [Cout]
+int fpt_quantise_q8(int dt, const float *rows, int Cout, int ntaps, int Cin, const float *s_in, unsigned char *q_out, float *sw_out) {
+  if (!fp::is_q8(dt) || !rows || !s_in || !q_out || !sw_out || Cout < 1 || ntaps < 1 || Cin < 1) return 1;
+  fp::ConvLayer L;
+  L.Cout = Cout; L.Cin = Cin; L.ntaps = ntaps;
+  L.rows_f32.assign(rows, rows + (size_t)Cout * ntaps * Cin);
+  std::vector<float> sw;
+  std::vector<double> qsum;
+  const auto q = fp::quantise_q8(L, dt, s_in, &sw, &qsum);
+  std::memcpy(q_out, q.data(), q.size());
+  std::memcpy(sw_out, sw.data(), sw.size() * sizeof(float));
+  return 0;
+}
 // HOST-ONLY (no HIP call: runs without a GPU, tests/test_conv_plan_cpu.py): the schedule plan_conv chooses for one convolution / Linear
 // layer under the current switches.  shape10 = {Cin, Cout, KH, KW, stride, pad, NB, H, W, ipad}; dt / odt = element type of the operands /
 // the kernels' output type (fp_nn.h, DT_*); flags: 1 = residual, 2 = a positional table is offered, 4 / 8 = the layer carries the
@@ -567,6 +582,180 @@ int fpt_attention_raw(const uint16_t *qkv_bits, int B, int T, int pitch, int dt,
   for (size_t i = 0; i < G * 512; i++)
     if (ho[i] != canary || ho[(G + rows) * 512 + i] != canary) { fp::set_error("fpt_attention_raw: the kernel wrote outside its output rows"); return 2; }
   if (hq2 != hq) { fp::set_error("fpt_attention_raw: the input buffer changed"); return 3; }
+  return 0;
+}
+
+// ---- the 8-bit convolutions and their helper kernels on raw bit patterns (tests/test_q8_conv_gpu.py, tests/test_q8_helpers_gpu.py) ----
+// One 3x3 / pad-1 convolution of the 8-bit trunk through run_conv, every operand in device form.
+//   cfg13 = {Cin, Cout, stride, NB, H (= W), dt, odt, relu, split_imgs, res_kind (0 none, 1 f16, 2 8-bit codes + rscale), opad, rpad, guard_imgs}
+//   dt / odt: the pair run_conv dispatches on (fp_nn.h DT_*); the call is refused when run_conv derives another ODT from the operands.
+//   x        dt 8-bit: codes [NB, H, H, Cin] (e4m3 bits, or u ^ 0x80); DT_F16 (encodeA.1): f16 bits.  The border of zero-codes is added here.
+//   w        f32 [Cout, 3, 3, Cin], bias f32 [Cout], s_in [Cin] (8-bit dt), s_out_fold [Cout] or null: through finish_layer and
+//            apply_q8_layer, layout copies included.
+//   res      [NB, OH + 2 rpad, OW + 2 rpad, Cout] f16 bits or 8-bit codes, border as the caller filled it; rscale [Cout] (res_kind 2)
+//   bias_img [NB][Cout] or null (DT_I8); oinv [Cout] (dual / scaled outputs); post f16 bits [OH * OW][Cout] or null (offered table)
+//   out16 / out8: [NBo + guard_imgs][OH + 2 opad][OW + 2 opad][out_ld] 2-byte / 1-byte patterns, NBo = split_imgs ? split_imgs : NB,
+//            out_ld = split_imgs ? 2 Cout : Cout.  Uploaded as given (the caller's canary) and downloaded whole after the launch; the one
+//            the output type does not write may be null.
+//   tables (8-bit dt; each may be null): wq [Cout][9 Cin] the codes quantise_q8 produced, sw [Cout], cscale [Cout] and bias [Cout] as
+//            uploaded (read back from the device; DT_I8: with the 128-offset fold), tmat_t [Cin][Cout] (DT_I8)
+//   plan26 = {steps, post_fused, then per step {kernel (ConvKernel), m_begin, M, post, grid, mi}} of the plan run_conv executed
+// Returns 0, 1 on failure (fp_last_error).
+int fpt_conv_q8_raw(const int *cfg13, const void *x, const float *w, const float *bias, const float *s_in, const float *s_out_fold, const void *res,
+                    const float *rscale, const float *bias_img, const float *oinv, const uint16_t *post, uint16_t *out16, unsigned char *out8,
+                    unsigned char *wq, float *sw, float *cscale, float *bias_up, float *tmat_t, int *plan26) {
+  using namespace fp;
+  FP_CHECK(cfg13 && x && w && bias && plan26, "fpt_conv_q8_raw: null argument");
+  const int Cin = cfg13[0], Cout = cfg13[1], stride = cfg13[2], NB = cfg13[3], H = cfg13[4], dt = cfg13[5], odt = cfg13[6], relu = cfg13[7],
+            split = cfg13[8], res_kind = cfg13[9], opad = cfg13[10], rpad = cfg13[11], guard = cfg13[12];
+  FP_CHECK((is_q8(dt) || dt == DT_F16) && odt >= 0 && odt <= DT_F16RQ_I8 && odt != DT_BF16 && (is_q8(dt) ? s_in != nullptr : !s_out_fold), "fpt_conv_q8_raw: invalid element types");
+  FP_CHECK(Cin >= 64 && Cin % 64 == 0 && Cin <= 512 && Cout >= 128 && Cout % 128 == 0 && Cout <= 512 && (stride == 1 || stride == 2) && NB >= 1 && NB <= 4096 && H >= 2 && H <= 80 &&
+               H % 2 == 0 && split >= 0 && split < NB && (split == 0 || NB <= 2 * split) && opad >= 0 && opad <= 1 && rpad >= 0 && rpad <= 1 && guard >= 1, "fpt_conv_q8_raw: invalid shape");
+  FP_CHECK(res_kind >= 0 && res_kind <= 2 && (res_kind == 0) == (res == nullptr) && (res_kind == 2) == (rscale != nullptr) && (res_kind == 2) == odt_rq(odt), "fpt_conv_q8_raw: residual arguments do not match the output type");
+  FP_CHECK((oinv != nullptr) == (odt_dual(odt) || odt_qs(odt)) && (!post || (odt_16(odt) == DT_F16 && !odt_dual(odt) && opad == 0 && split == 0)) && (!bias_img || dt == DT_I8),
+           "fpt_conv_q8_raw: table arguments do not match the output type");
+  const int es = elem_bytes(dt), Hp = H + 2, OH = (H + 2 - 3) / stride + 1, OHp = OH + 2 * opad, RHp = OH + 2 * rpad;
+  const int NBo = split ? split : NB, out_ld = split ? 2 * Cout : Cout;
+  const size_t nx = (size_t)NB * Hp * Hp * Cin * es, nw = (size_t)Cout * 9 * Cin, nout = (size_t)(NBo + guard) * OHp * OHp * out_ld;
+  const size_t nres = res ? (size_t)NB * RHp * RHp * Cout * (res_kind == 2 ? 1 : 2) : 0;
+  FP_CHECK((out16 != nullptr) == (odt_16(odt) >= 0) && (out8 != nullptr) == (odt_q(odt) >= 0), "fpt_conv_q8_raw: output buffers do not match the output type");
+  DevBuf<unsigned char> dx(nx), dres(nres), d16(out16 ? nout * 2 : 0), d8(out8 ? nout : 0), dpost(post ? (size_t)OH * OH * Cout * 2 : 0);
+  FP_CHECK(dx.p && dres.p && d16.p && d8.p && dpost.p, "fpt_conv_q8_raw: allocation failed");
+  {
+    std::vector<unsigned char> hx(nx, dt == DT_I8 ? 0x80 : 0x00);
+    const size_t row = (size_t)H * Cin * es;
+    for (int n = 0; n < NB; n++)
+      for (int y = 0; y < H; y++)
+        std::memcpy(&hx[(((size_t)n * Hp + y + 1) * Hp + 1) * Cin * es], (const unsigned char *)x + ((size_t)n * H + y) * row, row);
+    FP_HIP_OK(fp::memcpy_sync(dx.p, hx.data(), nx, hipMemcpyHostToDevice));
+  }
+  if (res) FP_HIP_OK(fp::memcpy_sync(dres.p, res, nres, hipMemcpyHostToDevice));
+  if (post) FP_HIP_OK(fp::memcpy_sync(dpost.p, post, (size_t)OH * OH * Cout * 2, hipMemcpyHostToDevice));
+  if (out16) FP_HIP_OK(fp::memcpy_sync(d16.p, out16, nout * 2, hipMemcpyHostToDevice));
+  if (out8) FP_HIP_OK(fp::memcpy_sync(d8.p, out8, nout, hipMemcpyHostToDevice));
+  Net net;
+  if (is_q8(dt)) { net.prec = dt == DT_FP8 ? PREC_FP8 : PREC_INT8; net.qdt = dt; }
+  ConvLayer L;
+  L.Cin = Cin; L.Cout = Cout; L.KH = 3; L.KW = 3; L.stride = stride; L.pad = 1;
+  FP_CHECK(finish_layer(&net, std::vector<float>(w, w + nw), std::vector<float>(bias, bias + Cout), Cout, 9, Cin, dt, &L), "fpt_conv_q8_raw: weight upload failed");
+  if (is_q8(dt)) {
+    if (apply_q8_layer(&net, L, dt, s_in, nullptr, s_out_fold, true)) return 1;
+    if (wq || sw) {   // the same quantiser call apply_q8_layer made (no calibration means): the codes in the caller's [Cout][tap][Cin] order
+      std::vector<float> hsw, tm; std::vector<double> qs;
+      const auto e = quantise_q8(L, dt, s_in, &hsw, &qs, nullptr, 0, dt == DT_I8 ? &tm : nullptr);
+      FP_CHECK(hsw == L.q_sw, "fpt_conv_q8_raw: the quantiser is not reproducible");
+      if (wq) std::memcpy(wq, e.data(), nw);
+      if (sw) std::memcpy(sw, hsw.data(), (size_t)Cout * 4);
+    }
+    if (cscale) FP_HIP_OK(fp::memcpy_sync(cscale, L.cscale, (size_t)Cout * 4, hipMemcpyDeviceToHost));
+    if (bias_up) FP_HIP_OK(fp::memcpy_sync(bias_up, L.bias, (size_t)Cout * 4, hipMemcpyDeviceToHost));
+    if (tmat_t && dt == DT_I8) FP_HIP_OK(fp::memcpy_sync(tmat_t, L.tmat_t, (size_t)Cin * Cout * 4, hipMemcpyDeviceToHost));
+  }
+  float *rscale_dev = nullptr, *oinv_dev = nullptr, *bimg_dev = nullptr;
+  if (rscale) { rscale_dev = upload(&net, std::vector<float>(rscale, rscale + Cout)); FP_CHECK(rscale_dev, "fpt_conv_q8_raw: allocation failed"); }
+  if (oinv) { oinv_dev = upload(&net, std::vector<float>(oinv, oinv + Cout)); FP_CHECK(oinv_dev, "fpt_conv_q8_raw: allocation failed"); }
+  if (bias_img) { bimg_dev = upload(&net, std::vector<float>(bias_img, bias_img + (size_t)NB * Cout)); FP_CHECK(bimg_dev, "fpt_conv_q8_raw: allocation failed"); }
+  Ctx c{nullptr, nullptr, &net};
+  const int qo = odt_q(odt);
+  const Act ain{dx.p, dt, 1.f}, a16{d16.p, DT_F16, 1.f}, aq{d8.p, qo >= 0 ? qo : DT_I8, 1.f}, ares{dres.p, res_kind == 2 ? DT_I8 : DT_F16, 1.f};
+  const bool two = odt_16(odt) >= 0;   // a 2-byte tensor is written (alone, or with its 8-bit copy)
+  bool fused = false;
+  g_last_conv_plan = ConvPlan{}; g_last_conv_odt = -1;
+  if (run_conv(c, "t", L, ain, NB, H, H, 1, two ? a16 : aq, opad, relu != 0, res ? &ares : nullptr, rpad, split, nullptr, post ? dpost.p : nullptr, &fused,
+               odt_dual(odt) ? &aq : nullptr, oinv_dev, rscale_dev, bimg_dev)) return 1;
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipDeviceSynchronize());
+  FP_CHECK(g_last_conv_odt == odt, "fpt_conv_q8_raw: run_conv dispatched another output type than the case names");
+  if (out16) FP_HIP_OK(fp::memcpy_sync(out16, d16.p, nout * 2, hipMemcpyDeviceToHost));
+  if (out8) FP_HIP_OK(fp::memcpy_sync(out8, d8.p, nout, hipMemcpyDeviceToHost));
+  const ConvPlan &pl = g_last_conv_plan;
+  FP_CHECK(pl.post_fused == fused, "fpt_conv_q8_raw: the recorded plan is not the one that ran");
+  std::memset(plan26, 0, 26 * sizeof(int));
+  plan26[0] = pl.n; plan26[1] = pl.post_fused ? 1 : 0;
+  for (int i = 0; i < pl.n; i++) {
+    const ConvStep &st = pl.step[i];
+    const int f[6] = {st.kernel, st.m_begin, st.M, st.post ? 1 : 0, (int)st.grid, st.mi};
+    std::memcpy(plan26 + 2 + 6 * i, f, sizeof(f));
+  }
+  return 0;
+}
+
+// q8_copy_kernel<qdt> through the product's launch (launch_q8_copy): x16 [imgs][HW + 2][HW + 2][C] f16 bits, q the 1-byte buffer of the same
+// shape plus guard_imgs images, uploaded as given and downloaded after the launch; oinv [C].  info2 = {grid, block}.
+int fpt_q8_copy_raw(const uint16_t *x16, const float *oinv, int imgs, int HW, int C, int qdt, int guard_imgs, unsigned char *q, int *info2) {
+  using namespace fp;
+  FP_CHECK(x16 && oinv && q && info2 && is_q8(qdt) && imgs >= 1 && HW >= 1 && C >= 8 && C % 8 == 0 && guard_imgs >= 1, "fpt_q8_copy_raw: invalid arguments");
+  const size_t px = (size_t)(HW + 2) * (HW + 2), nin = (size_t)imgs * px * C, nq = (size_t)(imgs + guard_imgs) * px * C;
+  DevBuf<uint16_t> dx(nin);
+  DevBuf<unsigned char> dq(nq);
+  DevBuf<float> doi(C);
+  FP_CHECK(dx.p && dq.p && doi.p, "fpt_q8_copy_raw: allocation failed");
+  FP_HIP_OK(fp::memcpy_sync(dx.p, x16, nin * 2, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dq.p, q, nq, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(doi.p, oinv, (size_t)C * 4, hipMemcpyHostToDevice));
+  info2[0] = (int)launch_q8_copy(nullptr, qdt, dx.p, dq.p, doi.p, imgs, HW, C); info2[1] = 256;
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipDeviceSynchronize());
+  FP_HIP_OK(fp::memcpy_sync(q, dq.p, nq, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// q8_img_bias_fused_kernel through the product's launch (launch_q8_img_bias_fused): xq [n_img][HW + 2][HW + 2][Cin] bytes (u ^ 0x80, border
+// included as the caller filled it), tmat_t [Cin][Cout], cscale / bias [Cout]; form 0 = the lattice sums, 1 = every pixel (wp2 = 0),
+// 2 = the three-launch form (q8_img_sum_kernel, q8_img_bias_kernel, clear).  out [n_img + guard_imgs][Cout] f32 bit patterns, uploaded as
+// given and downloaded after the launch.  info2 = {grid, block} (form 2: of the sum kernel's x dimension).
+int fpt_q8_img_bias_raw(const unsigned char *xq, const float *tmat_t, const float *cscale, const float *bias, int n_img, int HW, int Cin, int Cout,
+                        int form, int guard_imgs, uint32_t *out, int *info2) {
+  using namespace fp;
+  FP_CHECK(xq && tmat_t && cscale && bias && out && info2 && n_img >= 1 && (HW == 40 || HW == 20) && Cin >= 128 && Cin <= 512 && Cin % 128 == 0 && Cout >= 128 &&
+               Cout <= 512 && Cout % 128 == 0 && form >= 0 && form <= 2 && guard_imgs >= 1, "fpt_q8_img_bias_raw: invalid arguments");
+  const size_t nx = (size_t)n_img * (HW + 2) * (HW + 2) * Cin, no = (size_t)(n_img + guard_imgs) * Cout;
+  DevBuf<unsigned char> dx(nx);
+  DevBuf<float> dt_((size_t)Cin * Cout), dcs(Cout), dbi(Cout);
+  DevBuf<uint32_t> dout(no);
+  DevBuf<int> dsum((size_t)n_img * Cin);
+  FP_CHECK(dx.p && dt_.p && dcs.p && dbi.p && dout.p && dsum.p, "fpt_q8_img_bias_raw: allocation failed");
+  FP_HIP_OK(fp::memcpy_sync(dx.p, xq, nx, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dt_.p, tmat_t, (size_t)Cin * Cout * 4, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dcs.p, cscale, (size_t)Cout * 4, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dbi.p, bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dout.p, out, no * 4, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memset_sync(dsum.p, 0, (size_t)n_img * Cin * sizeof(int)));
+  ConvLayer L;
+  L.Cin = Cin; L.Cout = Cout; L.tmat_t = dt_.p; L.cscale = dcs.p; L.bias = dbi.p;
+  if (form == 2) { launch_q8_img_bias_3(nullptr, L, dx.p, n_img, HW, dsum.p, (float *)dout.p); info2[0] = n_img; info2[1] = 256; }
+  else { info2[0] = (int)launch_q8_img_bias_fused(nullptr, L, dx.p, n_img, HW, form == 0, (float *)dout.p); info2[1] = 1024; }
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipDeviceSynchronize());
+  FP_HIP_OK(fp::memcpy_sync(out, dout.p, no * 4, hipMemcpyDeviceToHost));
+  if (form == 2) {
+    std::vector<int> hs((size_t)n_img * Cin);
+    FP_HIP_OK(fp::memcpy_sync(hs.data(), dsum.p, hs.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int v : hs) FP_CHECK(v == 0, "fpt_q8_img_bias_raw: the three-launch form left its sums non-zero");
+  }
+  return 0;
+}
+
+// chan_stats_kernel<dt> through the product's launch (launch_chan_stats): x [pixels][C] raw elements of dt, scale [C] or null;
+// amax [C] f32 (null = not collected) and sum [C] 2^-20 fixed point, both uploaded as given (the kernel accumulates into them).
+// info2 = {grid, block}: grid * block / (C / 8) threads walk every channel.
+int fpt_chan_stats_raw(const void *x, long long pixels, int C, int dt, const float *scale, float *amax, long long *sum, int *info2) {
+  using namespace fp;
+  FP_CHECK(x && sum && info2 && pixels >= 1 && C >= 8 && C % 8 == 0 && dt >= DT_F16 && dt <= DT_I8, "fpt_chan_stats_raw: invalid arguments");
+  const size_t nb = (size_t)pixels * C * elem_bytes(dt);
+  DevBuf<unsigned char> dx(nb);
+  DevBuf<float> dsc(C), dam(C);
+  DevBuf<long long> dsum(C);
+  FP_CHECK(dx.p && dsc.p && dam.p && dsum.p, "fpt_chan_stats_raw: allocation failed");
+  FP_HIP_OK(fp::memcpy_sync(dx.p, x, nb, hipMemcpyHostToDevice));
+  if (scale) FP_HIP_OK(fp::memcpy_sync(dsc.p, scale, (size_t)C * 4, hipMemcpyHostToDevice));
+  if (amax) FP_HIP_OK(fp::memcpy_sync(dam.p, amax, (size_t)C * 4, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dsum.p, sum, (size_t)C * 8, hipMemcpyHostToDevice));
+  info2[0] = (int)launch_chan_stats(nullptr, dt, dx.p, (size_t)pixels, C, scale ? dsc.p : nullptr, amax ? dam.p : nullptr, dsum.p); info2[1] = 256;
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipDeviceSynchronize());
+  if (amax) FP_HIP_OK(fp::memcpy_sync(amax, dam.p, (size_t)C * 4, hipMemcpyDeviceToHost));
+  FP_HIP_OK(fp::memcpy_sync(sum, dsum.p, (size_t)C * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -1,9 +1,12 @@
 """bf16 and FP8 (OCP e4m3) paths: BASELINE.json configs[1] (Track, bf16 refine-net) and configs[4] (1280x720, textured +
 untextured, N = 252, FP8 convolutions).
 
-Kernel level (test build, fpt_conv_dt): every schedule an FP8 / bf16 layer can reach against a torch fp32 reference evaluated on the
-SAME quantised operands -- products of e4m3 / bf16 values are exact in fp32, so what is left is summation order and the
-rounding of the output.  End to end: poses against the f16 path and the oracle pipeline, tolerances stated per test.
+Kernel level (test build, fpt_conv_dt / fpt_conv_q8): a few hand-picked shapes of the bf16 and 8-bit layers against a torch reference
+evaluated on the SAME quantised operands -- products of e4m3 / bf16 values are exact in fp32, so what is left is summation order and the
+rounding of the output.  These are smoke checks with loose bounds.  SCHEDULE COVERAGE of the 8-bit convolutions -- every class of plan
+step an accepted batch size launches, codes held exactly to float64, canaries around every buffer -- is tests/test_q8_conv_gpu.py with
+tests/q8_conv_cases.py and tests/test_q8_conv_cases_cpu.py; the 8-bit helper kernels are tests/test_q8_helpers_gpu.py.
+End to end: poses against the f16 path and the oracle pipeline, tolerances stated per test.
 """
 import ctypes as C
 import os
