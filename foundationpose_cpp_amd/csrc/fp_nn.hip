@@ -22,7 +22,8 @@
 //                               the 9 taps are shifted LDS windows, only weights stream; 2 workgroups per CU.
 //     conv_stem_halo_kernel     the 7x7/s2 stem as a 4x4/s1 conv over the space-to-depth input, same resident-halo scheme.
 //     conv_big_pp_kernel        256x256 implicit-GEMM tile, 8 waves in two ping-pong groups, hand-counted s_waitcnt /
-//                               raw s_barrier; conv_512, the stride-2 convs, Linear layers (full rounds of the 256 CUs).
+//                               raw s_barrier; conv_512, the stride-2 convs, Linear layers (full rounds of the 256 CUs).  Ragged
+//                               rounds: some row tiles of the launch are 288 rows tall and absorb a small left-over (plan_conv).
 //     conv_s2_halo_kernel       the 3x3/s2 conv 64->128 on the 80x80 stem output: the input tile staged one column-parity
 //                               plane at a time (a stride-2 tap is a stride-1 window of one plane).  HBM-bound layer.
 //     conv_pp32_kernel<512,128> 32-wide K-steps, 4-stage ring; the same stride-2 conv below ~30 hypotheses.
@@ -1285,6 +1286,7 @@ FP_HOOK g_conv_variant = 0;    // 0 default; 7 force / 8 disable the resident-ha
 FP_HOOK g_conv_ablate = 0;     // timing-only ablations (wrong results) of conv_big_pp_kernel / conv_halo_kernel
 FP_HOOK g_splitk_ablate = 0;   // test build, wrong results: conv_splitk_reduce_kernel sums all slices but the last (the float64 checks must fail)
 FP_HOOK g_i8_stream = 0;       // test build A/B: 1 = INT8 networks with an 8-bit residual stream (run_trunk_i8; faster, but its common-mode error is frame-specific: DESIGN.md section 4.4)
+FP_HOOK g_conv_ragged = 1;     // 256x256 rounds with 288-row tiles that absorb the left-over rows (plan_conv); 0 = a separate left-over launch, as before them
 FP_HOOK g_smallm = 1;          // small problems (Track, a few objects) on conv_smallx_kernel: K split over the waves of a workgroup, no split-K slabs / reduce launch
                                // (0 = off, 2 = for every size, 3 = its first version, conv_smallm_kernel)
 // the five switches of the schedule behind the trunk: read by heads_override() alone, decided on by plan_heads alone (HeadsOverride)
@@ -1332,6 +1334,7 @@ struct ConvProblem {
   int grp_rows = 0;                    // rows per weight group (ConvGroup), 0 = none
   bool post = false;                   // a positional table is offered (ConvParams::post)
   int conv_variant = 0, conv_ablate = 0, smallm = 1;   // the test build's switches (g_conv_variant, g_conv_ablate, g_smallm)
+  int ragged = 1;                      // ... (g_conv_ragged)
 };
 
 struct ConvStep {
@@ -1343,6 +1346,7 @@ struct ConvStep {
   bool wpack = false;           // gemm_k32_kernel: WPACK
   int ablate = 0;               // test build: the timing-only ablation instantiated (0 = the real kernel)
   int m_begin = 0, M = 0;       // output rows [m_begin, M)
+  int n_tall = 0;               // conv_big_pp_kernel: row tiles of the grid that are 288 rows tall (the ragged rounds), 0 = all 256
   int ksplit = 1, kt_per = 0;   // split-K slices and 128-byte K-steps per slice
   unsigned grid = 0;
   int block = 256, lds = 0;     // threads per workgroup, dynamic LDS bytes
@@ -1378,6 +1382,7 @@ static int plan_conv(const ConvProblem &q, ConvPlan *plan) {
   constexpr int LDS_IG128 = 2 * (128 * 128 + 128 * 128), LDS_IG64 = 2 * (128 * 128 + 64 * 128);
   constexpr int LDS3_128 = 3 * (256 * 128 + 128 * 128);
   constexpr int LDS_BIG = 2 * (256 * 128 + 256 * 128);
+  constexpr int LDS_BIG_TALL = 2 * (288 * 128 + 256 * 128);
   constexpr int LDS_HALO40 = ((10 * 42 + 7) / 8) * 1024 + 3 * 128 * 64;
   constexpr int LDS_HALO8 = ((10 * 42 + 7) / 8) * 1024 + 128 * 128;
   constexpr int LDS_STEM_HALO = ((11 * 84 + 15) / 16) * 1024 + 3 * 64 * 64;
@@ -1497,6 +1502,17 @@ static int plan_conv(const ConvProblem &q, ConvPlan *plan) {
     // kernel for the left-over (N = 252); otherwise nobody adds it here and the caller launches add_pos_embed_kernel
     post_main = q.post && !QOUT && mt_big > 0 && q.conv_variant == 0 && q.conv_ablate == 0 && KT >= 16 &&
                 (rows_left == 0 || ((rows_left + 63) / 64) * (Cout / 128) <= 256);
+    // Ragged rounds: a left-over of at most one 32-row slice per first-round workgroup is absorbed by the rounds themselves -- n_tall of
+    // their row tiles are 288 rows tall, all dispatched in the first round (conv_big_pp_kernel) -- instead of a deep-ring launch of its
+    // own on an otherwise idle chip.  Every row keeps its K order, so the outputs are the same bits.  Not with the positional table
+    // offered (that schedule, rounds + deep ring both adding the table, stays as it is), not for the 8-bit types (no tall body), and
+    // only where the tile -> row map of the kernel holds: whole rounds, a channel-tile count that divides an XCD's share of a round.
+    const int n_tall = (rows_left + 31) / 32;
+    if (q.ragged && B2 && SAME && mt_big > 0 && rows_left > 0 && q.conv_variant == 0 && q.conv_ablate == 0 && !q.post && 256 % nt2 == 0 &&
+        n_tall * nt2 <= 256) {
+      add(CK_BIG_PP, "conv_big_pp_kernel", M, mt_big * nt2, 512, LDS_BIG_TALL).n_tall = n_tall;
+      return finish();
+    }
     if (mt_big > 0) {
       const int a = q.conv_ablate;
       ConvStep &st = add(CK_BIG_PP, "conv_big_pp_kernel", mt_big * 256, mt_big * nt2, 512, LDS_BIG, (double)(mt_big * 256) / (double)M);
@@ -2047,7 +2063,7 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
   p.out_ld = split_imgs > 0 ? 2 * L.Cout : L.Cout;
   p.res_ld = L.Cout;
   p.ksplit = 1; p.kt_per = p.krow_b / 128; p.partial = nullptr;
-  p.m_begin = 0;
+  p.m_begin = 0; p.n_tall = 0;
   FP_CHECK(ipad >= L.pad && (p.cin_b == 64 || p.cin_b % 128 == 0) && p.krow_b % 128 == 0 && (L.Cout % 64) == 0 &&
                (p.cin_b != 64 || L.KW % 2 == 0) && p.krow_b / 128 <= 80,
            "conv shape not supported by the MFMA kernel");
@@ -2109,7 +2125,7 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
   q.has_res = res != nullptr; q.split_imgs = split_imgs;
   q.grp_rows = grp ? grp->rows : 0;
   q.post = post != nullptr;
-  q.conv_variant = g_conv_variant; q.conv_ablate = g_conv_ablate; q.smallm = g_smallm;
+  q.conv_variant = g_conv_variant; q.conv_ablate = g_conv_ablate; q.smallm = g_smallm; q.ragged = g_conv_ragged;
   ConvPlan plan;
   if (plan_conv(q, &plan)) return 1;
   if (post_fused) *post_fused = plan.post_fused;
@@ -2118,7 +2134,7 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
 #endif
   for (int i = 0; i < plan.n; i++) {
     const ConvStep &st = plan.step[i];
-    p.m_begin = st.m_begin; p.M = st.M;
+    p.m_begin = st.m_begin; p.M = st.M; p.n_tall = st.n_tall;
     p.ksplit = st.ksplit; p.kt_per = st.kt_per;
     p.post = st.post ? (const unsigned char *)post : nullptr;
     if (st.ksplit > 1 && ensure_splitk(c, (size_t)st.ksplit * (st.M - st.m_begin) * L.Cout, &p.partial)) return 1;

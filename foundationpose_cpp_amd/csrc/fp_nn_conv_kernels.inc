@@ -82,6 +82,7 @@ struct ConvParams {
   unsigned koff[80];
   unsigned koff32[160];  // same per 64-byte K-step (conv_pp32_kernel)
   int m_begin;            // first output row handled by this launch (hybrid 256^2 + 128^2 launches)
+  int n_tall;             // conv_big_pp_kernel: row tiles that are 288 rows tall instead of 256 (the ragged rounds), 0 = none
   int ksplit, kt_per;     // split-K (small problems): K-steps [split*kt_per, ...) per workgroup, fp32 partial slabs
   float *partial;         // [ksplit][M - m_begin][Cout]
   // weight groups along M (the refiner's two heads in ONE launch at small N, conv_igemm_kernel only): rows
@@ -130,7 +131,9 @@ __device__ __forceinline__ int pack4_u8(float a, float b, float c, float d) {
   w = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(d), 3, w);
   return (int)(w ^ 0x80808080u);
 }
-template <int MI, int NI, int DT, int ODT, int EABL = 0, int NIT = NI, int NI0 = 0, class PixFn>  // EABL: 1 = no stores, 2 = no residual loads (timing ablations / layers without residual), 4 = add ConvParams::post
+// EABL: 1 = no stores, 2 = no residual loads (timing ablations / layers without residual), 4 = add ConvParams::post, 8 = pass 1 ends before
+// the pixel groups begin (below)
+template <int MI, int NI, int DT, int ODT, int EABL = 0, int NIT = NI, int NI0 = 0, class PixFn>
 __device__ __forceinline__ void conv_epilogue_px(const ConvParams &p, f4 (&acc)[NIT][MI], int n_base, int lane, PixFn pix,
                                                  int bias_off = 0, int res_img_off = 0) {
   static_assert(NI == 4 || NI == 2, "wave covers 64 or 32 channels");
@@ -171,6 +174,15 @@ __device__ __forceinline__ void conv_epilogue_px(const ConvParams &p, f4 (&acc)[
         else acc[NI0 + ni][mi][jj] += bv[e];
       }
     }
+  }
+  // EABL & 8 (conv_big_pp_kernel with its two tile heights): every accumulator is final here, so no bias value stays live into the pixel
+  // groups.  Without it the compiler interleaves the bias pass with the groups' residual loads and, in the kernel that holds both bodies,
+  // runs out of its 256 registers (16 spilled, 36 bytes of scratch); with it 241 and none.  Same operations, same values.
+  if constexpr ((EABL & 8) != 0) {
+#pragma unroll
+    for (int a = 0; a < NI; a++)
+#pragma unroll
+      for (int b = 0; b < MI; b++) asm volatile("" : "+v"(acc[NI0 + a][b]));
   }
   float oi[SCALED ? NS : 1][8];  // 1 / (scale of output channel c in the 8-bit copy)
   if constexpr (SCALED) {
@@ -1008,40 +1020,40 @@ __global__ __launch_bounds__(512, 2) void conv_pp_kernel(const ConvParams p) {
 // under the matrix pipe.  8 waves (2 along pixels x 4 along channels), wave tile 128 x 64 (32 accumulators), BK = 64,
 // two 64-KB LDS stages, one workgroup per CU.  Needs Cout % 256 == 0.
 // -------------------------------------------------------------------------------------------------
-// Ping-pong schedule of the 256 x 256 tile (see the slot comment inside).
-template <int ABL, int DT, int ODT = DT, bool POST = false, bool LSTORE = false>  // LSTORE: epilogue stores staged through LDS (conv_epilogue_lds)
-__global__ __launch_bounds__(512, 2) void conv_big_pp_kernel(const ConvParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int BM = 256, BN = 256;
+// Ping-pong schedule of the 256 x 256 tile (see the slot comment inside), as a device function of the pixel fragments per wave:
+// MI = 8 is the 256-row tile, MI = 9 the 288-row tile of the ragged rounds (two ping-pong groups of 144 rows; the weight side -- BN,
+// NI, wpack128, stage_w -- is the same, an LDS stage is 288 * 128 + 256 * 128 bytes).  m0 / nt: first output row / channel tile.
+template <int MI, int ABL, int DT, int ODT, bool POST, bool LSTORE>
+__device__ __forceinline__ void conv_big_pp_body(const ConvParams &p, unsigned char *smem, const int m0, const int nt) {
+  constexpr int BM = MI * 32, BN = 256;
   constexpr int XB = BM * 128, WB = BN * 128, STAGE = XB + WB;
-  constexpr int MI = 8, NI = 4;
+  constexpr int NI = 4;
+  // the X tile is BM / 8 pieces of 8 rows x 128 bytes: every wave stages PLO of them, the first PREM waves one more (288 rows: 36
+  // pieces, waves 0-3 five, waves 4-7 four).  The loop only ever waits with vmcnt(0), so the uneven counts need no re-counted waits.
+  constexpr int NPX = BM / 8, PLO = NPX / 8, PREM = NPX % 8, PHI = PLO + (PREM ? 1 : 0);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;  // wm doubles as the ping-pong group: waves w and w+4 share a SIMD
-  const int n_tiles = p.Cout / BN;
-  int logical;
-  {
-    const int nblk = gridDim.x, b = blockIdx.x;
-    const int xcd = b & 7, within = b >> 3, q = nblk >> 3, r = nblk & 7;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
-  const int mt = logical / n_tiles, nt = logical - mt * n_tiles;
-  const int m0 = mt * BM, n0 = nt * BN;
+  const int n0 = nt * BN;
   const int ohw = p.OH * p.OW;
   const int IHp = p.H + 2 * p.ipad, IWp = p.W + 2 * p.ipad;
 
   const int srow = lane >> 3;
   const int g = (lane & 7) ^ srow;
-  unsigned xoff[4], woffv[4];
+  const int px0 = wave * PLO + min(wave, PREM);   // the wave's first X piece
+  unsigned xoff[PHI], woffv[4];
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    int m = min(m0 + (wave * 4 + i) * 8 + srow, p.M - 1);
+  for (int i = 0; i < PHI; i++) {
+    int m = min(m0 + (px0 + i) * 8 + srow, p.M - 1);
     int img = m / ohw;
     int rem = m - img * ohw;
     int oh = rem / p.OW, ow = rem - oh * p.OW;
     int ih0 = oh * p.stride - p.pad + p.ipad, iw0 = ow * p.stride - p.pad + p.ipad;
     xoff[i] = (unsigned)(((img * IHp + ih0) * IWp + iw0) * p.cin_b + g * 16);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
     int row = (wave * 4 + i) * 8 + srow;
     woffv[i] = (unsigned)((n0 + row) * p.krow_b + g * 16);
   }
@@ -1049,13 +1061,14 @@ __global__ __launch_bounds__(512, 2) void conv_big_pp_kernel(const ConvParams p)
   const unsigned char *w_b = p.w;
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
 
-  // the 8 LDS-DMA instructions of a K-step are issued in two halves (X pieces in the wave's L0 slot, W pieces at the
+  // the 8 (9) LDS-DMA instructions of a K-step are issued in two halves (X pieces in the wave's L0 slot, W pieces at the
   // head of its M0 slot) so the address path (64 B/clk/CU) sees them spread over three slots instead of bunched in two
   auto stage_x = [&](int kt, int buf) {
     const unsigned xs = lds_base + buf * STAGE;
     const unsigned char *xb = in_b + p.koff[kt];
 #pragma unroll
-    for (int i = 0; i < 4; i++) glds16_asm(xb + xoff[i], xs + (wave * 4 + i) * 1024);
+    for (int i = 0; i < PHI; i++)
+      if (i < PLO || wave < PREM) glds16_asm(xb + xoff[i], xs + (px0 + i) * 1024);   // (wave-uniform)
   };
   // (ConvParams::wpack128, pack_stage_w128) this wave's 4 KB of every K-step as one run: one address + one M0 per stage
   const bool packed = p.wpack128 != nullptr;   // (wave-uniform: a scalar branch)
@@ -1079,7 +1092,7 @@ __global__ __launch_bounds__(512, 2) void conv_big_pp_kernel(const ConvParams p)
 #pragma unroll
   for (int ks = 0; ks < 2; ks++) {
     int slot = (ks * 4 + fk) ^ (lane & 7);
-    xfo[ks] = (wm * 128 + frow) * 128 + slot * 16;
+    xfo[ks] = (wm * (MI * 16) + frow) * 128 + slot * 16;   // (MI * 16 is a multiple of 8: row & 7 == lane & 7 in both groups)
     wfo[ks] = XB + (wn * 64 + frow) * 128 + slot * 16;
   }
 
@@ -1095,7 +1108,7 @@ __global__ __launch_bounds__(512, 2) void conv_big_pp_kernel(const ConvParams p)
   // so on every SIMD one wave issues MFMAs from registers while its partner refills fragments from LDS / issues the next
   // tile's LDS-DMA.  The slot sequence is the same for every element type (FP_PP_LOOP); what a half-slot reads and
   // multiplies differs:
-  //   2-byte types: half h = the 32-wide k-step h over all 8 pixel fragments (12 fragment reads, 32 MFMAs);
+  //   2-byte types: half h = the 32-wide k-step h over all MI pixel fragments (8 + 4 fragment reads, 32 MFMAs; the 288-row tile 9 + 4, 36);
   //   FP8: one 128-wide MFMA consumes the whole 128-byte row, so the halves split the PIXEL fragments instead: half 0 reads
   //        the 4 weight operands (kept for both halves) + pixel fragments 0..3, half 1 pixel fragments 4..7.
 #define FP_PP_LOOP(LD0, LD1, MF0, MF1)                                   \
@@ -1213,12 +1226,47 @@ __global__ __launch_bounds__(512, 2) void conv_big_pp_kernel(const ConvParams p)
       for (int b = 0; b < MI; b++) asm volatile("" ::"v"(acc[a][b]));
     return;
   }
-  if constexpr (LSTORE && ABL == 0 && !POST && !is_q8(DT) && odt_q(ODT) < 0) {
+  if constexpr (LSTORE && MI == 8 && ABL == 0 && !POST && !is_q8(DT) && odt_q(ODT) < 0) {
     __syncthreads();   // both ping-pong groups are done with the ring: 8 x (8 KB tile + 256 B offsets) of it become the staging area
     conv_epilogue_lds<MI, NI, DT, ODT, 4>(p, acc, m0 + wm * 128, n0 + wn * 64, lane, smem + wave * (4 * 16 * 128 + 4 * 64));
     return;
   }
-  conv_epilogue<MI, NI, DT, ODT, ((ABL >> 3) & 3) | (POST ? 4 : 0)>(p, acc, m0 + wm * 128, n0 + wn * 64, lane);
+  constexpr bool RAGGED = ABL == 0 && !POST && !LSTORE && !is_q8(DT) && odt_q(ODT) < 0;   // the kernel holds this body at both heights
+  conv_epilogue<MI, NI, DT, ODT, ((ABL >> 3) & 3) | (POST ? 4 : 0) | (RAGGED ? 8 : 0)>(p, acc, m0 + wm * (MI * 16), n0 + wn * 64, lane);
+}
+
+// The launch: workgroup -> (row tile, channel tile).  `logical` hands each XCD a contiguous chunk of tiles (the two channel tiles of a
+// row tile are neighbours on one XCD and share the X tile in its L2).
+// Ragged rounds (ConvParams::n_tall > 0; plan_conv): the grid is whole rounds of the 256 CUs and n_tall of its row tiles are 288 rows
+// tall instead of 256, so that the rounds cover [m_begin, M) without a left-over launch.  The hardware dispatches workgroups in
+// blockIdx order, round-robin over the XCDs, so the first round is the workgroups with blockIdx.x >> 3 < 32: the tall row tiles are the
+// FIRST t_x row tiles of each XCD's chunk (t_x = n_tall / 8, one more on the first n_tall % 8 XCDs; t_x * n_tiles <= 32), all in the
+// first round -- in the last they would be its tail.  Row tiles stay in row order, each 32 rows further down per tall tile in front of
+// it: an exact partition of [m_begin, m_begin + 256 * row tiles + 32 * n_tall), which reaches M; rows >= M are clamped on load and
+// masked in the epilogue.  A wave-uniform branch picks the body.  The 8-bit, POST, LSTORE and ablation instantiations have no tall body.
+template <int ABL, int DT, int ODT = DT, bool POST = false, bool LSTORE = false>  // LSTORE: epilogue stores staged through LDS (conv_epilogue_lds)
+__global__ __launch_bounds__(512, 2) void conv_big_pp_kernel(const ConvParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr bool RAGGED = ABL == 0 && !POST && !LSTORE && !is_q8(DT) && odt_q(ODT) < 0;
+  const int n_tiles = p.Cout / 256;
+  const int nblk = gridDim.x, b = blockIdx.x;
+  const int xcd = b & 7, within = b >> 3, q = nblk >> 3, r = nblk & 7;
+  const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
+  const int mt = logical / n_tiles, nt = logical - mt * n_tiles;
+  int m0 = p.m_begin + mt * 256;
+  if constexpr (RAGGED) {
+    if (p.n_tall > 0) {   // (nblk % 256 == 0 and 256 % n_tiles == 0: r == 0, an XCD's chunk is q / n_tiles whole row tiles)
+      const int tq = p.n_tall >> 3, tr = p.n_tall & 7;
+      const int t_x = tq + (xcd < tr ? 1 : 0);   // tall row tiles of this XCD
+      const int lt = within / n_tiles;           // row tile within the XCD's chunk: mt == xcd * (q / n_tiles) + lt
+      m0 += 32 * (xcd * tq + min(xcd, tr) + min(lt, t_x));
+      if (lt < t_x) {
+        conv_big_pp_body<9, ABL, DT, ODT, POST, LSTORE>(p, smem, m0, nt);
+        return;
+      }
+    }
+  }
+  conv_big_pp_body<8, ABL, DT, ODT, POST, LSTORE>(p, smem, m0, nt);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -163,7 +163,10 @@ int fpt_quantise_q8(int dt, const float *rows, int Cout, int ntaps, int Cin, con
 // the kernels' output type (fp_nn.h, DT_*); flags: 1 = residual, 2 = a positional table is offered, 4 / 8 = the layer carries the
 // fragment-order / gemm_k32_kernel's stage-order copy of its weights.  Returns the number of steps (-1 = no plan) and copies up to `max`
 // of them out: fields11 [max][11] = the launch-log record {net = -1, prec = -1, side = 0, m_begin, M, ksplit, pe} + {kernel (ConvKernel),
-// kt_per, grid, LDS bytes}, names [max][name_cap]; *post_fused = every row got the positional table.
+// kt_per, grid, LDS bytes}, names [max][name_cap]; *post_fused = every row got the positional table.  fpt_plan_conv_tall(i): the 288-row
+// tiles (ConvStep::n_tall) of step i of the plan the last fpt_plan_conv call returned, -1 = no such step.
+static fp::ConvPlan g_hook_conv_plan;
+int fpt_plan_conv_tall(int i) { return i >= 0 && i < g_hook_conv_plan.n ? g_hook_conv_plan.step[i].n_tall : -1; }
 int fpt_plan_conv(const int *shape10, int dt, int odt, int flags, int split_imgs, int grp_rows, int *fields11, char *names, int name_cap, int max, int *post_fused) {
   fp::ConvProblem q;
   q.Cin = shape10[0]; q.Cout = shape10[1]; q.KH = shape10[2]; q.KW = shape10[3]; q.stride = shape10[4]; q.pad = shape10[5];
@@ -171,9 +174,11 @@ int fpt_plan_conv(const int *shape10, int dt, int odt, int flags, int split_imgs
   q.dt = dt; q.odt = odt;
   q.has_res = (flags & 1) != 0; q.post = (flags & 2) != 0; q.wfrag = (flags & 4) != 0; q.wpack = (flags & 8) != 0;
   q.split_imgs = split_imgs; q.grp_rows = grp_rows;
-  q.conv_variant = fp::g_conv_variant; q.conv_ablate = fp::g_conv_ablate; q.smallm = fp::g_smallm;
+  q.conv_variant = fp::g_conv_variant; q.conv_ablate = fp::g_conv_ablate; q.smallm = fp::g_smallm; q.ragged = fp::g_conv_ragged;
   fp::ConvPlan plan;
+  g_hook_conv_plan = fp::ConvPlan{};
   if (fp::plan_conv(q, &plan)) return -1;
+  g_hook_conv_plan = plan;
   for (int i = 0; i < plan.n && i < max; i++) {
     const fp::ConvStep &st = plan.step[i];
     const int f[11] = {-1, -1, 0, st.m_begin, st.M, st.ksplit, st.post ? 1 : 0, st.kernel, st.kt_per, (int)st.grid, st.lds};
@@ -210,6 +215,7 @@ void fpt_plan_track_window(const float *K9, float diameter, const float *poses16
 }
 void fpt_depth_filter_tile(int *tile_w, int *tile_h) { *tile_w = fp::DEPTH_FILTER_TILE_W; *tile_h = fp::DEPTH_FILTER_TILE_H; }
 void fpt_set_conv_variant(int v) { fp::g_conv_variant = v; }
+void fpt_set_conv_ragged(int v) { fp::g_conv_ragged = v != 0; }   // (a captured graph keeps the schedule it was captured with: an A/B must re-capture)
 void fpt_set_i8_stream(int v) { fp::g_i8_stream = v; }
 void fpt_set_q8_blocks(int v) { fp::g_q8_blocks = v & fp::Q8_BLOCKS_ALL; }   // [r6] stage mask of 8-bit networks loaded from now on (tools/q8_blocks.py)
 void fpt_set_conv_ablate(int v) { fp::g_conv_ablate = v; }
@@ -243,7 +249,9 @@ int fpt_clk_probe(int blocks, double *mhz_out, double *loop_cycles_out) {
 // x [NB,H,W,Cin] NHWC f32, w [Cout,KH,KW,Cin] f32, bias [Cout], res (optional) [NB,OH,OW,Cout]
 // -> out f32 [NB,OH,OW,Cout] (or, with split_imgs > 0, [NB-split,OH,OW,2*Cout]).  iters > 1: returns mean ms in *ms_out.
 // dt = element type of x / w / res on the device (DT_F16 / DT_BF16), out_dt = element type of the output; the scale arguments are
-// ignored (kept for the callers' signature).  8-bit layers: fpt_conv_q8.
+// ignored (kept for the callers' signature).  8-bit layers: fpt_conv_q8.  The output buffer carries CONV_DT_GUARD canary bytes in front
+// and behind: returns 2 when the launches changed one (a store outside the output rows).
+static constexpr size_t CONV_DT_GUARD = 64 * 1024;
 int fpt_conv_dt(const float *x, const float *w, const float *bias, const float *res, int NB, int H, int W, int Cin, int Cout,
                 int KH, int KW, int stride, int pad, int OH, int OW, int relu, int split_imgs, float *out, int iters,
                 float *ms_out, int dt, int out_dt, float in_scale, float res_scale, float out_scale) {
@@ -254,8 +262,11 @@ int fpt_conv_dt(const float *x, const float *w, const float *bias, const float *
   size_t nx = (size_t)NB * Hp * Wp * Cin, nw = (size_t)Cout * KH * KW * Cin;
   size_t M = (size_t)NB * OH * OW;
   size_t nout = M * Cout;
-  DevBuf<unsigned char> dx(nx * es), dres(nout * es), dout(nout * 2 * oes);
-  FP_CHECK(dx.p && dres.p && dout.p, "fpt_conv: allocation failed");
+  const size_t G = CONV_DT_GUARD;
+  DevBuf<unsigned char> dx(nx * es), dres(nout * es), dguard(nout * oes + 2 * G);
+  FP_CHECK(dx.p && dres.p && dguard.p, "fpt_conv: allocation failed");
+  struct { unsigned char *p; } dout{dguard.p + G};
+  FP_HIP_OK(fp::memset_sync(dguard.p, 0xA5, nout * oes + 2 * G));
   std::vector<float> xp(nx, 0.f);
   for (int n = 0; n < NB; n++)
     for (int y = 0; y < H; y++)
@@ -264,7 +275,7 @@ int fpt_conv_dt(const float *x, const float *w, const float *bias, const float *
           xp[(((size_t)n * Hp + y + ip) * Wp + xx + ip) * Cin + c] = x[(((size_t)n * H + y) * W + xx) * Cin + c];
   auto hx = encode(xp.data(), nx, dt, in_scale);
   FP_HIP_OK(fp::memcpy_sync(dx.p, hx.data(), hx.size(), hipMemcpyHostToDevice));
-  FP_HIP_OK(fp::memset_sync(dout.p, 0, nout * 2 * oes));
+  FP_HIP_OK(fp::memset_sync(dout.p, 0, nout * oes));
   if (res) {
     auto hr = encode(res, nout, dt, res_scale);
     FP_HIP_OK(fp::memcpy_sync(dres.p, hr.data(), hr.size(), hipMemcpyHostToDevice));
@@ -297,6 +308,11 @@ int fpt_conv_dt(const float *x, const float *w, const float *bias, const float *
   std::vector<unsigned char> ho(nout * oes);
   FP_HIP_OK(fp::memcpy_sync(ho.data(), dout.p, ho.size(), hipMemcpyDeviceToHost));
   decode(ho.data(), nout, out_dt, out_scale, out);
+  std::vector<unsigned char> hg(2 * G);
+  FP_HIP_OK(fp::memcpy_sync(hg.data(), dguard.p, G, hipMemcpyDeviceToHost));
+  FP_HIP_OK(fp::memcpy_sync(hg.data() + G, dout.p + nout * oes, G, hipMemcpyDeviceToHost));
+  for (unsigned char v : hg)
+    if (v != 0xA5) { fp::set_error("fpt_conv_dt: the kernels wrote outside the output buffer"); return 2; }
   return 0;
 }
 // One 8-bit convolution exactly as the 8-bit trunk runs it (net_apply_q8 / run_trunk_q8).
