@@ -1692,6 +1692,21 @@ static AttLaunch plan_attention(int B, int T, int pitch, const HeadsOverride &ov
   return a;
 }
 
+// the launch of qkv_tile_kernel over `rows` tokens and of ONE enc_tail_kernel form over `tiles` tiles per head: workgroups and dynamic LDS.
+// The only copies of this arithmetic: plan_heads fills its plan through them, the test build's fpt_qkv_tile_raw / fpt_enc_tail_raw
+// build theirs from them alone.
+static void qkv_tile_launch(int rows, HeadsPlan *plan) {
+  plan->qkv = QKV_TILE;
+  plan->qkv_grid = (unsigned)(rows / QKV_TILE_TOKENS);
+  plan->qkv_lds = LDS_QKV_TILE;
+}
+static void enc_tail_launch(int form, int tiles, HeadsPlan *plan) {
+  plan->tail = form;
+  plan->tail_tiles = tiles;
+  plan->tail_grid = (unsigned)(2 * tiles);
+  plan->tail_lds = form == TAIL_ONE_1 ? LDS_ENC_TAIL_1 : LDS_ENC_TAIL_5;
+}
+
 static int plan_heads(const HeadsQuery &q, HeadsPlan *plan) {
   *plan = HeadsPlan{};
   FP_CHECK(q.dt == DT_F16 || q.dt == DT_BF16, "plan_heads: the transformer part runs on 2-byte elements");
@@ -1710,9 +1725,7 @@ static int plan_heads(const HeadsQuery &q, HeadsPlan *plan) {
   if (track) {
     plan->qkv = QKV_GROUPED;
   } else if (!chain && rows % QKV_TILE_TOKENS == 0 && rows >= QKV_TILE_MIN_ROWS) {
-    plan->qkv = QKV_TILE;
-    plan->qkv_grid = (unsigned)(rows / QKV_TILE_TOKENS);
-    plan->qkv_lds = LDS_QKV_TILE;
+    qkv_tile_launch(rows, plan);
     const int a = ov.qkv_ablate;
     plan->qkv_ablate = (q.dt == DT_F16 && (a == 1 || a == 2 || a == 3 || a == 4 || a == 7)) ? a : 0;
   }
@@ -1721,11 +1734,7 @@ static int plan_heads(const HeadsQuery &q, HeadsPlan *plan) {
   if (!chain) {
     // [r5] everything row-wise behind the attention -- out_proj, LayerNorm 1, FFN, LayerNorm 2 and each tile's share of the read-out -- as ONE
     // launch for both heads, and one small launch that adds the shares up
-    const int tok = track ? ENC_TAIL_TOKENS_1 : ENC_TAIL_TOKENS_5;
-    plan->tail = track ? TAIL_ONE_1 : TAIL_ONE_5;
-    plan->tail_tiles = rows / tok;
-    plan->tail_grid = (unsigned)(2 * plan->tail_tiles);
-    plan->tail_lds = track ? LDS_ENC_TAIL_1 : LDS_ENC_TAIL_5;
+    enc_tail_launch(track ? TAIL_ONE_1 : TAIL_ONE_5, rows / (track ? ENC_TAIL_TOKENS_1 : ENC_TAIL_TOKENS_5), plan);
     plan->pool = POOL_TAIL_PDOT;
     plan->readout = RO_ENC_HEADS;
     plan->fuse_pose = track && q.fuse_offer && ov.fuse_pose;
@@ -2719,6 +2728,19 @@ static EncTailParams enc_tail_params(const Net *net, const void *x, const void *
   return q;
 }
 
+// the launch sites of enc_tail_kernel and enc_heads_kernel (one site each: the dynamic-LDS opt-in of FP_LAUNCH belongs to the site), shared by
+// heads_one_launch and the test build's fpt_enc_tail_raw / fpt_enc_heads_raw
+static void launch_enc_tail(const Ctx &c, int dt, const HeadsPlan &hp, const EncTailParams &q) {
+  with_dt(dt, [&](auto t) {
+    constexpr int DT = decltype(t)::value;
+    if (hp.tail == TAIL_ONE_1) FP_LAUNCH((enc_tail_kernel<DT, 1>), dim3(hp.tail_grid), dim3(512), hp.tail_lds, c.s, q);
+    else FP_LAUNCH((enc_tail_kernel<DT, 5>), dim3(hp.tail_grid), dim3(512), hp.tail_lds, c.s, q);
+  });
+}
+static void launch_enc_heads(const Ctx &c, const EncHeadsParams &p, const PoseUpdateFuse *fuse) {
+  FP_LAUNCH_RAW(enc_heads_kernel, dim3((unsigned)p.n), dim3(64), 0, c.s, p, fuse ? *fuse : PoseUpdateFuse{}, fuse ? 1 : 0);
+}
+
 // The refiner heads of the product (TAIL_ONE_1 / TAIL_ONE_5): QKV projection + self-attention per head (Track: grouped), then ONE launch for
 // everything row-wise behind them (enc_tail_kernel, fp_nn_enc_kernels.inc: five dependent launches per head before, 33 us of Track's 202 us
 // graph) and one for the token mean + Linear(512,3) of both heads, which at Track also applies RefinePostProcess when the plan says so
@@ -2744,17 +2766,13 @@ static int heads_one_launch(const Ctx &c, const HeadsPlan &hp, const Arena &a, i
   {
     NetScope ps(c, "enc_tail", 2.0 * 3.0 * 2.0 * (double)rows * EMBED * EMBED, 2.0 * 2.0 * (double)rows * EMBED * 2.0);
     const EncTailParams q = enc_tail_params(net, a.tokens, att[0], att[1], pdot, hp.tail_tiles);
-    with_dt(dt, [&](auto t) {
-      constexpr int DT = decltype(t)::value;
-      if (hp.tail == TAIL_ONE_1) FP_LAUNCH((enc_tail_kernel<DT, 1>), dim3(hp.tail_grid), dim3(512), hp.tail_lds, c.s, q);
-      else FP_LAUNCH((enc_tail_kernel<DT, 5>), dim3(hp.tail_grid), dim3(512), hp.tail_lds, c.s, q);
-    });
+    launch_enc_tail(c, dt, hp, q);
   }
   FP_TAP(c, TAP_PDOT, pdot, (size_t)2 * hp.tail_tiles * 4 * sizeof(float));
   {
     NetScope ps(c, "small_linear", 2.0 * 2 * N * net->trans.head.out * EMBED, 0);
     const EncHeadsParams p{pdot, {net->trans.head.b, net->rot.head.b}, {trans_dev, rot_dev}, N, hp.tail_tiles / N, net->trans.head.out, (float)SEQ_TOKENS};
-    FP_LAUNCH_RAW(enc_heads_kernel, dim3((unsigned)N), dim3(64), 0, c.s, p, hp.fuse_pose ? *fuse : PoseUpdateFuse{}, hp.fuse_pose ? 1 : 0);
+    launch_enc_heads(c, p, hp.fuse_pose ? fuse : nullptr);
   }
   return 0;
 }

@@ -601,6 +601,211 @@ int fpt_attention_raw(const uint16_t *qkv_bits, int B, int T, int pitch, int dt,
   return 0;
 }
 
+// ---- the tile kernels of the heads on raw operands (tests/test_enc_tail_gpu.py; cases, reference and bounds: tests/enc_tail_cases.py) ----
+// Conventions of fpt_attention_raw: device inputs between TILE_RAW_GUARD guard rows of quiet NaNs, outputs between rows of a canary, the inputs
+// downloaded again after the launch and compared; returns 0, 1 on failure (fp_last_error), 2 when an output guard changed, 3 when an input
+// (or one of its guard rows) changed.
+static constexpr int TILE_RAW_GUARD = 128;            // rows of 512 elements
+static constexpr uint32_t TILE_RAW_CANARY32 = 0xA5C3A5C3u;
+namespace {
+// [guard | rows | guard] of `width` 2-byte elements on the device; the host keeps what it uploaded
+struct GuardedRows {
+  std::vector<uint16_t> host;
+  DevBuf<uint16_t> dev;
+  size_t rows, width;
+  GuardedRows(const uint16_t *bits, size_t rows_, size_t width_, uint16_t fill)
+      : host((rows_ + 2 * TILE_RAW_GUARD) * width_, fill), dev(host.size()), rows(rows_), width(width_) {
+    std::memcpy(host.data() + TILE_RAW_GUARD * width, bits, rows * width * 2);
+  }
+  bool upload() { return dev.p && fp::memcpy_sync(dev.p, host.data(), host.size() * 2, hipMemcpyHostToDevice) == hipSuccess; }
+  uint16_t *data() const { return dev.p + TILE_RAW_GUARD * width; }
+  int changed() const {   // 0 same, 1 changed, -1 the download failed
+    std::vector<uint16_t> now(host.size());
+    if (fp::memcpy_sync(now.data(), dev.p, now.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return now != host;
+  }
+};
+// f32 parameter blocks in ONE device buffer, TILE_RAW_GUARD * 4 quiet NaNs in front of the first, between any two and behind the last: a read
+// past a block lands in NaNs, not in its neighbour.  add() before upload(); at(i) = device address of block i.
+struct GuardedF32 {
+  static constexpr size_t G = (size_t)TILE_RAW_GUARD * 4;
+  std::vector<uint32_t> host = std::vector<uint32_t>(G, 0x7FC00000u);
+  std::vector<size_t> off;
+  uint32_t *dev = nullptr;
+  ~GuardedF32() { if (dev) (void)hipFree(dev); }
+  int add(const float *src, size_t n) {
+    off.push_back(host.size());
+    host.resize(host.size() + n + G, 0x7FC00000u);
+    std::memcpy(host.data() + off.back(), src, n * 4);
+    return (int)off.size() - 1;
+  }
+  bool upload() {
+    return hipMalloc((void **)&dev, host.size() * 4) == hipSuccess && fp::memcpy_sync(dev, host.data(), host.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  const float *at(int i) const { return reinterpret_cast<const float *>(dev + off[(size_t)i]); }
+  int changed() const {
+    std::vector<uint32_t> now(host.size());
+    if (fp::memcpy_sync(now.data(), dev, now.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return now != host;
+  }
+};
+}  // namespace
+
+// One enc_tail_kernel<dt, MI> problem (MI = 1: 16-token tiles, MI = 5: 80-token tiles) of `tiles` tiles per head, launched P times on the same
+// operands -- once per probe set -- through the product's launch site (launch_enc_tail) with the grid and LDS bytes of enc_tail_launch, the
+// arithmetic plan_heads uses; one synchronisation.
+//   att_bits [2][16 MI tiles][512] (per head) and x_bits [16 MI tiles][512]: 2-byte patterns of dt
+//   w [2][3][512][512] f32 (per head: out_proj, lin1, lin2; through finish_layer, so the step-major copy is the loader's), bias [2][3][512],
+//   ln_g / ln_b [2][2][512], head_w [P][2][3][512] f32
+//   pdot [P][2][tiles][4]: uploaded as given (the caller's canary) and downloaded after the launches: slot 3 of every tile must come back as sent
+//   info4 = {MI, tiles, grid, LDS bytes}
+int fpt_enc_tail_raw(int dt, int MI, int tiles, const uint16_t *att_bits, const uint16_t *x_bits, const float *w, const float *bias, const float *ln_g,
+                     const float *ln_b, const float *head_w, int P, float *pdot, int *info4) {
+  using namespace fp;
+  FP_CHECK(att_bits && x_bits && w && bias && ln_g && ln_b && head_w && pdot && info4, "fpt_enc_tail_raw: null argument");
+  FP_CHECK(dt == DT_F16 || dt == DT_BF16, "fpt_enc_tail_raw: the kernel runs on 2-byte elements");
+  FP_CHECK(MI == 1 || MI == 5, "fpt_enc_tail_raw: MI is 1 (16-token tiles) or 5 (80-token tiles)");
+  FP_CHECK(tiles >= 1 && tiles <= 5 * MAX_BATCH && P >= 1 && P <= 1024, "fpt_enc_tail_raw: invalid shape");
+  HeadsPlan hp;
+  enc_tail_launch(MI == 1 ? TAIL_ONE_1 : TAIL_ONE_5, tiles, &hp);
+  const size_t rows = (size_t)tiles * 16 * MI, G = TILE_RAW_GUARD;
+  const uint16_t qnan = dt == DT_BF16 ? 0x7FC0 : 0x7E00;
+  GuardedRows a0(att_bits, rows, EMBED, qnan), a1(att_bits + rows * EMBED, rows, EMBED, qnan), xr(x_bits, rows, EMBED, qnan);
+  FP_CHECK(a0.upload() && a1.upload() && xr.upload(), "fpt_enc_tail_raw: allocation failed");
+  const size_t np = (size_t)P * 2 * tiles * 4, gp = G * 4;
+  std::vector<uint32_t> hp_out(np + 2 * gp, TILE_RAW_CANARY32);
+  std::memcpy(hp_out.data() + gp, pdot, np * 4);
+  DevBuf<uint32_t> dp(hp_out.size());
+  FP_CHECK(dp.p, "fpt_enc_tail_raw: allocation failed");
+  FP_HIP_OK(fp::memcpy_sync(dp.p, hp_out.data(), hp_out.size() * 4, hipMemcpyHostToDevice));
+  Net net;
+  net.act_dt = dt;
+  ConvLayer L[2][3];
+  EncTailParams q{};
+  q.x = (const unsigned char *)xr.data();
+  q.att[0] = (const unsigned char *)a0.data(); q.att[1] = (const unsigned char *)a1.data();
+  q.tiles = tiles;
+  q.head_out = 3;
+  const size_t WW = (size_t)EMBED * EMBED;
+  for (int h = 0; h < 2; h++) {
+    for (int i = 0; i < 3; i++) {
+      ConvLayer &l = L[h][i];
+      l.Cout = l.Cin = EMBED; l.KH = l.KW = 1;
+      const float *wp = w + (size_t)(h * 3 + i) * WW, *bp = bias + (size_t)(h * 3 + i) * EMBED;
+      FP_CHECK(finish_layer(&net, std::vector<float>(wp, wp + WW), std::vector<float>(bp, bp + EMBED), EMBED, 1, EMBED, dt, &l) && l.wstep, "fpt_enc_tail_raw: weight upload failed");
+      q.w[h][i] = l.wstep; q.bias[h][i] = l.bias;
+    }
+  }
+  GuardedF32 par;   // LayerNorm parameters and every (probe set, head) block of read-out rows, NaNs between them (the biases are the loader's uploads)
+  for (int j = 0; j < 4; j++) { par.add(ln_g + (size_t)j * EMBED, EMBED); par.add(ln_b + (size_t)j * EMBED, EMBED); }
+  for (int j = 0; j < 2 * P; j++) par.add(head_w + (size_t)j * 3 * EMBED, (size_t)3 * EMBED);
+  FP_CHECK(par.upload(), "fpt_enc_tail_raw: allocation failed");
+  for (int h = 0; h < 2; h++)
+    for (int i = 0; i < 2; i++) { q.ln_g[h][i] = par.at(2 * (h * 2 + i)); q.ln_b[h][i] = par.at(2 * (h * 2 + i) + 1); }
+  Ctx c{nullptr, nullptr, &net};
+  for (int pi = 0; pi < P; pi++) {
+    q.head_w[0] = par.at(8 + pi * 2);
+    q.head_w[1] = par.at(8 + pi * 2 + 1);
+    q.pdot = reinterpret_cast<float *>(dp.p + gp) + (size_t)pi * 2 * tiles * 4;
+    launch_enc_tail(c, dt, hp, q);
+  }
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipDeviceSynchronize());
+  FP_HIP_OK(fp::memcpy_sync(hp_out.data(), dp.p, hp_out.size() * 4, hipMemcpyDeviceToHost));
+  std::memcpy(pdot, hp_out.data() + gp, np * 4);
+  info4[0] = MI; info4[1] = hp.tail_tiles; info4[2] = (int)hp.tail_grid; info4[3] = hp.tail_lds;
+  for (size_t i = 0; i < gp; i++)
+    if (hp_out[i] != TILE_RAW_CANARY32 || hp_out[gp + np + i] != TILE_RAW_CANARY32) { fp::set_error("fpt_enc_tail_raw: the kernel wrote outside pdot"); return 2; }
+  const int ch[4] = {a0.changed(), a1.changed(), xr.changed(), par.changed()};
+  FP_CHECK(ch[0] >= 0 && ch[1] >= 0 && ch[2] >= 0 && ch[3] >= 0, "fpt_enc_tail_raw: download failed");
+  if (ch[0] || ch[1] || ch[2] || ch[3]) { fp::set_error("fpt_enc_tail_raw: an input buffer changed"); return 3; }
+  return 0;
+}
+
+// qkv_tile_kernel<dt> on `tiles` 80-token tiles through the product's launch (run_qkv) with the grid and LDS bytes of qkv_tile_launch.
+//   x_bits [80 tiles][512] 2-byte patterns, w [1536][512] f32 and bias [1536] (through finish_layer)
+//   out_bits [80 tiles][1536]: uploaded as given and downloaded after the launch;  info3 = {tiles, grid, LDS bytes}
+int fpt_qkv_tile_raw(int dt, int tiles, const uint16_t *x_bits, const float *w, const float *bias, uint16_t *out_bits, int *info3) {
+  using namespace fp;
+  FP_CHECK(x_bits && w && bias && out_bits && info3, "fpt_qkv_tile_raw: null argument");
+  FP_CHECK(dt == DT_F16 || dt == DT_BF16, "fpt_qkv_tile_raw: the kernel runs on 2-byte elements");
+  FP_CHECK(tiles >= 1 && tiles <= 5 * MAX_BATCH, "fpt_qkv_tile_raw: invalid shape");
+  const size_t rows = (size_t)tiles * QKV_TILE_TOKENS;
+  HeadsPlan hp;
+  qkv_tile_launch((int)rows, &hp);
+  GuardedRows xr(x_bits, rows, EMBED, dt == DT_BF16 ? 0x7FC0 : 0x7E00), out(out_bits, rows, 3 * EMBED, 0xA5C3);
+  FP_CHECK(xr.upload() && out.upload(), "fpt_qkv_tile_raw: allocation failed");
+  Net net;
+  net.act_dt = dt;
+  ConvLayer L;
+  L.Cout = 3 * EMBED; L.Cin = EMBED; L.KH = L.KW = 1;
+  FP_CHECK(finish_layer(&net, std::vector<float>(w, w + (size_t)3 * EMBED * EMBED), std::vector<float>(bias, bias + 3 * EMBED), 3 * EMBED, 1, EMBED, dt, &L) && L.wstep,
+           "fpt_qkv_tile_raw: weight upload failed");
+  Ctx c{nullptr, nullptr, &net};
+  if (run_qkv(c, hp, L, xr.data(), (int)rows, out.data())) return 1;
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipDeviceSynchronize());
+  std::vector<uint16_t> ho(out.host.size());
+  FP_HIP_OK(fp::memcpy_sync(ho.data(), out.dev.p, ho.size() * 2, hipMemcpyDeviceToHost));
+  const size_t go = (size_t)TILE_RAW_GUARD * 3 * EMBED;
+  std::memcpy(out_bits, ho.data() + go, rows * 3 * EMBED * 2);
+  info3[0] = tiles; info3[1] = (int)hp.qkv_grid; info3[2] = hp.qkv_lds;
+  for (size_t i = 0; i < go; i++)
+    if (ho[i] != 0xA5C3 || ho[go + rows * 3 * EMBED + i] != 0xA5C3) { fp::set_error("fpt_qkv_tile_raw: the kernel wrote outside its output rows"); return 2; }
+  const int ch = xr.changed();
+  FP_CHECK(ch >= 0, "fpt_qkv_tile_raw: download failed");
+  if (ch) { fp::set_error("fpt_qkv_tile_raw: the input buffer changed"); return 3; }
+  return 0;
+}
+
+// enc_heads_kernel on a caller's pdot [2][n * parts][4] f32 through the product's launch (launch_enc_heads): bias [2][3], tokens.
+//   y [2][n][3]: both heads' outputs.  fused == 0: the product's unfused launch -- a pose (pose_io [16]) and a completion flag (flag_io) sit
+//   on the device all the same, and what the caller put there must come back.  fused != 0 (n == 1): the kernel applies RefinePostProcess to
+//   pose_io [16] (in: the pose, out: the updated pose) with `diameter` and raises the flag; pose_ref [16] = the product's own
+//   pose_update launch (launch_pose_update) on the SAME pose and the y the kernel returned.
+//   y sits between canary floats on the device, pdot and the biases between quiet NaNs.  Returns 0 / 1 / 2 (a guard of y changed) / 3 (pdot,
+//   the biases or a guard of theirs changed).
+int fpt_enc_heads_raw(const float *pdot, const float *bias6, int n, int parts, float tokens, int fused, float diameter, float *pose_io, unsigned *flag_io,
+                      float *pose_ref, float *y) {
+  using namespace fp;
+  FP_CHECK(pdot && bias6 && y && pose_io && flag_io && pose_ref, "fpt_enc_heads_raw: null argument");
+  FP_CHECK(n >= 1 && n <= MAX_BATCH && parts >= 1 && parts <= 25 && tokens > 0.f && (!fused || n == 1), "fpt_enc_heads_raw: invalid shape");
+  const size_t np = (size_t)2 * n * parts * 4, ny = (size_t)2 * n * 3, G = 256;
+  std::vector<uint32_t> hy(ny + 2 * G, TILE_RAW_CANARY32);
+  DevBuf<float> dpose(32);
+  DevBuf<uint32_t> dy(hy.size()), dflag(1);
+  GuardedF32 in;   // block 0: pdot, block 1: the biases, quiet NaNs around both
+  in.add(pdot, np); in.add(bias6, 6);
+  FP_CHECK(dpose.p && dy.p && dflag.p && in.upload(), "fpt_enc_heads_raw: allocation failed");
+  FP_HIP_OK(fp::memcpy_sync(dy.p, hy.data(), hy.size() * 4, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dpose.p, pose_io, 64, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dpose.p + 16, pose_io, 64, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(dflag.p, flag_io, 4, hipMemcpyHostToDevice));
+  float *const y0 = reinterpret_cast<float *>(dy.p + G);
+  const EncHeadsParams p{in.at(0), {in.at(1), in.at(1) + 3}, {y0, y0 + (size_t)n * 3}, n, parts, 3, tokens};
+  const PoseUpdateFuse fuse{dpose.p, diameter, nullptr, nullptr, dflag.p};
+  Ctx c{nullptr, nullptr, nullptr};
+  launch_enc_heads(c, p, fused ? &fuse : nullptr);
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipDeviceSynchronize());
+  if (fused) {   // the product's unfused RefinePostProcess on the other copy of the pose and the y just written
+    launch_pose_update(nullptr, dpose.p + 16, y0, y0 + 3, 1, diameter, nullptr, nullptr);
+    FP_HIP_OK(hipGetLastError());
+    FP_HIP_OK(hipDeviceSynchronize());
+  }
+  FP_HIP_OK(fp::memcpy_sync(hy.data(), dy.p, hy.size() * 4, hipMemcpyDeviceToHost));
+  std::memcpy(y, hy.data() + G, ny * 4);
+  FP_HIP_OK(fp::memcpy_sync(pose_io, dpose.p, 64, hipMemcpyDeviceToHost));
+  FP_HIP_OK(fp::memcpy_sync(pose_ref, dpose.p + 16, 64, hipMemcpyDeviceToHost));
+  FP_HIP_OK(fp::memcpy_sync(flag_io, dflag.p, 4, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < G; i++)
+    if (hy[i] != TILE_RAW_CANARY32 || hy[G + ny + i] != TILE_RAW_CANARY32) { fp::set_error("fpt_enc_heads_raw: the kernel wrote outside y"); return 2; }
+  const int ch = in.changed();
+  FP_CHECK(ch >= 0, "fpt_enc_heads_raw: download failed");
+  if (ch) { fp::set_error("fpt_enc_heads_raw: an input buffer changed"); return 3; }
+  return 0;
+}
+
 // ---- the 8-bit convolutions and their helper kernels on raw bit patterns (tests/test_q8_conv_gpu.py, tests/test_q8_helpers_gpu.py) ----
 // One 3x3 / pad-1 convolution of the 8-bit trunk through run_conv, every operand in device form.
 //   cfg13 = {Cin, Cout, stride, NB, H (= W), dt, odt, relu, split_imgs, res_kind (0 none, 1 f16, 2 8-bit codes + rscale), opad, rpad, guard_imgs}

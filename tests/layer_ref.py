@@ -237,16 +237,36 @@ def refiner_head_names(h):
             "l2_b": L + "linear2.bias", "ln1": L + "norm1", "ln2": L + "norm2", "head_w": p + ".1.weight", "head_b": p + ".1.bias"}
 
 
-def encoder_chain(w: Weights, h, x, att):
+class TensorWeights:
+    """the Weights interface over explicit tensors {name: f32 / float64 tensor} instead of a .fpw file (tests/enc_tail_cases.py)"""
+
+    def __init__(self, tensors, dt, device="cpu"):
+        self.st, self.dt, self.device = tensors, dt, device
+
+    def w(self, name):
+        a = self.st[name]
+        if self.dt is not None:
+            a = a.to(TORCH_DT[self.dt])
+        return a.to(self.device, torch.float64)
+
+    def f(self, name):
+        return self.st[name].to(self.device, torch.float64)
+
+
+def encoder_chain(w, h, x, att, names=None, readout=True):
     """post-norm TransformerEncoderLayer behind the attention, every intermediate rounded where the five-launch form stores it:
-    -> dict y1, x1, hid, y2, ln2 (not rounded), pooled [B, 512] (mean over tokens), out [B, O] (head Linear on the mean)"""
-    n = refiner_head_names(h)
+    -> dict y1, x1, hid, y2, ln2 (not rounded), pooled [B, 512] (mean over tokens), out [B, O] (head Linear on the mean).
+    w: Weights of a .fpw file or TensorWeights; names: the tensor names of the layer (default: refiner head h of the file);
+    readout = False: the chain up to LayerNorm 2, without pooled / out"""
+    n = names or refiner_head_names(h)
     r = {}
     r["y1"], _ = linear(w, n["out_w"], n["out_b"], att, res=x.to(torch.float64))
     r["x1"], _ = layernorm(w, n["ln1"], r["y1"])
     r["hid"], _ = linear(w, n["l1_w"], n["l1_b"], r["x1"], relu=True)
     r["y2"], _ = linear(w, n["l2_w"], n["l2_b"], r["hid"], res=r["x1"])
     r["ln2"], _ = layernorm(w, n["ln2"], r["y2"], out_dt=None)
+    if not readout:
+        return r
     r["pooled"] = r["ln2"].mean(-2)
     r["out"], _ = linear(w, n["head_w"], n["head_b"], r["pooled"], out_dt=None, f32_weights=True)
     return r
