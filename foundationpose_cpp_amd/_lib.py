@@ -26,7 +26,7 @@ SYMBOLS = [
     "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
     "fp_set_depth_filter", "fp_get_depth_filter",
-    "fp_render_pose",
+    "fp_render_pose", "fp_render_scene",
 ]
 
 
@@ -41,6 +41,18 @@ class FpFrameRender(C.Structure):
     """fp_frame_render of include/foundationpose_amd.h: every pointer optional, all in the call's memspace"""
     _fields_ = [("model_depth", C.c_void_p), ("model_mask", C.c_void_p), ("visible_mask", C.c_void_p), ("tri_id", C.c_void_p),
                 ("overlay", C.c_void_p)]
+
+
+class FpSceneRender(C.Structure):
+    """fp_scene_render of include/foundationpose_amd.h: every pointer optional, all in the call's memspace"""
+    _fields_ = [("model_depth", C.c_void_p), ("instance_id", C.c_void_p), ("visible_mask", C.c_void_p), ("tri_id", C.c_void_p),
+                ("cover_bits", C.c_void_p), ("overlay", C.c_void_p)]
+
+
+class FpSceneObject(C.Structure):
+    """fp_scene_object of include/foundationpose_amd.h"""
+    _fields_ = [("n_covered", C.c_int32), ("n_front", C.c_int32), ("n_hidden", C.c_int32), ("n_visible", C.c_int32),
+                ("n_occluded", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class FpMesh(C.Structure):
@@ -145,6 +157,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_mesh_color_source": [vp], "fp_set_vertex_colors": [vp, cs, vp, ci], "fp_get_color_source": [vp, cs],
         "fp_set_depth_filter": [vp, ci], "fp_get_depth_filter": [vp],
         "fp_render_pose": [vp, cs, vp, cf, vp, ci],
+        "fp_render_scene": [vp, ci, vp, vp, cf, vp, vp, ci],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

@@ -393,6 +393,38 @@ class FoundationPose:
         self._must(self._L.fp_render_pose(self._h, target_name.encode(), _p(p), tol_m, C.byref(rec), FP_HOST))
         return out
 
+    # ---- all tracked objects at frame resolution (include/foundationpose_amd.h "all tracked objects of a frame") ----
+    SCENE_OUTPUTS = {"model_depth": (np.float32, ()), "instance_id": (np.uint8, ()), "visible_mask": (np.uint8, ()),
+                     "tri_id": (np.int32, ()), "cover_bits": (np.uint64, ()), "overlay": (np.uint8, (3,))}
+    SCENE_RECORD = np.dtype([("n_covered", np.int32), ("n_front", np.int32), ("n_hidden", np.int32), ("n_visible", np.int32),
+                             ("n_occluded", np.int32), ("reserved", np.int32, (3,))])
+
+    def render_scene(self, target_names, poses, tol_m: float = 0.005,
+                     want=("model_depth", "instance_id", "visible_mask", "tri_id", "cover_bits", "overlay"), records: bool = True):
+        """fp_render_scene: the K targets `target_names` under `poses` ([K,4,4], what track_multi returns) rasterised into ONE picture of
+        the uploaded frame's size -> ({name: array} for the names in `want`, records).  instance_id [H,W] u8 is the object index + 1 of
+        the nearest model surface, tri_id the triangle + 1 within that object's mesh, cover_bits [H,W] u64 has bit o set where object
+        o's own silhouette covers the pixel, the overlay draws object o in tint o % 8.  records (None when `records` is false): a
+        structured array [K] of SCENE_RECORD -- n_covered, n_front, n_hidden (behind another object of the call), n_visible,
+        n_occluded (behind something observed).  Raises FoundationPoseError when any object's pose would need clipping."""
+        hw = getattr(self, "_hw", None)
+        if hw is None:
+            self.last_error = "[FoundationPose] fp_render_scene: no frame uploaded"
+            raise FoundationPoseError(self.last_error)
+        unknown = [n for n in want if n not in self.SCENE_OUTPUTS]
+        if unknown:
+            raise FoundationPoseError(f"[FoundationPose] render_scene: unknown outputs {unknown}")
+        names = [n.encode() for n in target_names]
+        p = to_colmajor(np.asarray(poses, np.float32).reshape(-1, 4, 4))
+        if len(p) != len(names):
+            raise FoundationPoseError(f"[FoundationPose] render_scene: {len(names)} names but {len(p)} poses")
+        out = {n: np.zeros(tuple(hw) + self.SCENE_OUTPUTS[n][1], self.SCENE_OUTPUTS[n][0]) for n in want}
+        rec = _lib.FpSceneRender(**{n: _p(a) for n, a in out.items()})
+        recs = np.zeros(max(len(names), 1), self.SCENE_RECORD) if records else None
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        self._must(self._L.fp_render_scene(self._h, len(names), arr, _p(p), tol_m, C.byref(rec), _p(recs) if records else None, FP_HOST))
+        return out, (recs[:len(names)] if records else None)
+
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):
         """Register, Track and the stage operators read bilateral(erode(depth)) instead of the depth itself, like FoundationPose as

@@ -504,6 +504,17 @@ struct fp_model {
   uint8_t *fr_out = nullptr;    // FP_HOST outputs are rendered here first: [depth | tri_id | overlay | model_mask | visible_mask] of fr_out_px pixels
   size_t fr_vert_cap = 0, fr_out_px = 0;
 
+  // all tracked objects at frame resolution (fp_render_scene): the same terms -- allocated at the first call, grow-only,
+  // read by no captured graph.
+  SceneTable *sc_table = nullptr;          // device copy of sc_table_host
+  SceneTable *sc_table_host = nullptr;     // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
+  int4 *sc_snap = nullptr;                 // [sc_vert_cap] scene vertices, frame_vertex_kernel's format
+  float4 *sc_cam = nullptr;
+  int *sc_work = nullptr;                  // [sc_work_cap] flags | total | counters | tile counts | offsets | cursors (scene_work_words)
+  unsigned *sc_list = nullptr;             // [sc_list_cap] the tiles' triangle lists
+  uint8_t *sc_out = nullptr;               // FP_HOST outputs: [cover_bits | depth | tri_id | overlay | instance_id | visible_mask] of sc_out_px pixels
+  size_t sc_vert_cap = 0, sc_work_cap = 0, sc_list_cap = 0, sc_out_px = 0;
+
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
   // into a hipGraph and replayed.  The graph bakes buffer addresses, so it is keyed by g_alloc_epoch.
   // (Register's ~110 launches are replayed the same way: inter-kernel gaps are ~4 % of a 12 ms Register.)
@@ -854,6 +865,14 @@ int fpt_frame_tile_bound(const float pose[16], const float K[9], double radius, 
   return 0;
 }
 
+// fp_render_scene's sizing without a GPU (tests/test_scene_render_ref_cpu.py): the tile grid of an H x W frame and the 32-bit words of the
+// binning block that holds the refusal words, the counters and three per-tile arrays
+int fpt_scene_sizing(int H, int W, int out3[3]) {
+  out3[0] = scene_tiles_x(W); out3[1] = scene_tiles_y(H);
+  out3[2] = (int)scene_work_words(H, W);
+  return 0;
+}
+
 // debug: enable the stage digests and read them back (16 slots; zeroed by every read)
 int fpt_digests(fp_model *m, unsigned long long out[16]) {
   if (!m->digests) {
@@ -1167,6 +1186,8 @@ static void destroy_model_impl(fp_model *m) {
   if (m->digests) (void)hipFree(m->digests);
   dev_free(m->fit_acc); dev_free(m->fit_rec);
   dev_free(m->fr_snap); dev_free(m->fr_cam); dev_free(m->fr_flag); dev_free(m->fr_out);
+  dev_free(m->sc_table); dev_free(m->sc_snap); dev_free(m->sc_cam); dev_free(m->sc_work); dev_free(m->sc_list); dev_free(m->sc_out);
+  delete m->sc_table_host; m->sc_table_host = nullptr;
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
@@ -2446,6 +2467,160 @@ int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], f
     if (out->visible_mask) FP_HIP_OK(hipMemcpyAsync(out->visible_mask, o.vis, px, hipMemcpyDeviceToHost, s));
   }
   FP_HIP_OK(hipStreamSynchronize(s));
+  return 0;
+} FP_CATCH_INT
+
+// ---- all tracked objects of a frame at frame resolution
+static_assert(FP_SCENE_MAX_OBJECTS == fp::SCENE_MAX_OBJECTS, "include/foundationpose_amd.h: the object limit of fp_render_scene is that of fp_internal.h");
+static_assert(sizeof(fp_scene_object) == 32, "fp_scene_object: eight 32-bit words");
+int fp_render_scene(fp_model *m, int K, const char *const *target_names, const float *poses, float tol_m, const fp_scene_render *out,
+                    fp_scene_object *objects, int memspace) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m != nullptr, "[FoundationPose] null model");
+  FP_CHECK(K >= 1 && K <= FP_SCENE_MAX_OBJECTS, "[FoundationPose] fp_render_scene: " + std::to_string(K) + " objects (1..FP_SCENE_MAX_OBJECTS = 64)");
+  FP_CHECK(target_names && poses, "[FoundationPose] fp_render_scene: invalid arguments");
+  FP_CHECK(memspace == FP_HOST || memspace == FP_DEVICE, "[FoundationPose] fp_render_scene: memspace must be FP_HOST or FP_DEVICE");
+  static const fp_scene_render none = {};
+  const fp_scene_render &want = out ? *out : none;
+  FP_CHECK(want.model_depth || want.instance_id || want.visible_mask || want.tri_id || want.cover_bits || want.overlay || objects,
+           "[FoundationPose] fp_render_scene: no output requested");
+  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_render_scene: tol_m must be finite and >= 0 (metres)");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_render_scene: a submitted Track has not been waited for (fp_track_wait)");
+  FP_CHECK(m->depth != nullptr && m->rgb != nullptr && m->H > 0, "[FoundationPose] fp_render_scene: no frame uploaded");
+  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  if (!m->sc_table_host) m->sc_table_host = new SceneTable();
+  SceneTable &tb = *m->sc_table_host;
+  unsigned long long faces = 0, verts = 0;
+  for (int o = 0; o < K; o++) {
+    Target *t = m->find(target_names[o] ? target_names[o] : "");
+    FP_CHECK(t != nullptr, "[FoundationPose] fp_render_scene: unknown target_name of object " + std::to_string(o));
+    FramePose &P = tb.pose[o];
+    const float *pose = poses + (size_t)o * 16;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) P.r[r * 3 + c] = pose[c * 4 + r];
+      P.t[r] = pose[12 + r];
+    }
+    P.fx = m->K[0]; P.cx = m->K[2]; P.fy = m->K[4]; P.cy = m->K[5];
+    tb.verts[o] = t->mesh.verts;
+    tb.faces[o] = t->mesh.faces;
+    tb.vert_start[o] = (int)verts;
+    tb.face_start[o] = (unsigned)faces;
+    verts += (unsigned long long)t->mesh.V;
+    faces += (unsigned long long)t->mesh.F;
+    FP_CHECK(faces < 0xffffffffull, "[FoundationPose] fp_render_scene: the objects' face counts must sum to less than 2^32 - 1");
+    FP_CHECK(verts <= 0x7fffffffull, "[FoundationPose] fp_render_scene: the objects' vertex counts must sum to at most 2^31 - 1");
+  }
+  for (int o = K; o <= SCENE_MAX_OBJECTS; o++) { tb.vert_start[o] = (int)verts; tb.face_start[o] = (unsigned)faces; }
+  tb.K = K;
+  const int H = m->H, W = m->W;
+  const size_t px = (size_t)H * W;
+  const int ntiles = scene_tiles_x(W) * scene_tiles_y(H);
+  hipStream_t s = m->stream;
+  // buffers: grow-only; nothing of the stream may still read a block that is replaced
+  const size_t work_words = scene_work_words(H, W);
+  if (!m->sc_table || (size_t)verts > m->sc_vert_cap || work_words > m->sc_work_cap) {
+    FP_HIP_OK(hipStreamSynchronize(s));
+    if (!m->sc_table && dev_alloc(&m->sc_table, 1)) return 1;
+    if ((size_t)verts > m->sc_vert_cap) {
+      dev_free(m->sc_snap); dev_free(m->sc_cam);
+      m->sc_vert_cap = 0;
+      if (dev_alloc(&m->sc_snap, (size_t)verts) || dev_alloc(&m->sc_cam, (size_t)verts)) return 1;
+      m->sc_vert_cap = (size_t)verts;
+    }
+    if (work_words > m->sc_work_cap) {
+      dev_free(m->sc_work);
+      m->sc_work_cap = 0;
+      if (dev_alloc(&m->sc_work, work_words)) return 1;
+      m->sc_work_cap = work_words;
+    }
+  }
+  int *flags = m->sc_work + SCENE_WORK_FLAGS, *counters = m->sc_work + SCENE_WORK_COUNTERS;
+  unsigned long long *total_dev = reinterpret_cast<unsigned long long *>(m->sc_work + SCENE_WORK_TOTAL);
+  unsigned *count = reinterpret_cast<unsigned *>(m->sc_work + SCENE_WORK_COUNT), *offset = count + ntiles, *cursor = offset + ntiles + 1;
+  FP_HIP_OK(hipMemcpyAsync(m->sc_table, &tb, sizeof(SceneTable), hipMemcpyHostToDevice, s));
+  FP_HIP_OK(hipMemsetAsync(m->sc_work, 0, ((size_t)SCENE_WORK_COUNT + ntiles) * sizeof(int), s));   // flags, total, counters, tile counts
+  // (a) vertex pass, (b) binning: count + scan.  Then the call's one early read-back: the refusal words and the size of the lists.
+  {
+    ProfScope ps(&m->prof, s, "scene_vertex", 0, (double)verts * (12.0 + 32.0));
+    launch_scene_vertex(s, m->sc_table, (int)verts, m->sc_snap, m->sc_cam, flags);
+    FP_HIP_OK(hipGetLastError());
+  }
+  {
+    ProfScope ps(&m->prof, s, "scene_bin", 0, (double)faces * (12.0 + 48.0));
+    launch_scene_bin_count(s, m->sc_table, (unsigned)faces, m->sc_snap, H, W, count, offset, cursor, total_dev);
+    FP_HIP_OK(hipGetLastError());
+  }
+  int early[SCENE_WORK_TOTAL + 2] = {0};
+  FP_HIP_OK(hipMemcpyAsync(early, m->sc_work, sizeof(early), hipMemcpyDeviceToHost, s));
+  FP_HIP_OK(hipStreamSynchronize(s));
+  for (int o = 0; o < K; o++) {
+    FP_CHECK(!(early[o] & FRAME_RENDER_FLAG_NEAR), "[FoundationPose] fp_render_scene: pose refused: object " + std::to_string(o) +
+                 ": a vertex lies nearer than FP_RENDER_NEAR_M (0.01 m) to the camera plane, or behind it (there is no clipper)");
+    FP_CHECK(!(early[o] & FRAME_RENDER_FLAG_RANGE), "[FoundationPose] fp_render_scene: pose refused: object " + std::to_string(o) +
+                 ": a vertex projects beyond FP_RENDER_SNAP_MAX sixteenths of a pixel (the exact range of the edge functions)");
+  }
+  unsigned long long entries = 0;
+  std::memcpy(&entries, early + SCENE_WORK_TOTAL, sizeof(entries));
+  FP_CHECK(entries <= (unsigned long long)SCENE_MAX_ENTRIES, "[FoundationPose] fp_render_scene: " + std::to_string(entries) +
+               " (tile, triangle) pairs, above the limit of 2^31 - 1");
+  if ((size_t)entries > m->sc_list_cap) {   // (the stream is idle: just synchronised)
+    dev_free(m->sc_list);
+    m->sc_list_cap = 0;
+    const size_t cap = (size_t)std::min<unsigned long long>(entries + entries / 2, (unsigned long long)SCENE_MAX_ENTRIES);
+    if (dev_alloc(&m->sc_list, cap)) return 1;
+    m->sc_list_cap = cap;
+  }
+  // (c) fill the lists, raster + resolve straight into the caller's device memory or into the model's staging block
+  SceneRenderOut o = {want.model_depth, want.instance_id, want.visible_mask, want.tri_id, reinterpret_cast<unsigned long long *>(want.cover_bits),
+                      want.overlay, objects ? counters : nullptr};
+  const size_t off_depth = fr_align(px * 8), off_tri = off_depth + fr_align(px * 4), off_ovl = off_tri + fr_align(px * 4),
+               off_inst = off_ovl + fr_align(px * 3), off_vis = off_inst + fr_align(px);
+  if (memspace == FP_HOST && (want.model_depth || want.instance_id || want.visible_mask || want.tri_id || want.cover_bits || want.overlay)) {
+    if (px > m->sc_out_px) {
+      dev_free(m->sc_out);
+      m->sc_out_px = 0;
+      if (dev_alloc(&m->sc_out, off_vis + fr_align(px))) return 1;
+      m->sc_out_px = px;
+    }
+    o.cover = want.cover_bits ? reinterpret_cast<unsigned long long *>(m->sc_out) : nullptr;
+    o.depth = want.model_depth ? reinterpret_cast<float *>(m->sc_out + off_depth) : nullptr;
+    o.tri = want.tri_id ? reinterpret_cast<int32_t *>(m->sc_out + off_tri) : nullptr;
+    o.overlay = want.overlay ? m->sc_out + off_ovl : nullptr;
+    o.inst = want.instance_id ? m->sc_out + off_inst : nullptr;
+    o.vis = want.visible_mask ? m->sc_out + off_vis : nullptr;
+  }
+  {
+    ProfScope ps(&m->prof, s, "scene_bin", 0, (double)faces * (12.0 + 48.0) + (double)entries * 4.0);
+    launch_scene_bin_fill(s, m->sc_table, (unsigned)faces, m->sc_snap, H, W, cursor, m->sc_list);
+    FP_HIP_OK(hipGetLastError());
+  }
+  {
+    const double wr = (o.depth ? 4.0 : 0.0) + (o.tri ? 4.0 : 0.0) + (o.cover ? 8.0 : 0.0) + (o.overlay ? 3.0 : 0.0) + (o.inst ? 1.0 : 0.0) + (o.vis ? 1.0 : 0.0);
+    const double rd = (o.overlay ? 3.0 : 0.0) + (o.vis || o.overlay || o.counters ? 4.0 : 0.0);
+    ProfScope ps(&m->prof, s, "scene_raster", 0, (double)px * (wr + rd) + (double)entries * 4.0);
+    launch_scene_raster(s, m->sc_table, m->sc_snap, m->sc_cam, offset, m->sc_list, m->rgb, m->depth, H, W, tol_m, o);
+    FP_HIP_OK(hipGetLastError());
+  }
+  if (memspace == FP_HOST) {
+    if (want.cover_bits) FP_HIP_OK(hipMemcpyAsync(want.cover_bits, o.cover, px * 8, hipMemcpyDeviceToHost, s));
+    if (want.model_depth) FP_HIP_OK(hipMemcpyAsync(want.model_depth, o.depth, px * 4, hipMemcpyDeviceToHost, s));
+    if (want.tri_id) FP_HIP_OK(hipMemcpyAsync(want.tri_id, o.tri, px * 4, hipMemcpyDeviceToHost, s));
+    if (want.overlay) FP_HIP_OK(hipMemcpyAsync(want.overlay, o.overlay, px * 3, hipMemcpyDeviceToHost, s));
+    if (want.instance_id) FP_HIP_OK(hipMemcpyAsync(want.instance_id, o.inst, px, hipMemcpyDeviceToHost, s));
+    if (want.visible_mask) FP_HIP_OK(hipMemcpyAsync(want.visible_mask, o.vis, px, hipMemcpyDeviceToHost, s));
+  }
+  int sums[SCENE_MAX_OBJECTS * 3] = {0};
+  if (objects) FP_HIP_OK(hipMemcpyAsync(sums, counters, (size_t)K * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+  FP_HIP_OK(hipStreamSynchronize(s));
+  if (objects) {
+    for (int i = 0; i < K; i++) {
+      fp_scene_object &r = objects[i];
+      r = fp_scene_object{};
+      r.n_covered = sums[i * 3]; r.n_front = sums[i * 3 + 1]; r.n_visible = sums[i * 3 + 2];
+      r.n_hidden = r.n_covered - r.n_front;
+      r.n_occluded = r.n_front - r.n_visible;
+    }
+  }
   return 0;
 } FP_CATCH_INT
 

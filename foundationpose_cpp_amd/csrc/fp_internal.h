@@ -342,6 +342,47 @@ void launch_frame_vertex(hipStream_t s, const DeviceMesh &m, const FramePose &po
 void launch_frame_raster(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const uint8_t *rgb, const float *depth,
                          int H, int W, const FrameTileBound &bound, float tol_m, const FrameRenderOut &out);
 
+// frame-resolution rendering of all tracked objects of a frame in one pass (fp_render_scene; fp_scene_render.hip).
+// Per object the rules and constants are those of section 4.8 above; the objects meet in one z-buffer of keys bits(z) << 32 | g with
+// g the GLOBAL triangle index (face_start[o] + t).
+constexpr int SCENE_MAX_OBJECTS = 64;               // = FP_SCENE_MAX_OBJECTS
+constexpr int SCENE_PALETTE[8][3] = {               // tint of object o is SCENE_PALETTE[o % 8]; entry 0 is fp_render_pose's
+    {FRAME_RENDER_TINT_R, FRAME_RENDER_TINT_G, FRAME_RENDER_TINT_B}, {230, 80, 60}, {70, 130, 240}, {240, 200, 40},
+    {200, 80, 220}, {40, 210, 220}, {250, 140, 30}, {160, 230, 60}};
+constexpr long long SCENE_MAX_ENTRIES = 0x7fffffffll;   // (tile, triangle) entries of one call: the lists are indexed with 32 bits
+struct SceneTable {   // device-resident description of the call's objects, in call order
+  FramePose pose[SCENE_MAX_OBJECTS];
+  const float *verts[SCENE_MAX_OBJECTS];
+  const int32_t *faces[SCENE_MAX_OBJECTS];
+  int vert_start[SCENE_MAX_OBJECTS + 1];        // object o owns scene vertices [vert_start[o], vert_start[o + 1])
+  unsigned face_start[SCENE_MAX_OBJECTS + 1];   // ... and global triangles [face_start[o], face_start[o + 1])
+  int K;
+};
+struct SceneRenderOut {   // device pointers, null = not wanted
+  float *depth;
+  uint8_t *inst, *vis;
+  int32_t *tri;
+  unsigned long long *cover;
+  uint8_t *overlay;
+  int *counters;   // [K, 3] {covered, front, visible}, zero on entry
+};
+// pure host functions: the tile grid of a frame, and the int32 words of the binning block [flags 64 | total 2 | counters 192 |
+// count ntiles | offset ntiles + 1 | cursor ntiles]
+constexpr int SCENE_WORK_FLAGS = 0, SCENE_WORK_TOTAL = 64, SCENE_WORK_COUNTERS = 66, SCENE_WORK_COUNT = 258;
+inline int scene_tiles_x(int W) { return (W + FRAME_RENDER_TILE - 1) / FRAME_RENDER_TILE; }
+inline int scene_tiles_y(int H) { return (H + FRAME_RENDER_TILE - 1) / FRAME_RENDER_TILE; }
+inline size_t scene_work_words(int H, int W) { return (size_t)SCENE_WORK_COUNT + (size_t)3 * scene_tiles_x(W) * scene_tiles_y(H) + 1; }
+// snap / cam [vert_start[K]] in frame_vertex_kernel's format; flags [K] must be zero on entry
+void launch_scene_vertex(hipStream_t s, const SceneTable *table, int total_verts, int4 *snap, float4 *cam, int *flags);
+// count [ntiles] must be zero on entry; leaves offset [ntiles + 1] (exclusive scan), cursor = offset and *total (64-bit) = all entries
+void launch_scene_bin_count(hipStream_t s, const SceneTable *table, unsigned total_faces, const int4 *snap, int H, int W, unsigned *count,
+                            unsigned *offset, unsigned *cursor, unsigned long long *total);
+// list [total]: the global triangle indices of every tile, tile after tile (order inside a tile: whatever the atomics gave)
+void launch_scene_bin_fill(hipStream_t s, const SceneTable *table, unsigned total_faces, const int4 *snap, int H, int W, unsigned *cursor,
+                           unsigned *list);
+void launch_scene_raster(hipStream_t s, const SceneTable *table, const int4 *snap, const float4 *cam, const unsigned *offset,
+                         const unsigned *list, const uint8_t *rgb, const float *depth, int H, int W, float tol_m, const SceneRenderOut &out);
+
 // host helpers (fp_host.cpp part of fp_api.hip)
 std::vector<float> make_rotation_grid(int min_views, int inplane_steps);
 

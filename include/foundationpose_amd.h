@@ -234,6 +234,49 @@ typedef struct fp_frame_render {      /* every pointer optional (NULL = not want
 int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], float tol_m,
                    const fp_frame_render *out, int memspace);
 
+/* ---- all tracked objects of a frame at frame resolution, in one pass (new; the reference has no counterpart) -------------------
+ * fp_render_scene rasterises K (1..FP_SCENE_MAX_OBJECTS) objects -- target_names[o] under poses[o], K column-major 4x4 matrices as
+ * fp_track_multi takes and returns them; names may repeat -- into ONE picture of the uploaded frame's size.  Per object the rules
+ * are fp_render_pose's, unchanged (snap to 1/16 px, sample point (c, r), 64-bit edge functions with the top-left rule, both windings,
+ * perspective-correct z, every f32 operation separately rounded, independent of fp_set_float_model).  The
+ * objects meet in one z-buffer whose key is bits(z) << 32 | g, g = the number of faces of the objects before o in the call + the
+ * triangle's index: the nearest surface wins, at equal depth the lower object index, then the lower triangle.  The face counts of
+ * the call must sum to less than 2^32 - 1.
+ * cover_bits: bit o of a pixel is set when ANY triangle of object o covers the sample point, whoever wins the depth test: the full
+ * (amodal) silhouettes of all K objects.  A pixel is VISIBLE by fp_render_pose's rule applied to the winning z against the raw
+ * uploaded depth D: occluded when !(D < 0.001f) && D < z - tol_m.  The overlay draws every visible model pixel as
+ * (rgb + (tint * k + 127) / 255 + 1) >> 1 with k the flat shade of the winning triangle (as in fp_render_pose) and tint the entry
+ * o % 8 of the palette (40,220,120) (230,80,60) (70,130,240) (240,200,40) (200,80,220) (40,210,220) (250,140,30) (160,230,60).
+ * objects (HOST memory whatever the memspace; may be NULL): per object the integer pixel counts below; all are sums of integers, so
+ * bit-identical from call to call.  n_hidden separates "behind another tracked object" from n_occluded, "behind something observed".
+ * Refused with an error before anything is rasterised and before any output is written: K outside 1..64, an unknown name (the
+ * message says which index), tol_m not finite or negative, no / a partial frame, a pending Track, all seven outputs NULL, and a
+ * pose fp_render_pose would refuse (the message contains "pose refused" and the lowest refused object index).  An object wholly
+ * outside the frame is not an error: its counts are zero.
+ * Every image pointer is optional and lives in `memspace`; FP_DEVICE outputs are written by the kernel directly, FP_HOST outputs
+ * are copied on the model's stream.  One synchronisation inside the call (refusal words + the size of the tile lists), one at its
+ * end.  Works on geometry-only models.  fp_render_pose, Register, Track and their captured graphs are untouched: the call's buffers
+ * are its own, allocated at its first use, grow-only. */
+#define FP_SCENE_MAX_OBJECTS 64            /* = fp_track_multi's K limit */
+typedef struct fp_scene_object {           /* one per object, all integers, order-independent */
+  int32_t n_covered;   /* frame pixels inside the object's own silhouette (amodal)                         */
+  int32_t n_front;     /* of those, pixels where this object is the nearest model                          */
+  int32_t n_hidden;    /* n_covered - n_front: another object of the call is in front (or wins the tie)    */
+  int32_t n_visible;   /* of n_front, pixels not occluded by the observed depth (fp_render_pose's rule)    */
+  int32_t n_occluded;  /* n_front - n_visible                                                              */
+  int32_t reserved[3];
+} fp_scene_object;
+typedef struct fp_scene_render {           /* every pointer optional; all in the call's memspace */
+  float    *model_depth;   /* [H,W]   z of the nearest model surface over all objects, 0 = background                */
+  uint8_t  *instance_id;   /* [H,W]   object index + 1 of that surface, 0 = background                               */
+  uint8_t  *visible_mask;  /* [H,W]   255 where a model is nearest and nothing observed is in front of it            */
+  int32_t  *tri_id;        /* [H,W]   triangle index + 1 WITHIN the winning object's mesh, 0 = background            */
+  uint64_t *cover_bits;    /* [H,W]   bit o set where object o's silhouette covers the pixel (amodal masks of all K) */
+  uint8_t  *overlay;       /* [H,W,3] the uploaded rgb with every visible model pixel drawn in its object's tint     */
+} fp_scene_render;
+int fp_render_scene(fp_model *m, int K, const char *const *target_names, const float *poses /* K column-major 4x4 */,
+                    float tol_m, const fp_scene_render *out, fp_scene_object *objects /* host [K], may be NULL */, int memspace);
+
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 
 /* UploadDataToDevice + convert_depth_to_xyz_map (src/foundationpose.cpp:267-315, src/foundationpose_utils.cu:3-32). */

@@ -194,6 +194,20 @@ public:
   bool RenderPose(const std::string &target_name, const Pose &pose, const fp_frame_render &out, float tol_m = 0.005f, int memspace = FP_HOST) {
     return ok(fp_render_pose(h_, target_name.c_str(), pose.data(), tol_m, &out, memspace));
   }
+  // all tracked objects of a frame in one pass (foundationpose_amd.h "all tracked objects of a frame"): instance map, amodal coverage
+  // bits, visible mask, overlay in per-object tints; `objects` (may be null) receives one record of pixel counts per object.
+  bool RenderScene(const std::vector<std::string> &target_names, const std::vector<Pose> &poses, const fp_scene_render &out,
+                   std::vector<fp_scene_object> *objects = nullptr, float tol_m = 0.005f, int memspace = FP_HOST) {
+    if (target_names.size() != poses.size()) {
+      err_ = "[FoundationPose] RenderScene: one pose per target name";
+      return false;
+    }
+    std::vector<const char *> names;
+    for (const auto &n : target_names) names.push_back(n.c_str());
+    if (objects) objects->resize(poses.size());
+    return ok(fp_render_scene(h_, (int)poses.size(), names.data(), poses.empty() ? nullptr : poses[0].data(), tol_m, &out,
+                              objects ? objects->data() : nullptr, memspace));
+  }
 
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
