@@ -959,6 +959,57 @@ int fpt_depth_filter_rect(fp_model *m, int x0, int y0, int x1, int y1, float *ou
   return 0;
 } FP_CATCH_INT
 
+// the product's launch site launch_sampler on caller-given values (tests/test_pose_rules_gpu.py): vals_hw [H, W] f32 stands for the filtered
+// depth, mask_hw [H, W] u8, K and min_depth are the caller's; N = 1 pose of the model's rotation grid.  The scan state is the MODEL's
+// (m->samp_state, which a first fp_get_hyp_poses has allocated and every launch leaves reset), so a sequence of calls on one model
+// runs the way a sequence of frames does.  center_out [3] = the translation written into the pose (quiet NaNs when the status is not
+// 0: the kernel then writes none), *status_out = state[6], state_out [5] = state[0..4] after the call.  The compacted list `vals` the
+// two kernels share lies between SAMPLER_RAW_GUARD canary words.  Returns 0, 1 on failure (fp_last_error), 2 when a canary word changed.
+static constexpr size_t SAMPLER_RAW_GUARD = 1024;
+int fpt_sampler_raw(fp_model *m, const float *vals_hw, const uint8_t *mask_hw, int H, int W, const float K[9], float min_depth,
+                    float center_out[3], int *status_out, int state_out[5]) try {
+  FP_CHECK(m && vals_hw && mask_hw && K && center_out && status_out && state_out, "[FoundationPose] fpt_sampler_raw: null argument");
+  FP_CHECK(H >= 1 && W >= 1 && (long long)H * W <= (1 << 24), "[FoundationPose] fpt_sampler_raw: invalid frame size");
+  FP_CHECK(m->samp_state && m->grid_dev, "[FoundationPose] fpt_sampler_raw: call fp_get_hyp_poses once first (it allocates the scan state)");
+  SerialGuard serial(m->device);
+  const size_t px = (size_t)H * W, G = SAMPLER_RAW_GUARD;
+  const uint32_t canary = 0xA5C3F00Du;
+  struct Bufs {
+    float *depth = nullptr, *pose = nullptr;
+    uint32_t *vals = nullptr;
+    uint8_t *mask = nullptr;
+    ~Bufs() { dev_free(depth); dev_free(pose); dev_free(vals); dev_free(mask); }
+  } b;
+  if (dev_alloc(&b.depth, px) || dev_alloc(&b.mask, px) || dev_alloc(&b.vals, px + 2 * G) || dev_alloc(&b.pose, 16)) return 1;
+  std::vector<uint32_t> hv(px + 2 * G, canary);
+  const std::vector<uint32_t> qnan(16, 0x7FC00000u);
+  FP_HIP_OK(fp::memcpy_sync(b.depth, vals_hw, px * 4, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(b.mask, mask_hw, px, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(b.vals, hv.data(), hv.size() * 4, hipMemcpyHostToDevice));
+  FP_HIP_OK(fp::memcpy_sync(b.pose, qnan.data(), qnan.size() * 4, hipMemcpyHostToDevice));
+  {   // the scan appends at state[4]: a count that is not zero on entry would carry the list past its guard words, so nothing is launched then
+    int before[8];
+    FP_HIP_OK(hipStreamSynchronize(m->stream));
+    FP_HIP_OK(fp::memcpy_sync(before, m->samp_state, sizeof(before), hipMemcpyDeviceToHost));
+    FP_CHECK(before[0] == 0x7fffffff && before[1] == -1 && before[2] == 0x7fffffff && before[3] == -1 && before[4] == 0,
+             "[FoundationPose] fpt_sampler_raw: the scan state is not the reset state on entry");
+  }
+  launch_sampler(m->stream, b.depth, b.mask, H, W, min_depth, K, m->grid_dev, 0, 1, m->samp_state, reinterpret_cast<float *>(b.vals + G), b.pose);
+  FP_HIP_OK(hipGetLastError());
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  float pose[16];
+  int state[8];
+  FP_HIP_OK(fp::memcpy_sync(pose, b.pose, sizeof(pose), hipMemcpyDeviceToHost));
+  FP_HIP_OK(fp::memcpy_sync(state, m->samp_state, sizeof(state), hipMemcpyDeviceToHost));
+  FP_HIP_OK(fp::memcpy_sync(hv.data(), b.vals, hv.size() * 4, hipMemcpyDeviceToHost));
+  for (int k = 0; k < 3; k++) center_out[k] = pose[12 + k];
+  *status_out = state[6];
+  for (int k = 0; k < 5; k++) state_out[k] = state[k];
+  for (size_t i = 0; i < G; i++)
+    if (hv[i] != canary || hv[G + px + i] != canary) { fp::set_error("[FoundationPose] fpt_sampler_raw: the kernels wrote outside the value list"); return 2; }
+  return 0;
+} FP_CATCH_INT
+
 #endif  // FP_TEST_HOOKS
 
 const char *fp_last_error(void) { return g_last_error.c_str(); }

@@ -112,7 +112,8 @@ def case(name):
 
 
 def window_tf(c, ratio, poses=None):
-    """[N, 9] f32 crop windows (ComputeCropWindowTF; the oracle's, which its own known-answer test pins)"""
+    """[N, 9] f32 crop windows (ComputeCropWindowTF; the oracle's, pinned to the float64 rule crop_window_ref of tests/pose_rules_ref.py by
+    tests/test_pose_rules_ref_cpu.py and, for the device's PoseRec, tests/test_pose_rules_gpu.py: DESIGN.md section 2.2)"""
     return fo.crop_window_tf(syn.to_colmajor(c.poses if poses is None else poses), c.K, ratio, c.mesh.diameter)
 
 
