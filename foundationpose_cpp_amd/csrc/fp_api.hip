@@ -1180,6 +1180,19 @@ fp_model *fp_create_on(int device, const fp_mesh *meshes, int n_meshes, const fl
     d.max_norm = (float)(std::sqrt(norm2) * (1.0 + 1e-6));   // (rounded up: fp_render_pose's screen bound must contain every vertex)
     std::vector<int32_t> f((size_t)d.F * 3);
     for (size_t k = 0; k < f.size(); k++) f[k] = (int32_t)src.faces[k];
+    // A face whose centred corners are exactly collinear has no surface, but the rasterisers cull on the area of the SNAPPED corners:
+    // under most poses three collinear points snap to a sliver up to 1/16 px wide, which can cover a sample and win a depth tie against
+    // the surface it lies in.  Such a face is stored as (i0, i0, i0): a repeated index snaps to one point under every pose, so every
+    // rasteriser of the library culls it, and the numbering of the other faces stays.  The differences of two
+    // f32 and the products of two such differences are exact in double, so the cross product is zero exactly when the corners are collinear.
+    for (int k = 0; k < d.F; k++) {
+      int32_t *i = &f[(size_t)k * 3];
+      if ((uint32_t)i[0] >= (uint32_t)d.V || (uint32_t)i[1] >= (uint32_t)d.V || (uint32_t)i[2] >= (uint32_t)d.V) continue;
+      const float *p0 = &v[(size_t)i[0] * 3], *p1 = &v[(size_t)i[1] * 3], *p2 = &v[(size_t)i[2] * 3];
+      const double a[3] = {(double)p1[0] - p0[0], (double)p1[1] - p0[1], (double)p1[2] - p0[2]};
+      const double b[3] = {(double)p2[0] - p0[0], (double)p2[1] - p0[1], (double)p2[2] - p0[2]};
+      if (a[1] * b[2] == a[2] * b[1] && a[2] * b[0] == a[0] * b[2] && a[0] * b[1] == a[1] * b[0]) i[1] = i[2] = i[0];
+    }
     bool ok = !dev_alloc(&d.verts, v.size()) && !dev_alloc(&d.normals, v.size()) && !dev_alloc(&d.uvs, uv.size()) &&
               !dev_alloc(&d.faces, f.size()) && !dev_alloc(&d.tex, (size_t)d.TH * d.TW * 3);
     ok = ok && fp::memcpy_sync(d.verts, v.data(), v.size() * 4, hipMemcpyHostToDevice) == hipSuccess;

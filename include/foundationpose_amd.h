@@ -54,7 +54,8 @@ typedef struct fp_mesh {
   const float *vertices;     /* GetMeshVertices()       [V,3], mesh frame (NOT centred) */
   const float *normals;      /* GetMeshVertexNormals()  [V,3] */
   const float *texcoords;    /* GetMeshTextureCoords()  [V,2] = (u,v) as loaded (v is flipped internally) */
-  const uint32_t *faces;     /* GetMeshTriangleFaces()  [F,3] */
+  const uint32_t *faces;     /* GetMeshTriangleFaces()  [F,3]; a face whose centred corners are exactly collinear is never drawn
+                              * (its number stays reserved): snapped to 1/16 px it could open into a sliver */
   const uint8_t *texture;    /* GetTextureMap()         [tex_height,tex_width,3] RGB u8 */
   int tex_height, tex_width;
   float diameter;            /* GetMeshDiameter() */

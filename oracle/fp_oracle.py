@@ -54,6 +54,20 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def stored_faces(centred_verts, faces):
+    """The faces as the renderer holds them: a face whose centred corners are exactly collinear is stored as (i0, i0, i0).  CudaRaster
+    culls on the area of the SNAPPED corners, so three collinear points can surface as a sliver and win a depth tie against the surface
+    they lie in; a repeated index snaps to one point under every pose and never shows (this project's rule, the
+    reference draws the sliver).  Differences of f32 and products of two of them are exact in float64."""
+    f = np.array(faces, dtype=np.int32).reshape(-1, 3)
+    v = np.asarray(centred_verts, np.float64)
+    ok = np.nonzero(((f >= 0) & (f < len(v))).all(1))[0]
+    a, b = v[f[ok, 1]] - v[f[ok, 0]], v[f[ok, 2]] - v[f[ok, 0]]
+    flat = (a[:, 1] * b[:, 2] == a[:, 2] * b[:, 1]) & (a[:, 2] * b[:, 0] == a[:, 0] * b[:, 2]) & (a[:, 0] * b[:, 1] == a[:, 1] * b[:, 0])
+    f[ok[flat]] = f[ok[flat], :1]
+    return np.ascontiguousarray(f)
+
+
 class OracleMesh:
     """Holds the renderer-side view of a mesh: centred vertices, (u,1-v) uvs (foundationpose_render.cpp:396-406)."""
 
@@ -62,7 +76,7 @@ class OracleMesh:
         self.normals = _f32(mesh.normals)
         uv = np.asarray(mesh.texcoords, dtype=np.float32)
         self.uvs = _f32(np.stack([uv[:, 0], np.float32(1) - uv[:, 1]], 1))
-        self.faces = np.ascontiguousarray(mesh.faces, dtype=np.int32)
+        self.faces = stored_faces(self.verts, mesh.faces)
         self.tex = np.ascontiguousarray(mesh.texture, dtype=np.uint8)
         self.diameter = float(mesh.diameter)
         self.c = _Mesh(len(self.verts), len(self.faces), _p(self.verts), _p(self.normals), _p(self.uvs),

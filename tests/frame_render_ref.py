@@ -23,6 +23,18 @@ def centred(mesh):
     return mesh.vertices.astype(f32) - np.asarray(mesh.center, f32)
 
 
+def stored_faces(verts, faces):
+    """the faces the library renders: a face whose CENTRED corners are exactly collinear is stored as (i0, i0, i0), because three collinear
+    points may snap to a sliver that covers a sample, while a repeated index snaps to one point under every pose"""
+    f = np.array(faces, np.int64).reshape(-1, 3)
+    v = np.asarray(verts, f32).astype(np.float64)
+    ok = np.nonzero(((f >= 0) & (f < len(v))).all(1))[0]
+    a, b = v[f[ok, 1]] - v[f[ok, 0]], v[f[ok, 2]] - v[f[ok, 0]]
+    flat = (a[:, 1] * b[:, 2] == a[:, 2] * b[:, 1]) & (a[:, 2] * b[:, 0] == a[:, 0] * b[:, 2]) & (a[:, 0] * b[:, 1] == a[:, 1] * b[:, 0])
+    f[ok[flat]] = f[ok[flat], :1]
+    return f
+
+
 def project(verts, pose, K):
     """-> (cam [V,3] f32, snapped [V,2] i64, near [V] bool, out_of_range [V] bool).  pose: numpy 4x4 (row-major as numpy prints it)."""
     v = np.asarray(verts, f32)
@@ -118,6 +130,7 @@ def render(verts, faces, pose, K, rgb, depth, tol_m=0.005):
         raise Refused("range")
     depth = np.asarray(depth, f32)
     H, W = depth.shape
+    faces = stored_faces(verts, faces)
     keys = rasterize(cam, snap, faces, H, W)
     model = keys != EMPTY
     z = np.where(model, (keys >> np.uint64(32)).astype(np.uint32).view(f32), f32(0)).astype(f32)

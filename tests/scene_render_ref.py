@@ -44,7 +44,7 @@ def render(objects, K, rgb, depth, tol_m=0.005):
     cover = np.zeros((H, W), np.uint64)
     start = 0                                  # faces of the objects before o
     for o, ((verts, faces, pose), (cam, snap)) in enumerate(zip(objects, proj)):
-        own = FR.rasterize(cam, snap, faces, H, W)                    # bits(z) << 32 | t
+        own = FR.rasterize(cam, snap, FR.stored_faces(verts, faces), H, W)   # bits(z) << 32 | t
         hit = own != FR.EMPTY
         g = (own & LOW32) + np.uint64(start)                          # the global index: below 2^32 - 1 by the check above
         composed = np.where(hit, (own & ~LOW32) | g, FR.EMPTY)
