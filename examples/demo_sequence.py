@@ -2,7 +2,8 @@
 """Python twin of examples/fp_demo.cpp: Register the first frame, Track the rest, write poses.txt + box overlays.
 
     python examples/demo_sequence.py --data test_data/mustard0 --refiner refiner.fpw --scorer scorer.fpw --out out
-    python examples/demo_sequence.py --synthetic 8 --out out      # seeded synthetic sequence + synthetic weights
+    python examples/demo_sequence.py --synthetic 8 --out out      # seeded synthetic sequence + synthetic weights; its ground truth also
+                                                                  # gives out/errors.txt (ADD, ADD-S, MSSD, MSPD per frame) and the two AUCs
     python examples/demo_sequence.py --synthetic 8 --fit 5        # + pose-fit columns (tolerance 5 mm) and a LOST? marker per frame
     python examples/demo_sequence.py --synthetic 8 --depth-filter # the networks see bilateral(erode(depth)), like FoundationPose as published
     python examples/demo_sequence.py --synthetic 8 --render       # + <id>_render.png beside every box plot: the model's visible pixels, flat-shaded over the frame
@@ -16,16 +17,19 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from foundationpose_cpp_amd import FoundationPose, _lib, dataset as D, load_mesh, weights as W  # noqa: E402
+from foundationpose_cpp_amd import FoundationPose, _lib, auc, dataset as D, load_mesh, weights as W  # noqa: E402
 from foundationpose_cpp_amd.synthetic import to_colmajor  # noqa: E402
 
 
-def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, fit_mm=None, lost_below=0.5, depth_filter=False, render=False):
+def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, fit_mm=None, lost_below=0.5, depth_filter=False, render=False,
+        gt_poses=None):
     """fit_mm: pose-fit tolerance in millimetres (None = off: the log is the plain pose log).  With it every log line also carries
     n_model and the inlier / front / behind shares of the model, and LOST? when the inlier share is under lost_below.  Track's record
     describes the pose the frame STARTED from (the previous frame's answer) against this frame's depth.
     render: beside every <id>_plot.png also write <id>_render.png, the overlay of fp_render_pose at the frame's pose (a silhouette shows
-    a rotation about the object's long axis that the 12-edge box cannot)."""
+    a rotation about the object's long axis that the 12-edge box cannot).
+    gt_poses: ground truth per frame (centred-mesh -> camera): also write errors.txt -- frame id, ADD, ADD-S, MSSD in metres, MSPD in
+    pixels (fp_pose_errors, after the last frame: poses.txt and the plots do not change) -- and print the AUC of ADD and of ADD-S."""
     seq = D.Sequence(data)
     mesh = load_mesh(name, seq.mesh_path())
     model = FoundationPose(mesh, seq.K, refiner, scorer, max_input_image_height=max(seq.H, 1080), max_input_image_width=max(seq.W, 1920))
@@ -67,6 +71,11 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
             poses.append(pose)
         if len(seq) > 1:
             print(f"tracked {len(seq) - 1} frames, {(len(seq) - 1) / (time.perf_counter() - t0):.1f} fps including PNG decode")
+    if gt_poses is not None:
+        errs = model.pose_errors(name, np.stack(poses), np.stack(gt_poses))
+        with open(os.path.join(out, "errors.txt"), "w") as f:
+            f.writelines("%s %.9g %.9g %.9g %.9g\n" % (fid, e.add_m, e.adds_m, e.mssd_m, e.mspd_px) for fid, e in zip(seq.ids, errs))
+        print(f"ADD AUC {auc([e.add_m for e in errs]):.4f}, ADD-S AUC {auc([e.adds_m for e in errs]):.4f} (thresholds 0 .. 0.1 m) over {len(errs)} frames")
     model.close()
     return np.stack(poses)
 
@@ -89,16 +98,17 @@ def main():
                     help="beside every <id>_plot.png write <id>_render.png: the model at the frame's pose, its visible pixels flat-shaded over the frame; default off")
     ap.add_argument("--synthetic", type=int, metavar="N", help="write and use an N-frame synthetic sequence + synthetic weights")
     a = ap.parse_args()
+    gts = None
     if a.synthetic:
         d = tempfile.mkdtemp()
         a.data = os.path.join(d, "synthetic0")
-        D.write_synthetic_sequence(a.data, a.synthetic)
+        _, gts = D.write_synthetic_sequence(a.data, a.synthetic)
         a.refiner, a.scorer = os.path.join(d, "refiner.fpw"), os.path.join(d, "scorer.fpw")
         W.pack_synthetic("refiner", a.refiner)
         W.pack_synthetic("scorer", a.scorer)
         print("synthetic sequence:", a.data, "(synthetic weights: poses are not meaningful, only reproducible)")
-    run(a.data, a.refiner, a.scorer, a.out, a.name, a.refine_itr, a.plots, a.fit, a.lost_below, a.depth_filter, a.render)
-    print("wrote", os.path.join(a.out, "poses.txt"))
+    run(a.data, a.refiner, a.scorer, a.out, a.name, a.refine_itr, a.plots, a.fit, a.lost_below, a.depth_filter, a.render, gts)
+    print("wrote", os.path.join(a.out, "poses.txt") + (" and errors.txt" if gts is not None else ""))
 
 
 if __name__ == "__main__":

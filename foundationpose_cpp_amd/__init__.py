@@ -1,2 +1,2 @@
 """foundationpose_cpp_amd -- MI355X-native FoundationPose Register/Track hot path."""
-from .api import FoundationPose, FoundationPoseError, PoseFit, load_mesh  # noqa: F401
+from .api import FoundationPose, FoundationPoseError, PoseError, PoseFit, auc, load_mesh, recall  # noqa: F401

@@ -26,7 +26,7 @@ SYMBOLS = [
     "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
     "fp_set_depth_filter", "fp_get_depth_filter",
-    "fp_render_pose", "fp_render_scene",
+    "fp_render_pose", "fp_render_scene", "fp_pose_errors",
 ]
 
 
@@ -53,6 +53,13 @@ class FpSceneObject(C.Structure):
     """fp_scene_object of include/foundationpose_amd.h"""
     _fields_ = [("n_covered", C.c_int32), ("n_front", C.c_int32), ("n_hidden", C.c_int32), ("n_visible", C.c_int32),
                 ("n_occluded", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class FpPoseError(C.Structure):
+    """fp_pose_error of include/foundationpose_amd.h"""
+    _fields_ = [("add_m", C.c_float), ("adds_m", C.c_float), ("mssd_m", C.c_float), ("mspd_px", C.c_float), ("rot_deg", C.c_float),
+                ("trans_m", C.c_float), ("best_sym", C.c_int32), ("best_sym_mspd", C.c_int32), ("add_sum_q20", C.c_int64),
+                ("adds_sum_q20", C.c_int64), ("n_vertices", C.c_int32), ("reserved", C.c_int32)]
 
 
 class FpMesh(C.Structure):
@@ -158,6 +165,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_set_depth_filter": [vp, ci], "fp_get_depth_filter": [vp],
         "fp_render_pose": [vp, cs, vp, cf, vp, ci],
         "fp_render_scene": [vp, ci, vp, vp, cf, vp, vp, ci],
+        "fp_pose_errors": [vp, cs, vp, ci, vp, ci, vp, ci, ci, ci, vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

@@ -57,6 +57,39 @@ def _fit(r) -> PoseFit:
     return PoseFit(r.n_model, r.n_observed, r.n_inlier, r.n_front, r.n_behind, r.sum_dz_q20, float(r.mean_dz_m), float(r.tol_n))
 
 
+@dataclasses.dataclass(frozen=True)
+class PoseError:
+    """fp_pose_error (include/foundationpose_amd.h): one estimated pose E against ground truth G over the used vertices of the target"""
+    add_m: float          # mean_v |E v - G v|
+    adds_m: float         # mean_u min_v |G u - E v| (NaN when ADD-S was not asked for)
+    mssd_m: float         # min_s max_v |E v - G S_s v|
+    mspd_px: float        # min_s max_v |proj(E v) - proj(G S_s v)| (inf: a vertex nearer than 1 cm to the camera plane)
+    rot_deg: float        # E against G S_best_sym
+    trans_m: float
+    best_sym: int         # arg-min of MSSD: 0 = identity, k = the caller's symmetry k - 1
+    best_sym_mspd: int    # arg-min of MSPD, -1 when mspd_px is inf
+    add_sum_q20: int
+    adds_sum_q20: int
+    n_vertices: int
+
+
+def recall(errors, threshold: float) -> float:
+    """share of `errors` that are <= threshold (a NaN or inf error never is); 0 for no errors"""
+    e = np.asarray(errors, np.float64).ravel()
+    return float(np.count_nonzero(e <= threshold)) / e.size if e.size else 0.0
+
+
+def auc(errors, max_value: float = 0.1, step: float = 0.001) -> float:
+    """area under the recall-versus-threshold curve over thresholds 0, step, ..., max_value (trapezoids), normalised to 1: what
+    YCB-Video and FoundationPose report for ADD / ADD-S with max_value 0.1 m"""
+    n = int(round(max_value / step))
+    if n < 1:
+        raise ValueError("auc: max_value must be at least one step")
+    x = np.linspace(0.0, max_value, n + 1)
+    y = np.array([recall(errors, t) for t in x])
+    return float(((y[1:] + y[:-1]) / 2 * np.diff(x)).sum() / max_value)
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -424,6 +457,21 @@ class FoundationPose:
         arr = (C.c_char_p * max(len(names), 1))(*names)
         self._must(self._L.fp_render_scene(self._h, len(names), arr, _p(p), tol_m, C.byref(rec), _p(recs) if records else None, FP_HOST))
         return out, (recs[:len(names)] if records else None)
+
+    # ---- pose errors (include/foundationpose_amd.h "pose errors") ----------------------------------
+    def pose_errors(self, target_name: str, est_poses, gt_poses, symmetries=None, vertex_step: int = 1, adds: bool = True):
+        """fp_pose_errors: ADD, ADD-S, MSSD and MSPD of est_poses [N,4,4] against gt_poses ([N,4,4], or one [4,4] for all of them: every
+        hypothesis of a Register against one truth) -> [PoseError] * N.  symmetries: [S,4,4] in the MESH frame (BOP's models_info.json,
+        already discretised), None = none; the identity is always symmetry 0 of best_sym.  vertex_step: use every vertex_step-th vertex.
+        adds=False skips the Vs^2 nearest-neighbour part (adds_m is NaN then).  Needs no frame."""
+        e = to_colmajor(np.asarray(est_poses, np.float32).reshape(-1, 4, 4))
+        g = to_colmajor(np.asarray(gt_poses, np.float32).reshape(-1, 4, 4))
+        s = None if symmetries is None or len(symmetries) == 0 else to_colmajor(np.asarray(symmetries, np.float32).reshape(-1, 4, 4))
+        out = (_lib.FpPoseError * max(len(e), 1))()
+        self._must(self._L.fp_pose_errors(self._h, target_name.encode(), _p(e), len(e), _p(g), len(g), _p(s), 0 if s is None else len(s),
+                                          int(vertex_step), 1 if adds else 0, out))
+        return [PoseError(float(r.add_m), float(r.adds_m), float(r.mssd_m), float(r.mspd_px), float(r.rot_deg), float(r.trans_m), r.best_sym,
+                          r.best_sym_mspd, r.add_sum_q20, r.adds_sum_q20, r.n_vertices) for r in out[:len(e)]]
 
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):

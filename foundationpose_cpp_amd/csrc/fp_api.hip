@@ -515,6 +515,14 @@ struct fp_model {
   uint8_t *sc_out = nullptr;               // FP_HOST outputs: [cover_bits | depth | tri_id | overlay | instance_id | visible_mask] of sc_out_px pixels
   size_t sc_vert_cap = 0, sc_work_cap = 0, sc_list_cap = 0, sc_out_px = 0;
 
+  // pose errors (fp_pose_errors): the same terms -- allocated at the first call, grow-only, read by no captured graph.
+  float *pe_mats = nullptr;                // [pe_mat_cap] floats: estimates [N, 12] | relative transforms [N, 12] | composites [N (S + 1), 12]
+  PoseErrPair *pe_pairs = nullptr;         // [pe_pair_cap] the paired kernel's record per (pose, symmetry)
+  unsigned long long *pe_sums = nullptr;   // [FP_MAX_BATCH] the nearest-neighbour kernel's sums
+  size_t pe_mat_cap = 0, pe_pair_cap = 0;
+  std::vector<float> pe_mats_host;         // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
+  std::vector<PoseErrPair> pe_pairs_host;
+
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
   // into a hipGraph and replayed.  The graph bakes buffer addresses, so it is keyed by g_alloc_epoch.
   // (Register's ~110 launches are replayed the same way: inter-kernel gaps are ~4 % of a 12 ms Register.)
@@ -1252,6 +1260,7 @@ static void destroy_model_impl(fp_model *m) {
   dev_free(m->fr_snap); dev_free(m->fr_cam); dev_free(m->fr_flag); dev_free(m->fr_out);
   dev_free(m->sc_table); dev_free(m->sc_snap); dev_free(m->sc_cam); dev_free(m->sc_work); dev_free(m->sc_list); dev_free(m->sc_out);
   delete m->sc_table_host; m->sc_table_host = nullptr;
+  dev_free(m->pe_mats); dev_free(m->pe_pairs); dev_free(m->pe_sums);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
@@ -2684,6 +2693,186 @@ int fp_render_scene(fp_model *m, int K, const char *const *target_names, const f
       r.n_hidden = r.n_covered - r.n_front;
       r.n_occluded = r.n_front - r.n_visible;
     }
+  }
+  return 0;
+} FP_CATCH_INT
+
+// ---- pose errors: ADD, ADD-S, MSSD, MSPD with object symmetries
+namespace {
+struct Rigid {   // host side, double: linear part ROW-major, then t
+  double r[9], t[3];
+};
+Rigid rigid_from_colmajor(const float *p) {
+  Rigid x;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) x.r[r * 3 + c] = (double)p[c * 4 + r];
+    x.t[r] = (double)p[12 + r];
+  }
+  return x;
+}
+Rigid rigid_mul(const Rigid &a, const Rigid &b) {   // a b
+  Rigid x;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) x.r[r * 3 + c] = (a.r[r * 3] * b.r[c] + a.r[r * 3 + 1] * b.r[3 + c]) + a.r[r * 3 + 2] * b.r[6 + c];
+    x.t[r] = ((a.r[r * 3] * b.t[0] + a.r[r * 3 + 1] * b.t[1]) + a.r[r * 3 + 2] * b.t[2]) + a.t[r];
+  }
+  return x;
+}
+Rigid rigid_inv_mul(const Rigid &a, const Rigid &b) {   // a^-1 b for a rigid a: (Ra^T Rb, Ra^T (tb - ta))
+  Rigid x;
+  const double d[3] = {b.t[0] - a.t[0], b.t[1] - a.t[1], b.t[2] - a.t[2]};
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) x.r[r * 3 + c] = (a.r[r] * b.r[c] + a.r[3 + r] * b.r[3 + c]) + a.r[6 + r] * b.r[6 + c];
+    x.t[r] = (a.r[r] * d[0] + a.r[3 + r] * d[1]) + a.r[6 + r] * d[2];
+  }
+  return x;
+}
+void rigid_to_f32(const Rigid &x, float *o) {
+  for (int k = 0; k < 9; k++) o[k] = (float)x.r[k];
+  for (int k = 0; k < 3; k++) o[9 + k] = (float)x.t[k];
+}
+// every entry finite, no translation component beyond +-1000 m
+bool pose_error_matrix_ok(const float *p) {
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(p[k])) return false;
+  return std::fabs(p[12]) <= 1000.0f && std::fabs(p[13]) <= 1000.0f && std::fabs(p[14]) <= 1000.0f;
+}
+long long pose_error_vs(int V, long long step) { return ((long long)V + step - 1) / step; }
+bool pose_error_adds_fits(int N, int V, long long step) {
+  const unsigned __int128 vs = (unsigned __int128)pose_error_vs(V, step);
+  return (unsigned __int128)N * vs * vs <= (unsigned __int128)FP_POSE_ERROR_MAX_PAIRS;
+}
+}  // namespace
+static_assert(sizeof(fp_pose_error) == 56, "fp_pose_error: six floats, two 32-bit words, two 64-bit sums, two 32-bit words");
+static_assert(FP_POSE_ERROR_MAX_PAIRS / 640 >= 1, "the launch shares of fp_pose_errors are whole numbers");
+int fp_pose_errors(fp_model *m, const char *target_name, const float *est_poses, int N, const float *gt_poses, int n_gt,
+                   const float *symmetries, int S, int vertex_step, int flags, fp_pose_error *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && est_poses && gt_poses && out, "[FoundationPose] fp_pose_errors: invalid arguments");
+  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fp_pose_errors: " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  FP_CHECK(n_gt == 1 || n_gt == N, "[FoundationPose] fp_pose_errors: n_gt must be 1 or N");
+  FP_CHECK(S >= 0 && S <= FP_MAX_SYMMETRIES, "[FoundationPose] fp_pose_errors: " + std::to_string(S) + " symmetries (0..FP_MAX_SYMMETRIES = " + std::to_string(FP_MAX_SYMMETRIES) + ")");
+  FP_CHECK(S == 0 || symmetries, "[FoundationPose] fp_pose_errors: invalid arguments (S > 0 without symmetries)");
+  FP_CHECK(vertex_step >= 1, "[FoundationPose] fp_pose_errors: vertex_step must be >= 1");
+  FP_CHECK(!(flags & ~FP_POSE_ERROR_ADDS), "[FoundationPose] fp_pose_errors: unknown flag bits");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_pose_errors: a submitted Track has not been waited for (fp_track_wait)");
+  Target *t = m->find(target_name ? target_name : "");
+  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  const char *bad = "a non-finite entry or a translation beyond +-1000 m in ";
+  for (int i = 0; i < N; i++)
+    FP_CHECK(pose_error_matrix_ok(est_poses + (size_t)i * 16), std::string("[FoundationPose] fp_pose_errors: ") + bad + "est_poses[" + std::to_string(i) + "]");
+  for (int i = 0; i < n_gt; i++)
+    FP_CHECK(pose_error_matrix_ok(gt_poses + (size_t)i * 16), std::string("[FoundationPose] fp_pose_errors: ") + bad + "gt_poses[" + std::to_string(i) + "]");
+  for (int i = 0; i < S; i++)
+    FP_CHECK(pose_error_matrix_ok(symmetries + (size_t)i * 16), std::string("[FoundationPose] fp_pose_errors: ") + bad + "symmetries[" + std::to_string(i) + "]");
+  const DeviceMesh &mesh = t->mesh;
+  const bool adds = (flags & FP_POSE_ERROR_ADDS) != 0;
+  const int S1 = S + 1;
+  const int Vs = (int)pose_error_vs(mesh.V, vertex_step);
+  if (adds && !pose_error_adds_fits(N, mesh.V, vertex_step)) {
+    long long lo = vertex_step, hi = mesh.V;   // (hi: one vertex, N pairs, always fits)
+    while (lo < hi) {
+      const long long mid = lo + (hi - lo) / 2;
+      if (pose_error_adds_fits(N, mesh.V, mid)) hi = mid;
+      else lo = mid + 1;
+    }
+    FP_CHECK(false, "[FoundationPose] fp_pose_errors: ADD-S over " + std::to_string(N) + " poses x " + std::to_string(Vs) + "^2 point pairs is above FP_POSE_ERROR_MAX_PAIRS = " +
+                        std::to_string((long long)FP_POSE_ERROR_MAX_PAIRS) + "; the smallest vertex_step that fits is " + std::to_string(lo));
+  }
+  const long long n_pairs = (long long)N * S1;
+  FP_CHECK(n_pairs * Vs <= FP_POSE_ERROR_MAX_PAIRS / 64, "[FoundationPose] fp_pose_errors: " + std::to_string(N) + " poses x " + std::to_string(S1) + " symmetries x " +
+               std::to_string(Vs) + " vertices is above FP_POSE_ERROR_MAX_PAIRS / 64 = " + std::to_string((long long)FP_POSE_ERROR_MAX_PAIRS / 64) + " transformed vertex pairs: raise vertex_step");
+  // host, double: the conjugated symmetries x' = R_s (x + c) + t_s - c (identity first), the composites G S_s and D = E^-1 G
+  std::vector<Rigid> sym((size_t)S1);
+  sym[0] = Rigid{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
+  const double c[3] = {(double)mesh.center[0], (double)mesh.center[1], (double)mesh.center[2]};
+  for (int s = 0; s < S; s++) {
+    Rigid x = rigid_from_colmajor(symmetries + (size_t)s * 16);
+    for (int r = 0; r < 3; r++) x.t[r] = (((x.r[r * 3] * c[0] + x.r[r * 3 + 1] * c[1]) + x.r[r * 3 + 2] * c[2]) + x.t[r]) - c[r];
+    sym[(size_t)s + 1] = x;
+  }
+  const size_t mat_floats = ((size_t)2 * N + (size_t)n_pairs) * 12;
+  m->pe_mats_host.resize(mat_floats);
+  float *est_h = m->pe_mats_host.data(), *rel_h = est_h + (size_t)N * 12, *comp_h = rel_h + (size_t)N * 12;
+  for (int i = 0; i < N; i++) {
+    const Rigid E = rigid_from_colmajor(est_poses + (size_t)i * 16), G = rigid_from_colmajor(gt_poses + (size_t)(n_gt == 1 ? 0 : i) * 16);
+    rigid_to_f32(E, est_h + (size_t)i * 12);
+    rigid_to_f32(rigid_inv_mul(E, G), rel_h + (size_t)i * 12);
+    for (int s = 0; s < S1; s++) rigid_to_f32(rigid_mul(G, sym[(size_t)s]), comp_h + ((size_t)i * S1 + s) * 12);
+  }
+  // buffers: grow-only; nothing of the stream may still read a block that is replaced
+  hipStream_t st = m->stream;
+  if (mat_floats > m->pe_mat_cap || (size_t)n_pairs > m->pe_pair_cap || !m->pe_sums) {
+    FP_HIP_OK(hipStreamSynchronize(st));
+    if (mat_floats > m->pe_mat_cap) {
+      dev_free(m->pe_mats);
+      m->pe_mat_cap = 0;
+      if (dev_alloc(&m->pe_mats, mat_floats)) return 1;
+      m->pe_mat_cap = mat_floats;
+    }
+    if ((size_t)n_pairs > m->pe_pair_cap) {
+      dev_free(m->pe_pairs);
+      m->pe_pair_cap = 0;
+      if (dev_alloc(&m->pe_pairs, (size_t)n_pairs)) return 1;
+      m->pe_pair_cap = (size_t)n_pairs;
+    }
+    if (!m->pe_sums && dev_alloc(&m->pe_sums, (size_t)FP_MAX_BATCH)) return 1;
+  }
+  const float *est_d = m->pe_mats, *rel_d = est_d + (size_t)N * 12, *comp_d = rel_d + (size_t)N * 12;
+  FP_HIP_OK(hipMemcpyAsync(m->pe_mats, est_h, mat_floats * sizeof(float), hipMemcpyHostToDevice, st));
+  {
+    // no launch above a tenth of the cap: whole pairs (one workgroup each) per launch
+    const long long per_launch = std::min<long long>(std::max<long long>(FP_POSE_ERROR_MAX_PAIRS / 640 / Vs, 1), 1 << 30);
+    ProfScope ps(&m->prof, st, "pose_error_pairs", 0, (double)n_pairs * ((double)Vs * 12.0 + 72.0));
+    for (long long p0 = 0; p0 < n_pairs; p0 += per_launch) {
+      launch_pose_error_pairs(st, mesh.verts, Vs, vertex_step, m->K[0], m->K[4], m->K[2], m->K[5], est_d, comp_d, S1, p0,
+                              (int)std::min(per_launch, n_pairs - p0), m->pe_pairs);
+      FP_HIP_OK(hipGetLastError());
+    }
+  }
+  if (adds) {
+    FP_HIP_OK(hipMemsetAsync(m->pe_sums, 0, (size_t)N * sizeof(unsigned long long), st));
+    const int per_launch = (int)std::min<long long>(std::max<long long>(FP_POSE_ERROR_MAX_PAIRS / 10 / ((long long)Vs * Vs), 1), N);
+    ProfScope ps(&m->prof, st, "pose_error_nn", (double)N * Vs * Vs * 8.0, (double)N * Vs * 12.0);
+    for (int p0 = 0; p0 < N; p0 += per_launch) {
+      launch_pose_error_nn(st, mesh.verts, Vs, vertex_step, rel_d, p0, std::min(per_launch, N - p0), m->pe_sums);
+      FP_HIP_OK(hipGetLastError());
+    }
+  }
+  m->pe_pairs_host.resize((size_t)n_pairs);
+  std::vector<unsigned long long> sums((size_t)N, 0);
+  FP_HIP_OK(hipMemcpyAsync(m->pe_pairs_host.data(), m->pe_pairs, (size_t)n_pairs * sizeof(PoseErrPair), hipMemcpyDeviceToHost, st));
+  if (adds) FP_HIP_OK(hipMemcpyAsync(sums.data(), m->pe_sums, (size_t)N * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  FP_HIP_OK(hipStreamSynchronize(st));
+  // the min over the symmetries (lowest index on ties) and the host-derived fields
+  const auto as_float = [](unsigned bits) { float f; std::memcpy(&f, &bits, sizeof(f)); return f; };
+  for (int i = 0; i < N; i++) {
+    const PoseErrPair *pr = m->pe_pairs_host.data() + (size_t)i * S1;
+    fp_pose_error r = {};
+    int best = 0, best_px = 0, near = 0;
+    for (int s = 0; s < S1; s++) {
+      if (as_float(pr[s].max_d_bits) < as_float(pr[best].max_d_bits)) best = s;
+      if (as_float(pr[s].max_px_bits) < as_float(pr[best_px].max_px_bits)) best_px = s;
+      near |= pr[s].near;
+    }
+    r.add_sum_q20 = pr[0].sum_q20;
+    r.add_m = (float)((double)pr[0].sum_q20 / 1048576.0 / (double)Vs);
+    r.adds_sum_q20 = adds ? (int64_t)sums[(size_t)i] : -1;
+    r.adds_m = adds ? (float)((double)sums[(size_t)i] / 1048576.0 / (double)Vs) : std::nanf("");
+    r.mssd_m = as_float(pr[best].max_d_bits);
+    r.best_sym = best;
+    r.mspd_px = near ? INFINITY : as_float(pr[best_px].max_px_bits);
+    r.best_sym_mspd = near ? -1 : best_px;
+    const Rigid E = rigid_from_colmajor(est_poses + (size_t)i * 16);
+    const Rigid GS = rigid_mul(rigid_from_colmajor(gt_poses + (size_t)(n_gt == 1 ? 0 : i) * 16), sym[(size_t)best]);
+    const Rigid D = rigid_inv_mul(E, GS);
+    // angle of E^T (G S): atan2 of the skew part's length and the trace term -- exactly 0 for equal matrices, accurate for small angles
+    const double sx = (D.r[7] - D.r[5]) / 2, sy = (D.r[2] - D.r[6]) / 2, sz = (D.r[3] - D.r[1]) / 2;
+    r.rot_deg = (float)(std::atan2(std::sqrt((sx * sx + sy * sy) + sz * sz), ((D.r[0] + D.r[4] + D.r[8]) - 1.0) / 2) * (180.0 / 3.14159265358979323846));
+    const double dx = E.t[0] - GS.t[0], dy = E.t[1] - GS.t[1], dz = E.t[2] - GS.t[2];
+    r.trans_m = (float)std::sqrt((dx * dx + dy * dy) + dz * dz);
+    r.n_vertices = Vs;
+    out[i] = r;
   }
   return 0;
 } FP_CATCH_INT

@@ -383,6 +383,23 @@ void launch_scene_bin_fill(hipStream_t s, const SceneTable *table, unsigned tota
 void launch_scene_raster(hipStream_t s, const SceneTable *table, const int4 *snap, const float4 *cam, const unsigned *offset,
                          const unsigned *list, const uint8_t *rgb, const float *depth, int H, int W, float tol_m, const SceneRenderOut &out);
 
+// pose errors (fp_pose_errors; fp_pose_error.hip).  Matrices are 12 floats: the linear part ROW-major, then t.
+constexpr int POSE_ERROR_THREADS = 256;
+constexpr int POSE_ERROR_QUERIES = 4;      // query points a lane of the nearest-neighbour kernel keeps in registers
+constexpr int POSE_ERROR_TILE = 1024;      // target points staged in LDS at a time (structure of arrays, 12 KB)
+struct PoseErrPair {                       // what the paired kernel leaves per (pose, symmetry)
+  unsigned max_d_bits, max_px_bits;        // bit patterns of max_v |a - b| and of the largest projected distance (both >= 0)
+  int near, pad;                           // non-zero: a used vertex has !(z >= FRAME_RENDER_NEAR) under either transform
+  long long sum_q20;                       // sum_v llrintf(|a - b| * 2^20)
+};
+// pair p = pose * S1 + s of [pair0, pair0 + n_pairs): a = est[pose] v, b = comp[p] v over the vertices 0, step, ... (Vs of them); one
+// workgroup per pair, every entry of out [pair0, pair0 + n_pairs) is written
+void launch_pose_error_pairs(hipStream_t s, const float *verts, int Vs, int step, float fx, float fy, float cx, float cy, const float *est,
+                             const float *comp, int S1, long long pair0, int n_pairs, PoseErrPair *out);
+// poses [pose0, pose0 + n_poses): sums[pose] += sum_u llrintf(min_v |rel[pose] u - v| * 2^20) over the same Vs vertices on both sides
+void launch_pose_error_nn(hipStream_t s, const float *verts, int Vs, int step, const float *rel, int pose0, int n_poses,
+                          unsigned long long *sums);
+
 // host helpers (fp_host.cpp part of fp_api.hip)
 std::vector<float> make_rotation_grid(int min_views, int inplane_steps);
 

@@ -278,6 +278,57 @@ typedef struct fp_scene_render {           /* every pointer optional; all in the
 int fp_render_scene(fp_model *m, int K, const char *const *target_names, const float *poses /* K column-major 4x4 */,
                     float tol_m, const fp_scene_render *out, fp_scene_object *objects /* host [K], may be NULL */, int memspace);
 
+/* ---- pose errors: how wrong is a pose? ADD, ADD-S, MSSD, MSPD with object symmetries (new; the reference has no counterpart) ----
+ * fp_pose_errors compares N (1..FP_MAX_BATCH) estimated poses of `target_name` with ground truth: est_poses and gt_poses are column-major
+ * 4x4 matrices, centred-mesh -> camera, rigid (what Register and Track return); n_gt == N pairs estimate i with ground truth i,
+ * n_gt == 1 compares every estimate with the one ground truth (all hypotheses of a Register against one truth).  With E the
+ * estimate, G the ground truth and v the used vertices of the target's centred mesh:
+ *   ADD   = mean_v |E v - G v|                            (Hinterstoisser et al.; what FoundationPose reports the AUC of)
+ *   ADD-S = mean_u min_v |G u - E v|                      (the symmetric form: every ground-truth point to the NEAREST estimated point)
+ *   MSSD  = min_s max_v |E v - G S_s v|                   (BOP: maximum symmetry-aware surface distance)
+ *   MSPD  = min_s max_v |proj(E v) - proj(G S_s v)|       (BOP: ... projection distance, pixels, with the model's K)
+ * Symmetries: S column-major 4x4 matrices in the MESH frame (NOT centred), already discretised, as BOP's models_info.json has them;
+ * the library conjugates them with the target's centre on the host in double, x' = R_s (x + c) + t_s - c.  The identity is always
+ * symmetry 0 and the caller's set follows as 1..S, so best_sym / best_sym_mspd index that combined list; S may be 0 (symmetries may
+ * then be NULL).  best_sym is also the answer to "which symmetry-equivalent of G is nearest to E" (a serving loop that must not jump
+ * between equivalents).  The composites G S_s are formed on the host in double and rounded to f32; rot_deg / trans_m compare E with
+ * G S_best_sym on the host in double.
+ * Vertices: 0, vertex_step, 2 vertex_step, ... < V of the target, so n_vertices = Vs = ceil(V / vertex_step); vertex_step >= 1.
+ * ADD-S is brute force over Vs^2 point pairs per pose -- exact, no build step -- and is computed only with FP_POSE_ERROR_ADDS.
+ * Projection: u = fx * (x / z) + cx, w = fy * (y / z) + cy, every f32 operation separately rounded.  If any used vertex has
+ * z < FP_RENDER_NEAR_M under E or under any G S_s, the record gets mspd_px = INFINITY and best_sym_mspd = -1; its other fields
+ * are unaffected.
+ * Means: each distance d is an f32 and enters a 64-bit integer sum as llrintf(d * 2^20), so a record does not depend on thread order:
+ * pose i's record is bit-identical alone, in a batch and from call to call.  add_m = (float)(add_sum_q20 / 2^20 / Vs), in double.
+ * Refused with an error before anything is launched and before `out` is written: an unknown target, N outside 1..FP_MAX_BATCH, n_gt
+ * not 1 or N, S outside 0..FP_MAX_SYMMETRIES, vertex_step < 1, unknown flag bits, a non-finite entry or a translation component
+ * beyond +-1000 m in any matrix, a pending Track, with FP_POSE_ERROR_ADDS more than FP_POSE_ERROR_MAX_PAIRS point pairs N * Vs^2
+ * (the message names the smallest vertex_step that fits), and more than FP_POSE_ERROR_MAX_PAIRS / 64 transformed vertex pairs
+ * N * (S + 1) * Vs.  The caps keep the largest admitted call near one second of device time; no single launch covers more than a
+ * tenth of a cap (the call is split over poses).
+ * Needs no frame; works on geometry-only models; stream-ordered behind the model's work on the model's stream, one synchronisation
+ * at the end.  Register, Track, their captured graphs and every existing kernel are untouched: the call's buffers are its own,
+ * allocated at its first use, grow-only. */
+#define FP_POSE_ERROR_ADDS 1          /* flags: also compute ADD-S (the N * Vs^2 part) */
+#define FP_MAX_SYMMETRIES 1024
+#define FP_POSE_ERROR_MAX_PAIRS 8000000000000LL /* N * Vs^2 of one call with FP_POSE_ERROR_ADDS: 0.84 s at the 9.5e12 pairs/s measured */
+typedef struct fp_pose_error {
+  float   add_m;          /* mean_v |E v - G v|                                   */
+  float   adds_m;         /* mean_u min_v |G u - E v|   (NaN without the flag)    */
+  float   mssd_m;         /* min_s max_v |E v - G S_s v|                          */
+  float   mspd_px;        /* min_s max_v |proj(E v) - proj(G S_s v)|, model's K   */
+  float   rot_deg, trans_m; /* E against G S_best_sym, host, computed in double   */
+  int32_t best_sym;       /* arg-min of MSSD, lowest index on ties                */
+  int32_t best_sym_mspd;  /* arg-min of MSPD, -1 when mspd_px is INFINITY         */
+  int64_t add_sum_q20, adds_sum_q20;  /* the integer sums behind the two means (adds: -1 without the flag) */
+  int32_t n_vertices;     /* Vs */
+  int32_t reserved;
+} fp_pose_error;
+int fp_pose_errors(fp_model *m, const char *target_name, const float *est_poses, int N,
+                   const float *gt_poses, int n_gt /* 1 or N */,
+                   const float *symmetries /* S column-major 4x4, MESH frame; NULL = none */, int S,
+                   int vertex_step, int flags, fp_pose_error *out /* host [N] */);
+
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 
 /* UploadDataToDevice + convert_depth_to_xyz_map (src/foundationpose.cpp:267-315, src/foundationpose_utils.cu:3-32). */

@@ -209,6 +209,17 @@ public:
                               objects ? objects->data() : nullptr, memspace));
   }
 
+  // pose errors (foundationpose_amd.h "pose errors"): ADD, ADD-S, MSSD and MSPD of `est` against `gt` (one pose per estimate, or ONE for
+  // all of them: every hypothesis of a Register against one truth).  symmetries: mesh frame, already discretised (BOP's models_info.json);
+  // the identity is always symmetry 0 of best_sym.  adds = false skips the Vs^2 nearest-neighbour part (adds_m is NaN then).  Needs no frame.
+  bool PoseErrors(const std::string &target_name, const std::vector<Pose> &est, const std::vector<Pose> &gt, std::vector<fp_pose_error> &out,
+                  const std::vector<Pose> &symmetries = {}, int vertex_step = 1, bool adds = true) {
+    out.resize(est.size());
+    return ok(fp_pose_errors(h_, target_name.c_str(), est.empty() ? nullptr : est[0].data(), (int)est.size(), gt.empty() ? nullptr : gt[0].data(),
+                             (int)gt.size(), symmetries.empty() ? nullptr : symmetries[0].data(), (int)symmetries.size(), vertex_step,
+                             adds ? FP_POSE_ERROR_ADDS : 0, out.data()));
+  }
+
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
 
