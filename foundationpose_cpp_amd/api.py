@@ -403,6 +403,19 @@ class FoundationPose:
         self._must(self._L.fp_pose_fit_eval(self._h, target_name.encode(), _p(p), len(p), crop_ratio, tol_m, out))
         return [_fit(r) for r in out]
 
+    def _render_outputs(self, table: dict, record, fn: str, want):
+        """what render_pose and render_scene begin with -> ({name: zeroed array of the uploaded frame's size}, the ctypes record of their
+        addresses) for the names in `want`, all of which `table` ({name: (dtype, trailing shape)}) must know"""
+        hw = getattr(self, "_hw", None)
+        if hw is None:
+            self.last_error = f"[FoundationPose] fp_{fn}: no frame uploaded"
+            raise FoundationPoseError(self.last_error)
+        unknown = [n for n in want if n not in table]
+        if unknown:
+            raise FoundationPoseError(f"[FoundationPose] {fn}: unknown outputs {unknown}")
+        out = {n: np.zeros(tuple(hw) + table[n][1], table[n][0]) for n in want}
+        return out, record(**{n: _p(a) for n, a in out.items()})
+
     # ---- a pose at frame resolution (include/foundationpose_amd.h "a pose at frame resolution") ----
     RENDER_OUTPUTS = {"model_depth": (np.float32, ()), "model_mask": (np.uint8, ()), "visible_mask": (np.uint8, ()),
                       "tri_id": (np.int32, ()), "overlay": (np.uint8, (3,))}
@@ -413,15 +426,7 @@ class FoundationPose:
         -> {name: array} for the names in `want`: model_depth [H,W] f32 (0 = background), model_mask / visible_mask [H,W] u8 (255 / 0),
         tri_id [H,W] i32 (triangle + 1), overlay [H,W,3] u8.  A model pixel is visible unless the RAW observed depth is valid and more
         than tol_m in front of it.  Raises FoundationPoseError for a pose that would need clipping (a vertex nearer than 1 cm)."""
-        hw = getattr(self, "_hw", None)
-        if hw is None:
-            self.last_error = "[FoundationPose] fp_render_pose: no frame uploaded"
-            raise FoundationPoseError(self.last_error)
-        unknown = [n for n in want if n not in self.RENDER_OUTPUTS]
-        if unknown:
-            raise FoundationPoseError(f"[FoundationPose] render_pose: unknown outputs {unknown}")
-        out = {n: np.zeros(tuple(hw) + self.RENDER_OUTPUTS[n][1], self.RENDER_OUTPUTS[n][0]) for n in want}
-        rec = _lib.FpFrameRender(**{n: _p(a) for n, a in out.items()})
+        out, rec = self._render_outputs(self.RENDER_OUTPUTS, _lib.FpFrameRender, "render_pose", want)
         p = to_colmajor(np.asarray(pose, np.float32).reshape(4, 4))
         self._must(self._L.fp_render_pose(self._h, target_name.encode(), _p(p), tol_m, C.byref(rec), FP_HOST))
         return out
@@ -440,19 +445,11 @@ class FoundationPose:
         o's own silhouette covers the pixel, the overlay draws object o in tint o % 8.  records (None when `records` is false): a
         structured array [K] of SCENE_RECORD -- n_covered, n_front, n_hidden (behind another object of the call), n_visible,
         n_occluded (behind something observed).  Raises FoundationPoseError when any object's pose would need clipping."""
-        hw = getattr(self, "_hw", None)
-        if hw is None:
-            self.last_error = "[FoundationPose] fp_render_scene: no frame uploaded"
-            raise FoundationPoseError(self.last_error)
-        unknown = [n for n in want if n not in self.SCENE_OUTPUTS]
-        if unknown:
-            raise FoundationPoseError(f"[FoundationPose] render_scene: unknown outputs {unknown}")
+        out, rec = self._render_outputs(self.SCENE_OUTPUTS, _lib.FpSceneRender, "render_scene", want)
         names = [n.encode() for n in target_names]
         p = to_colmajor(np.asarray(poses, np.float32).reshape(-1, 4, 4))
         if len(p) != len(names):
             raise FoundationPoseError(f"[FoundationPose] render_scene: {len(names)} names but {len(p)} poses")
-        out = {n: np.zeros(tuple(hw) + self.SCENE_OUTPUTS[n][1], self.SCENE_OUTPUTS[n][0]) for n in want}
-        rec = _lib.FpSceneRender(**{n: _p(a) for n, a in out.items()})
         recs = np.zeros(max(len(names), 1), self.SCENE_RECORD) if records else None
         arr = (C.c_char_p * max(len(names), 1))(*names)
         self._must(self._L.fp_render_scene(self._h, len(names), arr, _p(p), tol_m, C.byref(rec), _p(recs) if records else None, FP_HOST))

@@ -340,6 +340,19 @@ static void dev_free(T *&p) {
   if (p) (void)hipFree(p);
   p = nullptr;
 }
+// Device scratch of the stage operators (a model's fr_*, sc_*, pe_* blocks, used on stream s): grow-only, and nothing of the stream may
+// still read a block that is replaced.  No captured graph reads these blocks, so unlike ensure_capacity / ensure_window this leaves
+// the allocation epoch alone.
+template <typename T>
+static int grow_scratch(hipStream_t s, T *&p, size_t &cap, size_t need) {
+  if (need <= cap) return 0;
+  FP_HIP_OK(hipStreamSynchronize(s));
+  dev_free(p);
+  cap = 0;
+  if (dev_alloc(&p, need)) return 1;
+  cap = need;
+  return 0;
+}
 // pinned host memory and the device's address of it; a block whose device address cannot be had is freed again (*host stays as it was)
 template <typename T>
 static hipError_t pinned_mapped_alloc(T **host, T **dev, size_t bytes, unsigned flags) {
@@ -496,24 +509,21 @@ struct fp_model {
   // record.  No buffer of its own: Register's sampler leaves the whole frame's D' there anyway, Track fills its window of it.
   bool dfilt_on = false;
 
-  // frame-resolution rendering (fp_render_pose).  Nothing below is allocated before the first call; no captured
-  // graph reads any of it, so growing it never touches the allocation epoch.
-  int4 *fr_snap = nullptr;      // [fr_vert_cap] {xi, yi, bits(z), 0}
+  // frame-resolution rendering (fp_render_pose, DESIGN.md section 4.8, and fp_render_scene, section 4.9).  Nothing below is allocated
+  // before the first call; no captured graph reads any of it, so growing it (grow_scratch) never touches the allocation epoch.  The two
+  // calls share fr_snap / fr_cam / fr_out: both hold the SerialGuard and leave the stream synchronised, so they never overlap.
+  int4 *fr_snap = nullptr;      // [fr_vert_cap] {xi, yi, bits(z), 0}: the mesh's vertices, or all objects' of a scene
   float4 *fr_cam = nullptr;     // [fr_vert_cap] camera-space vertices
-  int *fr_flag = nullptr;       // the vertex pass's refusal word
-  uint8_t *fr_out = nullptr;    // FP_HOST outputs are rendered here first: [depth | tri_id | overlay | model_mask | visible_mask] of fr_out_px pixels
-  size_t fr_vert_cap = 0, fr_out_px = 0;
+  int *fr_flag = nullptr;       // fp_render_pose's refusal word
+  uint8_t *fr_out = nullptr;    // [fr_out_bytes] FP_HOST outputs are rendered here first: the call's wanted planes, each 256-byte aligned
+  size_t fr_vert_cap = 0, fr_out_bytes = 0;
 
-  // all tracked objects at frame resolution (fp_render_scene): the same terms -- allocated at the first call, grow-only,
-  // read by no captured graph.
+  // what only fp_render_scene needs: the same terms -- allocated at the first call, grow-only, read by no captured graph.
   SceneTable *sc_table = nullptr;          // device copy of sc_table_host
   SceneTable *sc_table_host = nullptr;     // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
-  int4 *sc_snap = nullptr;                 // [sc_vert_cap] scene vertices, frame_vertex_kernel's format
-  float4 *sc_cam = nullptr;
   int *sc_work = nullptr;                  // [sc_work_cap] flags | total | counters | tile counts | offsets | cursors (scene_work_words)
   unsigned *sc_list = nullptr;             // [sc_list_cap] the tiles' triangle lists
-  uint8_t *sc_out = nullptr;               // FP_HOST outputs: [cover_bits | depth | tri_id | overlay | instance_id | visible_mask] of sc_out_px pixels
-  size_t sc_vert_cap = 0, sc_work_cap = 0, sc_list_cap = 0, sc_out_px = 0;
+  size_t sc_work_cap = 0, sc_list_cap = 0;
 
   // pose errors (fp_pose_errors): the same terms -- allocated at the first call, grow-only, read by no captured graph.
   float *pe_mats = nullptr;                // [pe_mat_cap] floats: estimates [N, 12] | relative transforms [N, 12] | composites [N (S + 1), 12]
@@ -1258,7 +1268,7 @@ static void destroy_model_impl(fp_model *m) {
   if (m->digests) (void)hipFree(m->digests);
   dev_free(m->fit_acc); dev_free(m->fit_rec);
   dev_free(m->fr_snap); dev_free(m->fr_cam); dev_free(m->fr_flag); dev_free(m->fr_out);
-  dev_free(m->sc_table); dev_free(m->sc_snap); dev_free(m->sc_cam); dev_free(m->sc_work); dev_free(m->sc_list); dev_free(m->sc_out);
+  dev_free(m->sc_table); dev_free(m->sc_work); dev_free(m->sc_list);
   delete m->sc_table_host; m->sc_table_host = nullptr;
   dev_free(m->pe_mats); dev_free(m->pe_pairs); dev_free(m->pe_sums);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
@@ -2464,38 +2474,86 @@ int fp_pose_fit_eval(fp_model *m, const char *target_name, const float *poses, i
   return 0;
 } FP_CATCH_INT
 
-// ---- frame-resolution rendering of one pose
+// ---- frame-resolution rendering of one pose, and the host steps it shares with section 4.9 below
+static int grow_render_verts(fp_model *m, size_t verts) {   // fr_snap and fr_cam share one cap: it holds only while both blocks do
+  size_t snap_cap = m->fr_vert_cap, cam_cap = m->fr_vert_cap;
+  m->fr_vert_cap = 0;
+  if (grow_scratch(m->stream, m->fr_snap, snap_cap, verts) || grow_scratch(m->stream, m->fr_cam, cam_cap, verts)) return 1;
+  m->fr_vert_cap = snap_cap;
+  return 0;
+}
+
+// An output plane of a frame-resolution render: the caller's pointer (null: not wanted) and its bytes per pixel.
+struct RenderPlane {
+  void *user;
+  size_t bpp;
+};
+static bool planes_wanted(const RenderPlane *pl, int n) {
+  for (int i = 0; i < n; i++) if (pl[i].user) return true;
+  return false;
+}
 static size_t fr_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], float tol_m, const fp_frame_render *out, int memspace) try {
-  SerialGuard serial(m ? m->device : -1);
-  FP_CHECK(m && pose && out, "[FoundationPose] fp_render_pose: invalid arguments");
-  FP_CHECK(memspace == FP_HOST || memspace == FP_DEVICE, "[FoundationPose] fp_render_pose: memspace must be FP_HOST or FP_DEVICE");
-  FP_CHECK(out->model_depth || out->model_mask || out->visible_mask || out->tri_id || out->overlay, "[FoundationPose] fp_render_pose: no output requested");
-  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_render_pose: tol_m must be finite and >= 0 (metres)");
-  FP_CHECK(!m->track_pending, "[FoundationPose] fp_render_pose: a submitted Track has not been waited for (fp_track_wait)");
-  FP_CHECK(m->depth != nullptr && m->rgb != nullptr && m->H > 0, "[FoundationPose] fp_render_pose: no frame uploaded");
-  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
-  Target *t = m->find(target_name ? target_name : "");
-  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
-  const DeviceMesh &mesh = t->mesh;
-  const int H = m->H, W = m->W;
-  const size_t px = (size_t)H * W;
-  hipStream_t s = m->stream;
-  if ((size_t)mesh.V > m->fr_vert_cap) {
-    FP_HIP_OK(hipStreamSynchronize(s));
-    dev_free(m->fr_snap); dev_free(m->fr_cam);
-    m->fr_vert_cap = 0;
-    if (dev_alloc(&m->fr_snap, (size_t)mesh.V) || dev_alloc(&m->fr_cam, (size_t)mesh.V)) return 1;
-    m->fr_vert_cap = (size_t)mesh.V;
+// dev[i] = where the kernel writes plane i (null: not wanted): the caller's own memory for FP_DEVICE; for FP_HOST a 256-byte-aligned
+// place in the model's staging block, the wanted planes one after the other in the order given.  (The offsets are those of THIS
+// frame size: a smaller frame than the block was sized for uses its front.)
+static int place_planes(fp_model *m, const RenderPlane *pl, int n, size_t px, int memspace, uint8_t **dev) {
+  size_t total = 0;
+  for (int i = 0; i < n; i++) if (pl[i].user) total += fr_align(px * pl[i].bpp);
+  if (memspace == FP_HOST && grow_scratch(m->stream, m->fr_out, m->fr_out_bytes, total)) return 1;
+  uint8_t *at = m->fr_out;
+  for (int i = 0; i < n; i++) {
+    dev[i] = memspace == FP_HOST && pl[i].user ? at : static_cast<uint8_t *>(pl[i].user);
+    if (pl[i].user) at += fr_align(px * pl[i].bpp);
   }
-  if (!m->fr_flag && dev_alloc(&m->fr_flag, 1)) return 1;
+  return 0;
+}
+static int download_planes(fp_model *m, const RenderPlane *pl, int n, size_t px, uint8_t *const *dev) {
+  for (int i = 0; i < n; i++)
+    if (pl[i].user) FP_HIP_OK(hipMemcpyAsync(pl[i].user, dev[i], px * pl[i].bpp, hipMemcpyDeviceToHost, m->stream));
+  return 0;
+}
+
+// what both calls ask of their arguments and of the model's frame, after their own argument checks
+static int render_preconditions(const fp_model *m, const std::string &fn, int memspace, bool any_output, float tol_m) {
+  FP_CHECK(memspace == FP_HOST || memspace == FP_DEVICE, "[FoundationPose] " + fn + ": memspace must be FP_HOST or FP_DEVICE");
+  FP_CHECK(any_output, "[FoundationPose] " + fn + ": no output requested");
+  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] " + fn + ": tol_m must be finite and >= 0 (metres)");
+  FP_CHECK(!m->track_pending, "[FoundationPose] " + fn + ": a submitted Track has not been waited for (fp_track_wait)");
+  FP_CHECK(m->depth != nullptr && m->rgb != nullptr && m->H > 0, "[FoundationPose] " + fn + ": no frame uploaded");
+  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  return 0;
+}
+static FramePose frame_pose(const fp_model *m, const float pose[16]) {   // pose: column-major 4 x 4
   FramePose P;
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) P.r[r * 3 + c] = pose[c * 4 + r];
     P.t[r] = pose[12 + r];
   }
   P.fx = m->K[0]; P.cx = m->K[2]; P.fy = m->K[4]; P.cy = m->K[5];
-  // (a) vertex pass + the refusal word: a pose that needs a clipper, or leaves the exact integer range, gives an error, not a picture
+  return P;
+}
+// the vertex pass's refusal word: a pose that needs a clipper, or leaves the exact integer range, gives an error, not a picture
+static int pose_refused(int flag, const std::string &prefix) {
+  FP_CHECK(!(flag & FRAME_RENDER_FLAG_NEAR), prefix + "a vertex lies nearer than FP_RENDER_NEAR_M (0.01 m) to the camera plane, or behind it (there is no clipper)");
+  FP_CHECK(!(flag & FRAME_RENDER_FLAG_RANGE), prefix + "a vertex projects beyond FP_RENDER_SNAP_MAX sixteenths of a pixel (the exact range of the edge functions)");
+  return 0;
+}
+
+int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], float tol_m, const fp_frame_render *out, int memspace) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && pose && out, "[FoundationPose] fp_render_pose: invalid arguments");
+  const RenderPlane pl[5] = {{out->model_depth, 4}, {out->tri_id, 4}, {out->overlay, 3}, {out->model_mask, 1}, {out->visible_mask, 1}};
+  if (render_preconditions(m, "fp_render_pose", memspace, planes_wanted(pl, 5), tol_m)) return 1;
+  Target *t = m->find(target_name ? target_name : "");
+  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  const DeviceMesh &mesh = t->mesh;
+  const int H = m->H, W = m->W;
+  const size_t px = (size_t)H * W;
+  hipStream_t s = m->stream;
+  if (grow_render_verts(m, (size_t)mesh.V)) return 1;
+  if (!m->fr_flag && dev_alloc(&m->fr_flag, 1)) return 1;
+  const FramePose P = frame_pose(m, pose);
+  // (a) vertex pass + the refusal word
   FP_HIP_OK(hipMemsetAsync(m->fr_flag, 0, sizeof(int), s));
   {
     ProfScope ps(&m->prof, s, "frame_vertex", 0, (double)mesh.V * (12.0 + 32.0));
@@ -2505,25 +2563,11 @@ int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], f
   int flag = 0;
   FP_HIP_OK(hipMemcpyAsync(&flag, m->fr_flag, sizeof(int), hipMemcpyDeviceToHost, s));
   FP_HIP_OK(hipStreamSynchronize(s));
-  FP_CHECK(!(flag & FRAME_RENDER_FLAG_NEAR), "[FoundationPose] fp_render_pose: pose refused: a vertex lies nearer than FP_RENDER_NEAR_M (0.01 m) to the camera plane, or behind it (there is no clipper)");
-  FP_CHECK(!(flag & FRAME_RENDER_FLAG_RANGE), "[FoundationPose] fp_render_pose: pose refused: a vertex projects beyond FP_RENDER_SNAP_MAX sixteenths of a pixel (the exact range of the edge functions)");
+  if (pose_refused(flag, "[FoundationPose] fp_render_pose: pose refused: ")) return 1;
   // (b) raster + resolve, straight into the caller's device memory or into the model's staging block
-  FrameRenderOut o = {out->model_depth, out->model_mask, out->visible_mask, out->tri_id, out->overlay};
-  const size_t off_tri = fr_align(px * 4), off_ovl = off_tri + fr_align(px * 4), off_mask = off_ovl + fr_align(px * 3), off_vis = off_mask + fr_align(px);
-  if (memspace == FP_HOST) {
-    if (px > m->fr_out_px) {
-      dev_free(m->fr_out);
-      m->fr_out_px = 0;
-      if (dev_alloc(&m->fr_out, off_vis + fr_align(px))) return 1;
-      m->fr_out_px = px;
-    }
-    // (offsets are those of THIS frame size: a smaller frame than the block was sized for uses its front)
-    o.depth = out->model_depth ? reinterpret_cast<float *>(m->fr_out) : nullptr;
-    o.tri = out->tri_id ? reinterpret_cast<int32_t *>(m->fr_out + off_tri) : nullptr;
-    o.overlay = out->overlay ? m->fr_out + off_ovl : nullptr;
-    o.mask = out->model_mask ? m->fr_out + off_mask : nullptr;
-    o.vis = out->visible_mask ? m->fr_out + off_vis : nullptr;
-  }
+  uint8_t *dev[5];
+  if (place_planes(m, pl, 5, px, memspace, dev)) return 1;
+  const FrameRenderOut o = {reinterpret_cast<float *>(dev[0]), dev[3], dev[4], reinterpret_cast<int32_t *>(dev[1]), dev[2]};
   const FrameTileBound bound = frame_tile_bound(P, (double)mesh.max_norm, H, W);
   {
     const double wr = (o.depth ? 4.0 : 0.0) + (o.tri ? 4.0 : 0.0) + (o.overlay ? 3.0 : 0.0) + (o.mask ? 1.0 : 0.0) + (o.vis ? 1.0 : 0.0);
@@ -2532,13 +2576,7 @@ int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], f
     launch_frame_raster(s, mesh, m->fr_snap, m->fr_cam, m->rgb, m->depth, H, W, bound, tol_m, o);
     FP_HIP_OK(hipGetLastError());
   }
-  if (memspace == FP_HOST) {
-    if (out->model_depth) FP_HIP_OK(hipMemcpyAsync(out->model_depth, o.depth, px * 4, hipMemcpyDeviceToHost, s));
-    if (out->tri_id) FP_HIP_OK(hipMemcpyAsync(out->tri_id, o.tri, px * 4, hipMemcpyDeviceToHost, s));
-    if (out->overlay) FP_HIP_OK(hipMemcpyAsync(out->overlay, o.overlay, px * 3, hipMemcpyDeviceToHost, s));
-    if (out->model_mask) FP_HIP_OK(hipMemcpyAsync(out->model_mask, o.mask, px, hipMemcpyDeviceToHost, s));
-    if (out->visible_mask) FP_HIP_OK(hipMemcpyAsync(out->visible_mask, o.vis, px, hipMemcpyDeviceToHost, s));
-  }
+  if (memspace == FP_HOST && download_planes(m, pl, 5, px, dev)) return 1;
   FP_HIP_OK(hipStreamSynchronize(s));
   return 0;
 } FP_CATCH_INT
@@ -2552,28 +2590,17 @@ int fp_render_scene(fp_model *m, int K, const char *const *target_names, const f
   FP_CHECK(m != nullptr, "[FoundationPose] null model");
   FP_CHECK(K >= 1 && K <= FP_SCENE_MAX_OBJECTS, "[FoundationPose] fp_render_scene: " + std::to_string(K) + " objects (1..FP_SCENE_MAX_OBJECTS = 64)");
   FP_CHECK(target_names && poses, "[FoundationPose] fp_render_scene: invalid arguments");
-  FP_CHECK(memspace == FP_HOST || memspace == FP_DEVICE, "[FoundationPose] fp_render_scene: memspace must be FP_HOST or FP_DEVICE");
   static const fp_scene_render none = {};
   const fp_scene_render &want = out ? *out : none;
-  FP_CHECK(want.model_depth || want.instance_id || want.visible_mask || want.tri_id || want.cover_bits || want.overlay || objects,
-           "[FoundationPose] fp_render_scene: no output requested");
-  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_render_scene: tol_m must be finite and >= 0 (metres)");
-  FP_CHECK(!m->track_pending, "[FoundationPose] fp_render_scene: a submitted Track has not been waited for (fp_track_wait)");
-  FP_CHECK(m->depth != nullptr && m->rgb != nullptr && m->H > 0, "[FoundationPose] fp_render_scene: no frame uploaded");
-  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  const RenderPlane pl[6] = {{want.cover_bits, 8}, {want.model_depth, 4}, {want.tri_id, 4}, {want.overlay, 3}, {want.instance_id, 1}, {want.visible_mask, 1}};
+  if (render_preconditions(m, "fp_render_scene", memspace, planes_wanted(pl, 6) || objects, tol_m)) return 1;
   if (!m->sc_table_host) m->sc_table_host = new SceneTable();
   SceneTable &tb = *m->sc_table_host;
   unsigned long long faces = 0, verts = 0;
   for (int o = 0; o < K; o++) {
     Target *t = m->find(target_names[o] ? target_names[o] : "");
     FP_CHECK(t != nullptr, "[FoundationPose] fp_render_scene: unknown target_name of object " + std::to_string(o));
-    FramePose &P = tb.pose[o];
-    const float *pose = poses + (size_t)o * 16;
-    for (int r = 0; r < 3; r++) {
-      for (int c = 0; c < 3; c++) P.r[r * 3 + c] = pose[c * 4 + r];
-      P.t[r] = pose[12 + r];
-    }
-    P.fx = m->K[0]; P.cx = m->K[2]; P.fy = m->K[4]; P.cy = m->K[5];
+    tb.pose[o] = frame_pose(m, poses + (size_t)o * 16);
     tb.verts[o] = t->mesh.verts;
     tb.faces[o] = t->mesh.faces;
     tb.vert_start[o] = (int)verts;
@@ -2589,24 +2616,8 @@ int fp_render_scene(fp_model *m, int K, const char *const *target_names, const f
   const size_t px = (size_t)H * W;
   const int ntiles = scene_tiles_x(W) * scene_tiles_y(H);
   hipStream_t s = m->stream;
-  // buffers: grow-only; nothing of the stream may still read a block that is replaced
-  const size_t work_words = scene_work_words(H, W);
-  if (!m->sc_table || (size_t)verts > m->sc_vert_cap || work_words > m->sc_work_cap) {
-    FP_HIP_OK(hipStreamSynchronize(s));
-    if (!m->sc_table && dev_alloc(&m->sc_table, 1)) return 1;
-    if ((size_t)verts > m->sc_vert_cap) {
-      dev_free(m->sc_snap); dev_free(m->sc_cam);
-      m->sc_vert_cap = 0;
-      if (dev_alloc(&m->sc_snap, (size_t)verts) || dev_alloc(&m->sc_cam, (size_t)verts)) return 1;
-      m->sc_vert_cap = (size_t)verts;
-    }
-    if (work_words > m->sc_work_cap) {
-      dev_free(m->sc_work);
-      m->sc_work_cap = 0;
-      if (dev_alloc(&m->sc_work, work_words)) return 1;
-      m->sc_work_cap = work_words;
-    }
-  }
+  if (!m->sc_table && dev_alloc(&m->sc_table, 1)) return 1;
+  if (grow_render_verts(m, (size_t)verts) || grow_scratch(s, m->sc_work, m->sc_work_cap, scene_work_words(H, W))) return 1;
   int *flags = m->sc_work + SCENE_WORK_FLAGS, *counters = m->sc_work + SCENE_WORK_COUNTERS;
   unsigned long long *total_dev = reinterpret_cast<unsigned long long *>(m->sc_work + SCENE_WORK_TOTAL);
   unsigned *count = reinterpret_cast<unsigned *>(m->sc_work + SCENE_WORK_COUNT), *offset = count + ntiles, *cursor = offset + ntiles + 1;
@@ -2615,73 +2626,44 @@ int fp_render_scene(fp_model *m, int K, const char *const *target_names, const f
   // (a) vertex pass, (b) binning: count + scan.  Then the call's one early read-back: the refusal words and the size of the lists.
   {
     ProfScope ps(&m->prof, s, "scene_vertex", 0, (double)verts * (12.0 + 32.0));
-    launch_scene_vertex(s, m->sc_table, (int)verts, m->sc_snap, m->sc_cam, flags);
+    launch_scene_vertex(s, m->sc_table, (int)verts, m->fr_snap, m->fr_cam, flags);
     FP_HIP_OK(hipGetLastError());
   }
   {
     ProfScope ps(&m->prof, s, "scene_bin", 0, (double)faces * (12.0 + 48.0));
-    launch_scene_bin_count(s, m->sc_table, (unsigned)faces, m->sc_snap, H, W, count, offset, cursor, total_dev);
+    launch_scene_bin_count(s, m->sc_table, (unsigned)faces, m->fr_snap, H, W, count, offset, cursor, total_dev);
     FP_HIP_OK(hipGetLastError());
   }
   int early[SCENE_WORK_TOTAL + 2] = {0};
   FP_HIP_OK(hipMemcpyAsync(early, m->sc_work, sizeof(early), hipMemcpyDeviceToHost, s));
   FP_HIP_OK(hipStreamSynchronize(s));
-  for (int o = 0; o < K; o++) {
-    FP_CHECK(!(early[o] & FRAME_RENDER_FLAG_NEAR), "[FoundationPose] fp_render_scene: pose refused: object " + std::to_string(o) +
-                 ": a vertex lies nearer than FP_RENDER_NEAR_M (0.01 m) to the camera plane, or behind it (there is no clipper)");
-    FP_CHECK(!(early[o] & FRAME_RENDER_FLAG_RANGE), "[FoundationPose] fp_render_scene: pose refused: object " + std::to_string(o) +
-                 ": a vertex projects beyond FP_RENDER_SNAP_MAX sixteenths of a pixel (the exact range of the edge functions)");
-  }
+  for (int o = 0; o < K; o++)
+    if (pose_refused(early[o], "[FoundationPose] fp_render_scene: pose refused: object " + std::to_string(o) + ": ")) return 1;
   unsigned long long entries = 0;
   std::memcpy(&entries, early + SCENE_WORK_TOTAL, sizeof(entries));
   FP_CHECK(entries <= (unsigned long long)SCENE_MAX_ENTRIES, "[FoundationPose] fp_render_scene: " + std::to_string(entries) +
                " (tile, triangle) pairs, above the limit of 2^31 - 1");
-  if ((size_t)entries > m->sc_list_cap) {   // (the stream is idle: just synchronised)
-    dev_free(m->sc_list);
-    m->sc_list_cap = 0;
-    const size_t cap = (size_t)std::min<unsigned long long>(entries + entries / 2, (unsigned long long)SCENE_MAX_ENTRIES);
-    if (dev_alloc(&m->sc_list, cap)) return 1;
-    m->sc_list_cap = cap;
-  }
+  if ((size_t)entries > m->sc_list_cap &&   // (half as much again, so that a scene that grows a little does not allocate every frame)
+      grow_scratch(s, m->sc_list, m->sc_list_cap, (size_t)std::min<unsigned long long>(entries + entries / 2, (unsigned long long)SCENE_MAX_ENTRIES)))
+    return 1;
   // (c) fill the lists, raster + resolve straight into the caller's device memory or into the model's staging block
-  SceneRenderOut o = {want.model_depth, want.instance_id, want.visible_mask, want.tri_id, reinterpret_cast<unsigned long long *>(want.cover_bits),
-                      want.overlay, objects ? counters : nullptr};
-  const size_t off_depth = fr_align(px * 8), off_tri = off_depth + fr_align(px * 4), off_ovl = off_tri + fr_align(px * 4),
-               off_inst = off_ovl + fr_align(px * 3), off_vis = off_inst + fr_align(px);
-  if (memspace == FP_HOST && (want.model_depth || want.instance_id || want.visible_mask || want.tri_id || want.cover_bits || want.overlay)) {
-    if (px > m->sc_out_px) {
-      dev_free(m->sc_out);
-      m->sc_out_px = 0;
-      if (dev_alloc(&m->sc_out, off_vis + fr_align(px))) return 1;
-      m->sc_out_px = px;
-    }
-    o.cover = want.cover_bits ? reinterpret_cast<unsigned long long *>(m->sc_out) : nullptr;
-    o.depth = want.model_depth ? reinterpret_cast<float *>(m->sc_out + off_depth) : nullptr;
-    o.tri = want.tri_id ? reinterpret_cast<int32_t *>(m->sc_out + off_tri) : nullptr;
-    o.overlay = want.overlay ? m->sc_out + off_ovl : nullptr;
-    o.inst = want.instance_id ? m->sc_out + off_inst : nullptr;
-    o.vis = want.visible_mask ? m->sc_out + off_vis : nullptr;
-  }
+  uint8_t *dev[6];
+  if (place_planes(m, pl, 6, px, memspace, dev)) return 1;
+  const SceneRenderOut o = {reinterpret_cast<float *>(dev[1]), dev[4], dev[5], reinterpret_cast<int32_t *>(dev[2]), reinterpret_cast<unsigned long long *>(dev[0]),
+                            dev[3], objects ? counters : nullptr};
   {
     ProfScope ps(&m->prof, s, "scene_bin", 0, (double)faces * (12.0 + 48.0) + (double)entries * 4.0);
-    launch_scene_bin_fill(s, m->sc_table, (unsigned)faces, m->sc_snap, H, W, cursor, m->sc_list);
+    launch_scene_bin_fill(s, m->sc_table, (unsigned)faces, m->fr_snap, H, W, cursor, m->sc_list);
     FP_HIP_OK(hipGetLastError());
   }
   {
     const double wr = (o.depth ? 4.0 : 0.0) + (o.tri ? 4.0 : 0.0) + (o.cover ? 8.0 : 0.0) + (o.overlay ? 3.0 : 0.0) + (o.inst ? 1.0 : 0.0) + (o.vis ? 1.0 : 0.0);
     const double rd = (o.overlay ? 3.0 : 0.0) + (o.vis || o.overlay || o.counters ? 4.0 : 0.0);
     ProfScope ps(&m->prof, s, "scene_raster", 0, (double)px * (wr + rd) + (double)entries * 4.0);
-    launch_scene_raster(s, m->sc_table, m->sc_snap, m->sc_cam, offset, m->sc_list, m->rgb, m->depth, H, W, tol_m, o);
+    launch_scene_raster(s, m->sc_table, m->fr_snap, m->fr_cam, offset, m->sc_list, m->rgb, m->depth, H, W, tol_m, o);
     FP_HIP_OK(hipGetLastError());
   }
-  if (memspace == FP_HOST) {
-    if (want.cover_bits) FP_HIP_OK(hipMemcpyAsync(want.cover_bits, o.cover, px * 8, hipMemcpyDeviceToHost, s));
-    if (want.model_depth) FP_HIP_OK(hipMemcpyAsync(want.model_depth, o.depth, px * 4, hipMemcpyDeviceToHost, s));
-    if (want.tri_id) FP_HIP_OK(hipMemcpyAsync(want.tri_id, o.tri, px * 4, hipMemcpyDeviceToHost, s));
-    if (want.overlay) FP_HIP_OK(hipMemcpyAsync(want.overlay, o.overlay, px * 3, hipMemcpyDeviceToHost, s));
-    if (want.instance_id) FP_HIP_OK(hipMemcpyAsync(want.instance_id, o.inst, px, hipMemcpyDeviceToHost, s));
-    if (want.visible_mask) FP_HIP_OK(hipMemcpyAsync(want.visible_mask, o.vis, px, hipMemcpyDeviceToHost, s));
-  }
+  if (memspace == FP_HOST && download_planes(m, pl, 6, px, dev)) return 1;
   int sums[SCENE_MAX_OBJECTS * 3] = {0};
   if (objects) FP_HIP_OK(hipMemcpyAsync(sums, counters, (size_t)K * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
   FP_HIP_OK(hipStreamSynchronize(s));
@@ -2800,24 +2782,9 @@ int fp_pose_errors(fp_model *m, const char *target_name, const float *est_poses,
     rigid_to_f32(rigid_inv_mul(E, G), rel_h + (size_t)i * 12);
     for (int s = 0; s < S1; s++) rigid_to_f32(rigid_mul(G, sym[(size_t)s]), comp_h + ((size_t)i * S1 + s) * 12);
   }
-  // buffers: grow-only; nothing of the stream may still read a block that is replaced
   hipStream_t st = m->stream;
-  if (mat_floats > m->pe_mat_cap || (size_t)n_pairs > m->pe_pair_cap || !m->pe_sums) {
-    FP_HIP_OK(hipStreamSynchronize(st));
-    if (mat_floats > m->pe_mat_cap) {
-      dev_free(m->pe_mats);
-      m->pe_mat_cap = 0;
-      if (dev_alloc(&m->pe_mats, mat_floats)) return 1;
-      m->pe_mat_cap = mat_floats;
-    }
-    if ((size_t)n_pairs > m->pe_pair_cap) {
-      dev_free(m->pe_pairs);
-      m->pe_pair_cap = 0;
-      if (dev_alloc(&m->pe_pairs, (size_t)n_pairs)) return 1;
-      m->pe_pair_cap = (size_t)n_pairs;
-    }
-    if (!m->pe_sums && dev_alloc(&m->pe_sums, (size_t)FP_MAX_BATCH)) return 1;
-  }
+  if (grow_scratch(st, m->pe_mats, m->pe_mat_cap, mat_floats) || grow_scratch(st, m->pe_pairs, m->pe_pair_cap, (size_t)n_pairs)) return 1;
+  if (!m->pe_sums && dev_alloc(&m->pe_sums, (size_t)FP_MAX_BATCH)) return 1;
   const float *est_d = m->pe_mats, *rel_d = est_d + (size_t)N * 12, *comp_d = rel_d + (size_t)N * 12;
   FP_HIP_OK(hipMemcpyAsync(m->pe_mats, est_h, mat_floats * sizeof(float), hipMemcpyHostToDevice, st));
   {

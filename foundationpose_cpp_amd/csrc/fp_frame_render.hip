@@ -1,8 +1,8 @@
 // Frame-resolution rendering of one pose (fp_render_pose): model depth, model / visible masks, triangle ids and
-// a flat-shaded overlay at the size of the uploaded frame.  Two kernels, both new; nothing here is shared with the 160x160 crop
-// rasteriser of fp_geometry.hip.  Compiled with -ffp-contract=off like the rest of the geometry: every f32 operation below is
-// separately rounded, in the order written, and tests/frame_render_ref.py restates it operation by operation.
-#include "fp_internal.h"
+// a flat-shaded overlay at the size of the uploaded frame.  Two kernels: index bookkeeping, the tile's z-buffer and the output planes
+// are here, every rule that decides a pixel is in fp_frame_rules.h, shared with fp_scene_render.hip.  Compiled with
+// -ffp-contract=off like the rest of the geometry.
+#include "fp_frame_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -13,36 +13,14 @@ namespace {
 
 constexpr unsigned long long FR_EMPTY = ~0ull;   // a z-buffer entry no triangle has reached: larger than every key
 
-// (a) vertex pass: p = R v + t, projection with K, snap to 1/16 px.  A vertex in front of the near constant, or one whose snapped
-// coordinates would leave the exact range of the edge functions, raises its bit of *flag and stores zeros (the host refuses the pose
-// before the raster kernel is launched).
+// (a) vertex pass: the vertex rule per vertex; a refused vertex raises its bit of *flag.
 __global__ __launch_bounds__(256) void frame_vertex_kernel(const float *__restrict__ verts, int V, FramePose P, int4 *__restrict__ snap,
                                                            float4 *__restrict__ cam, int *__restrict__ flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= V) return;
-  const float vx = verts[(size_t)i * 3], vy = verts[(size_t)i * 3 + 1], vz = verts[(size_t)i * 3 + 2];
-  const float x = ((P.r[0] * vx + P.r[1] * vy) + P.r[2] * vz) + P.t[0];
-  const float y = ((P.r[3] * vx + P.r[4] * vy) + P.r[5] * vz) + P.t[1];
-  const float z = ((P.r[6] * vx + P.r[7] * vy) + P.r[8] * vz) + P.t[2];
-  int bad = 0;
-  int xi = 0, yi = 0;
-  if (!(z >= FRAME_RENDER_NEAR)) bad |= FRAME_RENDER_FLAG_NEAR;   // (also a NaN)
-  else {
-    const float u = P.fx * (x / z) + P.cx;
-    const float w = P.fy * (y / z) + P.cy;
-    const float us = u * 16.0f, ws = w * 16.0f;
-    if (!(fabsf(us) <= (float)FRAME_RENDER_SNAP_MAX) || !(fabsf(ws) <= (float)FRAME_RENDER_SNAP_MAX)) bad |= FRAME_RENDER_FLAG_RANGE;
-    else { xi = (int)rintf(us); yi = (int)rintf(ws); }
-  }
-  snap[i] = make_int4(xi, yi, __float_as_int(z), 0);
-  cam[i] = make_float4(x, y, z, 0.0f);
+  const int bad = frame_vertex_rule(verts, (size_t)i, P, snap[i], cam[i]);
   if (bad) atomicOr(flag, bad);
 }
-
-// top-left fill rule on an edge with direction (dx, dy) of a triangle of positive area (y grows downwards): a sample exactly on the
-// edge belongs to the triangle when the edge is a left edge (dy < 0) or a top edge (dy == 0, dx > 0).  Returned as the smallest
-// edge-function value that still counts as covered: 0 for such an edge, 1 for the others.
-__device__ __forceinline__ long long edge_bias(long long dx, long long dy) { return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1; }
 
 // (b) raster + resolve: one workgroup per FRAME_RENDER_TILE x FRAME_RENDER_TILE pixel tile.  The tile's z-buffer is 64-bit keys
 // bits(z) << 32 | triangle in LDS (8 KB), resolved with ds_min_u64; the threads walk all triangles, reject by bounding box against the
@@ -66,34 +44,9 @@ __global__ __launch_bounds__(FRAME_RENDER_THREADS) void frame_raster_kernel(cons
       const int i0 = faces[(size_t)t * 3], i1 = faces[(size_t)t * 3 + 1], i2 = faces[(size_t)t * 3 + 2];
       if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) continue;
       const int4 a = snap[i0], b = snap[i1], c = snap[i2];
-      // pixels whose sample point (16 px, 16 py) lies inside the triangle's bounding box, clipped to the tile and the frame
-      const int px0 = max((min(a.x, min(b.x, c.x)) + 15) >> 4, X0), px1 = min(max(a.x, max(b.x, c.x)) >> 4, X1);
-      const int py0 = max((min(a.y, min(b.y, c.y)) + 15) >> 4, Y0), py1 = min(max(a.y, max(b.y, c.y)) >> 4, Y1);
-      if (px0 > px1 || py0 > py1) continue;
-      const long long area = (long long)(b.x - a.x) * (c.y - a.y) - (long long)(b.y - a.y) * (c.x - a.x);
-      if (area == 0) continue;
-      const long long s = area < 0 ? -1 : 1, A = s * area;
-      // edge i is opposite corner i: 0 = b -> c, 1 = c -> a, 2 = a -> b; both windings are brought to positive area by the sign s
-      const long long d0x = s * (c.x - b.x), d0y = s * (c.y - b.y);
-      const long long d1x = s * (a.x - c.x), d1y = s * (a.y - c.y);
-      const long long d2x = s * (b.x - a.x), d2y = s * (b.y - a.y);
-      const long long b0 = edge_bias(d0x, d0y), b1 = edge_bias(d1x, d1y), b2 = edge_bias(d2x, d2y);
-      const float za = __int_as_float(a.z), zb = __int_as_float(b.z), zc = __int_as_float(c.z);
-      const float fA = (float)A;
-      const long long sx = 16ll * px0;
-      for (int py = py0; py <= py1; py++) {
-        const long long sy = 16ll * py;
-        long long e0 = d0x * (sy - b.y) - d0y * (sx - b.x);
-        long long e1 = d1x * (sy - c.y) - d1y * (sx - c.x);
-        long long e2 = d2x * (sy - a.y) - d2y * (sx - a.x);
-        for (int px = px0; px <= px1; px++, e0 -= 16 * d0y, e1 -= 16 * d1y, e2 -= 16 * d2y) {
-          if (((e0 - b0) | (e1 - b1) | (e2 - b2)) < 0) continue;
-          const float w0 = (float)e0 / fA, w1 = (float)e1 / fA, w2 = (float)e2 / fA;
-          const float z = 1.0f / ((w0 / za + w1 / zb) + w2 / zc);
-          const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)t;
-          atomicMin(&zbuf[(py - Y0) * T + (px - X0)], key);
-        }
-      }
+      frame_tri_walk(a, b, c, X0, Y0, X1, Y1, [&](int px, int py, float z) {
+        atomicMin(&zbuf[(py - Y0) * T + (px - X0)], ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)t);
+      });
     }
   }
   __syncthreads();
@@ -106,10 +59,7 @@ __global__ __launch_bounds__(FRAME_RENDER_THREADS) void frame_raster_kernel(cons
     const float z = model ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
     const int tri = model ? (int)(unsigned)key : -1;
     bool visible = model;
-    if (model && (o.vis || o.overlay)) {
-      const float D = obs[at];
-      if (!(D < FP_MIN_DEPTH) && D < z - tol) visible = false;   // something observed in front of the model
-    }
+    if (model && (o.vis || o.overlay)) visible = !frame_occluded(obs[at], z, tol);   // something observed in front of the model?
     if (o.depth) o.depth[at] = z;
     if (o.mask) o.mask[at] = model ? 255 : 0;
     if (o.vis) o.vis[at] = visible ? 255 : 0;
@@ -117,17 +67,8 @@ __global__ __launch_bounds__(FRAME_RENDER_THREADS) void frame_raster_kernel(cons
     if (o.overlay) {
       int r = rgb[at * 3], g = rgb[at * 3 + 1], bl = rgb[at * 3 + 2];
       if (visible) {
-        // flat Lambert term of the triangle's camera-space normal (two-sided), quantised to the integer shade k in [64, 255]
-        const float4 p0 = cam[faces[(size_t)tri * 3]], p1 = cam[faces[(size_t)tri * 3 + 1]], p2 = cam[faces[(size_t)tri * 3 + 2]];
-        const float ax = p1.x - p0.x, ay = p1.y - p0.y, az = p1.z - p0.z;
-        const float bx = p2.x - p0.x, by = p2.y - p0.y, bz = p2.z - p0.z;
-        const float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-        const float len2 = (nx * nx + ny * ny) + nz * nz;
-        const float lam = len2 > 0.0f ? fabsf(nz) / sqrtf(len2) : 0.0f;
-        const int k = 64 + (int)rintf(lam * 191.0f);
-        r = (r + (FRAME_RENDER_TINT_R * k + 127) / 255 + 1) >> 1;
-        g = (g + (FRAME_RENDER_TINT_G * k + 127) / 255 + 1) >> 1;
-        bl = (bl + (FRAME_RENDER_TINT_B * k + 127) / 255 + 1) >> 1;
+        const int k = frame_shade(cam[faces[(size_t)tri * 3]], cam[faces[(size_t)tri * 3 + 1]], cam[faces[(size_t)tri * 3 + 2]]);
+        r = frame_tint(r, FRAME_RENDER_TINT_R, k); g = frame_tint(g, FRAME_RENDER_TINT_G, k); bl = frame_tint(bl, FRAME_RENDER_TINT_B, k);
       }
       o.overlay[at * 3] = (uint8_t)r; o.overlay[at * 3 + 1] = (uint8_t)g; o.overlay[at * 3 + 2] = (uint8_t)bl;
     }

@@ -1,9 +1,9 @@
 // Frame-resolution rendering of all tracked objects of a frame in one pass (fp_render_scene): nearest model depth,
 // instance map, visible mask, triangle ids, the amodal coverage word of every pixel, a per-object tinted overlay and the per-object
-// pixel counts.  Per object the arithmetic is that of fp_frame_render.hip, operation by operation (the same -ffp-contract=off); what
-// is new is that the triangles of all objects are binned into the 32 x 32 px tiles first, so a tile walks only its own list, and that
+// pixel counts.  Per object the rules are fp_render_pose's: both call fp_frame_rules.h (the same -ffp-contract=off); what is added
+// here is that the triangles of all objects are binned into the 32 x 32 px tiles first, so a tile walks only its own list, and that
 // the objects meet in one z-buffer whose keys carry the GLOBAL triangle index.  tests/scene_render_ref.py restates the rules.
-#include "fp_internal.h"
+#include "fp_frame_rules.h"
 
 namespace fp {
 
@@ -24,32 +24,13 @@ __device__ __forceinline__ int scene_owner(const I *start, int K, I g) {
   return lo;
 }
 
-// (a) vertex pass over the concatenated vertices of all objects: frame_vertex_kernel's arithmetic with the owner's pose; one refusal
-// word per object.
+// (a) vertex pass over the concatenated vertices of all objects: the vertex rule with the owner's pose; one refusal word per object.
 __global__ __launch_bounds__(256) void scene_vertex_kernel(const SceneTable *__restrict__ tb, int total, int4 *__restrict__ snap,
                                                            float4 *__restrict__ cam, int *__restrict__ flags) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int o = scene_owner(tb->vert_start, tb->K, i);
-  const FramePose &P = tb->pose[o];
-  const float *verts = tb->verts[o];
-  const int v = i - tb->vert_start[o];
-  const float vx = verts[(size_t)v * 3], vy = verts[(size_t)v * 3 + 1], vz = verts[(size_t)v * 3 + 2];
-  const float x = ((P.r[0] * vx + P.r[1] * vy) + P.r[2] * vz) + P.t[0];
-  const float y = ((P.r[3] * vx + P.r[4] * vy) + P.r[5] * vz) + P.t[1];
-  const float z = ((P.r[6] * vx + P.r[7] * vy) + P.r[8] * vz) + P.t[2];
-  int bad = 0;
-  int xi = 0, yi = 0;
-  if (!(z >= FRAME_RENDER_NEAR)) bad |= FRAME_RENDER_FLAG_NEAR;   // (also a NaN)
-  else {
-    const float u = P.fx * (x / z) + P.cx;
-    const float w = P.fy * (y / z) + P.cy;
-    const float us = u * 16.0f, ws = w * 16.0f;
-    if (!(fabsf(us) <= (float)FRAME_RENDER_SNAP_MAX) || !(fabsf(ws) <= (float)FRAME_RENDER_SNAP_MAX)) bad |= FRAME_RENDER_FLAG_RANGE;
-    else { xi = (int)rintf(us); yi = (int)rintf(ws); }
-  }
-  snap[i] = make_int4(xi, yi, __float_as_int(z), 0);
-  cam[i] = make_float4(x, y, z, 0.0f);
+  const int bad = frame_vertex_rule(tb->verts[o], (size_t)(i - tb->vert_start[o]), tb->pose[o], snap[i], cam[i]);
   if (bad) atomicOr(flags + o, bad);
 }
 
@@ -71,8 +52,8 @@ __device__ __forceinline__ bool scene_load_tri(const SceneTable *__restrict__ tb
   return true;
 }
 
-// (b) binning.  The tiles of triangle g: those its bounding box of sample points reaches, frame_raster_kernel's test clipped to the
-// frame; none for a bad face, zero area or a box that misses the frame.  FILL = false counts per tile, FILL = true appends g to the
+// (b) binning.  The tiles of triangle g: those its bounding box of sample points reaches, the triangle walk's own box and area tests
+// with the whole frame as the clip rectangle; none for a bad face, zero area or a box that misses the frame.  FILL = false counts per tile, FILL = true appends g to the
 // lists at the cursors the scan left.  Neighbouring triangles of a mesh fall into the same few tiles, and one global atomic per
 // (tile, triangle) pair serialises on those few addresses; so a workgroup first counts its 256 triangles per tile in LDS and then
 // claims, per tile it touched, its whole share with ONE global atomic.  The LDS histogram holds SC_BIN_CHUNK tiles (all 2040 of a
@@ -89,12 +70,9 @@ __global__ __launch_bounds__(256) void scene_bin_kernel(const SceneTable *__rest
   int tx0 = 0, tx1 = -1, ty0 = 0, ty1 = -1;   // (empty: the thread still meets every barrier)
   SceneTri t;
   if (g < total && scene_load_tri(tb, tb->vert_start, tb->face_start, tb->K, snap, g, t)) {
-    const int4 a = t.a, b = t.b, c = t.c;
-    const int px0 = max((min(a.x, min(b.x, c.x)) + 15) >> 4, 0), px1 = min(max(a.x, max(b.x, c.x)) >> 4, W - 1);
-    const int py0 = max((min(a.y, min(b.y, c.y)) + 15) >> 4, 0), py1 = min(max(a.y, max(b.y, c.y)) >> 4, H - 1);
-    const long long area = (long long)(b.x - a.x) * (c.y - a.y) - (long long)(b.y - a.y) * (c.x - a.x);
-    if (px0 <= px1 && py0 <= py1 && area != 0) {   // inside the grid: 0 <= p < W, H
-      tx0 = px0 / SC_T; tx1 = px1 / SC_T; ty0 = py0 / SC_T; ty1 = py1 / SC_T;
+    FrameBox q;
+    if (frame_tri_box(t.a, t.b, t.c, 0, 0, W - 1, H - 1, q) && frame_tri_area(t.a, t.b, t.c) != 0) {   // inside the grid: 0 <= p < W, H
+      tx0 = q.px0 / SC_T; tx1 = q.px1 / SC_T; ty0 = q.py0 / SC_T; ty1 = q.py1 / SC_T;
     }
   }
   for (int c0 = 0; c0 < ntiles; c0 += SC_BIN_CHUNK) {   // uniform
@@ -157,8 +135,6 @@ __global__ __launch_bounds__(256) void scene_scan_kernel(const unsigned *__restr
   }
 }
 
-__device__ __forceinline__ long long scene_edge_bias(long long dx, long long dy) { return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1; }
-
 // (c) raster + resolve: one workgroup per tile walks the tile's list.  LDS: the tile's z-buffer of 64-bit keys bits(z) << 32 | g
 // (ds_min_u64), its coverage words (bit o: a triangle of object o covers the sample; 64-bit LDS OR), the offset tables and 64 x 3
 // counters.  After the barrier every requested output of the tile is written once and the tile's per-object counts are added to the
@@ -191,39 +167,13 @@ __global__ __launch_bounds__(SC_THREADS) void scene_raster_kernel(const SceneTab
       const unsigned g = list[e];
       SceneTri tr;
       if (!scene_load_tri(tb, vert_start, face_start, K, snap, g, tr)) continue;
-      const int4 a = tr.a, b = tr.b, c = tr.c;
       const unsigned long long obit = 1ull << tr.o;
       mine |= obit;
-      // pixels whose sample point (16 px, 16 py) lies inside the triangle's bounding box, clipped to the tile and the frame
-      const int px0 = max((min(a.x, min(b.x, c.x)) + 15) >> 4, X0), px1 = min(max(a.x, max(b.x, c.x)) >> 4, X1);
-      const int py0 = max((min(a.y, min(b.y, c.y)) + 15) >> 4, Y0), py1 = min(max(a.y, max(b.y, c.y)) >> 4, Y1);
-      if (px0 > px1 || py0 > py1) continue;
-      const long long area = (long long)(b.x - a.x) * (c.y - a.y) - (long long)(b.y - a.y) * (c.x - a.x);
-      if (area == 0) continue;
-      const long long s = area < 0 ? -1 : 1, A = s * area;
-      // edge i is opposite corner i: 0 = b -> c, 1 = c -> a, 2 = a -> b; both windings are brought to positive area by the sign s
-      const long long d0x = s * (c.x - b.x), d0y = s * (c.y - b.y);
-      const long long d1x = s * (a.x - c.x), d1y = s * (a.y - c.y);
-      const long long d2x = s * (b.x - a.x), d2y = s * (b.y - a.y);
-      const long long b0 = scene_edge_bias(d0x, d0y), b1 = scene_edge_bias(d1x, d1y), b2 = scene_edge_bias(d2x, d2y);
-      const float za = __int_as_float(a.z), zb = __int_as_float(b.z), zc = __int_as_float(c.z);
-      const float fA = (float)A;
-      const long long sx = 16ll * px0;
-      for (int py = py0; py <= py1; py++) {
-        const long long sy = 16ll * py;
-        long long e0 = d0x * (sy - b.y) - d0y * (sx - b.x);
-        long long e1 = d1x * (sy - c.y) - d1y * (sx - c.x);
-        long long e2 = d2x * (sy - a.y) - d2y * (sx - a.x);
-        for (int px = px0; px <= px1; px++, e0 -= 16 * d0y, e1 -= 16 * d1y, e2 -= 16 * d2y) {
-          if (((e0 - b0) | (e1 - b1) | (e2 - b2)) < 0) continue;
-          const float w0 = (float)e0 / fA, w1 = (float)e1 / fA, w2 = (float)e2 / fA;
-          const float z = 1.0f / ((w0 / za + w1 / zb) + w2 / zc);
-          const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | g;
-          const int at = (py - Y0) * T + (px - X0);
-          atomicMin(&zbuf[at], key);
-          atomicOr(&cover[at], obit);
-        }
-      }
+      frame_tri_walk(tr.a, tr.b, tr.c, X0, Y0, X1, Y1, [&](int px, int py, float z) {
+        const int at = (py - Y0) * T + (px - X0);
+        atomicMin(&zbuf[at], ((unsigned long long)__float_as_uint(z) << 32) | g);
+        atomicOr(&cover[at], obit);
+      });
     }
     if (mine) atomicOr(&present, mine);
     __syncthreads();
@@ -245,10 +195,7 @@ __global__ __launch_bounds__(SC_THREADS) void scene_raster_kernel(const SceneTab
       tri = (int)(g - face_start[o]);
     }
     const float z = model ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
-    if (model && (out.vis || out.overlay || out.counters)) {
-      const float D = obs[at];
-      if (!(D < FP_MIN_DEPTH) && D < z - tol) visible = false;   // something observed in front of the nearest model
-    }
+    if (model && (out.vis || out.overlay || out.counters)) visible = !frame_occluded(obs[at], z, tol);   // ... in front of the nearest model?
     if (in) {
       if (out.depth) out.depth[at] = z;
       if (out.inst) out.inst[at] = (uint8_t)(o + 1);
@@ -258,20 +205,12 @@ __global__ __launch_bounds__(SC_THREADS) void scene_raster_kernel(const SceneTab
       if (out.overlay) {
         int r = rgb[at * 3], gr = rgb[at * 3 + 1], bl = rgb[at * 3 + 2];
         if (visible) {
-          // flat Lambert term of the winning triangle's camera-space normal (two-sided), quantised to the integer shade k in [64, 255]
+          // shade of the winning triangle, tint of its object
           const int32_t *f = tb->faces[o] + (size_t)tri * 3;
           const int base = vert_start[o];
-          const float4 p0 = cam[base + f[0]], p1 = cam[base + f[1]], p2 = cam[base + f[2]];
-          const float ax = p1.x - p0.x, ay = p1.y - p0.y, az = p1.z - p0.z;
-          const float bx = p2.x - p0.x, by = p2.y - p0.y, bz = p2.z - p0.z;
-          const float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-          const float len2 = (nx * nx + ny * ny) + nz * nz;
-          const float lam = len2 > 0.0f ? fabsf(nz) / sqrtf(len2) : 0.0f;
-          const int k = 64 + (int)rintf(lam * 191.0f);
+          const int k = frame_shade(cam[base + f[0]], cam[base + f[1]], cam[base + f[2]]);
           const int p = o & 7;
-          r = (r + (SCENE_PALETTE[p][0] * k + 127) / 255 + 1) >> 1;
-          gr = (gr + (SCENE_PALETTE[p][1] * k + 127) / 255 + 1) >> 1;
-          bl = (bl + (SCENE_PALETTE[p][2] * k + 127) / 255 + 1) >> 1;
+          r = frame_tint(r, SCENE_PALETTE[p][0], k); gr = frame_tint(gr, SCENE_PALETTE[p][1], k); bl = frame_tint(bl, SCENE_PALETTE[p][2], k);
         }
         out.overlay[at * 3] = (uint8_t)r; out.overlay[at * 3 + 1] = (uint8_t)gr; out.overlay[at * 3 + 2] = (uint8_t)bl;
       }

@@ -3,6 +3,7 @@ the per-object records -- the rules are integer coverage, separately rounded f32
 scenes are those of tests/scene_render_cases.py, which tests/test_scene_render_ref_cpu.py holds to what each is for.  Outputs are
 pre-filled with 77 so that every pixel must be WRITTEN."""
 import ctypes as C
+import functools
 from unittest import mock
 
 import numpy as np
@@ -192,6 +193,71 @@ def test_subsets_records_only_device_outputs_and_repeats():
         _same("device outputs", back, ref)
         assert [[getattr(r, f) for f in SR.RECORD] for r in recs] == ref_rec.tolist()
         torch.cuda.synchronize()
+    finally:
+        m.close()
+
+
+def _pose(m, name, pose, hw):
+    """fp_render_pose with host outputs through the raw ABI, pre-filled like _scene's"""
+    spec = FoundationPose.RENDER_OUTPUTS
+    out = {n: np.full(tuple(hw) + spec[n][1], 77, spec[n][0]) for n in FR.OUTPUTS}
+    rec = _lib.FpFrameRender(**{n: _p(a) for n, a in out.items()})
+    m._must(m._L.fp_render_pose(m._h, name.encode(), _p(syn.to_colmajor(np.asarray(pose, np.float32))), 0.005, C.byref(rec), FP_HOST))
+    return out
+
+
+def _on_device(m, spec, record, hw, call):
+    """call(record of FP_DEVICE outputs pre-filled with 77) -> the planes, read back with fp_download"""
+    dev = {n: torch.full(tuple(hw) + spec[n][1] + (np.dtype(spec[n][0]).itemsize,), 77, dtype=torch.uint8, device="cuda") for n in spec}
+    torch.cuda.synchronize()
+    call(record(**{n: C.c_void_p(t.data_ptr()) for n, t in dev.items()}))
+    back = {n: np.zeros(tuple(hw) + spec[n][1], spec[n][0]) for n in spec}
+    for n, t in dev.items():
+        m._must(m._L.fp_download(m._h, _p(back[n]), C.c_void_p(t.data_ptr()), back[n].nbytes))
+    torch.cuda.synchronize()
+    return back
+
+
+@functools.lru_cache(maxsize=None)
+def _shared_scratch_references():
+    """what test_pose_and_scene_calls_share_their_scratch compares with, in the order of its calls; a model has ONE camera, so the
+    frame of single() is rendered with overlap()'s intrinsics here.  Computed once, not to be modified."""
+    big, small = SC.overlap(), SC.single()
+    ms, poses, K = big[0], big[2], big[3]
+    pose_a = FR.render(FR.centred(ms["a"]), ms["a"].faces, poses[0], K, big[4], big[5])
+    pose_b = FR.render(FR.centred(ms["b"]), ms["b"].faces, poses[1], K, small[4], small[5])
+    return pose_a, SC.reference("overlap"), pose_b, SR.render(SC.objects_of(small), K, small[4], small[5])
+
+
+def test_pose_and_scene_calls_share_their_scratch():
+    """fp_render_pose and fp_render_scene render into the same vertex scratch and the same FP_HOST staging block.  On ONE model: a pose,
+    a scene with more vertices and more bytes per pixel (both blocks grow), then a pose and a scene on a SMALLER frame (each uses the
+    front of a block sized for the larger one), then the first two again with FP_DEVICE outputs.  Every result is the reference's."""
+    big, small = SC.overlap(), SC.single()
+    ms, names, poses, K, rgb, depth, hw = big
+    ref_a, (ref_big, rec_big), ref_b, (ref_small, rec_small) = _shared_scratch_references()
+    assert small[6][0] * small[6][1] < hw[0] * hw[1] and (ref_b["model_mask"] > 0).sum() > 500 and rec_small[0, 0] > 500
+    m = _model(big)
+    try:
+        _same("1: pose of object 0", _pose(m, names[0], poses[0], hw), ref_a)
+        got, rec = _scene(m, names, poses, hw)
+        _same("2: scene overlap", got, ref_big)
+        _same_records("2: scene overlap", rec, rec_big)
+        m.upload_frame(small[4], small[5])
+        _same("3: pose of object 1, smaller frame", _pose(m, names[1], poses[1], small[6]), ref_b)
+        got, rec = _scene(m, small[1], small[2], small[6])
+        _same("4: scene single, smaller frame", got, ref_small)
+        _same_records("4: scene single, smaller frame", rec, rec_small)
+        m.upload_frame(rgb, depth)
+        p16 = syn.to_colmajor(np.asarray(poses, np.float32))
+        back = _on_device(m, FoundationPose.RENDER_OUTPUTS, _lib.FpFrameRender, hw, lambda r: m._must(
+            m._L.fp_render_pose(m._h, names[0].encode(), _p(p16[0]), 0.005, C.byref(r), FP_DEVICE)))
+        _same("1 again, device outputs", back, ref_a)
+        recs = (_lib.FpSceneObject * 4)()
+        back = _on_device(m, SPEC, _lib.FpSceneRender, hw, lambda r: m._must(
+            m._L.fp_render_scene(m._h, 4, _names(names), _p(p16), 0.005, C.byref(r), recs, FP_DEVICE)))
+        _same("2 again, device outputs", back, ref_big)
+        assert [[getattr(r, f) for f in SR.RECORD] for r in recs] == rec_big.tolist()
     finally:
         m.close()
 
