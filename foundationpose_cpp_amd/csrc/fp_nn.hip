@@ -281,8 +281,6 @@ struct EncLayer {  // transformer encoder layer (refiner heads)
 // trunk activation ids (FP8 scales / calibration): 0 stem, 1 a1, 2..5 encodeA blocks, 6..9 encodeAB 256 blocks, 10 b2,
 // 11..14 encodeAB 512 blocks (14 = the token tensor, never quantised)
 static constexpr int N_TRUNK_ACT = 15;
-// trunk layer i (0..12, q8_layers order) -> its stage bit
-static constexpr int q8_block_of(int i) { return i < 4 ? 1 : i < 8 ? 2 : i == 8 ? 4 : 8; }
 
 struct Net {
   bool scorer = false;
@@ -305,12 +303,12 @@ struct Net {
   // solved by the calibration sweeps (fp_api.hip: fp_calibrate)
   bool q8_ready = false;
   int qdt = DT_FP8;                                  // element type of the 8-bit layers
-  int q8_blocks = 0;                                 // [r6] stages on 8-bit operands (bits: q8_block_of); 0 for the 2-byte networks
-  // [r6] INT8: the per-image first-order compensation (run_trunk_q8: IB) belongs to records whose corrections were SOLVED with it on,
+  int q8_blocks = 0;                                 // [r6] stages on 8-bit operands (bits: TrunkRow::stage); 0 for the 2-byte networks
+  // [r6] INT8: the per-image first-order compensation (plan_trunk: img_bias) belongs to records whose corrections were SOLVED with it on,
   // i.e. records that carry frame means (version 2, fp_calibrate_*).  A round-4 record or fp_set_calibration's per-tensor scales
   // (no frame means) were solved without it: compensating on top would subtract the same term twice.
   bool q8_img_comp = false;
-  bool q8_on(int layer) const { return (q8_blocks & q8_block_of(layer)) != 0; }
+  bool q8_on(int layer) const;                       // 8-bit layer 0..12 (TRUNK row layer + 2): its stage is in the mask
   std::vector<float> act_scale[N_TRUNK_ACT];         // host, [channels of the activation]
   float *act_oinv[N_TRUNK_ACT] = {nullptr};          // device
   float *act_scale_dev[N_TRUNK_ACT] = {nullptr};     // device copy of act_scale (calibration statistics of 8-bit tensors)
@@ -344,6 +342,146 @@ struct Net {
   }
 };
 static unsigned char g_placeholder;   // what a deferred pointer field holds between net_prepare and net_commit (never dereferenced)
+
+// The shared CNN trunk, described once: the table of its 15 convolutions, what follows from the table alone, and plan_trunk, which
+// adds the precision policy.  run_trunk walks the plan and decides nothing.
+// Buffer slots of the trunk (Arena): the 2-byte tensor and, in an 8-bit network, its 1-byte operand copy
+enum TrunkSlot { TS_NONE = -1, TS_NN_IN = 0, TS_STEM = 1, TS_X128 = 2, TS_X256 = 5, TS_X512 = 8, TS_TOKENS = 11, TS_COUNT = 12 };
+struct TrunkRow {
+  const char *tag;                // the profiler's name
+  ConvLayer &(*layer)(Net &);
+  int in, out, res;               // TrunkSlot; res = the skip operand (TS_NONE: no residual)
+  bool ab;                        // runs over the N rendered + n_b observed images (otherwise over the N concatenated ones)
+  int HW;                         // input map size
+  int ipad, opad, rpad;           // zero borders of the input, output and residual tensors
+  bool concat;                    // the output is the a|b channel concat: image N + i lands in channels [C/2, C) of image i (split_imgs = N)
+  bool pe;                        // the layer is offered the positional table
+  int act, C;                     // the output's trunk activation id (= the row's index) and channel count
+  int stage;                      // bit of Net::q8_blocks; 0: 2-byte operands in every precision
+  int tap;                        // TapPoint of the output (test build)
+};
+#define FP_TL(m) [](Net &n) -> ConvLayer & { return n.m; }
+static constexpr int N_TRUNK = 15, Q8_FIRST_ROW = 2;   // rows 2..14 are the 13 layers an 8-bit network may quantise (its "layer" 0..12)
+static constexpr TrunkRow TRUNK[N_TRUNK] = {
+    {"conv_stem", FP_TL(a0),       TS_NN_IN,    TS_STEM,     TS_NONE,     true,  80, 2, 1, 0, false, false, 0,  64,  0, TAP_STEM},
+    {"conv_a1",   FP_TL(a1),       TS_STEM,     TS_X128 + 0, TS_NONE,     true,  80, 1, 1, 0, false, false, 1,  128, 0, TAP_ACT + 1},
+    // encodeA residual blocks @40x40x128; the last one writes the a|b concat directly
+    {"conv_128",  FP_TL(ra[0][0]), TS_X128 + 0, TS_X128 + 1, TS_NONE,     true,  40, 1, 1, 0, false, false, 2,  128, 1, TAP_ACT + 2},
+    {"conv_128",  FP_TL(ra[0][1]), TS_X128 + 1, TS_X128 + 2, TS_X128 + 0, true,  40, 1, 1, 1, false, false, 3,  128, 1, TAP_ACT + 3},
+    {"conv_128",  FP_TL(ra[1][0]), TS_X128 + 2, TS_X128 + 1, TS_NONE,     true,  40, 1, 1, 0, false, false, 4,  128, 1, TAP_ACT + 4},
+    {"conv_128",  FP_TL(ra[1][1]), TS_X128 + 1, TS_X256 + 0, TS_X128 + 2, true,  40, 1, 1, 1, true,  false, 5,  256, 1, TAP_ACT + 5},
+    // encodeAB @40x40x256, encodeAB.2 (stride 2), @20x20x512; the last conv writes the un-bordered token tensor [N,400,512]
+    {"conv_256",  FP_TL(rb[0][0]), TS_X256 + 0, TS_X256 + 1, TS_NONE,     false, 40, 1, 1, 0, false, false, 6,  256, 2, TAP_ACT + 6},
+    {"conv_256",  FP_TL(rb[0][1]), TS_X256 + 1, TS_X256 + 2, TS_X256 + 0, false, 40, 1, 1, 1, false, false, 7,  256, 2, TAP_ACT + 7},
+    {"conv_256",  FP_TL(rb[1][0]), TS_X256 + 2, TS_X256 + 1, TS_NONE,     false, 40, 1, 1, 0, false, false, 8,  256, 2, TAP_ACT + 8},
+    {"conv_256",  FP_TL(rb[1][1]), TS_X256 + 1, TS_X256 + 0, TS_X256 + 2, false, 40, 1, 1, 1, false, false, 9,  256, 2, TAP_ACT + 9},
+    {"conv_b2",   FP_TL(b2),       TS_X256 + 0, TS_X512 + 0, TS_NONE,     false, 40, 1, 1, 0, false, false, 10, 512, 4, TAP_ACT + 10},
+    {"conv_512",  FP_TL(rc[0][0]), TS_X512 + 0, TS_X512 + 1, TS_NONE,     false, 20, 1, 1, 0, false, false, 11, 512, 8, TAP_ACT + 11},
+    {"conv_512",  FP_TL(rc[0][1]), TS_X512 + 1, TS_X512 + 2, TS_X512 + 0, false, 20, 1, 1, 1, false, false, 12, 512, 8, TAP_ACT + 12},
+    {"conv_512",  FP_TL(rc[1][0]), TS_X512 + 2, TS_X512 + 1, TS_NONE,     false, 20, 1, 1, 0, false, false, 13, 512, 8, TAP_ACT + 13},
+    {"conv_512",  FP_TL(rc[1][1]), TS_X512 + 1, TS_TOKENS,   TS_X512 + 2, false, 20, 1, 0, 1, false, true,  14, 512, 8, TAP_ACT + 14},
+};
+#undef FP_TL
+static constexpr bool trunk_is_chain() {   // what plan_trunk relies on: row r writes activation r and row r + 1 reads it
+  for (int r = 0; r < N_TRUNK; r++)
+    if (TRUNK[r].act != r || (r + 1 < N_TRUNK && TRUNK[r + 1].in != TRUNK[r].out)) return false;
+  return N_TRUNK == N_TRUNK_ACT;
+}
+static_assert(trunk_is_chain(), "TRUNK: not a chain of the 15 trunk activations");
+static constexpr int trunk_writer(int r, int s) {   // the row that wrote slot s last in front of row r
+  for (int i = r - 1; i >= 0; i--)
+    if (TRUNK[i].out == s) return i;
+  return -1;
+}
+// row r starts or continues a residual stream: a later row reads its output as the skip operand
+static constexpr bool trunk_out_is_skip(int r) {
+  for (int i = r + 1; i < N_TRUNK; i++) {
+    if (TRUNK[i].res == TRUNK[r].out) return true;
+    if (TRUNK[i].out == TRUNK[r].out) return false;
+  }
+  return false;
+}
+// a block's first conv: no residual, and nobody but the next 8-bit convolution reads its output -- the consumer's scales fold into
+// cscale / bias (legal: no residual, ReLU)
+static constexpr bool trunk_folded_out(int r) { return TRUNK[r].stage != 0 && TRUNK[r].res == TS_NONE && !trunk_out_is_skip(r); }
+inline bool Net::q8_on(int layer) const { return (q8_blocks & TRUNK[Q8_FIRST_ROW + layer].stage) != 0; }
+static const ConvLayer &trunk_layer(const Net &n, int r) { return TRUNK[r].layer(const_cast<Net &>(n)); }
+static constexpr int trunk_layer_cout(int r) { return TRUNK[r].concat ? TRUNK[r].C / 2 : TRUNK[r].C; }   // (the concat row writes one half per image group)
+static constexpr int Q8_IMG_BIAS_MIN_N = 16;   // INT8: passes of fewer hypotheses run without the per-image compensation (plan_trunk)
+
+struct TrunkQuery {
+  int dt = DT_F16;          // the 2-byte element type: every tensor of a 2-byte network; nn_in, the stem, the residual stream and the tokens of an 8-bit one
+  int qdt = -1;             // DT_FP8 / DT_I8: an 8-bit network; -1: a 2-byte network
+  int mask = 0;             // 8-bit network: the stages on 8-bit operands (TrunkRow::stage bits)
+  bool i8_stream = false;   // test build, DT_I8: the residual stream itself is 8-bit
+  bool img_comp = false;    // INT8: the per-image compensation is available in this call (a record solved with it, its buffers, its switch) ...
+  unsigned comp_rows = 0;   // ... and bit r: row r's layer carries the tap sums of its rounding errors (ConvLayer::tmat_t)
+  int N = 1, n_b = 1;       // hypotheses; observed crops behind them (N, or 1 = shared)
+};
+// What one row does, in this order: per-image bias, convolution, 2-byte broadcast, 8-bit broadcast, q8_copy, calibration record, tap.
+// Slots are TrunkSlot, activation indices select a row of Net::act_oinv / act_scale_dev; TS_NONE / -1 = none.
+struct TrunkStep {
+  int op_dt = DT_F16;                           // element type of the weights and the input
+  int in = TS_NONE;   bool in_q = false;        // the input: the slot's 2-byte tensor or its 8-bit copy
+  int res = TS_NONE;  bool res_q = false;       // the skip operand, likewise ...
+  int rscale = -1;                              // ... and the activation whose scales de-quantise an 8-bit one in the epilogue
+  int out16 = TS_NONE, outq = TS_NONE;          // the epilogue writes the 2-byte tensor / the 8-bit copy (both: DT_DUAL_*) ...
+  int oinv = -1;                                // ... the copy scaled by this activation's inverse scales (-1: folded into the layer's tables)
+  bool img_bias = false;                        // INT8: the bias comes per image from q8_img_bias_fused_kernel on the 8-bit input
+  bool bcast16 = false, bcastq = false;         // the shared crop's half of the concat is replicated: 2-byte tensor / 8-bit copy
+  int qcopy = -1;                               // q8_copy_kernel makes the 8-bit copy from the 2-byte output, with this activation's inverse scales
+  int rec = TS_NONE;  bool rec_q = false;       // calibration statistics: of this slot's 2-byte tensor or 8-bit copy ...
+  int rec_dt = -1, rec_scale = -1;              // ... of this element type, de-quantised with this activation's scales
+};
+struct TrunkPlan { TrunkStep step[N_TRUNK]; };
+// The precision policy of the trunk: pure, no HIP call, no decision outside its arguments.
+//   2-byte network: every row on q.dt.
+//   8-bit network [r4, r6]: a stage in the mask reads 8-bit operands, the others keep their 2-byte weights and kernels.  The RESIDUAL
+//   STREAM stays f16, so the skip path is never re-quantised and the tensor a stage hands over always exists in f16 unless nobody reads
+//   it.  An 8-bit row's producer leaves the 8-bit copy as well: from its own epilogue when it is an 8-bit layer or one of the two
+//   2-byte rows in front of the stages (their kernels have the f16 -> dual-output form), through q8_copy_kernel when it is a 2-byte
+//   layer of a stage outside the mask (the resident-halo and 256x256 schedules have no such form).
+//   i8_stream [r4, test build: tools/q8_cross.py]: no f16 stream at all -- a block's second conv reads its skip operand from the 8-bit
+//   copy and writes only the new one (DT_QSR_I8); every stage is 8-bit whatever the mask says.  Not shipped: DESIGN.md section 4.4.
+static int plan_trunk(const TrunkQuery &q, TrunkPlan *plan) {
+  *plan = TrunkPlan{};
+  const bool q8 = q.qdt >= 0;
+  FP_CHECK(q.dt == DT_F16 || q.dt == DT_BF16, "plan_trunk: the stem and the token path run on 2-byte elements");
+  FP_CHECK(!q8 || (is_q8(q.qdt) && q.dt == DT_F16), "plan_trunk: an 8-bit trunk is FP8 or INT8 layers in an f16 network");
+  FP_CHECK(q.N >= 1 && (q.n_b == q.N || q.n_b == 1), "plan_trunk: invalid query");
+  const bool i8s = q.i8_stream && q.qdt == DT_I8;
+  const int mask = !q8 ? 0 : i8s ? ~0 : q.mask;
+  const auto on = [&](int r) { return r < N_TRUNK && (mask & TRUNK[r].stage) != 0; };
+  // the image's own first-order term of the weights' rounding error [r5, r6].  The decision is per CALL (N), not per layer: a pass of
+  // fewer than 16 hypotheses -- Track, small shards -- runs without it (26 more launches would double a Track) and carries that term
+  // uncorrected, the record's corrections being solved on full Registers WITH it: on Track 0.24 deg / 0.28 mm against f16
+  const bool comp = q.qdt == DT_I8 && !i8s && q.img_comp && q.N >= Q8_IMG_BIAS_MIN_N;
+  for (int r = 0; r < N_TRUNK; r++) {
+    const TrunkRow &t = TRUNK[r];
+    TrunkStep &s = plan->step[r];
+    const bool need_q = on(r + 1);                             // the next row reads 8-bit operands
+    const bool epi_q = need_q && (on(r) || t.stage == 0);      // ... and this row's epilogue can write them
+    // no 2-byte output: nobody reads it (the next row is 8-bit and no later row takes it as its skip operand)
+    const bool drop16 = need_q && (i8s || (on(r) && !trunk_out_is_skip(r)));
+    s.op_dt = on(r) ? q.qdt : q.dt;
+    s.in = t.in; s.in_q = on(r);
+    s.res = t.res; s.res_q = i8s && t.res != TS_NONE;
+    s.rscale = s.res_q ? TRUNK[trunk_writer(r, t.res)].act : -1;
+    s.out16 = drop16 ? TS_NONE : t.out; s.outq = epi_q ? t.out : TS_NONE;
+    s.oinv = epi_q && !trunk_folded_out(r) ? t.act : -1;
+    s.img_bias = comp && on(r) && ((q.comp_rows >> r) & 1u) != 0;
+    const bool bcast = t.concat && q.n_b == 1 && q.N > 1;
+    s.bcast16 = bcast && !drop16; s.bcastq = bcast && epi_q;
+    s.qcopy = need_q && !epi_q ? t.act : -1;
+    // every activation but the stem's is recorded, in the form the trunk keeps it; an f16-stream 8-bit trunk skips encodeA.1's too (a
+    // 2-byte layer in front of every stage: the correction sweeps have nothing to solve there)
+    if (t.act >= 1 && (t.stage != 0 || !q8 || i8s)) {
+      s.rec = t.out; s.rec_q = drop16;
+      s.rec_dt = drop16 ? q.qdt : q.dt; s.rec_scale = drop16 ? t.act : -1;
+    }
+  }
+  return 0;
+}
 
 template <typename T>
 static T *upload(Net *net, const std::vector<T> &h) {
@@ -932,7 +1070,6 @@ static Net *net_load_impl(const char *path, bool is_scorer, int prec, std::strin
   return net.release();
 }
 
-static void q8_layers(Net *n, ConvLayer *(&L)[13]);
 // Host phase of loading: the weight file is read and every device layout is built in host memory.  No HIP call, no device needed:
 // callers run it OUTSIDE the process-wide exclusive section (fp_create, fp_set_precision, fp_calibrate: fp_api.hip).
 Net *net_prepare(const char *path, bool is_scorer, int prec, std::string *err) {
@@ -970,10 +1107,10 @@ int net_commit(Net *net, std::string *err) {
   net->calib_sum = reinterpret_cast<long long *>(arena + calib_off);
   net->calib_amax = reinterpret_cast<float *>(arena + calib_off + (size_t)N_TRUNK_ACT * 512 * sizeof(long long));
   // fields that ALIAS another field's buffer were copied while both held the placeholder: ConvLayer::wdeep = wpack (8-bit 3x3 layers)
-  ConvLayer *q8l[13];
-  q8_layers(net, q8l);
-  for (ConvLayer *l : q8l)
-    if (is_q8(l->dt) && l->wdeep == &g_placeholder) l->wdeep = l->wpack;
+  for (int r = Q8_FIRST_ROW; r < N_TRUNK; r++) {
+    ConvLayer &l = TRUNK[r].layer(*net);
+    if (is_q8(l.dt) && l.wdeep == &g_placeholder) l.wdeep = l.wpack;
+  }
   net->pending.clear();
   net->pending.shrink_to_fit();
   net->deferred = false;
@@ -1016,17 +1153,8 @@ int net_calib_end(Net *net, hipStream_t s, float *amax_out /*[15][512] or null*/
 }
 void net_calib_abort(Net *net) { net->calib_mode = 0; net->calib_only = -1; }   // a calibration pass that failed half-way
 void net_q8_unready(Net *net) { net->q8_ready = false; }                          // the precision's record was dropped: quantise again before use
-// the 13 8-bit layers in trunk order; layer i reads activation i + 1 and writes activation i + 2
-static void q8_layers(Net *n, ConvLayer *(&L)[13]) {
-  ConvLayer *l[13] = {&n->ra[0][0], &n->ra[0][1], &n->ra[1][0], &n->ra[1][1], &n->rb[0][0], &n->rb[0][1], &n->rb[1][0],
-                      &n->rb[1][1], &n->b2, &n->rc[0][0], &n->rc[0][1], &n->rc[1][0], &n->rc[1][1]};
-  for (int i = 0; i < 13; i++) L[i] = l[i];
-}
-// channels of trunk activation a (a = 1..14)
-static int act_channels(int a) { return a <= 4 ? 128 : a <= 9 ? 256 : 512; }
-// layer i's output goes ONLY to the next 8-bit convolution (a block's first conv): the consumer's scales fold into cscale / bias
-static bool q8_folded_out(int i) { return i == 0 || i == 2 || i == 4 || i == 6 || i == 9 || i == 11; }
-int net_q8_bias_channels(int layer) { return layer < 4 ? 128 : layer < 8 ? 256 : 512; }
+// (8-bit layer i = 0..12 is TRUNK row i + 2: it reads activation i + 1 and writes activation i + 2)
+int net_q8_bias_channels(int layer) { return trunk_layer_cout(Q8_FIRST_ROW + layer); }
 bool net_q8_layer_on(const Net *n, int layer) { return n->q8_on(layer); }
 int net_q8_blocks(const Net *n) { return n->q8_blocks; }
 
@@ -1070,11 +1198,11 @@ static int apply_q8_layer(Net *net, ConvLayer &l, int dt, const float *s_in, con
 int net_apply_q8(Net *net, const float *amax, const float *bias_fix, const float *tok_fix, bool weights, const float *frame_means, int n_frames) {
   FP_CHECK(net->prec == PREC_FP8 || net->prec == PREC_INT8, "net_apply_q8: not an 8-bit network");
   const int dt = net->qdt;
-  ConvLayer *L[13];
-  q8_layers(net, L);
+  ConvLayer *L[13];   // the 8-bit layers in trunk order
+  for (int i = 0; i < 13; i++) L[i] = &TRUNK[Q8_FIRST_ROW + i].layer(*net);
   if (weights) {
     for (int a = 1; a <= 13; a++) {
-      const int C = act_channels(a);
+      const int C = TRUNK[a].C;
       std::vector<float> sc(C);
       // a channel that is (almost) dead on the calibration frame gets the floor tensor-|max| / 1024, NOT a scale of 1: the scales are
       // folded into the consumer's weights, and one large scale would take the whole range of every weight row
@@ -1112,7 +1240,7 @@ int net_apply_q8(Net *net, const float *amax, const float *bias_fix, const float
         for (int c = 0; c < Cin; c++) m_int[(size_t)j * Cin + c] = frame_means[((size_t)j * N_TRUNK_ACT + a) * 512 + c] / net->act_scale[a][c];
     }
     if (apply_q8_layer(net, *L[i], dt, net->act_scale[i + 1].data(), net->bias_fix[i].data(),
-                       q8_folded_out(i) ? net->act_scale[i + 2].data() : nullptr, weights, efr ? m_int.data() : nullptr, efr ? n_frames : 0)) return 1;
+                       trunk_folded_out(Q8_FIRST_ROW + i) ? net->act_scale[i + 2].data() : nullptr, weights, efr ? m_int.data() : nullptr, efr ? n_frames : 0)) return 1;
   }
   if (tok_fix) net->tok_fix.assign(tok_fix, tok_fix + EMBED);
   else if (net->tok_fix.empty()) net->tok_fix.assign(EMBED, 0.f);
@@ -1285,7 +1413,7 @@ FP_HOOK g_conv_variant = 0;    // 0 default; 7 force / 8 disable the resident-ha
                                // the halo kernels
 FP_HOOK g_conv_ablate = 0;     // timing-only ablations (wrong results) of conv_big_pp_kernel / conv_halo_kernel
 FP_HOOK g_splitk_ablate = 0;   // test build, wrong results: conv_splitk_reduce_kernel sums all slices but the last (the float64 checks must fail)
-FP_HOOK g_i8_stream = 0;       // test build A/B: 1 = INT8 networks with an 8-bit residual stream (run_trunk_i8; faster, but its common-mode error is frame-specific: DESIGN.md section 4.4)
+FP_HOOK g_i8_stream = 0;       // test build A/B: 1 = INT8 networks with an 8-bit residual stream (plan_trunk: i8_stream; faster, but its common-mode error is frame-specific: DESIGN.md section 4.4)
 FP_HOOK g_conv_ragged = 1;     // 256x256 rounds with 288-row tiles that absorb the left-over rows (plan_conv); 0 = a separate left-over launch, as before them
 FP_HOOK g_smallm = 1;          // small problems (Track, a few objects) on conv_smallx_kernel: K split over the waves of a workgroup, no split-K slabs / reduce launch
                                // (0 = off, 2 = for every size, 3 = its first version, conv_smallm_kernel)
@@ -2027,13 +2155,28 @@ static ConvPlan g_last_conv_plan;   // the plan and the kernels' ODT of the last
 static int g_last_conv_odt = -1;
 #endif
 
-// post / post_fused: a positional table the layer may add to its output (see ConvParams::post); *post_fused tells the
-// caller whether the plan did (otherwise the caller launches add_pos_embed_kernel)
-// out2 / oinv (8-bit networks): the layer also writes the 8-bit copy of its f16 output, value * oinv[channel] (DT_DUAL_*)
-static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act &in, int NB, int H, int W, int ipad,
-                    const Act &out, int opad, bool relu, const Act *res = nullptr, int rpad = 0, int split_imgs = 0,
-                    const ConvGroup *grp = nullptr, const void *post = nullptr, bool *post_fused = nullptr, const Act *out2 = nullptr,
-                    const float *oinv = nullptr, const float *rscale = nullptr, const float *bias_img = nullptr) {
+// what one run_conv call runs layer L on, by name
+struct ConvArgs {
+  Act in, out;
+  int NB = 0, H = 0, W = 0;          // images and interior size of `in`
+  int ipad = 0, opad = 0, rpad = 0;  // zero borders of in / out / res
+  bool relu = false;
+  const Act *res = nullptr;          // skip operand, added in front of the ReLU
+  int split_imgs = 0;                // > 0: the output is the a|b channel concat of images [0, split_imgs) and the ones behind them
+  const ConvGroup *grp = nullptr;
+  const void *post = nullptr;        // a positional table the layer may add to its output (see ConvParams::post); *post_fused tells the
+  bool *post_fused = nullptr;        // caller whether the plan did (otherwise the caller launches add_pos_embed_kernel)
+  const Act *out2 = nullptr;         // 8-bit networks: the layer also writes the 8-bit copy of its f16 output (DT_DUAL_*) ...
+  const float *oinv = nullptr;       // ... value * oinv[channel]; without out2: `out` is that scaled 8-bit copy alone (DT_QS_*)
+  const float *rscale = nullptr;     // res is an 8-bit tensor with these per-channel scales (DT_QSR_I8 / DT_F16RQ_I8)
+  const float *bias_img = nullptr;   // INT8: [NB][Cout] biases, one row per image
+};
+static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const ConvArgs &g) {
+  const Act &in = g.in, &out = g.out, *res = g.res, *out2 = g.out2;
+  const int NB = g.NB, H = g.H, W = g.W, ipad = g.ipad, opad = g.opad, rpad = g.rpad, split_imgs = g.split_imgs;
+  const ConvGroup *grp = g.grp;
+  const void *post = g.post; bool *post_fused = g.post_fused;
+  const float *oinv = g.oinv, *rscale = g.rscale, *bias_img = g.bias_img;
   ConvParams p;
   p.bias_img = bias_img;
   FP_CHECK(!bias_img || (L.dt == DT_I8 && !grp), "run_conv: a per-image bias belongs to an INT8 layer");
@@ -2067,7 +2210,7 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
   p.cin_b = L.Cin * es;
   p.krow_b = p.Ktot * es;
   p.ntaps = L.KH * L.KW;
-  p.relu = relu ? 1 : 0;
+  p.relu = g.relu ? 1 : 0;
   p.split_imgs = split_imgs;
   p.out_ld = split_imgs > 0 ? 2 * L.Cout : L.Cout;
   p.res_ld = L.Cout;
@@ -2100,7 +2243,7 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
     else if (L.dt == DT_I8 && out2->dt == DT_I8) FP_CONV_PAIR(DT_I8, DT_DUAL_I8);
     else if (L.dt == DT_F16 && out2->dt == DT_FP8) FP_CONV_PAIR(DT_F16, DT_DUAL_FP8);
     else if (L.dt == DT_F16 && out2->dt == DT_I8) FP_CONV_PAIR(DT_F16, DT_DUAL_I8);
-  } else if (rscale) {   // (run_trunk_i8) the residual is the 8-bit stream copy
+  } else if (rscale) {   // (plan_trunk: i8_stream) the residual is the 8-bit stream copy
 #ifdef FP_TEST_HOOKS
     FP_CHECK(oinv || out.dt == DT_F16, "run_conv: 8-bit residual with an unsupported output type");
     if (oinv) FP_CONV_PAIR(DT_I8, DT_QSR_I8); else FP_CONV_PAIR(DT_I8, DT_F16RQ_I8);
@@ -2111,7 +2254,7 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
     if (L.dt == DT_FP8) FP_CONV_PAIR(DT_FP8, DT_QS_FP8);
     else if (L.dt == DT_F16) {
 #ifdef FP_TEST_HOOKS
-      FP_CONV_PAIR(DT_F16, DT_QS_I8);   // (encodeA.1 in run_trunk_i8)
+      FP_CONV_PAIR(DT_F16, DT_QS_I8);   // (encodeA.1 of the i8_stream trunk)
 #else
       FP_CHECK(false, "run_conv: f16 -> scaled 8-bit alone exists in the test build only");
 #endif
@@ -2156,8 +2299,11 @@ static int run_conv(const Ctx &c, const char *tag, const ConvLayer &L, const Act
 // plain GEMM rows x Cin -> rows x Cout (Linear layer) on unpadded buffers
 static int run_gemm(const Ctx &c, const char *tag, const ConvLayer &L, const void *in, int rows, void *out, bool relu,
                     const void *res = nullptr, const ConvGroup *grp = nullptr) {
-  Act ai{const_cast<void *>(in), L.dt, 1.f}, ao{out, L.dt, 1.f}, ar{const_cast<void *>(res), L.dt, 1.f};
-  return run_conv(c, tag, L, ai, rows, 1, 1, 0, ao, 0, relu, res ? &ar : nullptr, 0, 0, grp);
+  const Act ar{const_cast<void *>(res), L.dt, 1.f};
+  ConvArgs g;
+  g.in = Act{const_cast<void *>(in), L.dt, 1.f}; g.NB = rows; g.H = 1; g.W = 1; g.out = Act{out, L.dt, 1.f};
+  g.relu = relu; g.res = res ? &ar : nullptr; g.grp = grp;
+  return run_conv(c, tag, L, g);
 }
 
 // f16 / bf16 dispatch of the transformer part: f(tag) with tag.value = DT_F16 or DT_BF16 as a constant, tag's E = the element type
@@ -2303,16 +2449,11 @@ static unsigned launch_chan_stats(hipStream_t s, int dt, const unsigned char *x,
   else FP_LAUNCH_RAW(chan_stats_kernel<DT_F16>, grid, blk, 0, s, x, pixels, C, scale, amax, sum);
   return grid.x;
 }
-// act_id: trunk activation (0..14); dt / scale describe the tensor at `buf`
-static void calib_record(const Ctx &c, int act_id, const void *buf, size_t pixels, int C, int dt, const float *scale = nullptr) {
+// act_id: trunk activation (0..14) = the tensor [imgs][HW + 2 pad][HW + 2 pad][C] at `buf`; dt / scale describe its elements
+static void calib_record(const Ctx &c, int act_id, const void *buf, int imgs, int HW, int pad, int C, int dt, const float *scale) {
   if (!c.net->calib_mode || (c.net->calib_only >= 0 && c.net->calib_only != act_id)) return;
-  // interior pixels: the padded tensors are [images][h+2][w+2] with h = w (40x40 / 20x20 maps), the token tensor has no border
-  {
-    double interior = (double)pixels;
-    if (act_id <= 9) interior = (double)pixels / (42.0 * 42.0) * 1600.0;
-    else if (act_id <= 13) interior = (double)pixels / (22.0 * 22.0) * 400.0;
-    c.net->calib_count[act_id] += interior;
-  }
+  const size_t pixels = (size_t)imgs * (HW + 2 * pad) * (HW + 2 * pad);
+  c.net->calib_count[act_id] += (double)imgs * HW * HW;   // interior pixels: what net_calib_end divides the sums by
   float *amax = c.net->calib_mode == 1 ? c.net->calib_amax + act_id * 512 : nullptr;
   long long *sum = c.net->calib_sum + act_id * 512;
   launch_chan_stats(c.s, dt, (const unsigned char *)buf, pixels, C, scale, amax, sum);
@@ -2406,68 +2547,7 @@ static void broadcast_b(const Ctx &c, unsigned char *cat, int N, int cb /* bytes
   FP_LAUNCH_RAW(broadcast_b_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.s, cat, N, 42, 42, 40, 40, 1, cb);
 }
 
-// 8-bit trunk (PREC_FP8 / PREC_INT8) [r4].  The 13 3x3 convolutions from encodeA.2 on read 8-bit operands; what differs from the
-// round-3 FP8 trunk: (1) the RESIDUAL STREAM stays f16 -- a block's second conv (and encodeA.1 / encodeAB.2, whose outputs start a
-// stream) writes the f16 tensor and, in the same epilogue, its 8-bit copy for the next conv (DT_DUAL_*), so the skip path is never
-// re-quantised; (2) activation scales are per CHANNEL and folded into the consumer's weights before those are quantised; (3) biases
-// carry the calibration's bias correction, the positional table the token correction (net_apply_q8).
-#ifdef FP_TEST_HOOKS
-// INT8 WITHOUT an f16 stream [r4, an experiment kept in the test build: tools/q8_cross.py].  The sums of a residual block are
-// re-quantised to the unsigned 8-bit copy the next conv reads anyway; here the block's second conv reads its skip operand from the
-// PREVIOUS 8-bit copy (1 byte instead of 2 per element, scaled per channel in the epilogue: DT_QSR_I8) and writes only the new 8-bit
-// copy: 3 bytes less per output element than the dual-output form, Register 720p 7.64 -> 7.08 ms, same-frame accuracy 98.8-100 %
-// within 1 mm / 1 deg.  NOT shipped: calibrated on one frame and run on another, the common-mode error of the refined poses is
-// 0.6-2.2 mm depending on the frame (f16 stream: 0.6-0.7 mm) -- the rounding bias of a coarsely quantised stream is a property of the
-// frame's activation distribution, which the one-frame bias correction cannot carry over.
-static int run_trunk_i8(const Ctx &c, const Arena &a, const void *nn_in, int N, int n_b) {
-  const Net *net = c.net;
-  const int NB2 = N + n_b, q = DT_I8;
-  auto F = [&](void *p) { return Act{p, DT_F16, 1.f}; };
-  auto Q = [&](void *p) { return Act{p, q, 1.f}; };
-  const size_t P1 = (size_t)NB2 * 42 * 42, P2 = (size_t)N * 42 * 42, P5 = (size_t)N * 22 * 22;
-  float *const *sc = net->act_scale_dev, *const *oi = net->act_oinv;
-  const Act in = F(const_cast<void *>(nn_in)), stem = F(a.stem);
-  if (run_conv(c, "conv_stem", net->a0, in, NB2, 80, 80, 2, stem, 1, true)) return 1;
-  const Act x0q = Q(a.q128[0]), x1q = Q(a.q128[1]), x2q = Q(a.q128[2]);
-  if (run_conv(c, "conv_a1", net->a1, stem, NB2, 80, 80, 1, x0q, 1, true, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, oi[1])) return 1;
-  calib_record(c, 1, a.q128[0], P1, 128, q, sc[1]);
-  if (run_conv(c, "conv_128", net->ra[0][0], x0q, NB2, 40, 40, 1, x1q, 1, true)) return 1;
-  calib_record(c, 2, a.q128[1], P1, 128, q, sc[2]);
-  if (run_conv(c, "conv_128", net->ra[0][1], x1q, NB2, 40, 40, 1, x2q, 1, true, &x0q, 1, 0, nullptr, nullptr, nullptr, nullptr, oi[3], sc[1])) return 1;
-  calib_record(c, 3, a.q128[2], P1, 128, q, sc[3]);
-  if (run_conv(c, "conv_128", net->ra[1][0], x2q, NB2, 40, 40, 1, x1q, 1, true)) return 1;
-  calib_record(c, 4, a.q128[1], P1, 128, q, sc[4]);
-  const Act catq = Q(a.q256[0]);   // the a|b channel concat
-  if (run_conv(c, "conv_128", net->ra[1][1], x1q, NB2, 40, 40, 1, catq, 1, true, &x2q, 1, N, nullptr, nullptr, nullptr, nullptr, oi[5], sc[3])) return 1;
-  if (n_b == 1 && N > 1) broadcast_b(c, a.q256[0], N, 128);
-  calib_record(c, 5, a.q256[0], P2, 256, q, sc[5]);
-  const Act y1q = Q(a.q256[1]), y2q = Q(a.q256[2]), y0q = Q(a.q256[0]);
-  if (run_conv(c, "conv_256", net->rb[0][0], catq, N, 40, 40, 1, y1q, 1, true)) return 1;
-  calib_record(c, 6, a.q256[1], P2, 256, q, sc[6]);
-  if (run_conv(c, "conv_256", net->rb[0][1], y1q, N, 40, 40, 1, y2q, 1, true, &catq, 1, 0, nullptr, nullptr, nullptr, nullptr, oi[7], sc[5])) return 1;
-  calib_record(c, 7, a.q256[2], P2, 256, q, sc[7]);
-  if (run_conv(c, "conv_256", net->rb[1][0], y2q, N, 40, 40, 1, y1q, 1, true)) return 1;
-  calib_record(c, 8, a.q256[1], P2, 256, q, sc[8]);
-  if (run_conv(c, "conv_256", net->rb[1][1], y1q, N, 40, 40, 1, y0q, 1, true, &y2q, 1, 0, nullptr, nullptr, nullptr, nullptr, oi[9], sc[7])) return 1;
-  calib_record(c, 9, a.q256[0], P2, 256, q, sc[9]);
-  const Act z0q = Q(a.q512[0]), z1q = Q(a.q512[1]), z2q = Q(a.q512[2]);
-  if (run_conv(c, "conv_b2", net->b2, y0q, N, 40, 40, 1, z0q, 1, true, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, oi[10])) return 1;
-  calib_record(c, 10, a.q512[0], P5, 512, q, sc[10]);
-  if (run_conv(c, "conv_512", net->rc[0][0], z0q, N, 20, 20, 1, z1q, 1, true)) return 1;
-  calib_record(c, 11, a.q512[1], P5, 512, q, sc[11]);
-  if (run_conv(c, "conv_512", net->rc[0][1], z1q, N, 20, 20, 1, z2q, 1, true, &z0q, 1, 0, nullptr, nullptr, nullptr, nullptr, oi[12], sc[10])) return 1;
-  calib_record(c, 12, a.q512[2], P5, 512, q, sc[12]);
-  if (run_conv(c, "conv_512", net->rc[1][0], z2q, N, 20, 20, 1, z1q, 1, true)) return 1;
-  calib_record(c, 13, a.q512[1], P5, 512, q, sc[13]);
-  const Act tok = F(a.tokens);
-  bool pe_done = false;
-  if (run_conv(c, "conv_512", net->rc[1][1], z1q, N, 20, 20, 1, tok, 0, true, &z2q, 1, 0, nullptr, net->pe, &pe_done, nullptr, nullptr, sc[12])) return 1;
-  if (!pe_done) add_pos_embed(c, a, N);
-  calib_record(c, 14, a.tokens, (size_t)N * 400, 512, DT_F16);
-  return 0;
-}
-#endif
-// the launch of q8_img_bias_fused_kernel for layer L on its 8-bit input xq [NBi, HW + 2, HW + 2, Cin] (run_trunk_q8; fpt_q8_img_bias_raw).
+// the launch of q8_img_bias_fused_kernel for layer L on its 8-bit input xq [NBi, HW + 2, HW + 2, Cin] (q8_img_bias; fpt_q8_img_bias_raw).
 // lattice: the sums run over the even rows x even columns of the padded image (HW + 2 is even): (HW/2 + 1)^2 lattice points, (HW/2)^2
 // of them interior; otherwise over every pixel
 static unsigned launch_q8_img_bias_fused(hipStream_t s, const ConvLayer &L, const unsigned char *xq, int NBi, int HW, bool lattice, float *out) {
@@ -2485,7 +2565,7 @@ static void launch_q8_img_bias_3(hipStream_t s, const ConvLayer &L, const unsign
   (void)hipMemsetAsync(sums, 0, (size_t)NBi * L.Cin * sizeof(int), s);
 }
 #endif
-// the launch of q8_copy_kernel: the 8-bit copy (type q) of the bordered f16 tensor x16 [imgs, HW + 2, HW + 2, Cc] (run_trunk_q8; fpt_q8_copy_raw)
+// the launch of q8_copy_kernel: the 8-bit copy (type q) of the bordered f16 tensor x16 [imgs, HW + 2, HW + 2, Cc] (run_trunk; fpt_q8_copy_raw)
 static unsigned launch_q8_copy(hipStream_t s, int q, const void *x16, void *xq, const float *oinv, int imgs, int HW, int Cc) {
   const size_t octs = (size_t)imgs * HW * HW * (Cc / 8);
   const dim3 grid((unsigned)((octs + 255) / 256));
@@ -2493,192 +2573,81 @@ static unsigned launch_q8_copy(hipStream_t s, int q, const void *x16, void *xq, 
   else FP_LAUNCH_RAW(q8_copy_kernel<DT_I8>, grid, dim3(256), 0, s, (const _Float16 *)x16, (unsigned char *)xq, oinv, HW + 2, HW + 2, 1, Cc, octs);
   return grid.x;
 }
-static int run_trunk_q8(const Ctx &c, const Arena &a, const void *nn_in, int N, int n_b) {
-  const Net *net = c.net;
+// INT8 [r5]: the per-image bias of layer L for its 8-bit input xq ([NBi, HW+2, HW+2, Cin] bytes): bias minus the first-order compensation
+// of the weights' rounding error for that image's channel means.  (The error-feedback rounding has already cancelled this term for the
+// calibration frames' means; what the compensation adds is the image's deviation from them.)
+static const float *q8_img_bias(const Ctx &c, const ConvLayer &L, const void *xq, int NBi, int HW) {
+  NetScope ps(c, "q8_img_bias", 0, (double)NBi * (HW + 2) * (HW + 2) * L.Cin);
 #ifdef FP_TEST_HOOKS
-  if (net->qdt == DT_I8 && g_i8_stream) return run_trunk_i8(c, a, nn_in, N, n_b);
+  if (g_q8_imgbias == 2) {   // A/B (test build): the three-launch form (sliced integer-atomic sums, 64-channel bias blocks, clear)
+    launch_q8_img_bias_3(c.s, L, (const unsigned char *)xq, NBi, HW, c.ws->img_sum, c.ws->img_bias);
+  } else
 #endif
-  const int NB2 = N + n_b, q = net->qdt;
-  auto F = [&](void *p) { return Act{p, DT_F16, 1.f}; };
-  auto Q = [&](void *p) { return Act{p, q, 1.f}; };
-  // INT8 [r5]: per-image bias of layer L for the 8-bit input tensor xq ([NBi, HW+2, HW+2, Cin] bytes): bias minus the first-order
-  // compensation of the weights' rounding error for that image's channel means (q8_img_sum_kernel / q8_img_bias_kernel); null when off
-  auto IB = [&](const ConvLayer &L, const void *xq, int NBi, int HW) -> const float * {
-    // (passes of fewer than 16 hypotheses -- Track, small shards -- run without it: the error-feedback rounding has already cancelled this
-    // term for the calibration frames' means, what the compensation adds is the image's deviation from them, and 26 more launches would
-    // double a Track.  The corrections of a record are solved on full Registers WITH it: a small pass therefore carries the image's own
-    // first-order term uncorrected -- measured on Track 0.24 deg / 0.28 mm against f16)
-    // [r6] the decision is per CALL (N, the hypotheses of this pass), not per layer: with NBi the 128-channel layers of a 15-hypothesis
-    // pass (NB2 = 16 or 30 images) compensated while its 256- / 512-channel layers (N = 15 images) did not
-    if (q != DT_I8 || !net->q8_img_comp || !L.tmat_t || !c.ws || !c.ws->img_sum || !g_q8_imgbias || N < 16) return nullptr;
-    NetScope ps(c, "q8_img_bias", 0, (double)NBi * (HW + 2) * (HW + 2) * L.Cin);
-#ifdef FP_TEST_HOOKS
-    if (g_q8_imgbias == 2) {   // A/B (test build): the three-launch form (sliced integer-atomic sums, 64-channel bias blocks, clear)
-      launch_q8_img_bias_3(c.s, L, (const unsigned char *)xq, NBi, HW, c.ws->img_sum, c.ws->img_bias);
-    } else
-#endif
-    {
-      launch_q8_img_bias_fused(c.s, L, (const unsigned char *)xq, NBi, HW, g_q8_imgbias != 3, c.ws->img_bias);
-    }
-    return c.ws->img_bias;
-  };
-  const size_t P1 = (size_t)NB2 * 42 * 42, P2 = (size_t)N * 42 * 42, P5 = (size_t)N * 22 * 22;
-  // [r6] every stage (encodeA.2-3 / encodeAB.0-1 / encodeAB.2 / encodeAB.3-4) is either on 8-bit operands or on its 2-byte weights and
-  // kernels (Net::q8_blocks).  The residual stream is f16 either way, so the tensor a stage hands over always exists in f16; an
-  // 8-bit stage's producer also leaves the 8-bit operand copy -- from its own epilogue (DT_DUAL_*) when it is an 8-bit layer or
-  // encodeA.1, through q8_copy_kernel when it is a 2-byte layer (those keep their SAME-type kernels: the resident-halo and 256x256
-  // schedules have no f16 -> dual-output instantiation).
-  const bool A = net->q8_on(0), B = net->q8_on(4), S = net->q8_on(8), C = net->q8_on(9);
-  const float *const *oinv = net->act_oinv;
-  float *const *scd = net->act_scale_dev;
-  auto qcopy = [&](const void *x16, void *xq, int imgs, int HW, int Cc, int act) {
-    NetScope ps(c, "q8_copy", 0, (double)imgs * HW * HW * Cc * 3.0);
-    launch_q8_copy(c.s, q, x16, xq, oinv[act], imgs, HW, Cc);
-  };
-  // first conv of a residual block (no skip operand): 8-bit -> 8-bit with the consumer's scales folded in, or plain f16
-  auto first = [&](const char *tag, const ConvLayer &L, bool on, const Act &x16, const Act &xq, int NB, int HW, const Act &y16, const Act &yq, int act, size_t P, int Cc) -> int {
-    if (on) {
-      if (run_conv(c, tag, L, xq, NB, HW, HW, 1, yq, 1, true, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, IB(L, xq.p, NB, HW))) return 1;
-      calib_record(c, act, yq.p, P, Cc, q, scd[act]);
-    } else {
-      if (run_conv(c, tag, L, x16, NB, HW, HW, 1, y16, 1, true)) return 1;
-      calib_record(c, act, y16.p, P, Cc, DT_F16);
-    }
-    return 0;
-  };
-  // second conv of a block (skip operand res16, always f16): writes the f16 stream tensor y16 and / or the 8-bit copy yq for an 8-bit consumer
-  auto second = [&](const char *tag, const ConvLayer &L, bool on, const Act &x16, const Act &xq, int NB, int HW, const Act &res16, const Act *y16, const Act *yq,
-                    int split, int act, size_t P, int Cc) -> int {
-    const Act &x = on ? xq : x16;
-    const float *bi = on ? IB(L, xq.p, NB, HW) : nullptr;
-    if (on && y16 && yq) { if (run_conv(c, tag, L, x, NB, HW, HW, 1, *y16, 1, true, &res16, 1, split, nullptr, nullptr, nullptr, yq, oinv[act], nullptr, bi)) return 1; }
-    else if (on && yq) { if (run_conv(c, tag, L, x, NB, HW, HW, 1, *yq, 1, true, &res16, 1, split, nullptr, nullptr, nullptr, nullptr, oinv[act], nullptr, bi)) return 1; }
-    else {
-      if (run_conv(c, tag, L, x, NB, HW, HW, 1, *y16, 1, true, &res16, 1, split, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bi)) return 1;
-      if (yq && !split) qcopy(y16->p, yq->p, NB, HW, Cc, act);   // (the concat layer's copy is made by its caller, behind broadcast_b)
-    }
-    if (split) return 0;   // (the concat tensor is complete -- and recorded -- only behind broadcast_b: its caller does both)
-    if (y16) calib_record(c, act, y16->p, P, Cc, DT_F16);
-    else calib_record(c, act, yq->p, P, Cc, q, scd[act]);
-    return 0;
-  };
-  const Act in = F(const_cast<void *>(nn_in)), stem = F(a.stem);
-  if (run_conv(c, "conv_stem", net->a0, in, NB2, 80, 80, 2, stem, 1, true)) return 1;
-  // encodeA.1 (f16 operands) starts the 128-channel stream: f16 x0 (+ its 8-bit copy)
-  const Act x0 = F(a.x128[0]), x1 = F(a.x128[1]), x2 = F(a.x128[2]), x0q = Q(a.q128[0]), x1q = Q(a.q128[1]), x2q = Q(a.q128[2]);
-  if (A) { if (run_conv(c, "conv_a1", net->a1, stem, NB2, 80, 80, 1, x0, 1, true, nullptr, 0, 0, nullptr, nullptr, nullptr, &x0q, oinv[1])) return 1; }
-  else if (run_conv(c, "conv_a1", net->a1, stem, NB2, 80, 80, 1, x0, 1, true)) return 1;
-  if (first("conv_128", net->ra[0][0], A, x0, x0q, NB2, 40, x1, x1q, 2, P1, 128)) return 1;
-  if (second("conv_128", net->ra[0][1], A, x1, x1q, NB2, 40, x0, &x2, A ? &x2q : nullptr, 0, 3, P1, 128)) return 1;
-  if (first("conv_128", net->ra[1][0], A, x2, x2q, NB2, 40, x1, x1q, 4, P1, 128)) return 1;
-  // the last encodeA conv writes the a|b channel concat
-  const Act cat = F(a.x256[0]), catq = Q(a.q256[0]);
-  if (second("conv_128", net->ra[1][1], A, x1, x1q, NB2, 40, x2, &cat, (A && B) ? &catq : nullptr, N, 5, P2, 256)) return 1;
-  if (n_b == 1 && N > 1) {  // image N landed in cat[0][..,128:256]; replicate it for the other hypotheses (both copies)
-    broadcast_b(c, a.x256[0], N, 256);
-    if (A && B) broadcast_b(c, a.q256[0], N, 128);
+  {
+    launch_q8_img_bias_fused(c.s, L, (const unsigned char *)xq, NBi, HW, g_q8_imgbias != 3, c.ws->img_bias);
   }
-  if (B && !A) qcopy(cat.p, catq.p, N, 40, 256, 5);
-  calib_record(c, 5, a.x256[0], P2, 256, DT_F16);
-  const Act y1 = F(a.x256[1]), y2 = F(a.x256[2]), y0 = F(a.x256[0]), y1q = Q(a.q256[1]), y2q = Q(a.q256[2]), y0q = Q(a.q256[0]);
-  if (first("conv_256", net->rb[0][0], B, cat, catq, N, 40, y1, y1q, 6, P2, 256)) return 1;
-  if (second("conv_256", net->rb[0][1], B, y1, y1q, N, 40, cat, &y2, B ? &y2q : nullptr, 0, 7, P2, 256)) return 1;
-  if (first("conv_256", net->rb[1][0], B, y2, y2q, N, 40, y1, y1q, 8, P2, 256)) return 1;
-  // y0 feeds only encodeAB.2: no f16 copy when that layer reads 8-bit operands from an 8-bit producer (0.2 GB per launch less; with a
-  // residual the consumer's scales cannot be folded into the tables, so the epilogue scales: DT_QS_*)
-  if (second("conv_256", net->rb[1][1], B, y1, y1q, N, 40, y2, (B && S) ? nullptr : &y0, S ? &y0q : nullptr, 0, 9, P2, 256)) return 1;
-  const Act z0 = F(a.x512[0]), z1 = F(a.x512[1]), z2 = F(a.x512[2]), z0q = Q(a.q512[0]), z1q = Q(a.q512[1]), z2q = Q(a.q512[2]);
-  if (S) {
-    const float *bi = IB(net->b2, y0q.p, N, 40);
-    if (C) { if (run_conv(c, "conv_b2", net->b2, y0q, N, 40, 40, 1, z0, 1, true, nullptr, 0, 0, nullptr, nullptr, nullptr, &z0q, oinv[10], nullptr, bi)) return 1; }
-    else if (run_conv(c, "conv_b2", net->b2, y0q, N, 40, 40, 1, z0, 1, true, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bi)) return 1;
-  } else {
-    if (run_conv(c, "conv_b2", net->b2, y0, N, 40, 40, 1, z0, 1, true)) return 1;
-    if (C) qcopy(z0.p, z0q.p, N, 20, 512, 10);
-  }
-  calib_record(c, 10, a.x512[0], P5, 512, DT_F16);
-  if (first("conv_512", net->rc[0][0], C, z0, z0q, N, 20, z1, z1q, 11, P5, 512)) return 1;
-  if (second("conv_512", net->rc[0][1], C, z1, z1q, N, 20, z0, &z2, C ? &z2q : nullptr, 0, 12, P5, 512)) return 1;
-  if (first("conv_512", net->rc[1][0], C, z2, z2q, N, 20, z1, z1q, 13, P5, 512)) return 1;
-  const Act tok = F(a.tokens);
-  bool pe_done = false;
-  if (run_conv(c, "conv_512", net->rc[1][1], C ? z1q : z1, N, 20, 20, 1, tok, 0, true, &z2, 1, 0, nullptr, net->pe, &pe_done, nullptr, nullptr, nullptr, C ? IB(net->rc[1][1], a.q512[1], N, 20) : nullptr)) return 1;
-  if (!pe_done) add_pos_embed(c, a, N);
-  calib_record(c, 14, a.tokens, (size_t)N * 400, 512, DT_F16);
-  return 0;
+  return c.ws->img_bias;
 }
 
 // shared CNN trunk: nn_in [2N,84,84,32] (s2d, border 2) -> tokens [N,400,512] + positional embedding
 // n_b = number of observed-crop (B) images following the N rendered (A) images: N, or 1 when all hypotheses share it
+// The rows come from TRUNK, what each does in this network from plan_trunk; nothing is decided here.
 static int run_trunk(const Ctx &c, const Arena &a, const void *nn_in, int N, int n_b) {
   const Net *net = c.net;
-  if (net->prec == PREC_FP8 || net->prec == PREC_INT8) return run_trunk_q8(c, a, nn_in, N, n_b);
+  TrunkQuery q;
+  q.dt = net->act_dt; q.N = N; q.n_b = n_b;
+  if (net->prec == PREC_FP8 || net->prec == PREC_INT8) {
+    q.qdt = net->qdt; q.mask = net->q8_blocks; q.i8_stream = g_i8_stream != 0;
+    q.img_comp = net->q8_img_comp && c.ws && c.ws->img_sum && g_q8_imgbias;
+    for (int r = 0; r < N_TRUNK; r++)
+      if (trunk_layer(*net, r).tmat_t) q.comp_rows |= 1u << r;
+  }
+  TrunkPlan tp;
+  if (plan_trunk(q, &tp)) return 1;
+  void *const s16[TS_COUNT] = {const_cast<void *>(nn_in), a.stem, a.x128[0], a.x128[1], a.x128[2], a.x256[0], a.x256[1], a.x256[2], a.x512[0], a.x512[1], a.x512[2], a.tokens};
+  void *const sq[TS_COUNT] = {nullptr, nullptr, a.q128[0], a.q128[1], a.q128[2], a.q256[0], a.q256[1], a.q256[2], a.q512[0], a.q512[1], a.q512[2], nullptr};
+  const auto tensor = [&](int slot, bool copy) { return Act{copy ? sq[slot] : s16[slot], copy ? q.qdt : q.dt, 1.f}; };
   const int NB2 = N + n_b;
-  const int adt = net->act_dt;
-  auto T = [&](void *p) { return Act{p, adt, 1.f}; };
-  const size_t P1 = (size_t)NB2 * 42 * 42, P2 = (size_t)N * 42 * 42, P5 = (size_t)N * 22 * 22;
-  const Act in = T(const_cast<void *>(nn_in)), stem = T(a.stem);
-  const Act x0 = T(a.x128[0]), x1 = T(a.x128[1]), x2 = T(a.x128[2]), cat = T(a.x256[0]);
   // ([r5] stem + encodeA.1 in chunks of 63 / 84 / 126 images, so that the stem's output would be read back from the 256 MB memory-side
   // cache instead of HBM: 10.93 -> 11.24 / 11.13 / 11.00 ms per Register, slower with every extra launch -- EXPERIMENTS.md R5.4)
   FP_TAP_IMGS(c, TAP_NN_IN, nn_in, (size_t)84 * 84 * 32 * 2, NB2, N);
-  if (run_conv(c, "conv_stem", net->a0, in, NB2, 80, 80, 2, stem, 1, true)) return 1;
-  FP_TAP_IMGS(c, TAP_STEM, a.stem, (size_t)82 * 82 * 64 * 2, NB2, N);
-  if (run_conv(c, "conv_a1", net->a1, stem, NB2, 80, 80, 1, x0, 1, true)) return 1;
-  calib_record(c, 1, a.x128[0], P1, 128, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 1, a.x128[0], (size_t)42 * 42 * 128 * 2, NB2, N);
-  // encodeA residual blocks @40x40x128; the last conv writes the a|b channel concat directly
-  if (run_conv(c, "conv_128", net->ra[0][0], x0, NB2, 40, 40, 1, x1, 1, true)) return 1;
-  calib_record(c, 2, a.x128[1], P1, 128, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 2, a.x128[1], (size_t)42 * 42 * 128 * 2, NB2, N);
-  if (run_conv(c, "conv_128", net->ra[0][1], x1, NB2, 40, 40, 1, x2, 1, true, &x0, 1)) return 1;
-  calib_record(c, 3, a.x128[2], P1, 128, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 3, a.x128[2], (size_t)42 * 42 * 128 * 2, NB2, N);
-  if (run_conv(c, "conv_128", net->ra[1][0], x2, NB2, 40, 40, 1, x1, 1, true)) return 1;
-  calib_record(c, 4, a.x128[1], P1, 128, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 4, a.x128[1], (size_t)42 * 42 * 128 * 2, NB2, N);
-  if (run_conv(c, "conv_128", net->ra[1][1], x1, NB2, 40, 40, 1, cat, 1, true, &x2, 1, N)) return 1;
-  if (n_b == 1 && N > 1) broadcast_b(c, a.x256[0], N, 256);  // image N landed in cat[0][..,128:256]; replicate it for the other hypotheses
-  calib_record(c, 5, a.x256[0], P2, 256, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 5, a.x256[0], (size_t)42 * 42 * 256 * 2, N, N);
-  // encodeAB
-  const Act y1 = T(a.x256[1]), y2 = T(a.x256[2]), y0 = T(a.x256[0]);
-  if (run_conv(c, "conv_256", net->rb[0][0], cat, N, 40, 40, 1, y1, 1, true)) return 1;
-  calib_record(c, 6, a.x256[1], P2, 256, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 6, a.x256[1], (size_t)42 * 42 * 256 * 2, N, N);
-  if (run_conv(c, "conv_256", net->rb[0][1], y1, N, 40, 40, 1, y2, 1, true, &cat, 1)) return 1;
-  calib_record(c, 7, a.x256[2], P2, 256, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 7, a.x256[2], (size_t)42 * 42 * 256 * 2, N, N);
-  if (run_conv(c, "conv_256", net->rb[1][0], y2, N, 40, 40, 1, y1, 1, true)) return 1;
-  calib_record(c, 8, a.x256[1], P2, 256, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 8, a.x256[1], (size_t)42 * 42 * 256 * 2, N, N);
-  if (run_conv(c, "conv_256", net->rb[1][1], y1, N, 40, 40, 1, y0, 1, true, &y2, 1)) return 1;
-  calib_record(c, 9, a.x256[0], P2, 256, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 9, a.x256[0], (size_t)42 * 42 * 256 * 2, N, N);
-  const Act z0 = T(a.x512[0]), z1 = T(a.x512[1]), z2 = T(a.x512[2]);
-  if (run_conv(c, "conv_b2", net->b2, y0, N, 40, 40, 1, z0, 1, true)) return 1;
-  calib_record(c, 10, a.x512[0], P5, 512, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 10, a.x512[0], (size_t)22 * 22 * 512 * 2, N, N);
-  if (run_conv(c, "conv_512", net->rc[0][0], z0, N, 20, 20, 1, z1, 1, true)) return 1;
-  calib_record(c, 11, a.x512[1], P5, 512, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 11, a.x512[1], (size_t)22 * 22 * 512 * 2, N, N);
-  if (run_conv(c, "conv_512", net->rc[0][1], z1, N, 20, 20, 1, z2, 1, true, &z0, 1)) return 1;
-  calib_record(c, 12, a.x512[2], P5, 512, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 12, a.x512[2], (size_t)22 * 22 * 512 * 2, N, N);
-  if (run_conv(c, "conv_512", net->rc[1][0], z2, N, 20, 20, 1, z1, 1, true)) return 1;
-  calib_record(c, 13, a.x512[1], P5, 512, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 13, a.x512[1], (size_t)22 * 22 * 512 * 2, N, N);
-  // last conv writes the un-bordered token tensor [N,400,512] (2-byte type in every precision)
-  const Act tok = T(a.tokens);
-  bool pe_done = false;
-  if (run_conv(c, "conv_512", net->rc[1][1], z1, N, 20, 20, 1, tok, 0, true, &z2, 1, 0, nullptr, net->pe, &pe_done)) return 1;
-  if (!pe_done) add_pos_embed(c, a, N);
+  for (int r = 0; r < N_TRUNK; r++) {
+    const TrunkRow &t = TRUNK[r];
+    const TrunkStep &st = tp.step[r];
+    const ConvLayer &L = trunk_layer(*net, r);
+    const int NB = t.ab ? NB2 : N, imgs = t.concat ? N : NB;   // images of the input / of the output
+    int OH, OW;
+    conv_out_hw(L.KH, L.KW, L.stride, L.pad, t.HW, t.HW, &OH, &OW);
+    const Act res = st.res != TS_NONE ? tensor(st.res, st.res_q) : Act{}, copy = st.outq != TS_NONE ? tensor(st.outq, true) : Act{};
+    ConvArgs g;
+    g.in = tensor(st.in, st.in_q); g.NB = NB; g.H = t.HW; g.W = t.HW; g.ipad = t.ipad; g.opad = t.opad; g.rpad = t.rpad;
+    g.out = st.out16 != TS_NONE ? tensor(st.out16, false) : copy; g.relu = true;
+    g.res = st.res != TS_NONE ? &res : nullptr; g.split_imgs = t.concat ? N : 0;
+    bool pe_done = false;
+    if (t.pe) { g.post = net->pe; g.post_fused = &pe_done; }
+    g.out2 = st.out16 != TS_NONE && st.outq != TS_NONE ? &copy : nullptr;
+    g.oinv = st.oinv >= 0 ? net->act_oinv[st.oinv] : nullptr; g.rscale = st.rscale >= 0 ? net->act_scale_dev[st.rscale] : nullptr;
+    if (st.img_bias) g.bias_img = q8_img_bias(c, L, g.in.p, NB, t.HW);
+    if (run_conv(c, t.tag, L, g)) return 1;
+    if (t.pe) {   // whoever did not fuse the positional table adds it here
+      if (!pe_done) add_pos_embed(c, a, N);
 #ifdef FP_TEST_HOOKS
-  g_tap_pe_fused[net->scorer ? 1 : 0] = pe_done ? 1 : 0;
+      g_tap_pe_fused[net->scorer ? 1 : 0] = pe_done ? 1 : 0;
 #endif
-  FP_TAP(c, TAP_PE, net->pe, (size_t)400 * EMBED * 2);
-  calib_record(c, 14, a.tokens, (size_t)N * 400, 512, adt);
-  FP_TAP_IMGS(c, TAP_ACT + 14, a.tokens, (size_t)400 * 512 * 2, N, N);
+      FP_TAP(c, TAP_PE, net->pe, (size_t)400 * EMBED * 2);
+    }
+    // image N landed in the concat's channels [C/2, C) of image 0; replicate it for the other hypotheses
+    if (st.bcast16) broadcast_b(c, (unsigned char *)s16[t.out], N, t.C / 2 * 2);
+    if (st.bcastq) broadcast_b(c, (unsigned char *)sq[t.out], N, t.C / 2);
+    if (st.qcopy >= 0) {
+      NetScope ps(c, "q8_copy", 0, (double)imgs * OH * OH * t.C * 3.0);
+      launch_q8_copy(c.s, q.qdt, s16[t.out], sq[t.out], net->act_oinv[st.qcopy], imgs, OH, t.C);
+      FP_HIP_OK(hipGetLastError());
+    }
+    if (st.rec != TS_NONE)
+      calib_record(c, t.act, st.rec_q ? sq[st.rec] : s16[st.rec], imgs, OH, t.opad, t.C, st.rec_dt, st.rec_scale >= 0 ? net->act_scale_dev[st.rec_scale] : nullptr);
+    if (st.out16 != TS_NONE) FP_TAP_IMGS(c, t.tap, s16[t.out], (size_t)(OH + 2 * t.opad) * (OH + 2 * t.opad) * t.C * 2, imgs, N);
+  }
   return 0;
 }
 

@@ -331,7 +331,7 @@ __global__ void cast_f32_kernel(const float *__restrict__ in, typename ElemT<DT>
 
 // [r6] 8-bit operand copy of a bordered f16 tensor [imgs][HP][WP][C] (interior pixels only; the copy's border bytes were set once
 // by ensure_scratch): value * oinv[c], rounded like the dual-output epilogues do.  Used where a 2-byte stage of a partly 8-bit trunk
-// hands its output to an 8-bit stage (run_trunk_q8) -- the 2-byte stage keeps its own kernels.  One thread = 8 channels of a pixel.
+// hands its output to an 8-bit stage (plan_trunk: qcopy) -- the 2-byte stage keeps its own kernels.  One thread = 8 channels of a pixel.
 template <int QDT>
 __global__ __launch_bounds__(256) void q8_copy_kernel(const _Float16 *__restrict__ x, unsigned char *__restrict__ q, const float *__restrict__ oinv,
                                                       int HP, int WP, int pad, int C, size_t octs) {

@@ -118,7 +118,7 @@ int fpt_launch_log_get_all(int *fields7, char *names, int name_cap, int max) {
   return n;
 }
 void fpt_launch_log_clear() { fp::g_launch_log.clear(); }
-// did the last 2-byte trunk of this network kind add the positional table in the epilogue of its last convolution (1) or separately (0)
+// did the last trunk of this network kind add the positional table in the epilogue of its last convolution (1) or separately (0)
 int fpt_tap_pe_fused(int net_kind) { return fp::g_tap_pe_fused[net_kind & 1]; }
 void fpt_set_att_variant(int v) { fp::g_att_variant = v; }
 void fpt_set_smallm(int v) { fp::g_smallm = v; }
@@ -204,6 +204,24 @@ int fpt_plan_heads(int pass, int N, int dt, int fuse_offer, int *fields18, int *
   std::memcpy(tail3, t, sizeof(t));
   return 0;
 }
+// HOST-ONLY (no HIP call: runs without a GPU, tests/test_trunk_plan_cpu.py): what plan_trunk decides for the 15 rows of the trunk.  dt: DT_F16 /
+// DT_BF16; qdt: DT_FP8 / DT_I8 or -1 (a 2-byte network); mask: the stages on 8-bit operands; i8_stream: the 8-bit residual stream;
+// img_comp / comp_rows: the per-image compensation is available / bit r = row r's layer carries its tap sums; N hypotheses and n_b
+// observed crops.  fields17 [15][17] = the fields of TrunkStep in their order (slots: TrunkSlot; -1 = none).  Returns 0, or 1 when the
+// query is refused.
+int fpt_plan_trunk(int dt, int qdt, int mask, int i8_stream, int img_comp, unsigned comp_rows, int N, int n_b, int *fields17) {
+  fp::TrunkQuery q;
+  q.dt = dt; q.qdt = qdt; q.mask = mask; q.i8_stream = i8_stream != 0; q.img_comp = img_comp != 0; q.comp_rows = comp_rows; q.N = N; q.n_b = n_b;
+  fp::TrunkPlan p;
+  if (fp::plan_trunk(q, &p)) return 1;
+  for (int r = 0; r < fp::N_TRUNK; r++) {
+    const fp::TrunkStep &s = p.step[r];
+    const int f[17] = {s.op_dt, s.in, s.in_q, s.res, s.res_q, s.rscale, s.out16, s.outq, s.oinv, s.img_bias, s.bcast16, s.bcastq, s.qcopy,
+                       s.rec, s.rec_q, s.rec_dt, s.rec_scale};
+    std::memcpy(fields17 + (size_t)r * 17, f, sizeof(f));
+  }
+  return 0;
+}
 // HOST-ONLY (no HIP call: runs without a GPU, tests/test_depth_filter_cpu.py): plan_track_window (fp_geometry.hip) of n poses.
 // K9 row-major intrinsics, poses16 [n][16] column-major -> out5 [n][5] = {kind (TrackWindowKind), row0, row1, col0, col1}
 void fpt_plan_track_window(const float *K9, float diameter, const float *poses16, int H, int W, int reach, int *out5, int n) {
@@ -287,16 +305,19 @@ int fpt_conv_dt(const float *x, const float *w, const float *bias, const float *
   FP_CHECK(!is_q8(dt) && !is_q8(out_dt), "fpt_conv_dt: 2-byte element types only (8-bit layers: fpt_conv_q8)");
   Ctx c{nullptr, nullptr, &net};
   (void)OH; (void)OW;
-  const Act ain{dx.p, dt, in_scale}, aout{dout.p, out_dt, out_scale}, ares{dres.p, dt, res_scale};
+  const Act ares{dres.p, dt, res_scale};
+  ConvArgs g;
+  g.in = Act{dx.p, dt, in_scale}; g.NB = NB; g.H = H; g.W = W; g.ipad = ip;
+  g.out = Act{dout.p, out_dt, out_scale}; g.relu = relu != 0; g.res = res ? &ares : nullptr; g.split_imgs = split_imgs;
   hipEvent_t e0, e1;
   FP_HIP_OK(hipEventCreate(&e0));
   FP_HIP_OK(hipEventCreate(&e1));
-  if (run_conv(c, "t", L, ain, NB, H, W, ip, aout, 0, relu != 0, res ? &ares : nullptr, 0, split_imgs)) return 1;
+  if (run_conv(c, "t", L, g)) return 1;
   FP_HIP_OK(hipDeviceSynchronize());
   if (iters > 1) {
     FP_HIP_OK(hipEventRecord(e0, nullptr));
     for (int i = 0; i < iters; i++)
-      if (run_conv(c, "t", L, ain, NB, H, W, ip, aout, 0, relu != 0, res ? &ares : nullptr, 0, split_imgs)) return 1;
+      if (run_conv(c, "t", L, g)) return 1;
     FP_HIP_OK(hipEventRecord(e1, nullptr));
     FP_HIP_OK(hipEventSynchronize(e1));
     float ms = 0;
@@ -315,14 +336,14 @@ int fpt_conv_dt(const float *x, const float *w, const float *bias, const float *
     if (v != 0xA5) { fp::set_error("fpt_conv_dt: the kernels wrote outside the output buffer"); return 2; }
   return 0;
 }
-// One 8-bit convolution exactly as the 8-bit trunk runs it (net_apply_q8 / run_trunk_q8).
+// One 8-bit convolution exactly as the 8-bit trunk runs it (net_apply_q8 / plan_trunk).
 //   x [NB,H,W,Cin] f32 (>= 0 for DT_I8), s_in [Cin] per-channel activation scales: the device input is e4m3(x / s) or
 //   (clamp(rint(x / s), 0, 255) ^ 0x80) with a border of "zero" bytes; w [Cout,KH,KW,Cin] f32 is quantised per row AFTER s_in is folded
 //   in; res (optional) [NB,OH,OW,Cout] is f16 on the device.
 //   mode 0: 8-bit output only, the consumer's scales s_out [Cout] folded into the epilogue tables -> outq (de-quantised values)
 //   mode 1: f16 output only -> out16;  mode 2: f16 output + its 8-bit copy (value / s_out[c]) -> out16, outq
 //   mode 3: the 8-bit copy alone, scaled in the epilogue (a layer with a residual whose f16 output nobody reads) -> outq
-//   mode 4 / 5 (DT_I8): the residual is an 8-bit tensor itself, clamp(rint(res / s_res), 0, 255) ^ 0x80 (run_trunk_i8); 4: scaled 8-bit
+//   mode 4 / 5 (DT_I8): the residual is an 8-bit tensor itself, clamp(rint(res / s_res), 0, 255) ^ 0x80 (plan_trunk: i8_stream); 4: scaled 8-bit
 //   output -> outq, 5: f16 output -> out16
 // split_imgs > 0: the a|b channel concat ([NB - split, OH, OW, 2 * Cout]; s_out still indexed by the layer's output channel).
 // wq_out (optional) [Cout*KH*KW*Cin]: the de-quantised weights the device used (w' / s_in, i.e. comparable with w), sw_out [Cout].
@@ -387,15 +408,13 @@ int fpt_conv_q8(const float *x, const float *s_in, const float *w, const float *
   }
   Ctx c{nullptr, nullptr, &net};
   (void)OH; (void)OW;
-  const Act ain{dx.p, dt, 1.f}, a16{d16.p, DT_F16, 1.f}, aq{dq.p, dt, 1.f}, ares{dres.p, mode >= 4 ? DT_I8 : DT_F16, 1.f};
-  auto once = [&]() {
-    if (mode == 4) return run_conv(c, "t", L, ain, NB, H, W, ip, aq, 0, relu != 0, &ares, 0, split_imgs, nullptr, nullptr, nullptr, nullptr, oinv_dev, rscale_dev);
-    if (mode == 5) return run_conv(c, "t", L, ain, NB, H, W, ip, a16, 0, relu != 0, &ares, 0, split_imgs, nullptr, nullptr, nullptr, nullptr, nullptr, rscale_dev);
-    if (mode == 0) return run_conv(c, "t", L, ain, NB, H, W, ip, aq, 0, relu != 0, res ? &ares : nullptr, 0, split_imgs);
-    if (mode == 1) return run_conv(c, "t", L, ain, NB, H, W, ip, a16, 0, relu != 0, res ? &ares : nullptr, 0, split_imgs);
-    if (mode == 3) return run_conv(c, "t", L, ain, NB, H, W, ip, aq, 0, relu != 0, res ? &ares : nullptr, 0, split_imgs, nullptr, nullptr, nullptr, nullptr, oinv_dev);
-    return run_conv(c, "t", L, ain, NB, H, W, ip, a16, 0, relu != 0, res ? &ares : nullptr, 0, split_imgs, nullptr, nullptr, nullptr, &aq, oinv_dev);
-  };
+  const Act a16{d16.p, DT_F16, 1.f}, aq{dq.p, dt, 1.f}, ares{dres.p, mode >= 4 ? DT_I8 : DT_F16, 1.f};
+  ConvArgs g;
+  g.in = Act{dx.p, dt, 1.f}; g.NB = NB; g.H = H; g.W = W; g.ipad = ip;
+  g.relu = relu != 0; g.res = res ? &ares : nullptr; g.split_imgs = split_imgs;
+  g.out = (mode == 1 || mode == 2 || mode == 5) ? a16 : aq;   // the f16 tensor, or the 8-bit one alone
+  g.out2 = mode == 2 ? &aq : nullptr; g.oinv = oinv_dev; g.rscale = rscale_dev;   // (the tables are null in the modes without them)
+  auto once = [&]() { return run_conv(c, "t", L, g); };
   if (once()) return 1;
   FP_HIP_OK(hipDeviceSynchronize());
   if (iters > 1) {
@@ -456,9 +475,11 @@ int fpt_conv_f16_dual(const float *x, const float *w, const float *bias, int NB,
   float *oinv_dev = upload(&net, inv);
   FP_CHECK(oinv_dev, "fpt_conv_f16_dual: allocation failed");
   Ctx c{nullptr, nullptr, &net};
-  const Act ain{dx.p, DT_F16, 1.f}, a16{d16.p, DT_F16, 1.f}, aq{dq.p, qdt, 1.f};
-  if (out16 ? run_conv(c, "t", L, ain, NB, H, W, ip, a16, 0, true, nullptr, 0, 0, nullptr, nullptr, nullptr, &aq, oinv_dev)
-            : run_conv(c, "t", L, ain, NB, H, W, ip, aq, 0, true, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, oinv_dev)) return 1;
+  const Act a16{d16.p, DT_F16, 1.f}, aq{dq.p, qdt, 1.f};
+  ConvArgs g;
+  g.in = Act{dx.p, DT_F16, 1.f}; g.NB = NB; g.H = H; g.W = W; g.ipad = ip;
+  g.out = out16 ? a16 : aq; g.relu = true; g.out2 = out16 ? &aq : nullptr; g.oinv = oinv_dev;
+  if (run_conv(c, "t", L, g)) return 1;
   FP_HIP_OK(hipDeviceSynchronize());
   std::vector<unsigned char> h16(nout * 2), hq(nout);
   FP_HIP_OK(fp::memcpy_sync(h16.data(), d16.p, h16.size(), hipMemcpyDeviceToHost));
@@ -878,12 +899,16 @@ int fpt_conv_q8_raw(const int *cfg13, const void *x, const float *w, const float
   if (bias_img) { bimg_dev = upload(&net, std::vector<float>(bias_img, bias_img + (size_t)NB * Cout)); FP_CHECK(bimg_dev, "fpt_conv_q8_raw: allocation failed"); }
   Ctx c{nullptr, nullptr, &net};
   const int qo = odt_q(odt);
-  const Act ain{dx.p, dt, 1.f}, a16{d16.p, DT_F16, 1.f}, aq{d8.p, qo >= 0 ? qo : DT_I8, 1.f}, ares{dres.p, res_kind == 2 ? DT_I8 : DT_F16, 1.f};
+  const Act a16{d16.p, DT_F16, 1.f}, aq{d8.p, qo >= 0 ? qo : DT_I8, 1.f}, ares{dres.p, res_kind == 2 ? DT_I8 : DT_F16, 1.f};
   const bool two = odt_16(odt) >= 0;   // a 2-byte tensor is written (alone, or with its 8-bit copy)
   bool fused = false;
   g_last_conv_plan = ConvPlan{}; g_last_conv_odt = -1;
-  if (run_conv(c, "t", L, ain, NB, H, H, 1, two ? a16 : aq, opad, relu != 0, res ? &ares : nullptr, rpad, split, nullptr, post ? dpost.p : nullptr, &fused,
-               odt_dual(odt) ? &aq : nullptr, oinv_dev, rscale_dev, bimg_dev)) return 1;
+  ConvArgs g;
+  g.in = Act{dx.p, dt, 1.f}; g.NB = NB; g.H = H; g.W = H; g.ipad = 1; g.opad = opad; g.rpad = rpad;
+  g.out = two ? a16 : aq; g.relu = relu != 0; g.res = res ? &ares : nullptr; g.split_imgs = split;
+  g.post = post ? dpost.p : nullptr; g.post_fused = &fused; g.out2 = odt_dual(odt) ? &aq : nullptr;
+  g.oinv = oinv_dev; g.rscale = rscale_dev; g.bias_img = bimg_dev;
+  if (run_conv(c, "t", L, g)) return 1;
   FP_HIP_OK(hipGetLastError());
   FP_HIP_OK(hipDeviceSynchronize());
   FP_CHECK(g_last_conv_odt == odt, "fpt_conv_q8_raw: run_conv dispatched another output type than the case names");
@@ -1031,11 +1056,15 @@ long long fpt_conv_stress(int NB0, int H0, int Cin0, int Cout0, int with_res, in
       L.w = (unsigned char *)dw.p; L.bias = db.p; L.Cin = Cin; L.Cout = Cout; L.KH = 3; L.KW = 3; L.stride = 1; L.pad = 1;
       NNScratch ws;
       Ctx c{s, nullptr, &net, &ws};
-      const Act ain{dx.p, DT_F16, 1.f}, aref{dref.p, DT_F16, 1.f}, aout{dout.p, DT_F16, 1.f}, ares{dres.p, DT_F16, 1.f};
-      if (run_conv(c, "t", L, ain, NB, H, H, 1, aref, 1, true, with_res ? &ares : nullptr, 1, 0)) return;
+      const Act ares{dres.p, DT_F16, 1.f};
+      ConvArgs g;
+      g.in = Act{dx.p, DT_F16, 1.f}; g.NB = NB; g.H = H; g.W = H; g.ipad = 1; g.opad = 1; g.rpad = 1;
+      g.out = Act{dref.p, DT_F16, 1.f}; g.relu = true; g.res = with_res ? &ares : nullptr;
+      if (run_conv(c, "t", L, g)) return;
       (void)hipStreamSynchronize(s);
       for (int i = 0; i < iters; i++) {
-        if (run_conv(c, "t", L, ain, NB, H, H, 1, aout, 1, true, with_res ? &ares : nullptr, 1, 0)) return;
+        g.out.p = dout.p;
+        if (run_conv(c, "t", L, g)) return;
         hipLaunchKernelGGL(fpt_count_diff_kernel, dim3(1024), dim3(256), 0, s, (const uint32_t *)dout.p, (const uint32_t *)dref.p,
                            nout / 2, dcnt.p);
       }

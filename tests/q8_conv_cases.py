@@ -13,7 +13,7 @@ conv_epilogue_px and the kernels' row loops):
   * the step starts at row 0 or behind another step (m_begin enters every row index);
   * the last tile of the step is ragged (rows % tile height; the halo kernels and the 256x256 rounds only ever get whole tiles);
   * the positional table is fused (POST instantiation);
-  * a per-image bias is present (INT8 operands in run_trunk_q8, passes of 16 hypotheses and more).
+  * a per-image bias is present (INT8 operands in the 8-bit trunk, plan_trunk: passes of 16 hypotheses and more).
 Classified per step, not per plan: "256x256 rounds with nothing left over" first happens at 1024 / 2048 images, but its step is the
 same code as the rounds of a plan that has a left-over.  No class's smallest member exceeds 96 images (test_q8_conv_cases_cpu.py).
 
@@ -32,7 +32,7 @@ DT_NAME = {F16: "f16", FP8: "fp8", I8: "i8", DUAL_FP8: "dual_fp8", DUAL_I8: "dua
            F16RQ_I8: "f16rq_i8"}
 TILE_ROWS = {"PP": 256, "DEEP64": 64, "IGEMM128": 128}       # kernels whose last tile can be ragged (conv_smallx_kernel: 16 * MI)
 SMALLX_LDS_MI2 = 4 * 3 * 2 * 2048 + 3 * 4 * 2 * 1024         # plan_conv: the LDS bytes of conv_smallx_kernel<2, 4>
-IMG_BIAS_MIN_N = 16                                          # run_trunk_q8 (IB): passes of fewer hypotheses run without the per-image bias
+IMG_BIAS_MIN_N = 16                                          # plan_trunk (Q8_IMG_BIAS_MIN_N): passes of fewer hypotheses run without the per-image bias
 Q8_LAYERS = [ly for ly in TRUNK if ly.name == "encodeA.1" or ly.Cin >= 128]
 CLASS_FIELDS = ("layer shape", "kernel", "MI", "dt", "odt", "residual", "concat", "m_begin > 0", "ragged last tile", "table fused", "per-image bias")
 

@@ -27,7 +27,7 @@ import torch
 
 import layer_ref as LR
 from foundationpose_cpp_amd import FoundationPose, _lib, synthetic as syn
-from foundationpose_cpp_amd.api import FP_DEVICE, FP_HOST, FP_PREC_BF16, FP_PREC_F16, FoundationPoseError, _p
+from foundationpose_cpp_amd.api import FP_DEVICE, FP_HOST, FP_PREC_BF16, FP_PREC_F16, FP_PREC_FP8, FP_PREC_INT8, FoundationPoseError, _p
 
 pytestmark = pytest.mark.gpu
 
@@ -799,6 +799,60 @@ def test_plan_equals_reality(tl, model, crops, disc_nets, syn_mesh, scene):
                 _same_launches(f"fp_net_infer scorer={scorer} batch={batch}", real, _plan(tl, model, PLAN_SCORER if scorer else PLAN_REFINER, batch))
         finally:
             tl.fp_net_destroy(n)
+
+
+@pytest.fixture(scope="module")
+def q8_blobs(tl, disc_nets, syn_mesh, scene):
+    """one-frame calibration records of FP8 and INT8 (every stage 8-bit), made once on a model of their own: the launches of a trunk
+    do not depend on the numbers in its record, so every stage mask below loads these"""
+    tl.fpt_set_q8_blocks(15)
+    with mock.patch.object(_lib, "lib", _typed_test_lib):
+        m = FoundationPose(syn_mesh, syn.intrinsics(), disc_nets[0], disc_nets[1])
+    try:
+        blobs = {}
+        for prec in (FP_PREC_FP8, FP_PREC_INT8):
+            m.calibrate(scene.rgb, scene.depth, scene.mask, syn_mesh.name, prec)
+            blobs[prec] = m.get_calibration_blob(prec)
+    finally:
+        m.close()
+    return blobs
+
+
+@pytest.mark.parametrize("mask", (15, 4, 6, 9))
+def test_plan_equals_reality_of_the_8bit_trunks(tl, crops, disc_nets, syn_mesh, scene, q8_blobs, mask):
+    """test_plan_equals_reality for FP8 and INT8 under the stage masks that between them reach every boundary form of plan_trunk -- a
+    dual epilogue (15), q8_copy behind a 2-byte producer in its three places (4: encodeAB.1, 6: the concat, 9: encodeAB.2), 8-bit ->
+    f16 only (4, 9) and 8-bit alone (6, 15): refiner and scorer with own crops at N = 1, 15, 16, 33 and the refiner on Register's shared
+    crop at N = 15, 16 -- both sides of the per-image-bias threshold, with and without the broadcast"""
+    da, db = (torch.from_numpy(x).to(DEV) for x in crops)
+    t, r, sc = (np.zeros((33, 3), np.float32), np.zeros((33, 3), np.float32), np.zeros(33, np.float32))
+    tl.fpt_set_q8_blocks(mask)          # (networks loaded from now on: the model below)
+    try:
+        with mock.patch.object(_lib, "lib", _typed_test_lib):
+            m = FoundationPose(syn_mesh, syn.intrinsics(), disc_nets[0], disc_nets[1])
+        try:
+            L = m._L
+            tl.fpt_model_use_graphs(m._h, 0)
+            for blob in q8_blobs.values():
+                m.set_calibration_blob(blob)
+            for prec in (FP_PREC_FP8, FP_PREC_INT8):
+                m.set_precision(prec)
+                for N in (1, 15, 16, 33):
+                    a, b = da[:N].contiguous(), db[:N].contiguous()
+                    torch.cuda.synchronize()
+                    pa, pb = C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr())
+                    real = _logged(tl, lambda: m._must(L.fp_refiner_infer(m._h, pa, pb, FP_DEVICE, N, _p(t), _p(r))))
+                    _same_launches(f"refiner mask={mask} prec={prec} N={N}", real, _plan(tl, m, PLAN_REFINER, N))
+                    real = _logged(tl, lambda: m._must(L.fp_scorer_infer(m._h, pa, pb, FP_DEVICE, N, _p(sc))))
+                    _same_launches(f"scorer mask={mask} prec={prec} N={N}", real, _plan(tl, m, PLAN_SCORER, N))
+                    del a, b
+                for N in (15, 16):
+                    real = _logged(tl, lambda: _shard_begin(m, scene, syn_mesh, 0, N))
+                    _same_launches(f"shard [0:{N}] mask={mask} prec={prec}", real, _shard_plan(tl, m, N))
+        finally:
+            m.close()
+    finally:
+        tl.fpt_set_q8_blocks(15)
 
 
 # fp_nn.hip: QkvForm, TailForm, PoolForm of fpt_plan_heads (fields18[0], [14], [15])

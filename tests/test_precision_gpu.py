@@ -584,7 +584,7 @@ def test_register_720p_fp8_meets_the_bar(disc_nets):
 
 
 def test_stage_mask_of_the_8bit_trunk(disc_nets, syn_mesh, syn_scene):
-    """[r6] run_trunk_q8 runs every residual stage either on 8-bit operands or on its 2-byte weights and kernels (Net::q8_blocks; test
+    """[r6] The 8-bit trunk (plan_trunk) runs every residual stage either on 8-bit operands or on its 2-byte weights and kernels (Net::q8_blocks; test
     build: fpt_set_q8_blocks).  Invariants that do not need an error budget:
       * mask 0 -- an "INT8" network none of whose stages is 8-bit -- IS the f16 network: Track and a 42-hypothesis Register return the
         f16 path's poses bit for bit (same weights, same kernels, same buffers; run without the calibration's correction steps, whose

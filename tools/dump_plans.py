@@ -1,9 +1,10 @@
 """Dump every launch record the networks' schedules produce, one line per record, field for field:
     net prec tag kernel m_begin M ksplit pe side
 for the refiner, the scorer and the scorer's features at every N in 1..FP_MAX_BATCH and the refiner on Register's shared crop at every
-N in 2..42 * FP_MAX_INPLANE_STEPS, in f16 and bf16; FP8 and INT8 (after a one-frame calibration) at PLAN_SIZES; and PLAN_SIZES under every
-alternative schedule the test build keeps (conv_variant 3 / 5 / 7 / 8, smallm 0 / 2 / 3, enc_tail 0).  Nothing is launched: the records
-come from fpt_plan_forward and the launch log.  Two builds decide alike exactly when their dumps are equal:
+N in 2..42 * FP_MAX_INPLANE_STEPS, in f16 and bf16; FP8 and INT8 (after a one-frame calibration) at PLAN_SIZES; PLAN_SIZES under every
+alternative schedule the test build keeps (conv_variant 3 / 5 / 7 / 8, smallm 0 / 2 / 3, enc_tail 0); and FP8 and INT8 at PLAN_SIZES under
+every stage mask 0..15 of the 8-bit trunk (fpt_set_q8_blocks: a model per mask, on the calibration records of the first) and INT8 with the
+8-bit residual stream (fpt_set_i8_stream).  Nothing is launched: the records come from fpt_plan_forward and the launch log.  Two builds decide alike exactly when their dumps are equal:
 
     FP_TEST_LIB_PATH=<build A>/libfoundationpose_amd_test.so python tools/dump_plans.py a.txt
     FP_TEST_LIB_PATH=<build B>/libfoundationpose_amd_test.so python tools/dump_plans.py b.txt && cmp a.txt b.txt
@@ -39,6 +40,7 @@ def main(out_path):
     W.pack_synthetic("refiner", rp)
     W.pack_synthetic("scorer", sp)
     model = FoundationPose(mesh, scene.K, rp, sp)
+    models = [model]                                      # plan() asks the last one
     sha, lines = hashlib.sha256(), 0
     out = open(out_path, "w")
 
@@ -51,7 +53,7 @@ def main(out_path):
     def plan(what, kind, N, shared=0):
         emit(f"# {what} {KINDS[kind]} N={N} shared={shared}")
         T.fpt_launch_log_arm(1)
-        rc = T.fpt_plan_forward(model._h, kind, N, shared)
+        rc = T.fpt_plan_forward(models[-1]._h, kind, N, shared)
         T.fpt_launch_log_arm(0)
         if rc != 0:
             emit("plan-only failed: " + T.fp_last_error().decode())
@@ -85,12 +87,32 @@ def main(out_path):
                     sweep(f"{setter[8:]}={v} {name}", PLAN_SIZES, 42 * STEPS_MAX)
             getattr(T, setter)(values[-1])                        # back to the default
         model.set_precision(FP_PREC_F16)
+        blobs = []
         for name, prec in (("fp8", FP_PREC_FP8), ("int8", FP_PREC_INT8)):
             model.calibrate(scene.rgb, scene.depth, scene.mask, mesh.name, prec)
+            blobs.append(model.get_calibration_blob(prec))
             model.set_precision(prec)
             sweep(name, PLAN_SIZES, 42 * STEPS_MAX)
             model.set_precision(FP_PREC_F16)
+        for mask in range(16):                                # a network keeps the mask it was loaded with: a model per mask
+            T.fpt_set_q8_blocks(mask)
+            models.append(FoundationPose(mesh, scene.K, rp, sp))
+            try:
+                for blob in blobs:
+                    models[-1].set_calibration_blob(blob)
+                for name, prec in (("fp8", FP_PREC_FP8), ("int8", FP_PREC_INT8)):
+                    models[-1].set_precision(prec)
+                    sweep(f"q8_blocks={mask} {name}", PLAN_SIZES, 42 * STEPS_MAX)
+                    if mask == 15 and prec == FP_PREC_INT8:
+                        T.fpt_set_i8_stream(1)
+                        sweep(f"i8_stream=1 {name}", PLAN_SIZES, 42 * STEPS_MAX)
+                        T.fpt_set_i8_stream(0)
+            finally:
+                models.pop().close()
+        T.fpt_set_q8_blocks(15)
     finally:
+        T.fpt_set_i8_stream(0)
+        T.fpt_set_q8_blocks(15)
         model.close()
         out.close()
         weights_dir.cleanup()

@@ -1,6 +1,6 @@
 """[r6] Which STAGES of the trunk can run on 8-bit operands and still hold the configs[4] bar on frames the calibration never saw?
   Test build: fpt_set_q8_blocks(mask) -- bit 0 encodeA.2-3 (128 ch), bit 1 encodeAB.0-1 (256 ch), bit 2 encodeAB.2
-(3x3 / s2), bit 3 encodeAB.3-4 (512 ch); stages outside the mask keep their f16 weights and kernels (fp_nn.hip: run_trunk_q8).
+(3x3 / s2), bit 3 encodeAB.3-4 (512 ch); stages outside the mask keep their f16 weights and kernels (fp_nn.hip: plan_trunk).
 
 Per mask and mesh (textured / untextured), 1280x720, N = 252: calibrate on 16 frames of the scene family, measure on 6 OTHER frames
 against the f16 path of the same model: share of the 252 refined poses within 1 mm / 1 deg, p95, common-mode shift, winner index;
