@@ -26,7 +26,7 @@ SYMBOLS = [
     "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
     "fp_set_depth_filter", "fp_get_depth_filter",
-    "fp_render_pose", "fp_render_scene", "fp_pose_errors",
+    "fp_render_pose", "fp_render_scene", "fp_pose_errors", "fp_pose_vsd",
 ]
 
 
@@ -60,6 +60,16 @@ class FpPoseError(C.Structure):
     _fields_ = [("add_m", C.c_float), ("adds_m", C.c_float), ("mssd_m", C.c_float), ("mspd_px", C.c_float), ("rot_deg", C.c_float),
                 ("trans_m", C.c_float), ("best_sym", C.c_int32), ("best_sym_mspd", C.c_int32), ("add_sum_q20", C.c_int64),
                 ("adds_sum_q20", C.c_int64), ("n_vertices", C.c_int32), ("reserved", C.c_int32)]
+
+
+FP_VSD_MAX_TAUS = 16
+
+
+class FpPoseVsd(C.Structure):
+    """struct fp_pose_vsd of include/foundationpose_amd.h"""
+    _fields_ = [("n_model_est", C.c_int32), ("n_model_gt", C.c_int32), ("n_visib_est", C.c_int32), ("n_visib_gt", C.c_int32),
+                ("n_inter", C.c_int32), ("n_union", C.c_int32), ("n_fail", C.c_int32 * FP_VSD_MAX_TAUS), ("vsd", C.c_float * FP_VSD_MAX_TAUS),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
 class FpMesh(C.Structure):
@@ -166,6 +176,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_render_pose": [vp, cs, vp, cf, vp, ci],
         "fp_render_scene": [vp, ci, vp, vp, cf, vp, vp, ci],
         "fp_pose_errors": [vp, cs, vp, ci, vp, ci, vp, ci, ci, ci, vp],
+        "fp_pose_vsd": [vp, cs, vp, ci, vp, ci, cf, vp, ci, ci, vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

@@ -90,6 +90,34 @@ def auc(errors, max_value: float = 0.1, step: float = 0.001) -> float:
     return float(((y[1:] + y[:-1]) / 2 * np.diff(x)).sum() / max_value)
 
 
+BOP19_TAUS = tuple(round(0.05 * k, 2) for k in range(1, 11))   # 0.05, 0.10, ..., 0.50: BOP19's misalignment tolerances and its thresholds of correctness
+FP_VSD_NORMALIZED = 1
+FP_VSD_EST_REFUSED_NEAR, FP_VSD_EST_REFUSED_RANGE, FP_VSD_GT_REFUSED_NEAR, FP_VSD_GT_REFUSED_RANGE = 1, 2, 4, 8
+
+
+@dataclasses.dataclass(frozen=True)
+class PoseVsd:
+    """struct fp_pose_vsd (include/foundationpose_amd.h): the surface visible under an estimate against the surface visible under the ground
+    truth, given the observed depth; pixel counts of the uploaded frame"""
+    n_model_est: int
+    n_model_gt: int
+    n_visib_est: int
+    n_visib_gt: int
+    n_inter: int
+    n_union: int
+    n_fail: tuple         # per tau: intersection pixels whose distances differ by at least the threshold
+    vsd: tuple            # per tau: (n_fail + n_union - n_inter) / n_union, 1.0 without a visible pixel
+    status: int           # FP_VSD_*_REFUSED_* bits: the pose needs a clipper or leaves the raster's range (all counts 0, vsd 1.0)
+
+
+def vsd_recall(records, thetas=BOP19_TAUS) -> float:
+    """BOP's AR_VSD: the mean over all (record, tau, theta) of vsd[tau] < theta; 0 for no records"""
+    v = np.asarray([r.vsd for r in records], np.float64)
+    if v.size == 0:
+        return 0.0
+    return float(np.mean(v[:, :, None] < np.asarray(thetas, np.float64)[None, None, :]))
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -469,6 +497,22 @@ class FoundationPose:
                                           int(vertex_step), 1 if adds else 0, out))
         return [PoseError(float(r.add_m), float(r.adds_m), float(r.mssd_m), float(r.mspd_px), float(r.rot_deg), float(r.trans_m), r.best_sym,
                           r.best_sym_mspd, r.add_sum_q20, r.adds_sum_q20, r.n_vertices) for r in out[:len(e)]]
+
+    # ---- visible surface discrepancy (include/foundationpose_amd.h "visible surface discrepancy") ---
+    def pose_vsd(self, target_name: str, est_poses, gt_poses, delta_m: float = 0.015, taus=BOP19_TAUS, normalized: bool = True):
+        """fp_pose_vsd: BOP's VSD of est_poses [N,4,4] against gt_poses ([N,4,4], or one [4,4] for all of them) on the uploaded frame's
+        raw depth -> [PoseVsd] * N.  delta_m: the visibility tolerance; taus: up to 16 misalignment tolerances, fractions of the target's
+        diameter when `normalized` (BOP19) and metres otherwise.  A pose that would need a clipper does not fail the call: its record
+        carries the status bit and vsd 1.0 (one ground truth for all that does fails it)."""
+        e = to_colmajor(np.asarray(est_poses, np.float32).reshape(-1, 4, 4))
+        g = to_colmajor(np.asarray(gt_poses, np.float32).reshape(-1, 4, 4))
+        t = np.ascontiguousarray(np.asarray(taus, np.float32).ravel())
+        out = (_lib.FpPoseVsd * max(len(e), 1))()
+        self._must(self._L.fp_pose_vsd(self._h, target_name.encode(), _p(e), len(e), _p(g), len(g), delta_m, _p(t), len(t),
+                                       FP_VSD_NORMALIZED if normalized else 0, out))
+        n = min(len(t), _lib.FP_VSD_MAX_TAUS)
+        return [PoseVsd(r.n_model_est, r.n_model_gt, r.n_visib_est, r.n_visib_gt, r.n_inter, r.n_union, tuple(r.n_fail[:n]),
+                        tuple(float(x) for x in r.vsd[:n]), r.status) for r in out[:len(e)]]
 
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):

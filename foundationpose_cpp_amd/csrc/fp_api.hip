@@ -199,8 +199,10 @@ const RoctxApi &roctx_api() {
 void roctx_push(const char *name) { if (roctx_api().push) (void)roctx_api().push(name); }
 void roctx_pop() { if (roctx_api().pop) (void)roctx_api().pop(); }
 #ifdef FP_TEST_HOOKS
+static int g_vsd_chunk = 0;   // fpt_vsd_set_chunk: poses per chunk of fp_pose_vsd (0: sized by VSD_SCRATCH_BYTES); only the test build changes it
 static int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;   // A/B (fpt_set_calib_opts): steps of the 8-bit calibration
 #else
+static constexpr int g_vsd_chunk = 0;
 static constexpr int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;
 #endif
 
@@ -533,6 +535,16 @@ struct fp_model {
   std::vector<float> pe_mats_host;         // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
   std::vector<PoseErrPair> pe_pairs_host;
 
+  // visible surface discrepancy (fp_pose_vsd): the same terms -- allocated at the first call, grow-only, read by no captured graph.
+  int4 *vsd_snap = nullptr;                // [vsd_snap_cap] snapped vertices of one chunk of poses: estimates [chunk, V] | their truths [chunk, V], or the one truth [V]
+  FramePose *vsd_poses = nullptr;          // [vsd_pose_cap] estimates [N] | truths [n_gt]
+  int *vsd_words = nullptr;                // [vsd_word_cap] counters [N, VSD_WORDS] | refusal words of the estimates [N] | of the truths [n_gt]
+  int2 *vsd_items = nullptr;               // [vsd_item_cap] the (pose, tile) work list of one chunk
+  float *vsd_plane = nullptr;              // [vsd_plane_cap] n_gt == 1: the one truth's model depth [H, W]
+  size_t vsd_snap_cap = 0, vsd_pose_cap = 0, vsd_word_cap = 0, vsd_item_cap = 0, vsd_plane_cap = 0;
+  std::vector<FramePose> vsd_poses_host;   // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
+  std::vector<int2> vsd_items_host;
+
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
   // into a hipGraph and replayed.  The graph bakes buffer addresses, so it is keyed by g_alloc_epoch.
   // (Register's ~110 launches are replayed the same way: inter-kernel gaps are ~4 % of a 12 ms Register.)
@@ -827,6 +839,8 @@ static int caught_exception() noexcept {
 extern "C" {
 
 #ifdef FP_TEST_HOOKS
+// fp_pose_vsd works through its poses in chunks of `poses` (0: the library's own size): a batch test of the chunk seams at small N
+void fpt_vsd_set_chunk(int poses) { g_vsd_chunk = poses > 0 ? poses : 0; }
 void fpt_set_calib_opts(int sweeps, int tok, int out) { g_calib_sweeps = sweeps; g_calib_tok = tok; g_calib_out = out; }
 // A/B hook: hipGraph replay of the Track / Register bodies on or off for one model
 int fpt_model_use_graphs(fp_model *m, int on) {
@@ -1271,6 +1285,7 @@ static void destroy_model_impl(fp_model *m) {
   dev_free(m->sc_table); dev_free(m->sc_work); dev_free(m->sc_list);
   delete m->sc_table_host; m->sc_table_host = nullptr;
   dev_free(m->pe_mats); dev_free(m->pe_pairs); dev_free(m->pe_sums);
+  dev_free(m->vsd_snap); dev_free(m->vsd_poses); dev_free(m->vsd_words); dev_free(m->vsd_items); dev_free(m->vsd_plane);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
@@ -2841,6 +2856,153 @@ int fp_pose_errors(fp_model *m, const char *target_name, const float *est_poses,
     r.n_vertices = Vs;
     out[i] = r;
   }
+  return 0;
+} FP_CATCH_INT
+
+// ---- visible surface discrepancy
+namespace {
+bool bound_empty(const FrameTileBound &b) { return b.tx0 > b.tx1 || b.ty0 > b.ty1; }
+long long bound_tiles(const FrameTileBound &b) { return bound_empty(b) ? 0 : (long long)(b.tx1 - b.tx0 + 1) * (b.ty1 - b.ty0 + 1); }
+FrameTileBound bound_union(const FrameTileBound &a, const FrameTileBound &b) {
+  if (bound_empty(a)) return b;
+  if (bound_empty(b)) return a;
+  return {std::min(a.tx0, b.tx0), std::min(a.ty0, b.ty0), std::max(a.tx1, b.tx1), std::max(a.ty1, b.ty1)};
+}
+bool matrix_finite(const float *p) {
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(p[k])) return false;
+  return true;
+}
+}  // namespace
+static_assert(sizeof(fp_pose_vsd_t) == 160, "fp_pose_vsd: six counts, 16 counts, 16 floats, two 32-bit words");
+static_assert(FP_VSD_MAX_TAUS == fp::VSD_MAX_TAUS && 6 + FP_VSD_MAX_TAUS <= fp::VSD_WORDS, "include/foundationpose_amd.h: the thresholds of fp_pose_vsd are those of fp_internal.h");
+static_assert(FP_VSD_EST_REFUSED_NEAR == FRAME_RENDER_FLAG_NEAR && FP_VSD_EST_REFUSED_RANGE == FRAME_RENDER_FLAG_RANGE &&
+              FP_VSD_GT_REFUSED_NEAR == FRAME_RENDER_FLAG_NEAR << 2 && FP_VSD_GT_REFUSED_RANGE == FRAME_RENDER_FLAG_RANGE << 2,
+              "include/foundationpose_amd.h: the status bits of fp_pose_vsd are the refusal bits of the vertex rule");
+int fp_pose_vsd(fp_model *m, const char *target_name, const float *est_poses, int N, const float *gt_poses, int n_gt, float delta_m,
+                const float *taus, int T, int flags, fp_pose_vsd_t *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && est_poses && gt_poses && taus && out, "[FoundationPose] fp_pose_vsd: invalid arguments");
+  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fp_pose_vsd: " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  FP_CHECK(n_gt == 1 || n_gt == N, "[FoundationPose] fp_pose_vsd: n_gt must be 1 or N");
+  FP_CHECK(T >= 1 && T <= FP_VSD_MAX_TAUS, "[FoundationPose] fp_pose_vsd: " + std::to_string(T) + " thresholds (1..FP_VSD_MAX_TAUS = " + std::to_string(FP_VSD_MAX_TAUS) + ")");
+  FP_CHECK(std::isfinite(delta_m) && delta_m >= 0.0f, "[FoundationPose] fp_pose_vsd: delta_m must be finite and >= 0 (metres)");
+  for (int t = 0; t < T; t++)
+    FP_CHECK(std::isfinite(taus[t]) && taus[t] >= 0.0f, "[FoundationPose] fp_pose_vsd: taus[" + std::to_string(t) + "] must be finite and >= 0");
+  FP_CHECK(!(flags & ~FP_VSD_NORMALIZED), "[FoundationPose] fp_pose_vsd: unknown flag bits");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_pose_vsd: a submitted Track has not been waited for (fp_track_wait)");
+  Target *t = m->find(target_name ? target_name : "");
+  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  for (int i = 0; i < N; i++)
+    FP_CHECK(matrix_finite(est_poses + (size_t)i * 16), "[FoundationPose] fp_pose_vsd: a non-finite entry in est_poses[" + std::to_string(i) + "]");
+  for (int i = 0; i < n_gt; i++)
+    FP_CHECK(matrix_finite(gt_poses + (size_t)i * 16), "[FoundationPose] fp_pose_vsd: a non-finite entry in gt_poses[" + std::to_string(i) + "]");
+  FP_CHECK(m->depth != nullptr && m->H > 0, "[FoundationPose] fp_pose_vsd: no frame uploaded");
+  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  const DeviceMesh &mesh = t->mesh;
+  const int H = m->H, W = m->W, V = mesh.V;
+  const int ntx = scene_tiles_x(W);
+  const bool paired = n_gt == N && N > 1;   // (N == 1: the one truth goes through the plane like any n_gt == 1 call; same pixels)
+  // host: the poses in the kernels' form, every pose's tiles, the work they stand for
+  m->vsd_poses_host.resize((size_t)N + n_gt);
+  FramePose *est_h = m->vsd_poses_host.data(), *gt_h = est_h + N;
+  for (int i = 0; i < N; i++) est_h[i] = frame_pose(m, est_poses + (size_t)i * 16);
+  for (int i = 0; i < n_gt; i++) gt_h[i] = frame_pose(m, gt_poses + (size_t)i * 16);
+  std::vector<FrameTileBound> bounds((size_t)N);
+  const FrameTileBound truth_bound = frame_tile_bound(gt_h[0], (double)mesh.max_norm, H, W);
+  const long long walk = (long long)std::max(mesh.F, 1) * (paired ? 2 : 1);   // faces an item walks
+  long long work = paired ? 0 : bound_tiles(truth_bound) * std::max(mesh.F, 1);
+  for (int i = 0; i < N; i++) {
+    const FrameTileBound g = paired ? frame_tile_bound(gt_h[i], (double)mesh.max_norm, H, W) : truth_bound;
+    bounds[(size_t)i] = bound_union(frame_tile_bound(est_h[i], (double)mesh.max_norm, H, W), g);
+    work += bound_tiles(bounds[(size_t)i]) * walk;
+  }
+  FP_CHECK(work <= FP_VSD_MAX_WORK, "[FoundationPose] fp_pose_vsd: " + std::to_string(N) + " poses of " + std::to_string(mesh.F) + " faces walk " + std::to_string(work) +
+               " faces over their 32 x 32 px tiles, above FP_VSD_MAX_WORK = " + std::to_string((long long)FP_VSD_MAX_WORK) + ": pass fewer poses per call");
+  VsdParams P;
+  P.fx = m->K[0]; P.cx = m->K[2]; P.fy = m->K[4]; P.cy = m->K[5];
+  P.delta = delta_m;
+  P.T = T;
+  for (int k = 0; k < VSD_MAX_TAUS; k++) P.thr[k] = k >= T ? 0.0f : (flags & FP_VSD_NORMALIZED) ? taus[k] * mesh.diameter : taus[k];
+  // chunks of poses: the snapped vertices of a chunk (and of its truths) stay below VSD_SCRATCH_BYTES, one pose at least
+  const size_t per_pose = (size_t)std::max(V, 1) * sizeof(int4) * (paired ? 2 : 1);
+  int chunk = (int)std::min<size_t>(std::max<size_t>(VSD_SCRATCH_BYTES / per_pose, 1), (size_t)N);
+  if (g_vsd_chunk > 0) chunk = std::min(g_vsd_chunk, N);
+  hipStream_t s = m->stream;
+  const size_t n_words = (size_t)N * VSD_WORDS + N + n_gt;
+  if (grow_scratch(s, m->vsd_snap, m->vsd_snap_cap, (size_t)V * ((size_t)chunk * (paired ? 2 : 1) + (paired ? 0 : 1))) ||
+      grow_scratch(s, m->vsd_poses, m->vsd_pose_cap, (size_t)N + n_gt) || grow_scratch(s, m->vsd_words, m->vsd_word_cap, n_words) ||
+      (!paired && grow_scratch(s, m->vsd_plane, m->vsd_plane_cap, (size_t)H * W)))
+    return 1;
+  int *counters = m->vsd_words, *flags_est = counters + (size_t)N * VSD_WORDS, *flags_gt = flags_est + N;
+  const FramePose *est_d = m->vsd_poses, *gt_d = est_d + N;
+  FP_HIP_OK(hipMemcpyAsync(m->vsd_poses, est_h, ((size_t)N + n_gt) * sizeof(FramePose), hipMemcpyHostToDevice, s));
+  FP_HIP_OK(hipMemsetAsync(m->vsd_words, 0, n_words * sizeof(int), s));   // counters and refusal words together
+  std::vector<int> words(n_words, 0);
+  const int *flag_e = words.data() + (size_t)N * VSD_WORDS, *flag_g = flag_e + N;
+  for (int p0 = 0; p0 < N; p0 += chunk) {
+    const int c = std::min(chunk, N - p0);
+    const int c_gt = paired ? c : p0 == 0 ? 1 : 0;   // the chunk's own truths, or the one truth with the first chunk
+    int4 *snap_e = m->vsd_snap, *snap_g = snap_e + (size_t)c * V;
+    {
+      ProfScope ps(&m->prof, s, "vsd_vertex", 0, (double)(c + c_gt) * V * (12.0 + 16.0));
+      launch_vsd_vertex(s, mesh, est_d + p0, c, paired ? gt_d + p0 : gt_d, c_gt, snap_e, flags_est + p0, paired ? flags_gt + p0 : flags_gt);
+      FP_HIP_OK(hipGetLastError());
+    }
+    // the refusal words of this chunk decide its work list (everything the stream held before is finished after this)
+    FP_HIP_OK(hipMemcpyAsync(words.data() + (size_t)N * VSD_WORDS, flags_est, ((size_t)N + n_gt) * sizeof(int), hipMemcpyDeviceToHost, s));
+    FP_HIP_OK(hipStreamSynchronize(s));
+    if (!paired && p0 == 0) {
+      if (pose_refused(flag_g[0], "[FoundationPose] fp_pose_vsd: ground truth refused: ")) return 1;
+      // the one truth, once: fp_render_pose's own raster kernel writes its model depth over the whole frame
+      ProfScope ps(&m->prof, s, "vsd_tile", 0, (double)H * W * 4.0);
+      launch_frame_raster(s, mesh, snap_g, nullptr, nullptr, m->depth, H, W, truth_bound, 0.0f, FrameRenderOut{m->vsd_plane, nullptr, nullptr, nullptr, nullptr});
+      FP_HIP_OK(hipGetLastError());
+    }
+    std::vector<int2> &items = m->vsd_items_host;
+    items.clear();
+    std::vector<int> pose_end;   // items.size() after each pose of the chunk that has any
+    for (int l = 0; l < c; l++) {
+      const int i = p0 + l;
+      if (flag_e[i] || (paired && flag_g[i])) continue;
+      const FrameTileBound &b = bounds[(size_t)i];
+      if (bound_empty(b)) continue;
+      for (int ty = b.ty0; ty <= b.ty1; ty++)
+        for (int tx = b.tx0; tx <= b.tx1; tx++) items.push_back(make_int2(l, ty * ntx + tx));
+      pose_end.push_back((int)items.size());
+    }
+    if (items.empty()) continue;
+    if (grow_scratch(s, m->vsd_items, m->vsd_item_cap, items.size())) return 1;
+    FP_HIP_OK(hipMemcpyAsync(m->vsd_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    // no launch above a tenth of the cap: whole poses per launch, one at least
+    const long long per_launch = std::max<long long>(FP_VSD_MAX_WORK / 10 / walk, 1);
+    ProfScope ps(&m->prof, s, "vsd_tile", 0, (double)items.size() * (double)walk * 60.0);
+    int first = 0;
+    for (size_t k = 0; k < pose_end.size();) {
+      size_t last = k;
+      while (last + 1 < pose_end.size() && pose_end[last + 1] - first <= per_launch) last++;
+      launch_vsd_tiles(s, mesh, snap_e, paired ? snap_g : nullptr, m->vsd_plane, m->vsd_items + first, pose_end[last] - first, m->depth, H, W, P, p0, counters);
+      FP_HIP_OK(hipGetLastError());
+      first = pose_end[last];
+      k = last + 1;
+    }
+  }
+  FP_HIP_OK(hipMemcpyAsync(words.data(), counters, (size_t)N * VSD_WORDS * sizeof(int), hipMemcpyDeviceToHost, s));
+  FP_HIP_OK(hipStreamSynchronize(s));
+  std::vector<fp_pose_vsd_t> recs((size_t)N);
+  for (int i = 0; i < N; i++) {
+    fp_pose_vsd_t r = {};
+    r.status = flag_e[i] | (paired ? flag_g[i] << 2 : 0);
+    const int *w = words.data() + (size_t)i * VSD_WORDS;
+    if (!r.status) {
+      r.n_model_est = w[0]; r.n_model_gt = w[1]; r.n_visib_est = w[2]; r.n_visib_gt = w[3]; r.n_inter = w[4]; r.n_union = w[5];
+      for (int k = 0; k < T; k++) r.n_fail[k] = w[6 + k];
+    }
+    for (int k = 0; k < FP_VSD_MAX_TAUS; k++)
+      r.vsd[k] = k >= T ? std::nanf("") : r.n_union == 0 ? 1.0f : (float)(((double)r.n_fail[k] + (double)r.n_union - (double)r.n_inter) / (double)r.n_union);
+    recs[(size_t)i] = r;
+  }
+  std::memcpy(out, recs.data(), recs.size() * sizeof(fp_pose_vsd_t));
   return 0;
 } FP_CATCH_INT
 

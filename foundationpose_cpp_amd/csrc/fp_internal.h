@@ -400,6 +400,27 @@ void launch_pose_error_pairs(hipStream_t s, const float *verts, int Vs, int step
 void launch_pose_error_nn(hipStream_t s, const float *verts, int Vs, int step, const float *rel, int pose0, int n_poses,
                           unsigned long long *sums);
 
+// visible surface discrepancy (fp_pose_vsd; fp_pose_vsd.hip).  The renderings follow section 4.8's rules through
+// fp_frame_rules.h; a pose's counters are VSD_WORDS 32-bit words: n_model_est, n_model_gt, n_visib_est, n_visib_gt, n_inter, n_union,
+// n_fail[16], two unused.
+constexpr int VSD_MAX_TAUS = 16;                    // = FP_VSD_MAX_TAUS
+constexpr int VSD_WORDS = 24;
+constexpr size_t VSD_SCRATCH_BYTES = 128u << 20;    // snapped vertices of one chunk of poses (estimates + their ground truths) stay below this
+struct VsdParams {
+  float fx, fy, cx, cy;
+  float delta;               // the visibility tolerance delta_m
+  int T;                     // thresholds in use
+  float thr[VSD_MAX_TAUS];   // in metres (already multiplied by the diameter when normalised)
+};
+// pose p of the launch is poses_est[p] (p < n_est: the chunk's estimates) or poses_gt[p - n_est] (its ground truths); snap
+// [(n_est + n_gt) V] in frame_vertex_kernel's format; pose p raises flags_est[p] or flags_gt[p - n_est], which must be zero on entry
+void launch_vsd_vertex(hipStream_t s, const DeviceMesh &m, const FramePose *poses_est, int n_est, const FramePose *poses_gt, int n_gt, int4 *snap,
+                       int *flags_est, int *flags_gt);
+// items [n_items] = {pose of the chunk, tile}: counters[(pose0 + pose) VSD_WORDS ..] += the tile's pixel counts.  snap_g non-null: ground
+// truth `pose` of the chunk is walked like the estimate; null: plane_g [H,W] holds the one ground truth's model depth (0 = background)
+void launch_vsd_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap_e, const int4 *snap_g, const float *plane_g, const int2 *items, int n_items,
+                      const float *depth, int H, int W, const VsdParams &P, int pose0, int *counters);
+
 // host helpers (fp_host.cpp part of fp_api.hip)
 std::vector<float> make_rotation_grid(int min_views, int inplane_steps);
 

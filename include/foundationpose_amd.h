@@ -329,6 +329,51 @@ int fp_pose_errors(fp_model *m, const char *target_name, const float *est_poses,
                    const float *symmetries /* S column-major 4x4, MESH frame; NULL = none */, int S,
                    int vertex_step, int flags, fp_pose_error *out /* host [N] */);
 
+/* ---- visible surface discrepancy: BOP's VSD of N poses against the uploaded frame (new; the reference has no counterpart) ----
+ * fp_pose_vsd compares, pixel by pixel, the surface visible under each estimate with the surface visible under its ground truth,
+ * given the observed depth: the third of BOP's three errors next to MSSD and MSPD, ambiguity-invariant without a symmetry list.
+ * Poses as in fp_pose_errors (column-major 4x4, centred-mesh -> camera; n_gt == 1: every estimate against the one truth).  The frame is
+ * the uploaded one (fp_upload_frame, or what the last Register / device-frame Track left), read as the RAW depth whether
+ * fp_set_depth_filter is on or off; K is the model's.  DESIGN.md section 4.11 has the rules; in short, per pixel (c, r):
+ *   z_e, z_g   exactly fp_render_pose's model_depth of the estimate and of the truth
+ *   q = sqrtf((X * X + Y * Y) + 1), X = ((float)c - cx) / fx, Y = ((float)r - cy) / fy;  d_t = D * q, d_e = z_e * q, d_g = z_g * q
+ *              (BOP compares distances from the camera centre, not z; D the observed depth; every f32 operation separately rounded)
+ *   hidden(d)  = !(D < 0.001f) && (d - d_t) > delta_m             (missing depth, and NaN, hide nothing)
+ *   vis_g = model_g && !hidden(d_g);   vis_e = model_e && (!hidden(d_e) || vis_g)
+ *   on vis_g && vis_e the pixel fails threshold t when fabsf(d_g - d_e) >= thr_t, thr_t = taus[t] (* the target's diameter, one f32
+ *              product, with FP_VSD_NORMALIZED)
+ *   vsd[t] = (n_fail[t] + n_union - n_inter) / n_union: BOP's step cost (the tau-linear cost is not built)
+ * Every field but vsd is an integer pixel count, so pose i's record is byte-identical alone, in any batch, with n_gt == 1 or N copies
+ * of the truth, and from call to call.
+ * A refused pose (a vertex at z < FP_RENDER_NEAR_M, or beyond FP_RENDER_SNAP_MAX: fp_render_pose would fail) does not fail the call:
+ * its record gets the status bit, all counts 0 and vsd[t] = 1 for t < T; the same for the truth of a pair when n_gt == N.  With
+ * n_gt == 1 a refused truth fails the whole call before `out` is written.
+ * Refused with an error before anything is launched and before `out` is written: an unknown target, N outside 1..FP_MAX_BATCH, n_gt
+ * not 1 or N, T outside 1..FP_VSD_MAX_TAUS, a tau or delta_m that is not finite or is negative, unknown flag bits, a non-finite
+ * matrix entry, no frame, a partial frame, a pending Track, and more than FP_VSD_MAX_WORK faces walked: the sum over the call's
+ * (pose, 32 x 32 px tile) items -- the tiles of the union of the screen bounds of an estimate and its truth -- of the faces each walks
+ * (F, or 2 F when n_gt == N), plus the truth's own tiles once when n_gt == 1.  No single launch covers more than a tenth of it.
+ * Works on geometry-only models; stream-ordered on the model's stream; Register, Track, their captured graphs and every existing
+ * kernel are untouched: the call's buffers are its own, allocated at its first use, grow-only. */
+#define FP_VSD_MAX_TAUS 16
+#define FP_VSD_NORMALIZED 1          /* flags: taus are fractions of the target's diameter (BOP19: yes) */
+#define FP_VSD_EST_REFUSED_NEAR 1    /* status bits of a record */
+#define FP_VSD_EST_REFUSED_RANGE 2
+#define FP_VSD_GT_REFUSED_NEAR 4
+#define FP_VSD_GT_REFUSED_RANGE 8
+#define FP_VSD_MAX_WORK 250000000000LL /* faces walked by one call: 0.96 s at the 2.6e11 faces/s measured for 252 poses */
+typedef struct fp_pose_vsd {
+  int32_t n_model_est, n_model_gt;   /* frame pixels the rendering covers (before visibility) */
+  int32_t n_visib_est, n_visib_gt;
+  int32_t n_inter, n_union;          /* of the two visibility masks */
+  int32_t n_fail[FP_VSD_MAX_TAUS];   /* intersection pixels with |dist_gt - dist_est| >= threshold t; entries >= T are 0 */
+  float   vsd[FP_VSD_MAX_TAUS];      /* (n_fail[t] + n_union - n_inter) / n_union, in double, rounded once; 1.0 when n_union == 0; entries >= T are NaN */
+  int32_t status, reserved;
+} fp_pose_vsd_t; /* (C keeps typedef names and functions in one name space: the record is `struct fp_pose_vsd` or fp_pose_vsd_t) */
+int fp_pose_vsd(fp_model *m, const char *target_name, const float *est_poses, int N,
+                const float *gt_poses, int n_gt /* 1 or N */, float delta_m,
+                const float *taus, int T, int flags, fp_pose_vsd_t *out /* host [N] */);
+
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 
 /* UploadDataToDevice + convert_depth_to_xyz_map (src/foundationpose.cpp:267-315, src/foundationpose_utils.cu:3-32). */

@@ -220,6 +220,18 @@ public:
                              adds ? FP_POSE_ERROR_ADDS : 0, out.data()));
   }
 
+  // visible surface discrepancy (foundationpose_amd.h "visible surface discrepancy"): BOP's VSD of `est` against `gt` (one pose per
+  // estimate, or ONE for all of them) on the uploaded frame's raw depth.  taus: up to FP_VSD_MAX_TAUS tolerances, fractions of the target's
+  // diameter when `normalized` (BOP19) and metres otherwise.  A pose that would need a clipper gets its status bit and vsd 1, not an error.
+  bool PoseVsd(const std::string &target_name, const std::vector<Pose> &est, const std::vector<Pose> &gt, std::vector<fp_pose_vsd_t> &out,
+               float delta_m = 0.015f, const std::vector<float> &taus = {0.05f, 0.10f, 0.15f, 0.20f, 0.25f, 0.30f, 0.35f, 0.40f, 0.45f, 0.50f},
+               bool normalized = true) {
+    out.resize(est.size());
+    return ok(fp_pose_vsd(h_, target_name.c_str(), est.empty() ? nullptr : est[0].data(), (int)est.size(), gt.empty() ? nullptr : gt[0].data(),
+                          (int)gt.size(), delta_m, taus.empty() ? nullptr : taus.data(), (int)taus.size(), normalized ? FP_VSD_NORMALIZED : 0,
+                          out.data()));
+  }
+
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
 
