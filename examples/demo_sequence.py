@@ -22,14 +22,16 @@ from foundationpose_cpp_amd.synthetic import to_colmajor  # noqa: E402
 
 
 def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, fit_mm=None, lost_below=0.5, depth_filter=False, render=False,
-        gt_poses=None):
+        gt_poses=None, refine_depth_mm=None):
     """fit_mm: pose-fit tolerance in millimetres (None = off: the log is the plain pose log).  With it every log line also carries
     n_model and the inlier / front / behind shares of the model, and LOST? when the inlier share is under lost_below.  Track's record
     describes the pose the frame STARTED from (the previous frame's answer) against this frame's depth.
     render: beside every <id>_plot.png also write <id>_render.png, the overlay of fp_render_pose at the frame's pose (a silhouette shows
     a rotation about the object's long axis that the 12-edge box cannot).
     gt_poses: ground truth per frame (centred-mesh -> camera): also write errors.txt -- frame id, ADD, ADD-S, MSSD in metres, MSPD in
-    pixels (fp_pose_errors, after the last frame: poses.txt and the plots do not change) -- and print the AUC of ADD and of ADD-S."""
+    pixels (fp_pose_errors, after the last frame: poses.txt and the plots do not change) -- and print the AUC of ADD and of ADD-S.
+    refine_depth_mm: gate in millimetres (None = off): every Track answer is also refined on the frame's depth (fp_refine_depth, 10
+    iterations) and refine.txt gets the frame id, the refined pose, n_used and rms_m; poses.txt and what Track starts from do not change."""
     seq = D.Sequence(data)
     mesh = load_mesh(name, seq.mesh_path())
     model = FoundationPose(mesh, seq.K, refiner, scorer, max_input_image_height=max(seq.H, 1080), max_input_image_width=max(seq.W, 1920))
@@ -39,6 +41,7 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
         model.set_depth_filter(True)
     os.makedirs(out, exist_ok=True)
     poses = []
+    refined_log = open(os.path.join(out, "refine.txt"), "w") if refine_depth_mm is not None else None
     with open(os.path.join(out, "poses.txt"), "w") as log:
         def emit(i, pose, rgb, depth, plot, fit=None):
             tail = ""
@@ -69,6 +72,11 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
                 raise SystemExit(model.last_error)
             emit(i, pose, rgb, depth, plots or i + 1 == len(seq), model.last_track_fit()[0] if fit_mm is not None and refine_itr >= 1 else None)
             poses.append(pose)
+            if refined_log is not None:
+                model.upload_frame(rgb, depth)      # (a Track from a host frame uploaded only its crop window)
+                better, (rec,) = model.refine_depth(name, pose, iterations=10, max_dist_m=refine_depth_mm * 1e-3)
+                refined_log.write(seq.ids[i] + "".join(" %.9g" % v for v in to_colmajor(better)[0]) + " n_used %d rms_m %.9g\n" % (rec.n_used, rec.rms_m))
+                print(f"{seq.ids[i]}: refined on the depth: n_used {rec.n_used}, rms {rec.rms_m * 1e3:.3f} mm after {rec.iterations} updates")
         if len(seq) > 1:
             print(f"tracked {len(seq) - 1} frames, {(len(seq) - 1) / (time.perf_counter() - t0):.1f} fps including PNG decode")
     if gt_poses is not None:
@@ -76,6 +84,8 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
         with open(os.path.join(out, "errors.txt"), "w") as f:
             f.writelines("%s %.9g %.9g %.9g %.9g\n" % (fid, e.add_m, e.adds_m, e.mssd_m, e.mspd_px) for fid, e in zip(seq.ids, errs))
         print(f"ADD AUC {auc([e.add_m for e in errs]):.4f}, ADD-S AUC {auc([e.adds_m for e in errs]):.4f} (thresholds 0 .. 0.1 m) over {len(errs)} frames")
+    if refined_log is not None:
+        refined_log.close()
     model.close()
     return np.stack(poses)
 
@@ -96,6 +106,8 @@ def main():
                     help="Register and Track read bilateral(erode(depth)) instead of the raw depth (FoundationPose as published); default off")
     ap.add_argument("--render", action="store_true",
                     help="beside every <id>_plot.png write <id>_render.png: the model at the frame's pose, its visible pixels flat-shaded over the frame; default off")
+    ap.add_argument("--refine-depth", type=float, nargs="?", const=20.0, default=None, metavar="GATE_MM",
+                    help="also refine every Track answer on the frame's depth (fp_refine_depth; gate in mm, default 20) and log n_used and rms_m to refine.txt; default off")
     ap.add_argument("--synthetic", type=int, metavar="N", help="write and use an N-frame synthetic sequence + synthetic weights")
     a = ap.parse_args()
     gts = None
@@ -107,7 +119,7 @@ def main():
         W.pack_synthetic("refiner", a.refiner)
         W.pack_synthetic("scorer", a.scorer)
         print("synthetic sequence:", a.data, "(synthetic weights: poses are not meaningful, only reproducible)")
-    run(a.data, a.refiner, a.scorer, a.out, a.name, a.refine_itr, a.plots, a.fit, a.lost_below, a.depth_filter, a.render, gts)
+    run(a.data, a.refiner, a.scorer, a.out, a.name, a.refine_itr, a.plots, a.fit, a.lost_below, a.depth_filter, a.render, gts, a.refine_depth)
     print("wrote", os.path.join(a.out, "poses.txt") + (" and errors.txt" if gts is not None else ""))
 
 

@@ -26,7 +26,7 @@ SYMBOLS = [
     "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
     "fp_set_depth_filter", "fp_get_depth_filter",
-    "fp_render_pose", "fp_render_scene", "fp_pose_errors", "fp_pose_vsd",
+    "fp_render_pose", "fp_render_scene", "fp_pose_errors", "fp_pose_vsd", "fp_refine_depth",
 ]
 
 
@@ -70,6 +70,14 @@ class FpPoseVsd(C.Structure):
     _fields_ = [("n_model_est", C.c_int32), ("n_model_gt", C.c_int32), ("n_visib_est", C.c_int32), ("n_visib_gt", C.c_int32),
                 ("n_inter", C.c_int32), ("n_union", C.c_int32), ("n_fail", C.c_int32 * FP_VSD_MAX_TAUS), ("vsd", C.c_float * FP_VSD_MAX_TAUS),
                 ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FpDepthRefine(C.Structure):
+    """struct fp_depth_refine of include/foundationpose_amd.h"""
+    _fields_ = [("n_model", C.c_int32), ("n_valid", C.c_int32), ("n_used", C.c_int32), ("n_front", C.c_int32), ("n_behind", C.c_int32),
+                ("n_grazing", C.c_int32), ("iterations", C.c_int32), ("rank", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
+                ("rms_m", C.c_float), ("cond", C.c_float), ("last_rot_rad", C.c_float), ("last_trans_m", C.c_float),
+                ("sums_q32", C.c_int64 * 28)]
 
 
 class FpMesh(C.Structure):
@@ -177,6 +185,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_render_scene": [vp, ci, vp, vp, cf, vp, vp, ci],
         "fp_pose_errors": [vp, cs, vp, ci, vp, ci, vp, ci, ci, ci, vp],
         "fp_pose_vsd": [vp, cs, vp, ci, vp, ci, cf, vp, ci, ci, vp],
+        "fp_refine_depth": [vp, cs, vp, ci, ci, cf, ci, vp, vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

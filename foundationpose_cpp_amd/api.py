@@ -118,6 +118,30 @@ def vsd_recall(records, thetas=BOP19_TAUS) -> float:
     return float(np.mean(v[:, :, None] < np.asarray(thetas, np.float64)[None, None, :]))
 
 
+FP_ICP_TRANSLATION_ONLY = 1
+FP_ICP_CONVERGED, FP_ICP_TOO_FEW, FP_ICP_REFUSED_NEAR, FP_ICP_REFUSED_RANGE = 1, 2, 4, 8
+
+
+@dataclasses.dataclass(frozen=True)
+class DepthRefine:
+    """struct fp_depth_refine (include/foundationpose_amd.h): how a pose returned by refine_depth fits the uploaded frame's depth, and how
+    its refinement went; pixel counts of the frame"""
+    n_model: int
+    n_valid: int          # model pixels with an observed depth: n_used + n_front + n_behind + n_grazing
+    n_used: int
+    n_front: int          # something observed more than the gate in front of the model (an occluder)
+    n_behind: int
+    n_grazing: int
+    iterations: int       # updates applied
+    rank: int             # directions the last solve moved along (0: none was made)
+    status: int           # FP_ICP_CONVERGED | FP_ICP_TOO_FEW | FP_ICP_REFUSED_NEAR | FP_ICP_REFUSED_RANGE
+    rms_m: float          # point-to-plane RMS over the used pixels at the returned pose
+    cond: float           # lambda_min / lambda_max of the last solve
+    last_rot_rad: float
+    last_trans_m: float
+    sums_q32: tuple       # 28 integers: upper triangle of sum J J^T, sum J e, sum e^2, each term scaled by 2^32
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -513,6 +537,21 @@ class FoundationPose:
         n = min(len(t), _lib.FP_VSD_MAX_TAUS)
         return [PoseVsd(r.n_model_est, r.n_model_gt, r.n_visib_est, r.n_visib_gt, r.n_inter, r.n_union, tuple(r.n_fail[:n]),
                         tuple(float(x) for x in r.vsd[:n]), r.status) for r in out[:len(e)]]
+
+    # ---- depth refinement (include/foundationpose_amd.h "depth refinement") --------------------------
+    def refine_depth(self, target_name: str, poses, iterations: int = 10, max_dist_m: float = 0.02, translation_only: bool = False):
+        """fp_refine_depth: projective point-to-plane ICP of poses [N,4,4] on the uploaded frame's raw depth -> (poses [N,4,4] f32,
+        [DepthRefine] * N).  max_dist_m: the gate along the ray, at most the target's diameter; translation_only: leave the rotation alone
+        (a symmetric object's rotation about its axis would follow the noise).  iterations = 0 only measures the fit.  A pose that would
+        need a clipper does not fail the call: it comes back unchanged with its status bit."""
+        e = to_colmajor(np.asarray(poses, np.float32).reshape(-1, 4, 4))
+        out_p = np.zeros_like(e)
+        out = (_lib.FpDepthRefine * max(len(e), 1))()
+        self._must(self._L.fp_refine_depth(self._h, target_name.encode(), _p(e), len(e), iterations, max_dist_m,
+                                           FP_ICP_TRANSLATION_ONLY if translation_only else 0, _p(out_p), out))
+        recs = [DepthRefine(r.n_model, r.n_valid, r.n_used, r.n_front, r.n_behind, r.n_grazing, r.iterations, r.rank, r.status, float(r.rms_m),
+                            float(r.cond), float(r.last_rot_rad), float(r.last_trans_m), tuple(r.sums_q32)) for r in out[:len(e)]]
+        return from_colmajor(out_p), recs
 
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):

@@ -199,9 +199,11 @@ const RoctxApi &roctx_api() {
 void roctx_push(const char *name) { if (roctx_api().push) (void)roctx_api().push(name); }
 void roctx_pop() { if (roctx_api().pop) (void)roctx_api().pop(); }
 #ifdef FP_TEST_HOOKS
+static int g_icp_chunk = 0;   // fpt_icp_set_chunk: poses per chunk of fp_refine_depth (0: sized by ICP_SCRATCH_BYTES); only the test build changes it
 static int g_vsd_chunk = 0;   // fpt_vsd_set_chunk: poses per chunk of fp_pose_vsd (0: sized by VSD_SCRATCH_BYTES); only the test build changes it
 static int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;   // A/B (fpt_set_calib_opts): steps of the 8-bit calibration
 #else
+static constexpr int g_icp_chunk = 0;
 static constexpr int g_vsd_chunk = 0;
 static constexpr int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;
 #endif
@@ -545,6 +547,19 @@ struct fp_model {
   std::vector<FramePose> vsd_poses_host;   // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
   std::vector<int2> vsd_items_host;
 
+  // depth refinement (fp_refine_depth): the same terms -- allocated at the first call, grow-only, read by no captured graph.
+  int4 *icp_snap = nullptr;                // [icp_vert_cap] snapped vertices of one chunk of poses [chunk, V]
+  float4 *icp_cam = nullptr;               // [icp_vert_cap] their camera-space copies
+  FramePose *icp_poses = nullptr;          // [icp_pose_cap] the poses of one evaluation pass
+  IcpParams *icp_params = nullptr;         // [icp_pose_cap]
+  unsigned long long *icp_acc = nullptr;   // [icp_acc_cap] accumulators [n, ICP_WORDS] | refusal words [n] (32-bit, behind the accumulators)
+  int2 *icp_items = nullptr;               // [icp_item_cap] the (pose, tile) work list of one pass
+  size_t icp_vert_cap = 0, icp_cam_cap = 0, icp_pose_cap = 0, icp_param_cap = 0, icp_acc_cap = 0, icp_item_cap = 0;
+  std::vector<FramePose> icp_poses_host;   // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
+  std::vector<IcpParams> icp_params_host;
+  std::vector<int2> icp_items_host;
+  std::vector<unsigned long long> icp_acc_host;
+
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
   // into a hipGraph and replayed.  The graph bakes buffer addresses, so it is keyed by g_alloc_epoch.
   // (Register's ~110 launches are replayed the same way: inter-kernel gaps are ~4 % of a 12 ms Register.)
@@ -841,6 +856,8 @@ extern "C" {
 #ifdef FP_TEST_HOOKS
 // fp_pose_vsd works through its poses in chunks of `poses` (0: the library's own size): a batch test of the chunk seams at small N
 void fpt_vsd_set_chunk(int poses) { g_vsd_chunk = poses > 0 ? poses : 0; }
+// the same for fp_refine_depth
+void fpt_icp_set_chunk(int poses) { g_icp_chunk = poses > 0 ? poses : 0; }
 void fpt_set_calib_opts(int sweeps, int tok, int out) { g_calib_sweeps = sweeps; g_calib_tok = tok; g_calib_out = out; }
 // A/B hook: hipGraph replay of the Track / Register bodies on or off for one model
 int fpt_model_use_graphs(fp_model *m, int on) {
@@ -1285,6 +1302,7 @@ static void destroy_model_impl(fp_model *m) {
   dev_free(m->sc_table); dev_free(m->sc_work); dev_free(m->sc_list);
   delete m->sc_table_host; m->sc_table_host = nullptr;
   dev_free(m->pe_mats); dev_free(m->pe_pairs); dev_free(m->pe_sums);
+  dev_free(m->icp_snap); dev_free(m->icp_cam); dev_free(m->icp_poses); dev_free(m->icp_params); dev_free(m->icp_acc); dev_free(m->icp_items);
   dev_free(m->vsd_snap); dev_free(m->vsd_poses); dev_free(m->vsd_words); dev_free(m->vsd_items); dev_free(m->vsd_plane);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
@@ -3003,6 +3021,265 @@ int fp_pose_vsd(fp_model *m, const char *target_name, const float *est_poses, in
     recs[(size_t)i] = r;
   }
   std::memcpy(out, recs.data(), recs.size() * sizeof(fp_pose_vsd_t));
+  return 0;
+} FP_CATCH_INT
+
+// ---- depth refinement
+namespace {
+// cyclic Jacobi eigen-decomposition of the symmetric n x n matrix a (row-major, n <= 6; destroyed): eigenvalues w, eigenvectors the
+// COLUMNS of v.  A rotation is skipped where the off-diagonal entry is exactly 0, so a block of zero rows and columns keeps its axes.
+void jacobi_eigen(int n, double *a, double *w, double *v) {
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) v[i * n + j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 64; sweep++) {
+    double off = 0, diag = 0;
+    for (int i = 0; i < n; i++) {
+      diag += a[i * n + i] * a[i * n + i];
+      for (int j = i + 1; j < n; j++) off += a[i * n + j] * a[i * n + j];
+    }
+    if (off <= 1e-32 * diag) break;
+    for (int p = 0; p < n; p++)
+      for (int q = p + 1; q < n; q++) {
+        const double apq = a[p * n + q];
+        if (apq == 0.0) continue;
+        const double theta = (a[q * n + q] - a[p * n + p]) / (2.0 * apq);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < n; k++) {
+          const double akp = a[k * n + p], akq = a[k * n + q];
+          a[k * n + p] = c * akp - s * akq; a[k * n + q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < n; k++) {
+          const double apk = a[p * n + k], aqk = a[q * n + k];
+          a[p * n + k] = c * apk - s * aqk; a[q * n + k] = s * apk + c * aqk;
+        }
+        a[p * n + q] = a[q * n + p] = 0.0;
+        for (int k = 0; k < n; k++) {
+          const double vkp = v[k * n + p], vkq = v[k * n + q];
+          v[k * n + p] = c * vkp - s * vkq; v[k * n + q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  for (int i = 0; i < n; i++) w[i] = a[i * n + i];
+}
+// A xi = b from a record's integer sums, xi = (omega, upsilon / rad); only eigen-directions with lambda >= FP_ICP_RANK_EPS * lambda_max move
+struct IcpSolve {
+  double xi[6];
+  int rank;
+  double cond;
+};
+IcpSolve icp_solve(const int64_t *sums, bool translation_only) {
+  double A[36], b[6];
+  int j = 0;
+  for (int r = 0; r < 6; r++)
+    for (int c = r; c < 6; c++) A[r * 6 + c] = A[c * 6 + r] = (double)sums[j++] / 4294967296.0;
+  for (int r = 0; r < 6; r++) b[r] = (double)sums[21 + r] / 4294967296.0;
+  const int n = translation_only ? 3 : 6, o = 6 - n;
+  double a[36], w[6], v[36];
+  for (int r = 0; r < n; r++)
+    for (int c = 0; c < n; c++) a[r * n + c] = A[(o + r) * 6 + (o + c)];
+  jacobi_eigen(n, a, w, v);
+  IcpSolve S = {};
+  double lmax = w[0], lmin = w[0];
+  for (int k = 1; k < n; k++) { lmax = std::max(lmax, w[k]); lmin = std::min(lmin, w[k]); }
+  if (!(lmax > 0.0)) return S;
+  S.cond = lmin / lmax;
+  for (int k = 0; k < n; k++) {
+    if (!(w[k] >= FP_ICP_RANK_EPS * lmax)) continue;
+    double dot = 0;
+    for (int r = 0; r < n; r++) dot += v[r * n + k] * b[o + r];
+    for (int r = 0; r < n; r++) S.xi[o + r] += dot / w[k] * v[r * n + k];
+    S.rank++;
+  }
+  return S;
+}
+// R <- exp(omega) R (Rodrigues), t <- t + upsilon; R row-major
+void icp_apply(double *R, double *t, const double *omega, const double *upsilon) {
+  const double x = omega[0], y = omega[1], z = omega[2];
+  const double th2 = x * x + y * y + z * z, th = std::sqrt(th2);
+  const double A = th < 1e-6 ? 1.0 - th2 / 6.0 : std::sin(th) / th, B = th < 1e-6 ? 0.5 - th2 / 24.0 : (1.0 - std::cos(th)) / th2;
+  const double K[9] = {0, -z, y, z, 0, -x, -y, x, 0};
+  double E[9], out[9];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) {
+      double k2 = 0;
+      for (int k = 0; k < 3; k++) k2 += K[r * 3 + k] * K[k * 3 + c];
+      E[r * 3 + c] = (r == c ? 1.0 : 0.0) + A * K[r * 3 + c] + B * k2;
+    }
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) out[r * 3 + c] = (E[r * 3] * R[c] + E[r * 3 + 1] * R[3 + c]) + E[r * 3 + 2] * R[6 + c];
+  if (th2 > 0.0)   // (exp(0) R is R itself, the sign of a zero entry included)
+    for (int k = 0; k < 9; k++) R[k] = out[k];
+  for (int k = 0; k < 3; k++)
+    if (upsilon[k] != 0.0) t[k] += upsilon[k];
+}
+struct IcpState {
+  double R[9], t[3], R_prev[9], t_prev[3];
+  FramePose P, P_prev;   // the f32 form the device sees
+  int state;             // 0 active, 1 one more evaluation (the record of a converged pose), 2 stopped
+  fp_depth_refine_t rec;
+};
+void icp_round(IcpState &s) {
+  for (int k = 0; k < 9; k++) s.P.r[k] = (float)s.R[k];
+  for (int k = 0; k < 3; k++) s.P.t[k] = (float)s.t[k];
+}
+}  // namespace
+static_assert(sizeof(fp_depth_refine_t) == 280, "fp_refine_depth: ten 32-bit words, four floats, 28 64-bit sums");
+static_assert(FP_ICP_MIN_COS == fp::ICP_MIN_COS && fp::ICP_SUMS == 28 && fp::ICP_COUNTS == 6, "include/foundationpose_amd.h: the constants of fp_refine_depth are those of fp_internal.h");
+static_assert(FP_ICP_REFUSED_NEAR == FRAME_RENDER_FLAG_NEAR << 2 && FP_ICP_REFUSED_RANGE == FRAME_RENDER_FLAG_RANGE << 2,
+              "include/foundationpose_amd.h: the refusal bits of fp_refine_depth are the refusal bits of the vertex rule");
+int fp_refine_depth(fp_model *m, const char *target_name, const float *poses, int N, int iterations, float max_dist_m, int flags, float *out_poses,
+                    fp_depth_refine_t *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && poses && out_poses && out, "[FoundationPose] fp_refine_depth: invalid arguments");
+  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fp_refine_depth: " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  FP_CHECK(iterations >= 0 && iterations <= FP_ICP_MAX_ITERATIONS,
+           "[FoundationPose] fp_refine_depth: " + std::to_string(iterations) + " iterations (0..FP_ICP_MAX_ITERATIONS = " + std::to_string(FP_ICP_MAX_ITERATIONS) + ")");
+  FP_CHECK(!(flags & ~FP_ICP_TRANSLATION_ONLY), "[FoundationPose] fp_refine_depth: unknown flag bits");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_refine_depth: a submitted Track has not been waited for (fp_track_wait)");
+  Target *t = m->find(target_name ? target_name : "");
+  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  const DeviceMesh &mesh = t->mesh;
+  FP_CHECK(std::isfinite(max_dist_m) && max_dist_m > 0.0f && max_dist_m <= mesh.diameter,
+           "[FoundationPose] fp_refine_depth: max_dist_m must be finite, > 0 and at most the target's diameter (metres)");
+  for (int i = 0; i < N; i++)
+    FP_CHECK(matrix_finite(poses + (size_t)i * 16), "[FoundationPose] fp_refine_depth: a non-finite entry in poses[" + std::to_string(i) + "]");
+  FP_CHECK(m->depth != nullptr && m->H > 0, "[FoundationPose] fp_refine_depth: no frame uploaded");
+  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  const int H = m->H, W = m->W, V = mesh.V;
+  FP_CHECK((long long)H * W < (1ll << 26), "[FoundationPose] fp_refine_depth: a frame of 2^26 pixels or more (the 64-bit sums could overflow)");
+  const int ntx = scene_tiles_x(W);
+  const long long F = std::max(mesh.F, 1);
+  std::vector<IcpState> st((size_t)N);
+  long long work = 0;
+  for (int i = 0; i < N; i++) {
+    IcpState &s = st[(size_t)i];
+    s.P = frame_pose(m, poses + (size_t)i * 16);
+    for (int k = 0; k < 9; k++) s.R[k] = s.P.r[k];
+    for (int k = 0; k < 3; k++) s.t[k] = s.P.t[k];
+    s.state = 0;
+    s.rec = fp_depth_refine_t{};
+    work += bound_tiles(frame_tile_bound(s.P, (double)mesh.max_norm, H, W)) * F * (iterations + 1);
+  }
+  FP_CHECK(work <= FP_ICP_MAX_WORK, "[FoundationPose] fp_refine_depth: " + std::to_string(N) + " poses of " + std::to_string(mesh.F) + " faces walk " + std::to_string(work) +
+               " faces over their 32 x 32 px tiles in " + std::to_string(iterations + 1) + " evaluations, above FP_ICP_MAX_WORK = " +
+               std::to_string((long long)FP_ICP_MAX_WORK) + ": pass fewer poses or iterations per call");
+  const float rad = mesh.diameter * 0.5f;
+  // chunks of poses: the snapped and camera-space vertices of a chunk stay below ICP_SCRATCH_BYTES, one pose at least
+  const size_t per_pose = (size_t)std::max(V, 1) * (sizeof(int4) + sizeof(float4));
+  int chunk = (int)std::min<size_t>(std::max<size_t>(ICP_SCRATCH_BYTES / per_pose, 1), (size_t)N);
+  if (g_icp_chunk > 0) chunk = std::min(g_icp_chunk, N);
+  const long long per_launch = std::max<long long>(FP_ICP_MAX_WORK / 10 / F, 1);   // items: no launch above a tenth of the cap
+  hipStream_t s = m->stream;
+  if (grow_scratch(s, m->icp_snap, m->icp_vert_cap, (size_t)V * chunk) || grow_scratch(s, m->icp_cam, m->icp_cam_cap, (size_t)V * chunk) ||
+      grow_scratch(s, m->icp_poses, m->icp_pose_cap, (size_t)N) || grow_scratch(s, m->icp_params, m->icp_param_cap, (size_t)N) ||
+      grow_scratch(s, m->icp_acc, m->icp_acc_cap, (size_t)N * ICP_WORDS + ((size_t)N + 1) / 2))
+    return 1;
+  std::vector<int> active;
+  for (int pass = 0; pass <= iterations; pass++) {
+    active.clear();
+    for (int i = 0; i < N; i++)
+      if (st[(size_t)i].state != 2) active.push_back(i);
+    if (active.empty()) break;
+    // ---- one evaluation of the active poses: vertex pass and tile kernel per chunk, one read-back, one synchronisation
+    const int n = (int)active.size();
+    const size_t acc_words = (size_t)n * ICP_WORDS + ((size_t)n + 1) / 2;
+    m->icp_poses_host.resize((size_t)n);
+    m->icp_params_host.resize((size_t)n);
+    m->icp_acc_host.assign(acc_words, 0ull);
+    std::vector<int2> &items = m->icp_items_host;
+    items.clear();
+    std::vector<size_t> chunk_end;   // items.size() after each chunk
+    for (int a = 0; a < n; a++) {
+      const IcpState &p = st[(size_t)active[(size_t)a]];
+      m->icp_poses_host[(size_t)a] = p.P;
+      IcpParams q = {};
+      q.fx = p.P.fx; q.fy = p.P.fy; q.cx = p.P.cx; q.cy = p.P.cy;
+      q.max_dist = max_dist_m; q.rad = rad;
+      for (int k = 0; k < 3; k++) q.t[k] = p.P.t[k];
+      m->icp_params_host[(size_t)a] = q;
+      const FrameTileBound b = frame_tile_bound(p.P, (double)mesh.max_norm, H, W);
+      if (!bound_empty(b))
+        for (int ty = b.ty0; ty <= b.ty1; ty++)
+          for (int tx = b.tx0; tx <= b.tx1; tx++) items.push_back(make_int2(a % chunk, ty * ntx + tx));
+      if ((a + 1) % chunk == 0 || a + 1 == n) chunk_end.push_back(items.size());
+    }
+    if (grow_scratch(s, m->icp_items, m->icp_item_cap, std::max<size_t>(items.size(), 1))) return 1;
+    unsigned long long *acc = m->icp_acc;
+    int *flag_d = reinterpret_cast<int *>(acc + (size_t)n * ICP_WORDS);
+    FP_HIP_OK(hipMemcpyAsync(m->icp_poses, m->icp_poses_host.data(), (size_t)n * sizeof(FramePose), hipMemcpyHostToDevice, s));
+    FP_HIP_OK(hipMemcpyAsync(m->icp_params, m->icp_params_host.data(), (size_t)n * sizeof(IcpParams), hipMemcpyHostToDevice, s));
+    if (!items.empty()) FP_HIP_OK(hipMemcpyAsync(m->icp_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    FP_HIP_OK(hipMemsetAsync(acc, 0, acc_words * sizeof(unsigned long long), s));   // accumulators and refusal words together
+    size_t first = 0;
+    for (size_t c = 0; c < chunk_end.size(); c++) {
+      const int a0 = (int)c * chunk, cn = std::min(chunk, n - a0);
+      {
+        ProfScope ps(&m->prof, s, "icp_vertex", 0, (double)cn * V * (12.0 + 32.0));
+        launch_icp_vertex(s, mesh, m->icp_poses + a0, cn, m->icp_snap, m->icp_cam, flag_d + a0);
+        FP_HIP_OK(hipGetLastError());
+      }
+      if (chunk_end[c] > first) {
+        ProfScope ps(&m->prof, s, "icp_tile", 0, (double)(chunk_end[c] - first) * (double)F * 60.0);
+        while (first < chunk_end[c]) {
+          const size_t cnt = std::min<size_t>(chunk_end[c] - first, (size_t)per_launch);
+          launch_icp_tiles(s, mesh, m->icp_snap, m->icp_cam, m->icp_items + first, (int)cnt, m->depth, H, W, m->icp_params, flag_d, a0, acc);
+          FP_HIP_OK(hipGetLastError());
+          first += cnt;
+        }
+      }
+    }
+    FP_HIP_OK(hipMemcpyAsync(m->icp_acc_host.data(), acc, acc_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    FP_HIP_OK(hipStreamSynchronize(s));
+    const int *flag_h = reinterpret_cast<const int *>(m->icp_acc_host.data() + (size_t)n * ICP_WORDS);
+    // ---- per pose: the record of this evaluation, then the update (or the reason to stop)
+    for (int a = 0; a < n; a++) {
+      IcpState &p = st[(size_t)active[(size_t)a]];
+      fp_depth_refine_t &r = p.rec;
+      if (flag_h[a]) {   // fp_render_pose would refuse: the input stays as it is, an updated pose goes back to what it was (and to that record)
+        r.status |= flag_h[a] << 2;
+        if (pass > 0) {
+          std::memcpy(p.R, p.R_prev, sizeof(p.R)); std::memcpy(p.t, p.t_prev, sizeof(p.t));
+          p.P = p.P_prev;
+          r.iterations--;
+        }
+        p.state = 2;
+        continue;
+      }
+      const unsigned long long *w = m->icp_acc_host.data() + (size_t)a * ICP_WORDS;
+      for (int k = 0; k < ICP_SUMS; k++) r.sums_q32[k] = (int64_t)w[k];
+      r.n_model = (int32_t)w[28]; r.n_valid = (int32_t)w[29]; r.n_used = (int32_t)w[30];
+      r.n_front = (int32_t)w[31]; r.n_behind = (int32_t)w[32]; r.n_grazing = (int32_t)w[33];
+      r.rms_m = r.n_used ? (float)(std::sqrt((double)r.sums_q32[27] / 4294967296.0 / (double)r.n_used) * (double)rad) : 0.0f;
+      if (p.state == 1 || pass == iterations) { p.state = 2; continue; }
+      if (r.n_used < FP_ICP_MIN_PIXELS) { r.status |= FP_ICP_TOO_FEW; p.state = 2; continue; }
+      const IcpSolve S = icp_solve(r.sums_q32, (flags & FP_ICP_TRANSLATION_ONLY) != 0);
+      const double ups[3] = {S.xi[3] * (double)rad, S.xi[4] * (double)rad, S.xi[5] * (double)rad};
+      const double rot = std::sqrt(S.xi[0] * S.xi[0] + S.xi[1] * S.xi[1] + S.xi[2] * S.xi[2]);
+      const double trans = std::sqrt(ups[0] * ups[0] + ups[1] * ups[1] + ups[2] * ups[2]);
+      r.rank = S.rank; r.cond = (float)S.cond; r.last_rot_rad = (float)rot; r.last_trans_m = (float)trans;
+      std::memcpy(p.R_prev, p.R, sizeof(p.R)); std::memcpy(p.t_prev, p.t, sizeof(p.t));
+      p.P_prev = p.P;
+      icp_apply(p.R, p.t, S.xi, ups);
+      icp_round(p);
+      r.iterations++;
+      if (rot < (double)FP_ICP_EPS_ROT_RAD && trans < (double)FP_ICP_EPS_TRANS_M) {
+        r.status |= FP_ICP_CONVERGED;
+        p.state = std::memcmp(&p.P, &p.P_prev, sizeof(FramePose)) == 0 ? 2 : 1;   // the same f32 pose: the record is already that of the returned pose
+      }
+    }
+  }
+  for (int i = 0; i < N; i++) {
+    const IcpState &p = st[(size_t)i];
+    const float *in = poses + (size_t)i * 16;
+    float *o = out_poses + (size_t)i * 16;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) o[c * 4 + r] = p.P.r[r * 3 + c];
+      o[12 + r] = p.P.t[r];
+    }
+    o[3] = in[3]; o[7] = in[7]; o[11] = in[11]; o[15] = in[15];
+    out[i] = p.rec;
+  }
   return 0;
 } FP_CATCH_INT
 

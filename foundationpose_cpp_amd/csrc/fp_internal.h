@@ -421,6 +421,26 @@ void launch_vsd_vertex(hipStream_t s, const DeviceMesh &m, const FramePose *pose
 void launch_vsd_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap_e, const int4 *snap_g, const float *plane_g, const int2 *items, int n_items,
                       const float *depth, int H, int W, const VsdParams &P, int pose0, int *counters);
 
+// projective ICP on the observed depth (fp_refine_depth; fp_pose_icp.hip).  The renderings follow section 4.8's
+// rules through fp_frame_rules.h; a pose's accumulator is ICP_WORDS 64-bit words: the 21 upper-triangle entries of sum J J^T (row-major),
+// the 6 of sum J e, sum e^2 -- each term llrintf(product * 2^32) -- then n_model, n_valid, n_used, n_front, n_behind, n_grazing.
+constexpr int ICP_SUMS = 28, ICP_COUNTS = 6, ICP_WORDS = ICP_SUMS + ICP_COUNTS;
+constexpr float ICP_MIN_COS = 0.2f;                 // = FP_ICP_MIN_COS
+constexpr size_t ICP_SCRATCH_BYTES = 128u << 20;    // snapped + camera-space vertices of one chunk of poses stay below this
+struct IcpParams {
+  float fx, fy, cx, cy;
+  float max_dist;   // the gate max_dist_m
+  float rad;        // diameter * 0.5f
+  float t[3];       // the pose's translation
+  float pad;
+};
+// pose p of the launch is poses[p]; snap, cam [n V] in frame_vertex_kernel's formats; pose p raises flags[p], which must be zero on entry
+void launch_icp_vertex(hipStream_t s, const DeviceMesh &m, const FramePose *poses, int n, int4 *snap, float4 *cam, int *flags);
+// items [n_items] = {pose of the chunk, tile}: acc[(pose0 + pose) ICP_WORDS ..] += the tile's sums and counts, under params[pose0 + pose];
+// an item whose flags[pose0 + pose] is not zero does nothing
+void launch_icp_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const int2 *items, int n_items, const float *depth,
+                      int H, int W, const IcpParams *params, const int *flags, int pose0, unsigned long long *acc);
+
 // host helpers (fp_host.cpp part of fp_api.hip)
 std::vector<float> make_rotation_grid(int min_views, int inplane_steps);
 

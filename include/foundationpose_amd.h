@@ -374,6 +374,60 @@ int fp_pose_vsd(fp_model *m, const char *target_name, const float *est_poses, in
                 const float *gt_poses, int n_gt /* 1 or N */, float delta_m,
                 const float *taus, int T, int flags, fp_pose_vsd_t *out /* host [N] */);
 
+/* ---- depth refinement: projective point-to-plane ICP of N poses on the uploaded frame's depth (new; the reference has no counterpart) ----
+ * fp_refine_depth improves N poses of one target from the depth the model already holds: each iteration renders every pose at frame
+ * resolution (so self-occlusion is exact), associates each model pixel with the observed depth at the same pixel, sums the 6 x 6
+ * point-to-plane normal system on the device in integers and solves it on the host in double.  Poses as in fp_pose_errors (column-major
+ * 4x4, centred-mesh -> camera); the frame is the uploaded one, read as the RAW depth whether fp_set_depth_filter is on or off; K is the
+ * model's.  DESIGN.md section 4.12 has the rules; in short, per pixel (c, r) of a pose with translation t:
+ *   z, triangle  exactly fp_render_pose's model_depth and tri_id; n^ the unit normal of the triangle's camera-space corners (fp_render_pose's
+ *                shading normal, divided by its length; a triangle without one is never used)
+ *   X = ((float)c - cx) / fx, Y = ((float)r - cy) / fy, l = sqrtf((X * X + Y * Y) + 1), s = (n^x * X + n^y * Y) + n^z, dz = D - z
+ *   valid    D >= 0.001f and finite;  front  dz * l < -max_dist_m (an occluder);  behind  dz * l > max_dist_m;
+ *   grazing  neither, and fabsf(s) / l < FP_ICP_MIN_COS;  used  otherwise
+ *   used:    rad = diameter * 0.5f, e = (dz * s) / rad, q = (D * X, D * Y, D), qc = (q - t) / rad, J = (qc x n^, n^)
+ *   the 28 products J_i J_j (i <= j), J_i e, e e are one f32 multiplication each and enter 64-bit sums as llrintf(v * 2^32)
+ * (every f32 operation separately rounded), so pose i's record and pose are byte-identical alone, in any batch and from call to call.
+ * Per iteration the host solves (sum J J^T) xi = sum J e, xi = (omega, upsilon / rad), by a Jacobi eigen-decomposition in double, moves
+ * only along eigen-directions with lambda >= FP_ICP_RANK_EPS * lambda_max, and applies R <- exp(omega) R, t <- t + upsilon (the twist
+ * about the object's origin).  FP_ICP_TRANSLATION_ONLY solves the 3 x 3 translation block alone (a symmetric object's rotation about
+ * its axis would follow the noise).  `iterations` = I allows at most I updates and I + 1 evaluations; I = 0 measures the fit only.
+ * A pose stops when its update is below both epsilons (FP_ICP_CONVERGED; the update is applied, and the pose is evaluated once more
+ * unless its f32 form did not change), when fewer than FP_ICP_MIN_PIXELS pixels are used (FP_ICP_TOO_FEW, no update), or when
+ * fp_render_pose would refuse the updated pose (the status bit; the pose before that update and its record are returned, `iterations`
+ * does not count it).  The record always describes the returned pose.
+ * A pose refused at the input does not fail the call: its output equals its input, its counts are 0, its status bit is set.
+ * Refused with an error before anything is launched and before the outputs are written: an unknown target, N outside 1..FP_MAX_BATCH,
+ * iterations outside 0..FP_ICP_MAX_ITERATIONS, max_dist_m not finite, <= 0 or above the target's diameter, unknown flag bits, a
+ * non-finite matrix entry, no frame, a partial frame, a frame of 2^26 pixels or more, a pending Track, and more than FP_ICP_MAX_WORK
+ * faces walked: (iterations + 1) times the sum over the input poses' (pose, 32 x 32 px tile) items of F.  No launch covers more than a
+ * tenth of it.  Works on geometry-only models; stream-ordered on the model's stream with one synchronisation per evaluation; Register,
+ * Track, their captured graphs and every existing kernel are untouched: the call's buffers are its own, grow-only. */
+#define FP_ICP_MAX_ITERATIONS 32
+#define FP_ICP_TRANSLATION_ONLY 1        /* flags: solve the 3 x 3 translation block only (symmetric objects) */
+#define FP_ICP_MIN_COS 0.2f              /* a pixel whose surface is seen at more than ~78 deg from its normal is not used */
+#define FP_ICP_MIN_PIXELS 32             /* fewer used pixels: the pose stops */
+#define FP_ICP_EPS_ROT_RAD 1e-5f
+#define FP_ICP_EPS_TRANS_M 1e-6f         /* an update below both: converged, the pose stops */
+#define FP_ICP_RANK_EPS 1e-8             /* an eigen-direction with lambda < eps * lambda_max is not moved along */
+#define FP_ICP_MAX_WORK 280000000000LL /* faces walked by one call: 0.99 s at the 2.84e11 faces/s measured for 252 poses */
+#define FP_ICP_CONVERGED 1               /* status bits of a record */
+#define FP_ICP_TOO_FEW 2
+#define FP_ICP_REFUSED_NEAR 4            /* fp_render_pose would refuse the pose (at the input, or after an update) */
+#define FP_ICP_REFUSED_RANGE 8
+typedef struct fp_depth_refine {
+  int32_t n_model, n_valid, n_used, n_front, n_behind, n_grazing;  /* frame pixels; n_valid == n_used + n_front + n_behind + n_grazing */
+  int32_t iterations;      /* updates applied to this pose */
+  int32_t rank;            /* directions kept by the last solve (0 when none was made) */
+  int32_t status, reserved;
+  float   rms_m;           /* sqrt(sum e^2 / n_used) * (diameter / 2) at the RETURNED pose; 0 when n_used == 0 */
+  float   cond;            /* lambda_min / lambda_max of the last solve (0 when none was made) */
+  float   last_rot_rad, last_trans_m;   /* size of the last solve's update */
+  int64_t sums_q32[28];    /* at the RETURNED pose: 21 upper-triangle entries of sum J J^T (row-major), 6 of sum J e, sum e^2 */
+} fp_depth_refine_t;
+int fp_refine_depth(fp_model *m, const char *target_name, const float *poses, int N, int iterations /* 0..32 */,
+                    float max_dist_m, int flags, float *out_poses /* host [N*16] */, fp_depth_refine_t *out /* host [N] */);
+
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 
 /* UploadDataToDevice + convert_depth_to_xyz_map (src/foundationpose.cpp:267-315, src/foundationpose_utils.cu:3-32). */

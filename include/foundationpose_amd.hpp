@@ -232,6 +232,18 @@ public:
                           out.data()));
   }
 
+  // depth refinement (foundationpose_amd.h "depth refinement"): projective point-to-plane ICP of `poses` on the uploaded frame's raw depth;
+  // `refined` gets the poses, `out` how each fits and how its refinement went.  max_dist_m: the gate along the ray, at most the target's
+  // diameter.  translation_only: leave the rotation alone (symmetric objects).  A pose that would need a clipper comes back unchanged
+  // with its status bit, not an error.
+  bool RefineDepth(const std::string &target_name, const std::vector<Pose> &poses, std::vector<Pose> &refined, std::vector<fp_depth_refine_t> &out,
+                   int iterations = 10, float max_dist_m = 0.02f, bool translation_only = false) {
+    refined.resize(poses.size());
+    out.resize(poses.size());
+    return ok(fp_refine_depth(h_, target_name.c_str(), poses.empty() ? nullptr : poses[0].data(), (int)poses.size(), iterations, max_dist_m,
+                              translation_only ? FP_ICP_TRANSLATION_ONLY : 0, refined.empty() ? nullptr : refined[0].data(), out.data()));
+  }
+
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
 
