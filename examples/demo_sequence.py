@@ -7,6 +7,8 @@
     python examples/demo_sequence.py --synthetic 8 --fit 5        # + pose-fit columns (tolerance 5 mm) and a LOST? marker per frame
     python examples/demo_sequence.py --synthetic 8 --depth-filter # the networks see bilateral(erode(depth)), like FoundationPose as published
     python examples/demo_sequence.py --synthetic 8 --render       # + <id>_render.png beside every box plot: the model's visible pixels, flat-shaded over the frame
+    python examples/demo_sequence.py --synthetic 8 --no-weights   # no networks: fp_register_depth on the first frame, fp_refine_depth from the previous
+                                                                  # answer on the others; with --synthetic the error against the scene's truth per frame
 """
 import argparse
 import os
@@ -90,6 +92,54 @@ def run(data, refiner, scorer, out, name="mustard", refine_itr=1, plots=False, f
     return np.stack(poses)
 
 
+def run_no_weights(data, out, name="mustard", plots=False, gt_poses=None, symmetries=None, gate_mm=20.0):
+    """The sequence on a geometry-only model (no weights are read): the first frame's pose comes from fp_register_depth (the hypothesis grid
+    ranked on the depth alone, the best candidates refined by ICP), every later frame's from fp_refine_depth started at the previous answer
+    (15 iterations, gate gate_mm).  poses.txt gets the frame id, the pose, n_used and rms_m of the fit.
+    gt_poses: ground truth per frame: every log line is followed on the console by the error against it, and errors.txt is written as by
+    run().  symmetries: [S,4,4] of the mesh frame; with them MSSD / MSPD, the rotation and the translation are those against the nearest
+    equivalent of the truth (the search cannot tell the equivalent poses of a symmetric object apart, and need not)."""
+    seq = D.Sequence(data)
+    mesh = load_mesh(name, seq.mesh_path())
+    model = FoundationPose(mesh, seq.K, max_input_image_height=max(seq.H, 1080), max_input_image_width=max(seq.W, 1920))
+    os.makedirs(out, exist_ok=True)
+    poses = []
+    with open(os.path.join(out, "poses.txt"), "w") as log:
+        def emit(i, pose, rgb, rec, plot, how):
+            log.write(seq.ids[i] + "".join(" %.9g" % v for v in to_colmajor(pose[None])[0]) + " n_used %d rms_m %.9g\n" % (rec.n_used, rec.rms_m))
+            line = f"{seq.ids[i]}: {how}: n_used {rec.n_used}, behind {rec.n_behind}, rms {rec.rms_m * 1e3:.3f} mm after {rec.iterations} updates"
+            if gt_poses is not None:
+                e = model.pose_errors(name, pose[None], gt_poses[i], symmetries=symmetries, adds=False)[0]
+                line += f"; against the truth: MSSD {e.mssd_m * 1e3:.3f} mm, {e.rot_deg:.3f} deg, {e.trans_m * 1e3:.3f} mm"
+            print(line)
+            if plot:
+                img = D.draw_bbox3d(rgb, seq.K, D.convert_pose_mesh2bbox(pose, mesh), mesh.dimension)
+                _lib.lib().fp_image_write_png_rgb(os.path.join(out, seq.ids[i] + "_plot.png").encode(), img.ctypes.data, seq.H, seq.W)
+        rgb, depth, mask = seq.frame(0, with_mask=True)
+        ok, pose, reg = model.register_depth(rgb, depth, mask, name)
+        if not ok:
+            raise SystemExit(model.last_error)
+        emit(0, pose, rgb, reg.refine, True, f"registered on the depth (hypothesis {reg.hypothesis} of {reg.n_hypotheses}, {reg.n_candidates} refined, rank_key {reg.rank_key})")
+        poses.append(pose)
+        t0 = time.perf_counter()
+        for i in range(1, len(seq)):
+            rgb, depth = seq.frame(i)
+            model.upload_frame(rgb, depth)
+            refined, (rec,) = model.refine_depth(name, pose, iterations=15, max_dist_m=gate_mm * 1e-3)
+            pose = refined[0]
+            emit(i, pose, rgb, rec, plots or i + 1 == len(seq), "refined on the depth")
+            poses.append(pose)
+        if len(seq) > 1:
+            print(f"followed {len(seq) - 1} frames, {(len(seq) - 1) / (time.perf_counter() - t0):.1f} fps including PNG decode")
+    if gt_poses is not None:
+        errs = model.pose_errors(name, np.stack(poses), np.stack(gt_poses), symmetries=symmetries)
+        with open(os.path.join(out, "errors.txt"), "w") as f:
+            f.writelines("%s %.9g %.9g %.9g %.9g\n" % (fid, e.add_m, e.adds_m, e.mssd_m, e.mspd_px) for fid, e in zip(seq.ids, errs))
+        print(f"ADD-S AUC {auc([e.adds_m for e in errs]):.4f} (thresholds 0 .. 0.1 m), worst MSSD {max(e.mssd_m for e in errs) * 1e3:.3f} mm over {len(errs)} frames")
+    model.close()
+    return np.stack(poses)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data")
@@ -108,8 +158,25 @@ def main():
                     help="beside every <id>_plot.png write <id>_render.png: the model at the frame's pose, its visible pixels flat-shaded over the frame; default off")
     ap.add_argument("--refine-depth", type=float, nargs="?", const=20.0, default=None, metavar="GATE_MM",
                     help="also refine every Track answer on the frame's depth (fp_refine_depth; gate in mm, default 20) and log n_used and rms_m to refine.txt; default off")
+    ap.add_argument("--no-weights", action="store_true",
+                    help="no networks: fp_register_depth on the first frame, then fp_refine_depth (15 iterations, gate 20 mm) per frame from the previous "
+                         "answer; takes --data / --synthetic, --out, --name and --plots only; default off")
     ap.add_argument("--synthetic", type=int, metavar="N", help="write and use an N-frame synthetic sequence + synthetic weights")
     a = ap.parse_args()
+    if a.no_weights:
+        for flag, given in (("--refiner", a.refiner), ("--scorer", a.scorer), ("--fit", a.fit is not None), ("--depth-filter", a.depth_filter),
+                            ("--render", a.render), ("--refine-depth", a.refine_depth is not None), ("--refine-itr", a.refine_itr != 1)):
+            if given:
+                ap.error(f"{flag} belongs to the modes that run the networks: --no-weights does not take it")
+        gts = syms = None
+        if a.synthetic:
+            a.data = os.path.join(tempfile.mkdtemp(), "synthetic0")
+            _, gts = D.write_synthetic_sequence(a.data, a.synthetic)
+            syms = np.stack([np.diag(np.array(d, np.float32)) for d in ((1, -1, -1, 1), (-1, 1, -1, 1), (-1, -1, 1, 1))])   # the ellipsoid's
+            print("synthetic sequence:", a.data, "(no weights: the poses are held to the scene's truth)")
+        run_no_weights(a.data, a.out, a.name, a.plots, gts, syms)
+        print("wrote", os.path.join(a.out, "poses.txt") + (" and errors.txt" if gts is not None else ""))
+        return
     gts = None
     if a.synthetic:
         d = tempfile.mkdtemp()

@@ -26,7 +26,7 @@ SYMBOLS = [
     "fp_set_pose_fit", "fp_get_pose_fit", "fp_last_track_fit", "fp_last_register_fit", "fp_pose_fit_eval",
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
     "fp_set_depth_filter", "fp_get_depth_filter",
-    "fp_render_pose", "fp_render_scene", "fp_pose_errors", "fp_pose_vsd", "fp_refine_depth",
+    "fp_render_pose", "fp_render_scene", "fp_pose_errors", "fp_pose_vsd", "fp_refine_depth", "fp_pose_search", "fp_register_depth",
 ]
 
 
@@ -78,6 +78,18 @@ class FpDepthRefine(C.Structure):
                 ("n_grazing", C.c_int32), ("iterations", C.c_int32), ("rank", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
                 ("rms_m", C.c_float), ("cond", C.c_float), ("last_rot_rad", C.c_float), ("last_trans_m", C.c_float),
                 ("sums_q32", C.c_int64 * 28)]
+
+
+class FpPoseSearch(C.Structure):
+    """struct fp_pose_search of include/foundationpose_amd.h"""
+    _fields_ = [("n_facing", C.c_int32), ("n_inlier", C.c_int32), ("n_front", C.c_int32), ("n_behind", C.c_int32), ("n_outside", C.c_int32),
+                ("n_missing", C.c_int32), ("score", C.c_int32), ("best_step", C.c_int32), ("n_points", C.c_int32), ("status", C.c_int32)]
+
+
+class FpDepthRegister(C.Structure):
+    """struct fp_depth_register of include/foundationpose_amd.h"""
+    _fields_ = [("hypothesis", C.c_int32), ("n_hypotheses", C.c_int32), ("n_candidates", C.c_int32), ("rank_key", C.c_int32),
+                ("search", FpPoseSearch), ("refine", FpDepthRefine)]
 
 
 class FpMesh(C.Structure):
@@ -186,6 +198,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_pose_errors": [vp, cs, vp, ci, vp, ci, vp, ci, ci, ci, vp],
         "fp_pose_vsd": [vp, cs, vp, ci, vp, ci, cf, vp, ci, ci, vp],
         "fp_refine_depth": [vp, cs, vp, ci, ci, cf, ci, vp, vp],
+        "fp_pose_search": [vp, cs, vp, ci, ci, cf, cf, ci, vp],
+        "fp_register_depth": [vp, vp, vp, vp, ci, ci, ci, cs, ci, cf, ci, vp, vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

@@ -142,6 +142,45 @@ class DepthRefine:
     sums_q32: tuple       # 28 integers: upper triangle of sum J J^T, sum J e, sum e^2, each term scaled by 2^32
 
 
+FP_SEARCH_REFUSED_NEAR = 1
+
+
+@dataclasses.dataclass(frozen=True)
+class PoseSearch:
+    """struct fp_pose_search (include/foundationpose_amd.h): how the sampled vertices of a pose meet the uploaded frame's depth at the
+    best of the pose's steps along the ray of its origin; point counts"""
+    n_facing: int         # n_inlier + n_front + n_behind + n_outside + n_missing
+    n_inlier: int
+    n_front: int          # something observed more than the tolerance in front of the point (an occluder)
+    n_behind: int         # the camera saw through where the pose claims a surface
+    n_outside: int
+    n_missing: int
+    score: int            # n_inlier - n_behind - n_outside
+    best_step: int        # -1: every step was refused
+    n_points: int
+    status: int           # FP_SEARCH_REFUSED_NEAR
+
+
+@dataclasses.dataclass(frozen=True)
+class DepthRegister:
+    """struct fp_depth_register (include/foundationpose_amd.h): how register_depth found its pose"""
+    hypothesis: int       # index into get_hyp_poses of the pose the answer started from
+    n_hypotheses: int
+    n_candidates: int
+    rank_key: int         # n_used - n_behind of the winner
+    search: PoseSearch
+    refine: DepthRefine
+
+
+def _pose_search(r):
+    return PoseSearch(r.n_facing, r.n_inlier, r.n_front, r.n_behind, r.n_outside, r.n_missing, r.score, r.best_step, r.n_points, r.status)
+
+
+def _depth_refine(r):
+    return DepthRefine(r.n_model, r.n_valid, r.n_used, r.n_front, r.n_behind, r.n_grazing, r.iterations, r.rank, r.status, float(r.rms_m),
+                       float(r.cond), float(r.last_rot_rad), float(r.last_trans_m), tuple(r.sums_q32))
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -549,9 +588,36 @@ class FoundationPose:
         out = (_lib.FpDepthRefine * max(len(e), 1))()
         self._must(self._L.fp_refine_depth(self._h, target_name.encode(), _p(e), len(e), iterations, max_dist_m,
                                            FP_ICP_TRANSLATION_ONLY if translation_only else 0, _p(out_p), out))
-        recs = [DepthRefine(r.n_model, r.n_valid, r.n_used, r.n_front, r.n_behind, r.n_grazing, r.iterations, r.rank, r.status, float(r.rms_m),
-                            float(r.cond), float(r.last_rot_rad), float(r.last_trans_m), tuple(r.sums_q32)) for r in out[:len(e)]]
-        return from_colmajor(out_p), recs
+        return from_colmajor(out_p), [_depth_refine(r) for r in out[:len(e)]]
+
+    # ---- depth search and the Register built on it (include/foundationpose_amd.h "depth search") ----
+    def pose_search(self, target_name: str, poses, n_steps: int = 9, step_m: float = None, tol_m: float = 0.005, vertex_step: int = 1):
+        """fp_pose_search: poses [N,4,4] against the uploaded frame's raw depth -> [PoseSearch] * N.  Every pose is tried at n_steps pushes
+        of step_m (default: the target's diameter / 16) along the ray of its origin; the record is that of its best step.  vertex_step:
+        every vertex_step-th vertex is used, at most FP_SEARCH_MAX_POINTS of them."""
+        e = to_colmajor(np.asarray(poses, np.float32).reshape(-1, 4, 4))
+        if step_m is None:
+            step_m = float(np.float32(self.meshes[target_name].diameter) / np.float32(16)) if target_name in self.meshes else 0.0
+        out = (_lib.FpPoseSearch * max(len(e), 1))()
+        self._must(self._L.fp_pose_search(self._h, target_name.encode(), _p(e), len(e), n_steps, step_m, tol_m, vertex_step, out))
+        return [_pose_search(r) for r in out[:len(e)]]
+
+    def register_depth(self, rgb, depth, mask, target_name: str, top_k: int = 16, tol_m: float = 0.005, icp_iterations: int = 15):
+        """fp_register_depth: Register without weights -> (ok, pose [4,4], DepthRegister).  The hypothesis grid (set_inplane_steps) is ranked
+        by pose_search on the depth alone, the top_k candidates are refined by refine_depth, and the one that explains most of the depth
+        wins.  The frame stays uploaded.  A symmetric object's answer is one of its equivalent poses."""
+        rgb, depth, mask = self._frame(rgb, depth, mask)
+        if rgb is None:
+            return False, None, None
+        self._frame_keep = (rgb, depth)
+        out = np.zeros(16, np.float32)
+        rec = _lib.FpDepthRegister()
+        ok = self._ok(self._L.fp_register_depth(self._h, _p(rgb), _p(depth), _p(mask), FP_HOST, depth.shape[0], depth.shape[1], target_name.encode(),
+                                                top_k, tol_m, icp_iterations, _p(out), C.byref(rec)))
+        if not ok:
+            return False, None, None
+        return True, from_colmajor(out), DepthRegister(rec.hypothesis, rec.n_hypotheses, rec.n_candidates, rec.rank_key, _pose_search(rec.search),
+                                                       _depth_refine(rec.refine))
 
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):

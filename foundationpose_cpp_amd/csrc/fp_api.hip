@@ -560,6 +560,13 @@ struct fp_model {
   std::vector<int2> icp_items_host;
   std::vector<unsigned long long> icp_acc_host;
 
+  // depth search (fp_pose_search): the same terms -- allocated at the first call, grow-only, read by no captured graph.
+  FramePose *ps_poses = nullptr;           // [ps_pose_cap] the poses of the call
+  SearchRec *ps_recs = nullptr;            // [ps_rec_cap] their records
+  size_t ps_pose_cap = 0, ps_rec_cap = 0;
+  std::vector<FramePose> ps_poses_host;    // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
+  std::vector<SearchRec> ps_recs_host;
+
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
   // into a hipGraph and replayed.  The graph bakes buffer addresses, so it is keyed by g_alloc_epoch.
   // (Register's ~110 launches are replayed the same way: inter-kernel gaps are ~4 % of a 12 ms Register.)
@@ -1302,6 +1309,7 @@ static void destroy_model_impl(fp_model *m) {
   dev_free(m->sc_table); dev_free(m->sc_work); dev_free(m->sc_list);
   delete m->sc_table_host; m->sc_table_host = nullptr;
   dev_free(m->pe_mats); dev_free(m->pe_pairs); dev_free(m->pe_sums);
+  dev_free(m->ps_poses); dev_free(m->ps_recs);
   dev_free(m->icp_snap); dev_free(m->icp_cam); dev_free(m->icp_poses); dev_free(m->icp_params); dev_free(m->icp_acc); dev_free(m->icp_items);
   dev_free(m->vsd_snap); dev_free(m->vsd_poses); dev_free(m->vsd_words); dev_free(m->vsd_items); dev_free(m->vsd_plane);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
@@ -3279,6 +3287,134 @@ int fp_refine_depth(fp_model *m, const char *target_name, const float *poses, in
     }
     o[3] = in[3]; o[7] = in[7]; o[11] = in[11]; o[15] = in[15];
     out[i] = p.rec;
+  }
+  return 0;
+} FP_CATCH_INT
+
+// ---- depth search and the Register built on it
+static_assert(sizeof(fp_pose_search_t) == sizeof(SearchRec) && sizeof(fp_pose_search_t) == 40, "fp_pose_search: a record is ten 32-bit words, the kernel's layout");
+static_assert(FP_SEARCH_MAX_POINTS == fp::SEARCH_MAX_POINTS && FP_SEARCH_MAX_STEPS == fp::SEARCH_MAX_STEPS && FP_SEARCH_REFUSED_NEAR == fp::SEARCH_STATUS_REFUSED_NEAR,
+              "include/foundationpose_amd.h: the constants of fp_pose_search are those of fp_internal.h");
+static_assert(sizeof(fp_depth_register_t) == 336, "fp_register_depth: four 32-bit words, a search record, a refine record");
+int fp_pose_search(fp_model *m, const char *target_name, const float *poses, int N, int n_steps, float step_m, float tol_m, int vertex_step,
+                   fp_pose_search_t *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && poses && out, "[FoundationPose] fp_pose_search: invalid arguments");
+  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fp_pose_search: " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  FP_CHECK(n_steps >= 1 && n_steps <= FP_SEARCH_MAX_STEPS,
+           "[FoundationPose] fp_pose_search: " + std::to_string(n_steps) + " steps (1..FP_SEARCH_MAX_STEPS = " + std::to_string(FP_SEARCH_MAX_STEPS) + ")");
+  FP_CHECK(std::isfinite(step_m) && step_m >= 0.0f, "[FoundationPose] fp_pose_search: step_m must be finite and >= 0 (metres)");
+  FP_CHECK(std::isfinite(tol_m) && tol_m > 0.0f, "[FoundationPose] fp_pose_search: tol_m must be finite and > 0 (metres)");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_pose_search: a submitted Track has not been waited for (fp_track_wait)");
+  Target *t = m->find(target_name ? target_name : "");
+  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  const DeviceMesh &mesh = t->mesh;
+  const int V = mesh.V;
+  const int fits = std::max((V + FP_SEARCH_MAX_POINTS - 1) / FP_SEARCH_MAX_POINTS, 1);   // the smallest step with P <= the cap
+  FP_CHECK(vertex_step >= 1, "[FoundationPose] fp_pose_search: vertex_step must be >= 1");
+  FP_CHECK(vertex_step >= fits, "[FoundationPose] fp_pose_search: vertex_step " + std::to_string(vertex_step) + " takes " +
+               std::to_string((V + (long long)vertex_step - 1) / vertex_step) + " of the target's " + std::to_string(V) + " vertices, above FP_SEARCH_MAX_POINTS = " +
+               std::to_string(FP_SEARCH_MAX_POINTS) + ": the smallest vertex_step that fits is " + std::to_string(fits));
+  for (int i = 0; i < N; i++) {
+    FP_CHECK(matrix_finite(poses + (size_t)i * 16), "[FoundationPose] fp_pose_search: a non-finite entry in poses[" + std::to_string(i) + "]");
+    FP_CHECK(poses[(size_t)i * 16 + 14] >= FP_RENDER_NEAR_M, "[FoundationPose] fp_pose_search: poses[" + std::to_string(i) +
+                 "] has its origin nearer than FP_RENDER_NEAR_M (0.01 m) to the camera plane, or behind it");
+  }
+  FP_CHECK(m->depth != nullptr && m->H > 0, "[FoundationPose] fp_pose_search: no frame uploaded");
+  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  SearchParams S = {};
+  S.H = m->H; S.W = m->W;
+  S.P = (int)((V + (long long)vertex_step - 1) / vertex_step); S.vertex_step = vertex_step;
+  S.n_steps = n_steps; S.step_m = step_m; S.tol_m = tol_m;
+  hipStream_t s = m->stream;
+  if (grow_scratch(s, m->ps_poses, m->ps_pose_cap, (size_t)N) || grow_scratch(s, m->ps_recs, m->ps_rec_cap, (size_t)N)) return 1;
+  m->ps_poses_host.resize((size_t)N);
+  m->ps_recs_host.resize((size_t)N);
+  for (int i = 0; i < N; i++) m->ps_poses_host[(size_t)i] = frame_pose(m, poses + (size_t)i * 16);
+  FP_HIP_OK(hipMemcpyAsync(m->ps_poses, m->ps_poses_host.data(), (size_t)N * sizeof(FramePose), hipMemcpyHostToDevice, s));
+  {
+    ProfScope ps(&m->prof, s, "pose_search", 0, (double)N * S.P * (24.0 + 4.0 * n_steps));
+    launch_pose_search(s, mesh, m->ps_poses, N, m->depth, S, m->ps_recs);
+    FP_HIP_OK(hipGetLastError());
+  }
+  FP_HIP_OK(hipMemcpyAsync(m->ps_recs_host.data(), m->ps_recs, (size_t)N * sizeof(SearchRec), hipMemcpyDeviceToHost, s));
+  FP_HIP_OK(hipStreamSynchronize(s));
+  std::memcpy(out, m->ps_recs_host.data(), (size_t)N * sizeof(SearchRec));
+  return 0;
+} FP_CATCH_INT
+
+int fp_register_depth(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H, int W, const char *target_name,
+                      int top_k, float tol_m, int icp_iterations, float out_pose[16], fp_depth_register_t *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  RoctxRange range("fp_register_depth (sampler + depth search + ICP)");
+  FP_CHECK(m && out_pose, "[FoundationPose] fp_register_depth: invalid arguments");
+  FP_CHECK(top_k >= 0 && top_k <= FP_REGISTER_DEPTH_MAX_TOP_K,
+           "[FoundationPose] fp_register_depth: top_k " + std::to_string(top_k) + " (0 = 16, at most " + std::to_string(FP_REGISTER_DEPTH_MAX_TOP_K) + ")");
+  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_register_depth: tol_m must be finite and >= 0 (metres; 0 = 0.005)");
+  FP_CHECK(icp_iterations >= 0 && icp_iterations <= FP_ICP_MAX_ITERATIONS,
+           "[FoundationPose] fp_register_depth: " + std::to_string(icp_iterations) + " iterations (0 = 15, at most FP_ICP_MAX_ITERATIONS = " + std::to_string(FP_ICP_MAX_ITERATIONS) + ")");
+  FP_CHECK(!m->track_pending, "[FoundationPose] fp_register_depth: a submitted Track has not been waited for (fp_track_wait)");
+  if (top_k == 0) top_k = 16;
+  if (tol_m == 0.0f) tol_m = 0.005f;
+  if (icp_iterations == 0) icp_iterations = 15;
+  Target *t = nullptr;
+  if (check_frame_args(m, H, W, target_name ? target_name : "", &t)) return 1;
+  FP_CHECK(mask != nullptr, "[FoundationPose] fp_register_depth needs a mask");
+  // 1. the frame and the sampler's poses, as fp_upload_frame + fp_get_hyp_poses leave them
+  const int N = m->n_hyp();
+  if (upload_frame_async(m, rgb, depth, memspace, H, W)) return 1;
+  if (sample_hypotheses_async(m, t, mask, memspace, 0, N)) { (void)hipStreamSynchronize(m->stream); return 1; }
+  if (sampler_status(m)) return 1;
+  std::vector<float> hyp((size_t)N * 16);
+  FP_HIP_OK(hipMemcpyAsync(hyp.data(), m->poses_dev, (size_t)N * 64, hipMemcpyDeviceToHost, m->stream));
+  FP_HIP_OK(hipStreamSynchronize(m->stream));
+  // 2. the search
+  const float diameter = t->mesh.diameter;
+  const int n_steps = 9;
+  const float step_m = diameter / 16.0f;
+  const int vertex_step = std::max((t->mesh.V + 1023) / 1024, 1);
+  std::vector<fp_pose_search_t> found((size_t)N);
+  if (fp_pose_search(m, target_name, hyp.data(), N, n_steps, step_m, tol_m, vertex_step, found.data())) return 1;
+  // 3. the candidates: by score, ties to the lower index; each at its best step
+  std::vector<int> order;
+  for (int i = 0; i < N; i++)
+    if (found[(size_t)i].status == 0) order.push_back(i);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return found[(size_t)a].score > found[(size_t)b].score; });
+  if ((int)order.size() > top_k) order.resize((size_t)top_k);
+  FP_CHECK(!order.empty(), "[FoundationPose] fp_register_depth: no candidate: the search refused every hypothesis (the object would lie nearer than FP_RENDER_NEAR_M)");
+  const int n_cand = (int)order.size();
+  std::vector<float> cand((size_t)n_cand * 16), refined((size_t)n_cand * 16);
+  for (int c = 0; c < n_cand; c++) {
+    const float *src = hyp.data() + (size_t)order[(size_t)c] * 16;
+    float *dst = cand.data() + (size_t)c * 16;
+    std::memcpy(dst, src, 64);
+    const float s_k = (float)found[(size_t)order[(size_t)c]].best_step * step_m;
+    const float tx = src[12], ty = src[13], tz = src[14];
+    dst[12] = tx + s_k * (tx / tz); dst[13] = ty + s_k * (ty / tz); dst[14] = tz + s_k;
+  }
+  // 4. the ICP
+  const float gate = std::min(4.0f * tol_m, diameter);
+  std::vector<fp_depth_refine_t> recs((size_t)n_cand);
+  if (fp_refine_depth(m, target_name, cand.data(), n_cand, icp_iterations, gate, 0, refined.data(), recs.data())) return 1;
+  // 5. the winner
+  int win = -1;
+  for (int c = 0; c < n_cand; c++) {
+    const fp_depth_refine_t &r = recs[(size_t)c];
+    if (r.status & (FP_ICP_REFUSED_NEAR | FP_ICP_REFUSED_RANGE | FP_ICP_TOO_FEW)) continue;
+    if (win < 0) { win = c; continue; }
+    const fp_depth_refine_t &w = recs[(size_t)win];
+    const int key = r.n_used - r.n_behind, wkey = w.n_used - w.n_behind;
+    if (key > wkey || (key == wkey && (r.sums_q32[27] < w.sums_q32[27] || (r.sums_q32[27] == w.sums_q32[27] && order[(size_t)c] < order[(size_t)win])))) win = c;
+  }
+  FP_CHECK(win >= 0, "[FoundationPose] fp_register_depth: no candidate is left: fp_refine_depth refused every one of the " + std::to_string(n_cand) +
+               " candidates or found too few pixels of the object in the depth");
+  std::memcpy(out_pose, refined.data() + (size_t)win * 16, 64);
+  if (out) {
+    out->hypothesis = order[(size_t)win];
+    out->n_hypotheses = N; out->n_candidates = n_cand;
+    out->rank_key = recs[(size_t)win].n_used - recs[(size_t)win].n_behind;
+    out->search = found[(size_t)order[(size_t)win]];
+    out->refine = recs[(size_t)win];
   }
   return 0;
 } FP_CATCH_INT

@@ -441,6 +441,27 @@ void launch_icp_vertex(hipStream_t s, const DeviceMesh &m, const FramePose *pose
 void launch_icp_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const int2 *items, int n_items, const float *depth,
                       int H, int W, const IcpParams *params, const int *flags, int pose0, unsigned long long *acc);
 
+// depth search (fp_pose_search; fp_pose_search.hip): per pose the sampled vertices and their normals against the
+// frame's raw depth at n_steps pushes along the ray of the pose's origin; a record is ten 32-bit words, fp_pose_search_t's layout.
+constexpr int SEARCH_THREADS = 256;
+constexpr int SEARCH_MAX_STEPS = 64;                // = FP_SEARCH_MAX_STEPS (one wave picks the best step)
+constexpr int SEARCH_MAX_POINTS = 4096;             // = FP_SEARCH_MAX_POINTS
+constexpr int SEARCH_CLASSES = 6;                   // n_facing, n_inlier, n_front, n_behind, n_outside, n_missing
+constexpr float SEARCH_MIN_COS2 = 0.04f;            // a point faces the camera when cos(normal, -ray) > 0.2, tested on squares
+constexpr int SEARCH_STATUS_REFUSED_NEAR = 1;       // = FP_SEARCH_REFUSED_NEAR
+struct SearchParams {
+  int H, W;
+  int P, vertex_step;   // points vertex_step * i, i < P = ceil(V / vertex_step)
+  int n_steps;
+  float step_m, tol_m;
+};
+struct SearchRec {
+  int32_t n[SEARCH_CLASSES];
+  int32_t score, best_step, n_points, status;
+};
+// pose p of the launch is poses[p] and writes out[p]; depth [H,W] is the raw depth
+void launch_pose_search(hipStream_t s, const DeviceMesh &m, const FramePose *poses, int n, const float *depth, const SearchParams &S, SearchRec *out);
+
 // host helpers (fp_host.cpp part of fp_api.hip)
 std::vector<float> make_rotation_grid(int min_views, int inplane_steps);
 

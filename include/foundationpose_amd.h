@@ -428,6 +428,71 @@ typedef struct fp_depth_refine {
 int fp_refine_depth(fp_model *m, const char *target_name, const float *poses, int N, int iterations /* 0..32 */,
                     float max_dist_m, int flags, float *out_poses /* host [N*16] */, fp_depth_refine_t *out /* host [N] */);
 
+/* ---- depth search: N poses ranked by the uploaded frame's depth alone (new; the reference has no counterpart) ----
+ * fp_pose_search tests N poses of one target against the depth the model already holds, each at n_steps pushes along the ray of its own
+ * origin, and returns per pose the counts at its best step.  Poses as in fp_pose_errors (column-major 4x4, centred-mesh -> camera); the
+ * frame is the uploaded one, read as the RAW depth whether fp_set_depth_filter is on or off; K is the model's.  DESIGN.md section 4.13
+ * has the rules; every f32 operation is separately rounded:
+ *   points   the centred vertices 0, vertex_step, 2 vertex_step, ... with their vertex normals as loaded (not renormalised):
+ *            P = ceil(V / vertex_step) <= FP_SEARCH_MAX_POINTS
+ *   step k   of pose (R, t), k = 0 .. n_steps - 1: s_k = (float)k * step_m, t_k = (t.x + s_k * (t.x / t.z), t.y + s_k * (t.y / t.z), t.z + s_k)
+ *   point    q = R p + t_k, n' = R n, each component ((r0 * x + r1 * y) + r2 * z) + t in that order.  q.z < FP_RENDER_NEAR_M for ANY point
+ *            refuses that (pose, step): it competes with no score
+ *   facing   a = -((n'.x * q.x + n'.y * q.y) + n'.z * q.z); a > 0 and a * a > 0.04f * ((q.x * q.x + q.y * q.y) + q.z * q.z).  Only facing
+ *            points are counted
+ *   pixel    uf = rintf(fx * (q.x / q.z) + cx), vf = rintf(fy * (q.y / q.z) + cy); outside unless 0 <= uf <= W - 1 and 0 <= vf <= H - 1,
+ *            compared as floats (a NaN or a huge value is outside; nothing is read out of bounds)
+ *   class    D the depth at (uf, vf): missing unless D >= 0.001f and finite; dz = D - q.z; inlier fabsf(dz) <= tol_m, front dz < -tol_m
+ *            (an occluder), behind dz > tol_m (the pose claims a surface where the camera saw through)
+ *   score    n_inlier - n_behind - n_outside; best_step is its arg-max over the steps that were not refused, the lowest step on ties
+ * Everything is an integer count, so pose i's record is byte-identical alone, in any batch and from call to call.  A pose whose steps
+ * were all refused does not fail the call: its counts and score are 0, best_step is -1, status is FP_SEARCH_REFUSED_NEAR.
+ * Refused with an error before anything is launched and before `out` is written: an unknown target, N outside 1..FP_MAX_BATCH, n_steps
+ * outside 1..FP_SEARCH_MAX_STEPS, step_m not finite or negative, tol_m not finite or <= 0, vertex_step < 1 or P above the cap (the message
+ * names the smallest step that fits), a non-finite matrix entry, t.z < FP_RENDER_NEAR_M, no frame, a partial frame, a pending Track.
+ * Works on geometry-only models; stream-ordered on the model's stream with one synchronisation at the end; Register, Track, their
+ * captured graphs and every existing kernel are untouched: the call's buffers are its own, grow-only. */
+#define FP_SEARCH_MAX_POINTS 4096
+#define FP_SEARCH_MAX_STEPS 64
+#define FP_SEARCH_REFUSED_NEAR 1         /* status: every step of the pose had a point nearer than FP_RENDER_NEAR_M */
+typedef struct fp_pose_search {
+  int32_t n_facing, n_inlier, n_front, n_behind, n_outside, n_missing; /* at best_step; n_facing == the sum of the other five */
+  int32_t score;       /* n_inlier - n_behind - n_outside at best_step */
+  int32_t best_step;   /* arg-max of score over the steps, lowest step on ties; -1 when every step was refused */
+  int32_t n_points;    /* P */
+  int32_t status;      /* FP_SEARCH_REFUSED_NEAR when every step was refused */
+} fp_pose_search_t;
+int fp_pose_search(fp_model *m, const char *target_name, const float *poses, int N,
+                   int n_steps, float step_m, float tol_m, int vertex_step,
+                   fp_pose_search_t *out /* host [N] */);
+
+/* ---- Register without weights: depth search over the hypothesis grid, then fp_refine_depth on the best candidates (new) ----
+ * fp_register_depth finds the pose of a target from the depth and the mask alone.  It composes calls of this header and gives, byte for
+ * byte, what they give when called one after the other:
+ *   1. the frame is uploaded as by fp_register_ex and the sampler runs on the mask: the N = fp_num_hypotheses() poses of
+ *      fp_get_hyp_poses (fp_set_inplane_steps sets the density).  The sampler's errors (empty mask, no valid depth) are this call's.
+ *   2. fp_pose_search over them: n_steps = 9, step_m = diameter / 16 (one f32 division), tol_m, the smallest vertex_step with P <= 1024
+ *   3. candidates: the top_k poses by score, ties to the lower hypothesis index, refused poses dropped; each moved to its best step's t_k
+ *   4. fp_refine_depth on the candidates: gate min(4 * tol_m, diameter), icp_iterations, no flags
+ *   5. the winner: among candidates without a REFUSED or TOO_FEW status bit the largest n_used - n_behind, ties to the smaller
+ *      sums_q32[27] (sum e^2), then to the lower hypothesis index.  No candidate left: the call fails and says so; out_pose is not written.
+ * top_k = 0 means 16 (at most 64), tol_m = 0 means 0.005, icp_iterations = 0 means 15 (at most FP_ICP_MAX_ITERATIONS).  The frame stays
+ * uploaded as after a Register, so fp_render_pose, fp_pose_vsd and fp_refine_depth can follow.  Works with NULL weights; takes the
+ * guards of the calls it composes; never touches the networks or a captured graph.  A symmetric object's answer is one of its
+ * equivalent poses. */
+#define FP_REGISTER_DEPTH_MAX_TOP_K 64
+typedef struct fp_depth_register {
+  int32_t hypothesis;        /* index into the fp_get_hyp_poses grid of the returned pose's start */
+  int32_t n_hypotheses, n_candidates;   /* searched; refined */
+  int32_t rank_key;          /* n_used - n_behind of the winner */
+  fp_pose_search_t search;   /* the winner's search record */
+  fp_depth_refine_t refine;  /* the winner's fp_refine_depth record */
+} fp_depth_register_t;
+int fp_register_depth(fp_model *m, const void *rgb, const void *depth, const void *mask, int memspace, int H, int W,
+                      const char *target_name, int top_k /* 0 = 16, at most 64 */, float tol_m /* 0 = 0.005 */,
+                      int icp_iterations /* 0 = 15, at most FP_ICP_MAX_ITERATIONS */,
+                      float out_pose[16], fp_depth_register_t *out /* may be NULL */);
+
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 
 /* UploadDataToDevice + convert_depth_to_xyz_map (src/foundationpose.cpp:267-315, src/foundationpose_utils.cu:3-32). */

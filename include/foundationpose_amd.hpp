@@ -244,6 +244,28 @@ public:
                               translation_only ? FP_ICP_TRANSLATION_ONLY : 0, refined.empty() ? nullptr : refined[0].data(), out.data()));
   }
 
+  // depth search (foundationpose_amd.h "depth search"): `poses` against the uploaded frame's raw depth, each at n_steps pushes of step_m
+  // along the ray of its origin; `out` gets the counts at every pose's best step.  vertex_step: every vertex_step-th vertex is used.
+  bool PoseSearch(const std::string &target_name, const std::vector<Pose> &poses, std::vector<fp_pose_search_t> &out, int n_steps, float step_m,
+                  float tol_m = 0.005f, int vertex_step = 1) {
+    out.resize(poses.size());
+    return ok(fp_pose_search(h_, target_name.c_str(), poses.empty() ? nullptr : poses[0].data(), (int)poses.size(), n_steps, step_m, tol_m, vertex_step,
+                             out.data()));
+  }
+
+  // Register without weights (foundationpose_amd.h "Register without weights"): the hypothesis grid ranked by PoseSearch on the depth
+  // alone, the top_k candidates refined by RefineDepth, the one that explains most of the depth wins.  0 for top_k, tol_m or
+  // icp_iterations means the default (16, 0.005 m, 15).  The frame stays uploaded; `record` may be null.
+  bool RegisterDepth(const ImageU8 &rgb, const ImageF32 &depth, const ImageU8 &mask, const std::string &target_name, Pose &out_pose_in_mesh,
+                     fp_depth_register_t *record = nullptr, int top_k = 0, float tol_m = 0.0f, int icp_iterations = 0) {
+    if (rgb.rows != depth.rows || rgb.cols != depth.cols || mask.rows != depth.rows || mask.cols != depth.cols) {
+      err_ = "[FoundationPose] Got rgb/depth/mask with different size!";
+      return false;
+    }
+    return ok(fp_register_depth(h_, rgb.data, depth.data, mask.data, FP_HOST, depth.rows, depth.cols, target_name.c_str(), top_k, tol_m, icp_iterations,
+                                out_pose_in_mesh.data(), record));
+  }
+
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
 
