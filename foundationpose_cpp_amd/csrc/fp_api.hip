@@ -344,9 +344,9 @@ static void dev_free(T *&p) {
   if (p) (void)hipFree(p);
   p = nullptr;
 }
-// Device scratch of the stage operators (a model's fr_*, sc_*, pe_* blocks, used on stream s): grow-only, and nothing of the stream may
-// still read a block that is replaced.  No captured graph reads these blocks, so unlike ensure_capacity / ensure_window this leaves
-// the allocation epoch alone.
+// Device scratch of the stage operators (a model's st_*, fr_*, sc_*, pe_*, vsd_*, icp_*, ps_* blocks, used on stream s): grow-only,
+// and nothing of the stream may still read a block that is replaced.  No captured graph reads these blocks, so unlike
+// ensure_capacity / ensure_window this leaves the allocation epoch alone.
 template <typename T>
 static int grow_scratch(hipStream_t s, T *&p, size_t &cap, size_t need) {
   if (need <= cap) return 0;
@@ -355,6 +355,29 @@ static int grow_scratch(hipStream_t s, T *&p, size_t &cap, size_t need) {
   cap = 0;
   if (dev_alloc(&p, need)) return 1;
   cap = need;
+  return 0;
+}
+// Two host steps of the stage operators (the others stand next to render_preconditions below; templates cannot, inside extern "C").
+// A column-major 4 x 4 matrix as the linear part ROW-major and the translation, in the caller's number type: the one loop behind
+// frame_pose (f32, what the kernels read) and rigid_from_colmajor (double, fp_pose_errors' host algebra).
+template <typename T>
+static void rigid_parts(const float *p, T *r, T *t) {
+  for (int i = 0; i < 3; i++) {
+    for (int c = 0; c < 3; c++) r[i * 3 + c] = (T)p[c * 4 + i];
+    t[i] = (T)p[12 + i];
+  }
+}
+// The (pose, tile) items of fp_pose_vsd and fp_refine_depth: launch(first, count) over the items [first, end) in runs of at most
+// work_cap / 10 / walk items (walk: the faces an item walks), one at least: no launch above a tenth of the call's work cap.  The
+// counters are integer atomics indexed by pose, so where a run is cut changes no result.
+template <typename Launch>
+static int launch_item_runs(size_t first, size_t end, long long work_cap, long long walk, Launch launch) {
+  const size_t per_launch = (size_t)std::max<long long>(work_cap / 10 / walk, 1);
+  while (first < end) {
+    const size_t cnt = std::min(end - first, per_launch);
+    if (launch(first, (int)cnt)) return 1;
+    first += cnt;
+  }
   return 0;
 }
 // pinned host memory and the device's address of it; a block whose device address cannot be had is freed again (*host stays as it was)
@@ -513,23 +536,33 @@ struct fp_model {
   // record.  No buffer of its own: Register's sampler leaves the whole frame's D' there anyway, Track fills its window of it.
   bool dfilt_on = false;
 
-  // frame-resolution rendering (fp_render_pose, DESIGN.md section 4.8, and fp_render_scene, section 4.9).  Nothing below is allocated
-  // before the first call; no captured graph reads any of it, so growing it (grow_scratch) never touches the allocation epoch.  The two
-  // calls share fr_snap / fr_cam / fr_out: both hold the SerialGuard and leave the stream synchronised, so they never overlap.
-  int4 *fr_snap = nullptr;      // [fr_vert_cap] {xi, yi, bits(z), 0}: the mesh's vertices, or all objects' of a scene
-  float4 *fr_cam = nullptr;     // [fr_vert_cap] camera-space vertices
+  // Scratch of the stage operators (DESIGN.md sections 4.8 - 4.13: fp_render_pose, fp_render_scene, fp_pose_errors, fp_pose_vsd,
+  // fp_refine_depth, fp_pose_search).  Nothing below is allocated before the first call that needs it, and every block only grows
+  // (grow_scratch).  One rule makes all of it safe, and lets the calls share the st_* blocks: every one of these calls holds the
+  // SerialGuard from its first line to its last and leaves the stream synchronised, so no two of them are ever live together
+  // (fp_register_depth runs the search and then the ICP, each to its end); and no captured graph reads any of these blocks, so
+  // growing one never touches the allocation epoch.
+  int4 *st_snap = nullptr;                 // [st_snap_cap] {xi, yi, bits(z), 0}: the vertices of one mesh under one pose or a chunk of poses (VSD: estimates | truths), or all objects' of a scene
+  float4 *st_cam = nullptr;                // [st_cam_cap] their camera-space copies, for the calls that shade or need normals
+  FramePose *st_poses = nullptr;           // [st_pose_cap] the poses of a call (VSD: estimates [N] | truths [n_gt]; ICP: of one evaluation pass)
+  int2 *st_items = nullptr;                // [st_item_cap] the (pose of the chunk, tile) work list of a chunk (VSD) or a pass (ICP)
+  size_t st_snap_cap = 0, st_cam_cap = 0, st_pose_cap = 0, st_item_cap = 0;
+  std::vector<FramePose> st_poses_host;    // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
+  std::vector<int2> st_items_host;
+
+  // what only the frame-resolution renderers need (sections 4.8 and 4.9, which share fr_out)
   int *fr_flag = nullptr;       // fp_render_pose's refusal word
   uint8_t *fr_out = nullptr;    // [fr_out_bytes] FP_HOST outputs are rendered here first: the call's wanted planes, each 256-byte aligned
-  size_t fr_vert_cap = 0, fr_out_bytes = 0;
+  size_t fr_out_bytes = 0;
 
-  // what only fp_render_scene needs: the same terms -- allocated at the first call, grow-only, read by no captured graph.
+  // what only fp_render_scene needs
   SceneTable *sc_table = nullptr;          // device copy of sc_table_host
   SceneTable *sc_table_host = nullptr;     // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
   int *sc_work = nullptr;                  // [sc_work_cap] flags | total | counters | tile counts | offsets | cursors (scene_work_words)
   unsigned *sc_list = nullptr;             // [sc_list_cap] the tiles' triangle lists
   size_t sc_work_cap = 0, sc_list_cap = 0;
 
-  // pose errors (fp_pose_errors): the same terms -- allocated at the first call, grow-only, read by no captured graph.
+  // pose errors (fp_pose_errors)
   float *pe_mats = nullptr;                // [pe_mat_cap] floats: estimates [N, 12] | relative transforms [N, 12] | composites [N (S + 1), 12]
   PoseErrPair *pe_pairs = nullptr;         // [pe_pair_cap] the paired kernel's record per (pose, symmetry)
   unsigned long long *pe_sums = nullptr;   // [FP_MAX_BATCH] the nearest-neighbour kernel's sums
@@ -537,34 +570,21 @@ struct fp_model {
   std::vector<float> pe_mats_host;         // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
   std::vector<PoseErrPair> pe_pairs_host;
 
-  // visible surface discrepancy (fp_pose_vsd): the same terms -- allocated at the first call, grow-only, read by no captured graph.
-  int4 *vsd_snap = nullptr;                // [vsd_snap_cap] snapped vertices of one chunk of poses: estimates [chunk, V] | their truths [chunk, V], or the one truth [V]
-  FramePose *vsd_poses = nullptr;          // [vsd_pose_cap] estimates [N] | truths [n_gt]
+  // visible surface discrepancy (fp_pose_vsd): the blocks whose layout is the call's own
   int *vsd_words = nullptr;                // [vsd_word_cap] counters [N, VSD_WORDS] | refusal words of the estimates [N] | of the truths [n_gt]
-  int2 *vsd_items = nullptr;               // [vsd_item_cap] the (pose, tile) work list of one chunk
   float *vsd_plane = nullptr;              // [vsd_plane_cap] n_gt == 1: the one truth's model depth [H, W]
-  size_t vsd_snap_cap = 0, vsd_pose_cap = 0, vsd_word_cap = 0, vsd_item_cap = 0, vsd_plane_cap = 0;
-  std::vector<FramePose> vsd_poses_host;   // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
-  std::vector<int2> vsd_items_host;
+  size_t vsd_word_cap = 0, vsd_plane_cap = 0;
 
-  // depth refinement (fp_refine_depth): the same terms -- allocated at the first call, grow-only, read by no captured graph.
-  int4 *icp_snap = nullptr;                // [icp_vert_cap] snapped vertices of one chunk of poses [chunk, V]
-  float4 *icp_cam = nullptr;               // [icp_vert_cap] their camera-space copies
-  FramePose *icp_poses = nullptr;          // [icp_pose_cap] the poses of one evaluation pass
-  IcpParams *icp_params = nullptr;         // [icp_pose_cap]
+  // depth refinement (fp_refine_depth): likewise
+  IcpParams *icp_params = nullptr;         // [icp_param_cap] of the poses of one evaluation pass
   unsigned long long *icp_acc = nullptr;   // [icp_acc_cap] accumulators [n, ICP_WORDS] | refusal words [n] (32-bit, behind the accumulators)
-  int2 *icp_items = nullptr;               // [icp_item_cap] the (pose, tile) work list of one pass
-  size_t icp_vert_cap = 0, icp_cam_cap = 0, icp_pose_cap = 0, icp_param_cap = 0, icp_acc_cap = 0, icp_item_cap = 0;
-  std::vector<FramePose> icp_poses_host;   // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
-  std::vector<IcpParams> icp_params_host;
-  std::vector<int2> icp_items_host;
+  size_t icp_param_cap = 0, icp_acc_cap = 0;
+  std::vector<IcpParams> icp_params_host;  // (owned by the model, like st_poses_host)
   std::vector<unsigned long long> icp_acc_host;
 
-  // depth search (fp_pose_search): the same terms -- allocated at the first call, grow-only, read by no captured graph.
-  FramePose *ps_poses = nullptr;           // [ps_pose_cap] the poses of the call
-  SearchRec *ps_recs = nullptr;            // [ps_rec_cap] their records
-  size_t ps_pose_cap = 0, ps_rec_cap = 0;
-  std::vector<FramePose> ps_poses_host;    // (owned by the model: the source of an asynchronous copy must outlive the call's frame)
+  // depth search (fp_pose_search): likewise
+  SearchRec *ps_recs = nullptr;            // [ps_rec_cap] the records of the call's poses
+  size_t ps_rec_cap = 0;
   std::vector<SearchRec> ps_recs_host;
 
   // Track is launch-bound (~60 short kernels): after one eager call (allocations settle) the launch chain is captured
@@ -1305,13 +1325,12 @@ static void destroy_model_impl(fp_model *m) {
   dev_free(m->grid_dev); dev_free(m->samp_state); dev_free(m->samp_vals); dev_free(m->mask_dev);
   if (m->digests) (void)hipFree(m->digests);
   dev_free(m->fit_acc); dev_free(m->fit_rec);
-  dev_free(m->fr_snap); dev_free(m->fr_cam); dev_free(m->fr_flag); dev_free(m->fr_out);
+  dev_free(m->st_snap); dev_free(m->st_cam); dev_free(m->st_poses); dev_free(m->st_items);
+  dev_free(m->fr_flag); dev_free(m->fr_out);
   dev_free(m->sc_table); dev_free(m->sc_work); dev_free(m->sc_list);
   delete m->sc_table_host; m->sc_table_host = nullptr;
   dev_free(m->pe_mats); dev_free(m->pe_pairs); dev_free(m->pe_sums);
-  dev_free(m->ps_poses); dev_free(m->ps_recs);
-  dev_free(m->icp_snap); dev_free(m->icp_cam); dev_free(m->icp_poses); dev_free(m->icp_params); dev_free(m->icp_acc); dev_free(m->icp_items);
-  dev_free(m->vsd_snap); dev_free(m->vsd_poses); dev_free(m->vsd_words); dev_free(m->vsd_items); dev_free(m->vsd_plane);
+  dev_free(m->ps_recs); dev_free(m->icp_params); dev_free(m->icp_acc); dev_free(m->vsd_words); dev_free(m->vsd_plane);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
@@ -2515,13 +2534,12 @@ int fp_pose_fit_eval(fp_model *m, const char *target_name, const float *poses, i
   return 0;
 } FP_CATCH_INT
 
-// ---- frame-resolution rendering of one pose, and the host steps it shares with section 4.9 below
-static int grow_render_verts(fp_model *m, size_t verts) {   // fr_snap and fr_cam share one cap: it holds only while both blocks do
-  size_t snap_cap = m->fr_vert_cap, cam_cap = m->fr_vert_cap;
-  m->fr_vert_cap = 0;
-  if (grow_scratch(m->stream, m->fr_snap, snap_cap, verts) || grow_scratch(m->stream, m->fr_cam, cam_cap, verts)) return 1;
-  m->fr_vert_cap = snap_cap;
-  return 0;
+// ---- frame-resolution rendering of one pose, and the host steps the stage operators of sections 4.8 - 4.13 share
+// the shared stage scratch (fp_model::st_*) for this many vertices (snapped / camera-space), poses and work items; 0: not needed
+static int grow_stage(fp_model *m, size_t snap, size_t cam, size_t poses, size_t items) {
+  hipStream_t s = m->stream;
+  return grow_scratch(s, m->st_snap, m->st_snap_cap, snap) || grow_scratch(s, m->st_cam, m->st_cam_cap, cam) ||
+         grow_scratch(s, m->st_poses, m->st_pose_cap, poses) || grow_scratch(s, m->st_items, m->st_item_cap, items);
 }
 
 // An output plane of a frame-resolution render: the caller's pointer (null: not wanted) and its bytes per pixel.
@@ -2554,24 +2572,70 @@ static int download_planes(fp_model *m, const RenderPlane *pl, int n, size_t px,
   return 0;
 }
 
-// what both calls ask of their arguments and of the model's frame, after their own argument checks
+// (Two more shared steps are templates and stand above, next to grow_scratch, outside extern "C": rigid_parts and launch_item_runs.)
+// What the stage operators ask of their arguments and of the model, each check written once.  A call makes them in its own order,
+// between its own argument checks: the order decides which error a call with several faults reports.  fn: the call's name.
+static int batch_size_ok(const std::string &fn, int N) {
+  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] " + fn + ": " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  return 0;
+}
+static int no_pending_track(const fp_model *m, const std::string &fn) {
+  FP_CHECK(!m->track_pending, "[FoundationPose] " + fn + ": a submitted Track has not been waited for (fp_track_wait)");
+  return 0;
+}
+static int stage_target(fp_model *m, const std::string &fn, const char *target_name, Target **t) {   // no pending Track, then the target
+  if (no_pending_track(m, fn)) return 1;
+  *t = m->find(target_name ? target_name : "");
+  FP_CHECK(*t != nullptr, "[FoundationPose] unknown target_name");
+  return 0;
+}
+static int frame_ready(const fp_model *m, const std::string &fn, bool with_rgb) {   // a whole frame is on the device
+  FP_CHECK(m->depth != nullptr && (!with_rgb || m->rgb != nullptr) && m->H > 0, "[FoundationPose] " + fn + ": no frame uploaded");
+  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  return 0;
+}
+static bool matrix_finite(const float *p) {
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(p[k])) return false;
+  return true;
+}
+static int matrices_finite_ok(const std::string &fn, const char *name, const float *mats, int n) {   // the n matrices of the argument `name`
+  for (int i = 0; i < n; i++)
+    FP_CHECK(matrix_finite(mats + (size_t)i * 16), "[FoundationPose] " + fn + ": a non-finite entry in " + name + "[" + std::to_string(i) + "]");
+  return 0;
+}
+// what the two renderers ask of their arguments and of the model's frame, after their own argument checks
 static int render_preconditions(const fp_model *m, const std::string &fn, int memspace, bool any_output, float tol_m) {
   FP_CHECK(memspace == FP_HOST || memspace == FP_DEVICE, "[FoundationPose] " + fn + ": memspace must be FP_HOST or FP_DEVICE");
   FP_CHECK(any_output, "[FoundationPose] " + fn + ": no output requested");
   FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] " + fn + ": tol_m must be finite and >= 0 (metres)");
-  FP_CHECK(!m->track_pending, "[FoundationPose] " + fn + ": a submitted Track has not been waited for (fp_track_wait)");
-  FP_CHECK(m->depth != nullptr && m->rgb != nullptr && m->H > 0, "[FoundationPose] " + fn + ": no frame uploaded");
-  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
-  return 0;
+  return no_pending_track(m, fn) || frame_ready(m, fn, true);
 }
 static FramePose frame_pose(const fp_model *m, const float pose[16]) {   // pose: column-major 4 x 4
   FramePose P;
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) P.r[r * 3 + c] = pose[c * 4 + r];
-    P.t[r] = pose[12 + r];
-  }
+  rigid_parts(pose, P.r, P.t);
   P.fx = m->K[0]; P.cx = m->K[2]; P.fy = m->K[4]; P.cy = m->K[5];
   return P;
+}
+// The (pose, tile) work of fp_pose_vsd and fp_refine_depth.  Tiles of a bound:
+static bool bound_empty(const FrameTileBound &b) { return b.tx0 > b.tx1 || b.ty0 > b.ty1; }
+static long long bound_tiles(const FrameTileBound &b) { return bound_empty(b) ? 0 : (long long)(b.tx1 - b.tx0 + 1) * (b.ty1 - b.ty0 + 1); }
+static FrameTileBound bound_union(const FrameTileBound &a, const FrameTileBound &b) {
+  if (bound_empty(a)) return b;
+  if (bound_empty(b)) return a;
+  return {std::min(a.tx0, b.tx0), std::min(a.ty0, b.ty0), std::max(a.tx1, b.tx1), std::max(a.ty1, b.ty1)};
+}
+// poses per chunk: as many as keep bytes_per_pose of vertex scratch each below the budget, one at least, N at most; forced > 0 (the
+// test build's fpt_*_set_chunk) overrides the budget
+static int stage_chunk(size_t bytes_per_pose, size_t budget, int N, int forced) {
+  if (forced > 0) return std::min(forced, N);
+  return (int)std::min<size_t>(std::max<size_t>(budget / bytes_per_pose, 1), (size_t)N);
+}
+// one item {local_pose, tile} per tile of the bound, in a grid of ntx tiles per row
+static void append_tile_items(std::vector<int2> &items, int local_pose, const FrameTileBound &b, int ntx) {
+  if (bound_empty(b)) return;
+  for (int ty = b.ty0; ty <= b.ty1; ty++)
+    for (int tx = b.tx0; tx <= b.tx1; tx++) items.push_back(make_int2(local_pose, ty * ntx + tx));
 }
 // the vertex pass's refusal word: a pose that needs a clipper, or leaves the exact integer range, gives an error, not a picture
 static int pose_refused(int flag, const std::string &prefix) {
@@ -2591,14 +2655,14 @@ int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], f
   const int H = m->H, W = m->W;
   const size_t px = (size_t)H * W;
   hipStream_t s = m->stream;
-  if (grow_render_verts(m, (size_t)mesh.V)) return 1;
+  if (grow_stage(m, (size_t)mesh.V, (size_t)mesh.V, 0, 0)) return 1;
   if (!m->fr_flag && dev_alloc(&m->fr_flag, 1)) return 1;
   const FramePose P = frame_pose(m, pose);
   // (a) vertex pass + the refusal word
   FP_HIP_OK(hipMemsetAsync(m->fr_flag, 0, sizeof(int), s));
   {
     ProfScope ps(&m->prof, s, "frame_vertex", 0, (double)mesh.V * (12.0 + 32.0));
-    launch_frame_vertex(s, mesh, P, m->fr_snap, m->fr_cam, m->fr_flag);
+    launch_frame_vertex(s, mesh, P, m->st_snap, m->st_cam, m->fr_flag);
     FP_HIP_OK(hipGetLastError());
   }
   int flag = 0;
@@ -2614,7 +2678,7 @@ int fp_render_pose(fp_model *m, const char *target_name, const float pose[16], f
     const double wr = (o.depth ? 4.0 : 0.0) + (o.tri ? 4.0 : 0.0) + (o.overlay ? 3.0 : 0.0) + (o.mask ? 1.0 : 0.0) + (o.vis ? 1.0 : 0.0);
     const double rd = (o.overlay ? 3.0 : 0.0) + (o.vis || o.overlay ? 4.0 : 0.0);
     ProfScope ps(&m->prof, s, "frame_raster", 0, (double)px * (wr + rd));
-    launch_frame_raster(s, mesh, m->fr_snap, m->fr_cam, m->rgb, m->depth, H, W, bound, tol_m, o);
+    launch_frame_raster(s, mesh, m->st_snap, m->st_cam, m->rgb, m->depth, H, W, bound, tol_m, o);
     FP_HIP_OK(hipGetLastError());
   }
   if (memspace == FP_HOST && download_planes(m, pl, 5, px, dev)) return 1;
@@ -2658,7 +2722,7 @@ int fp_render_scene(fp_model *m, int K, const char *const *target_names, const f
   const int ntiles = scene_tiles_x(W) * scene_tiles_y(H);
   hipStream_t s = m->stream;
   if (!m->sc_table && dev_alloc(&m->sc_table, 1)) return 1;
-  if (grow_render_verts(m, (size_t)verts) || grow_scratch(s, m->sc_work, m->sc_work_cap, scene_work_words(H, W))) return 1;
+  if (grow_stage(m, (size_t)verts, (size_t)verts, 0, 0) || grow_scratch(s, m->sc_work, m->sc_work_cap, scene_work_words(H, W))) return 1;
   int *flags = m->sc_work + SCENE_WORK_FLAGS, *counters = m->sc_work + SCENE_WORK_COUNTERS;
   unsigned long long *total_dev = reinterpret_cast<unsigned long long *>(m->sc_work + SCENE_WORK_TOTAL);
   unsigned *count = reinterpret_cast<unsigned *>(m->sc_work + SCENE_WORK_COUNT), *offset = count + ntiles, *cursor = offset + ntiles + 1;
@@ -2667,12 +2731,12 @@ int fp_render_scene(fp_model *m, int K, const char *const *target_names, const f
   // (a) vertex pass, (b) binning: count + scan.  Then the call's one early read-back: the refusal words and the size of the lists.
   {
     ProfScope ps(&m->prof, s, "scene_vertex", 0, (double)verts * (12.0 + 32.0));
-    launch_scene_vertex(s, m->sc_table, (int)verts, m->fr_snap, m->fr_cam, flags);
+    launch_scene_vertex(s, m->sc_table, (int)verts, m->st_snap, m->st_cam, flags);
     FP_HIP_OK(hipGetLastError());
   }
   {
     ProfScope ps(&m->prof, s, "scene_bin", 0, (double)faces * (12.0 + 48.0));
-    launch_scene_bin_count(s, m->sc_table, (unsigned)faces, m->fr_snap, H, W, count, offset, cursor, total_dev);
+    launch_scene_bin_count(s, m->sc_table, (unsigned)faces, m->st_snap, H, W, count, offset, cursor, total_dev);
     FP_HIP_OK(hipGetLastError());
   }
   int early[SCENE_WORK_TOTAL + 2] = {0};
@@ -2694,14 +2758,14 @@ int fp_render_scene(fp_model *m, int K, const char *const *target_names, const f
                             dev[3], objects ? counters : nullptr};
   {
     ProfScope ps(&m->prof, s, "scene_bin", 0, (double)faces * (12.0 + 48.0) + (double)entries * 4.0);
-    launch_scene_bin_fill(s, m->sc_table, (unsigned)faces, m->fr_snap, H, W, cursor, m->sc_list);
+    launch_scene_bin_fill(s, m->sc_table, (unsigned)faces, m->st_snap, H, W, cursor, m->sc_list);
     FP_HIP_OK(hipGetLastError());
   }
   {
     const double wr = (o.depth ? 4.0 : 0.0) + (o.tri ? 4.0 : 0.0) + (o.cover ? 8.0 : 0.0) + (o.overlay ? 3.0 : 0.0) + (o.inst ? 1.0 : 0.0) + (o.vis ? 1.0 : 0.0);
     const double rd = (o.overlay ? 3.0 : 0.0) + (o.vis || o.overlay || o.counters ? 4.0 : 0.0);
     ProfScope ps(&m->prof, s, "scene_raster", 0, (double)px * (wr + rd) + (double)entries * 4.0);
-    launch_scene_raster(s, m->sc_table, m->fr_snap, m->fr_cam, offset, m->sc_list, m->rgb, m->depth, H, W, tol_m, o);
+    launch_scene_raster(s, m->sc_table, m->st_snap, m->st_cam, offset, m->sc_list, m->rgb, m->depth, H, W, tol_m, o);
     FP_HIP_OK(hipGetLastError());
   }
   if (memspace == FP_HOST && download_planes(m, pl, 6, px, dev)) return 1;
@@ -2727,10 +2791,7 @@ struct Rigid {   // host side, double: linear part ROW-major, then t
 };
 Rigid rigid_from_colmajor(const float *p) {
   Rigid x;
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) x.r[r * 3 + c] = (double)p[c * 4 + r];
-    x.t[r] = (double)p[12 + r];
-  }
+  rigid_parts(p, x.r, x.t);
   return x;
 }
 Rigid rigid_mul(const Rigid &a, const Rigid &b) {   // a b
@@ -2756,9 +2817,7 @@ void rigid_to_f32(const Rigid &x, float *o) {
 }
 // every entry finite, no translation component beyond +-1000 m
 bool pose_error_matrix_ok(const float *p) {
-  for (int k = 0; k < 16; k++)
-    if (!std::isfinite(p[k])) return false;
-  return std::fabs(p[12]) <= 1000.0f && std::fabs(p[13]) <= 1000.0f && std::fabs(p[14]) <= 1000.0f;
+  return matrix_finite(p) && std::fabs(p[12]) <= 1000.0f && std::fabs(p[13]) <= 1000.0f && std::fabs(p[14]) <= 1000.0f;
 }
 long long pose_error_vs(int V, long long step) { return ((long long)V + step - 1) / step; }
 bool pose_error_adds_fits(int N, int V, long long step) {
@@ -2772,15 +2831,14 @@ int fp_pose_errors(fp_model *m, const char *target_name, const float *est_poses,
                    const float *symmetries, int S, int vertex_step, int flags, fp_pose_error *out) try {
   SerialGuard serial(m ? m->device : -1);
   FP_CHECK(m && est_poses && gt_poses && out, "[FoundationPose] fp_pose_errors: invalid arguments");
-  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fp_pose_errors: " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  if (batch_size_ok("fp_pose_errors", N)) return 1;
   FP_CHECK(n_gt == 1 || n_gt == N, "[FoundationPose] fp_pose_errors: n_gt must be 1 or N");
   FP_CHECK(S >= 0 && S <= FP_MAX_SYMMETRIES, "[FoundationPose] fp_pose_errors: " + std::to_string(S) + " symmetries (0..FP_MAX_SYMMETRIES = " + std::to_string(FP_MAX_SYMMETRIES) + ")");
   FP_CHECK(S == 0 || symmetries, "[FoundationPose] fp_pose_errors: invalid arguments (S > 0 without symmetries)");
   FP_CHECK(vertex_step >= 1, "[FoundationPose] fp_pose_errors: vertex_step must be >= 1");
   FP_CHECK(!(flags & ~FP_POSE_ERROR_ADDS), "[FoundationPose] fp_pose_errors: unknown flag bits");
-  FP_CHECK(!m->track_pending, "[FoundationPose] fp_pose_errors: a submitted Track has not been waited for (fp_track_wait)");
-  Target *t = m->find(target_name ? target_name : "");
-  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  Target *t = nullptr;
+  if (stage_target(m, "fp_pose_errors", target_name, &t)) return 1;
   const char *bad = "a non-finite entry or a translation beyond +-1000 m in ";
   for (int i = 0; i < N; i++)
     FP_CHECK(pose_error_matrix_ok(est_poses + (size_t)i * 16), std::string("[FoundationPose] fp_pose_errors: ") + bad + "est_poses[" + std::to_string(i) + "]");
@@ -2886,20 +2944,6 @@ int fp_pose_errors(fp_model *m, const char *target_name, const float *est_poses,
 } FP_CATCH_INT
 
 // ---- visible surface discrepancy
-namespace {
-bool bound_empty(const FrameTileBound &b) { return b.tx0 > b.tx1 || b.ty0 > b.ty1; }
-long long bound_tiles(const FrameTileBound &b) { return bound_empty(b) ? 0 : (long long)(b.tx1 - b.tx0 + 1) * (b.ty1 - b.ty0 + 1); }
-FrameTileBound bound_union(const FrameTileBound &a, const FrameTileBound &b) {
-  if (bound_empty(a)) return b;
-  if (bound_empty(b)) return a;
-  return {std::min(a.tx0, b.tx0), std::min(a.ty0, b.ty0), std::max(a.tx1, b.tx1), std::max(a.ty1, b.ty1)};
-}
-bool matrix_finite(const float *p) {
-  for (int k = 0; k < 16; k++)
-    if (!std::isfinite(p[k])) return false;
-  return true;
-}
-}  // namespace
 static_assert(sizeof(fp_pose_vsd_t) == 160, "fp_pose_vsd: six counts, 16 counts, 16 floats, two 32-bit words");
 static_assert(FP_VSD_MAX_TAUS == fp::VSD_MAX_TAUS && 6 + FP_VSD_MAX_TAUS <= fp::VSD_WORDS, "include/foundationpose_amd.h: the thresholds of fp_pose_vsd are those of fp_internal.h");
 static_assert(FP_VSD_EST_REFUSED_NEAR == FRAME_RENDER_FLAG_NEAR && FP_VSD_EST_REFUSED_RANGE == FRAME_RENDER_FLAG_RANGE &&
@@ -2909,29 +2953,24 @@ int fp_pose_vsd(fp_model *m, const char *target_name, const float *est_poses, in
                 const float *taus, int T, int flags, fp_pose_vsd_t *out) try {
   SerialGuard serial(m ? m->device : -1);
   FP_CHECK(m && est_poses && gt_poses && taus && out, "[FoundationPose] fp_pose_vsd: invalid arguments");
-  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fp_pose_vsd: " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  if (batch_size_ok("fp_pose_vsd", N)) return 1;
   FP_CHECK(n_gt == 1 || n_gt == N, "[FoundationPose] fp_pose_vsd: n_gt must be 1 or N");
   FP_CHECK(T >= 1 && T <= FP_VSD_MAX_TAUS, "[FoundationPose] fp_pose_vsd: " + std::to_string(T) + " thresholds (1..FP_VSD_MAX_TAUS = " + std::to_string(FP_VSD_MAX_TAUS) + ")");
   FP_CHECK(std::isfinite(delta_m) && delta_m >= 0.0f, "[FoundationPose] fp_pose_vsd: delta_m must be finite and >= 0 (metres)");
   for (int t = 0; t < T; t++)
     FP_CHECK(std::isfinite(taus[t]) && taus[t] >= 0.0f, "[FoundationPose] fp_pose_vsd: taus[" + std::to_string(t) + "] must be finite and >= 0");
   FP_CHECK(!(flags & ~FP_VSD_NORMALIZED), "[FoundationPose] fp_pose_vsd: unknown flag bits");
-  FP_CHECK(!m->track_pending, "[FoundationPose] fp_pose_vsd: a submitted Track has not been waited for (fp_track_wait)");
-  Target *t = m->find(target_name ? target_name : "");
-  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
-  for (int i = 0; i < N; i++)
-    FP_CHECK(matrix_finite(est_poses + (size_t)i * 16), "[FoundationPose] fp_pose_vsd: a non-finite entry in est_poses[" + std::to_string(i) + "]");
-  for (int i = 0; i < n_gt; i++)
-    FP_CHECK(matrix_finite(gt_poses + (size_t)i * 16), "[FoundationPose] fp_pose_vsd: a non-finite entry in gt_poses[" + std::to_string(i) + "]");
-  FP_CHECK(m->depth != nullptr && m->H > 0, "[FoundationPose] fp_pose_vsd: no frame uploaded");
-  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  Target *t = nullptr;
+  if (stage_target(m, "fp_pose_vsd", target_name, &t) || matrices_finite_ok("fp_pose_vsd", "est_poses", est_poses, N) ||
+      matrices_finite_ok("fp_pose_vsd", "gt_poses", gt_poses, n_gt) || frame_ready(m, "fp_pose_vsd", false))
+    return 1;
   const DeviceMesh &mesh = t->mesh;
   const int H = m->H, W = m->W, V = mesh.V;
   const int ntx = scene_tiles_x(W);
   const bool paired = n_gt == N && N > 1;   // (N == 1: the one truth goes through the plane like any n_gt == 1 call; same pixels)
   // host: the poses in the kernels' form, every pose's tiles, the work they stand for
-  m->vsd_poses_host.resize((size_t)N + n_gt);
-  FramePose *est_h = m->vsd_poses_host.data(), *gt_h = est_h + N;
+  m->st_poses_host.resize((size_t)N + n_gt);
+  FramePose *est_h = m->st_poses_host.data(), *gt_h = est_h + N;
   for (int i = 0; i < N; i++) est_h[i] = frame_pose(m, est_poses + (size_t)i * 16);
   for (int i = 0; i < n_gt; i++) gt_h[i] = frame_pose(m, gt_poses + (size_t)i * 16);
   std::vector<FrameTileBound> bounds((size_t)N);
@@ -2951,28 +2990,25 @@ int fp_pose_vsd(fp_model *m, const char *target_name, const float *est_poses, in
   P.T = T;
   for (int k = 0; k < VSD_MAX_TAUS; k++) P.thr[k] = k >= T ? 0.0f : (flags & FP_VSD_NORMALIZED) ? taus[k] * mesh.diameter : taus[k];
   // chunks of poses: the snapped vertices of a chunk (and of its truths) stay below VSD_SCRATCH_BYTES, one pose at least
-  const size_t per_pose = (size_t)std::max(V, 1) * sizeof(int4) * (paired ? 2 : 1);
-  int chunk = (int)std::min<size_t>(std::max<size_t>(VSD_SCRATCH_BYTES / per_pose, 1), (size_t)N);
-  if (g_vsd_chunk > 0) chunk = std::min(g_vsd_chunk, N);
+  const int chunk = stage_chunk((size_t)std::max(V, 1) * sizeof(int4) * (paired ? 2 : 1), VSD_SCRATCH_BYTES, N, g_vsd_chunk);
   hipStream_t s = m->stream;
   const size_t n_words = (size_t)N * VSD_WORDS + N + n_gt;
-  if (grow_scratch(s, m->vsd_snap, m->vsd_snap_cap, (size_t)V * ((size_t)chunk * (paired ? 2 : 1) + (paired ? 0 : 1))) ||
-      grow_scratch(s, m->vsd_poses, m->vsd_pose_cap, (size_t)N + n_gt) || grow_scratch(s, m->vsd_words, m->vsd_word_cap, n_words) ||
-      (!paired && grow_scratch(s, m->vsd_plane, m->vsd_plane_cap, (size_t)H * W)))
+  if (grow_stage(m, (size_t)V * ((size_t)chunk * (paired ? 2 : 1) + (paired ? 0 : 1)), 0, (size_t)N + n_gt, 0) ||
+      grow_scratch(s, m->vsd_words, m->vsd_word_cap, n_words) || (!paired && grow_scratch(s, m->vsd_plane, m->vsd_plane_cap, (size_t)H * W)))
     return 1;
   int *counters = m->vsd_words, *flags_est = counters + (size_t)N * VSD_WORDS, *flags_gt = flags_est + N;
-  const FramePose *est_d = m->vsd_poses, *gt_d = est_d + N;
-  FP_HIP_OK(hipMemcpyAsync(m->vsd_poses, est_h, ((size_t)N + n_gt) * sizeof(FramePose), hipMemcpyHostToDevice, s));
+  const FramePose *est_d = m->st_poses, *gt_d = est_d + N;
+  FP_HIP_OK(hipMemcpyAsync(m->st_poses, est_h, ((size_t)N + n_gt) * sizeof(FramePose), hipMemcpyHostToDevice, s));
   FP_HIP_OK(hipMemsetAsync(m->vsd_words, 0, n_words * sizeof(int), s));   // counters and refusal words together
   std::vector<int> words(n_words, 0);
   const int *flag_e = words.data() + (size_t)N * VSD_WORDS, *flag_g = flag_e + N;
   for (int p0 = 0; p0 < N; p0 += chunk) {
     const int c = std::min(chunk, N - p0);
     const int c_gt = paired ? c : p0 == 0 ? 1 : 0;   // the chunk's own truths, or the one truth with the first chunk
-    int4 *snap_e = m->vsd_snap, *snap_g = snap_e + (size_t)c * V;
+    int4 *snap_e = m->st_snap, *snap_g = snap_e + (size_t)c * V;
     {
       ProfScope ps(&m->prof, s, "vsd_vertex", 0, (double)(c + c_gt) * V * (12.0 + 16.0));
-      launch_vsd_vertex(s, mesh, est_d + p0, c, paired ? gt_d + p0 : gt_d, c_gt, snap_e, flags_est + p0, paired ? flags_gt + p0 : flags_gt);
+      launch_pose_vertices(s, "vsd_vertex", mesh, est_d + p0, c, paired ? gt_d + p0 : gt_d, c_gt, snap_e, nullptr, flags_est + p0, paired ? flags_gt + p0 : flags_gt);
       FP_HIP_OK(hipGetLastError());
     }
     // the refusal words of this chunk decide its work list (everything the stream held before is finished after this)
@@ -2985,33 +3021,20 @@ int fp_pose_vsd(fp_model *m, const char *target_name, const float *est_poses, in
       launch_frame_raster(s, mesh, snap_g, nullptr, nullptr, m->depth, H, W, truth_bound, 0.0f, FrameRenderOut{m->vsd_plane, nullptr, nullptr, nullptr, nullptr});
       FP_HIP_OK(hipGetLastError());
     }
-    std::vector<int2> &items = m->vsd_items_host;
+    std::vector<int2> &items = m->st_items_host;
     items.clear();
-    std::vector<int> pose_end;   // items.size() after each pose of the chunk that has any
-    for (int l = 0; l < c; l++) {
-      const int i = p0 + l;
-      if (flag_e[i] || (paired && flag_g[i])) continue;
-      const FrameTileBound &b = bounds[(size_t)i];
-      if (bound_empty(b)) continue;
-      for (int ty = b.ty0; ty <= b.ty1; ty++)
-        for (int tx = b.tx0; tx <= b.tx1; tx++) items.push_back(make_int2(l, ty * ntx + tx));
-      pose_end.push_back((int)items.size());
-    }
+    for (int l = 0; l < c; l++)
+      if (!flag_e[p0 + l] && !(paired && flag_g[p0 + l])) append_tile_items(items, l, bounds[(size_t)(p0 + l)], ntx);
     if (items.empty()) continue;
-    if (grow_scratch(s, m->vsd_items, m->vsd_item_cap, items.size())) return 1;
-    FP_HIP_OK(hipMemcpyAsync(m->vsd_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-    // no launch above a tenth of the cap: whole poses per launch, one at least
-    const long long per_launch = std::max<long long>(FP_VSD_MAX_WORK / 10 / walk, 1);
+    if (grow_stage(m, 0, 0, 0, items.size())) return 1;
+    FP_HIP_OK(hipMemcpyAsync(m->st_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
     ProfScope ps(&m->prof, s, "vsd_tile", 0, (double)items.size() * (double)walk * 60.0);
-    int first = 0;
-    for (size_t k = 0; k < pose_end.size();) {
-      size_t last = k;
-      while (last + 1 < pose_end.size() && pose_end[last + 1] - first <= per_launch) last++;
-      launch_vsd_tiles(s, mesh, snap_e, paired ? snap_g : nullptr, m->vsd_plane, m->vsd_items + first, pose_end[last] - first, m->depth, H, W, P, p0, counters);
-      FP_HIP_OK(hipGetLastError());
-      first = pose_end[last];
-      k = last + 1;
-    }
+    if (launch_item_runs(0, items.size(), FP_VSD_MAX_WORK, walk, [&](size_t first, int cnt) {
+          launch_vsd_tiles(s, mesh, snap_e, paired ? snap_g : nullptr, m->vsd_plane, m->st_items + first, cnt, m->depth, H, W, P, p0, counters);
+          FP_HIP_OK(hipGetLastError());
+          return 0;
+        }))
+      return 1;
   }
   FP_HIP_OK(hipMemcpyAsync(words.data(), counters, (size_t)N * VSD_WORDS * sizeof(int), hipMemcpyDeviceToHost, s));
   FP_HIP_OK(hipStreamSynchronize(s));
@@ -3140,20 +3163,16 @@ int fp_refine_depth(fp_model *m, const char *target_name, const float *poses, in
                     fp_depth_refine_t *out) try {
   SerialGuard serial(m ? m->device : -1);
   FP_CHECK(m && poses && out_poses && out, "[FoundationPose] fp_refine_depth: invalid arguments");
-  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fp_refine_depth: " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  if (batch_size_ok("fp_refine_depth", N)) return 1;
   FP_CHECK(iterations >= 0 && iterations <= FP_ICP_MAX_ITERATIONS,
            "[FoundationPose] fp_refine_depth: " + std::to_string(iterations) + " iterations (0..FP_ICP_MAX_ITERATIONS = " + std::to_string(FP_ICP_MAX_ITERATIONS) + ")");
   FP_CHECK(!(flags & ~FP_ICP_TRANSLATION_ONLY), "[FoundationPose] fp_refine_depth: unknown flag bits");
-  FP_CHECK(!m->track_pending, "[FoundationPose] fp_refine_depth: a submitted Track has not been waited for (fp_track_wait)");
-  Target *t = m->find(target_name ? target_name : "");
-  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  Target *t = nullptr;
+  if (stage_target(m, "fp_refine_depth", target_name, &t)) return 1;
   const DeviceMesh &mesh = t->mesh;
   FP_CHECK(std::isfinite(max_dist_m) && max_dist_m > 0.0f && max_dist_m <= mesh.diameter,
            "[FoundationPose] fp_refine_depth: max_dist_m must be finite, > 0 and at most the target's diameter (metres)");
-  for (int i = 0; i < N; i++)
-    FP_CHECK(matrix_finite(poses + (size_t)i * 16), "[FoundationPose] fp_refine_depth: a non-finite entry in poses[" + std::to_string(i) + "]");
-  FP_CHECK(m->depth != nullptr && m->H > 0, "[FoundationPose] fp_refine_depth: no frame uploaded");
-  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  if (matrices_finite_ok("fp_refine_depth", "poses", poses, N) || frame_ready(m, "fp_refine_depth", false)) return 1;
   const int H = m->H, W = m->W, V = mesh.V;
   FP_CHECK((long long)H * W < (1ll << 26), "[FoundationPose] fp_refine_depth: a frame of 2^26 pixels or more (the 64-bit sums could overflow)");
   const int ntx = scene_tiles_x(W);
@@ -3174,13 +3193,9 @@ int fp_refine_depth(fp_model *m, const char *target_name, const float *poses, in
                std::to_string((long long)FP_ICP_MAX_WORK) + ": pass fewer poses or iterations per call");
   const float rad = mesh.diameter * 0.5f;
   // chunks of poses: the snapped and camera-space vertices of a chunk stay below ICP_SCRATCH_BYTES, one pose at least
-  const size_t per_pose = (size_t)std::max(V, 1) * (sizeof(int4) + sizeof(float4));
-  int chunk = (int)std::min<size_t>(std::max<size_t>(ICP_SCRATCH_BYTES / per_pose, 1), (size_t)N);
-  if (g_icp_chunk > 0) chunk = std::min(g_icp_chunk, N);
-  const long long per_launch = std::max<long long>(FP_ICP_MAX_WORK / 10 / F, 1);   // items: no launch above a tenth of the cap
+  const int chunk = stage_chunk((size_t)std::max(V, 1) * (sizeof(int4) + sizeof(float4)), ICP_SCRATCH_BYTES, N, g_icp_chunk);
   hipStream_t s = m->stream;
-  if (grow_scratch(s, m->icp_snap, m->icp_vert_cap, (size_t)V * chunk) || grow_scratch(s, m->icp_cam, m->icp_cam_cap, (size_t)V * chunk) ||
-      grow_scratch(s, m->icp_poses, m->icp_pose_cap, (size_t)N) || grow_scratch(s, m->icp_params, m->icp_param_cap, (size_t)N) ||
+  if (grow_stage(m, (size_t)V * chunk, (size_t)V * chunk, (size_t)N, 0) || grow_scratch(s, m->icp_params, m->icp_param_cap, (size_t)N) ||
       grow_scratch(s, m->icp_acc, m->icp_acc_cap, (size_t)N * ICP_WORDS + ((size_t)N + 1) / 2))
     return 1;
   std::vector<int> active;
@@ -3192,49 +3207,47 @@ int fp_refine_depth(fp_model *m, const char *target_name, const float *poses, in
     // ---- one evaluation of the active poses: vertex pass and tile kernel per chunk, one read-back, one synchronisation
     const int n = (int)active.size();
     const size_t acc_words = (size_t)n * ICP_WORDS + ((size_t)n + 1) / 2;
-    m->icp_poses_host.resize((size_t)n);
+    m->st_poses_host.resize((size_t)n);
     m->icp_params_host.resize((size_t)n);
     m->icp_acc_host.assign(acc_words, 0ull);
-    std::vector<int2> &items = m->icp_items_host;
+    std::vector<int2> &items = m->st_items_host;
     items.clear();
     std::vector<size_t> chunk_end;   // items.size() after each chunk
     for (int a = 0; a < n; a++) {
       const IcpState &p = st[(size_t)active[(size_t)a]];
-      m->icp_poses_host[(size_t)a] = p.P;
+      m->st_poses_host[(size_t)a] = p.P;
       IcpParams q = {};
       q.fx = p.P.fx; q.fy = p.P.fy; q.cx = p.P.cx; q.cy = p.P.cy;
       q.max_dist = max_dist_m; q.rad = rad;
       for (int k = 0; k < 3; k++) q.t[k] = p.P.t[k];
       m->icp_params_host[(size_t)a] = q;
-      const FrameTileBound b = frame_tile_bound(p.P, (double)mesh.max_norm, H, W);
-      if (!bound_empty(b))
-        for (int ty = b.ty0; ty <= b.ty1; ty++)
-          for (int tx = b.tx0; tx <= b.tx1; tx++) items.push_back(make_int2(a % chunk, ty * ntx + tx));
+      append_tile_items(items, a % chunk, frame_tile_bound(p.P, (double)mesh.max_norm, H, W), ntx);
       if ((a + 1) % chunk == 0 || a + 1 == n) chunk_end.push_back(items.size());
     }
-    if (grow_scratch(s, m->icp_items, m->icp_item_cap, std::max<size_t>(items.size(), 1))) return 1;
+    if (grow_stage(m, 0, 0, 0, items.size())) return 1;
     unsigned long long *acc = m->icp_acc;
     int *flag_d = reinterpret_cast<int *>(acc + (size_t)n * ICP_WORDS);
-    FP_HIP_OK(hipMemcpyAsync(m->icp_poses, m->icp_poses_host.data(), (size_t)n * sizeof(FramePose), hipMemcpyHostToDevice, s));
+    FP_HIP_OK(hipMemcpyAsync(m->st_poses, m->st_poses_host.data(), (size_t)n * sizeof(FramePose), hipMemcpyHostToDevice, s));
     FP_HIP_OK(hipMemcpyAsync(m->icp_params, m->icp_params_host.data(), (size_t)n * sizeof(IcpParams), hipMemcpyHostToDevice, s));
-    if (!items.empty()) FP_HIP_OK(hipMemcpyAsync(m->icp_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    if (!items.empty()) FP_HIP_OK(hipMemcpyAsync(m->st_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
     FP_HIP_OK(hipMemsetAsync(acc, 0, acc_words * sizeof(unsigned long long), s));   // accumulators and refusal words together
     size_t first = 0;
     for (size_t c = 0; c < chunk_end.size(); c++) {
       const int a0 = (int)c * chunk, cn = std::min(chunk, n - a0);
       {
         ProfScope ps(&m->prof, s, "icp_vertex", 0, (double)cn * V * (12.0 + 32.0));
-        launch_icp_vertex(s, mesh, m->icp_poses + a0, cn, m->icp_snap, m->icp_cam, flag_d + a0);
+        launch_pose_vertices(s, "icp_vertex", mesh, m->st_poses + a0, cn, nullptr, 0, m->st_snap, m->st_cam, flag_d + a0, nullptr);
         FP_HIP_OK(hipGetLastError());
       }
       if (chunk_end[c] > first) {
         ProfScope ps(&m->prof, s, "icp_tile", 0, (double)(chunk_end[c] - first) * (double)F * 60.0);
-        while (first < chunk_end[c]) {
-          const size_t cnt = std::min<size_t>(chunk_end[c] - first, (size_t)per_launch);
-          launch_icp_tiles(s, mesh, m->icp_snap, m->icp_cam, m->icp_items + first, (int)cnt, m->depth, H, W, m->icp_params, flag_d, a0, acc);
-          FP_HIP_OK(hipGetLastError());
-          first += cnt;
-        }
+        if (launch_item_runs(first, chunk_end[c], FP_ICP_MAX_WORK, F, [&](size_t at, int cnt) {
+              launch_icp_tiles(s, mesh, m->st_snap, m->st_cam, m->st_items + at, cnt, m->depth, H, W, m->icp_params, flag_d, a0, acc);
+              FP_HIP_OK(hipGetLastError());
+              return 0;
+            }))
+          return 1;
+        first = chunk_end[c];
       }
     }
     FP_HIP_OK(hipMemcpyAsync(m->icp_acc_host.data(), acc, acc_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -3300,14 +3313,13 @@ int fp_pose_search(fp_model *m, const char *target_name, const float *poses, int
                    fp_pose_search_t *out) try {
   SerialGuard serial(m ? m->device : -1);
   FP_CHECK(m && poses && out, "[FoundationPose] fp_pose_search: invalid arguments");
-  FP_CHECK(N >= 1 && N <= FP_MAX_BATCH, "[FoundationPose] fp_pose_search: " + std::to_string(N) + " poses (1..FP_MAX_BATCH = " + std::to_string(FP_MAX_BATCH) + ")");
+  if (batch_size_ok("fp_pose_search", N)) return 1;
   FP_CHECK(n_steps >= 1 && n_steps <= FP_SEARCH_MAX_STEPS,
            "[FoundationPose] fp_pose_search: " + std::to_string(n_steps) + " steps (1..FP_SEARCH_MAX_STEPS = " + std::to_string(FP_SEARCH_MAX_STEPS) + ")");
   FP_CHECK(std::isfinite(step_m) && step_m >= 0.0f, "[FoundationPose] fp_pose_search: step_m must be finite and >= 0 (metres)");
   FP_CHECK(std::isfinite(tol_m) && tol_m > 0.0f, "[FoundationPose] fp_pose_search: tol_m must be finite and > 0 (metres)");
-  FP_CHECK(!m->track_pending, "[FoundationPose] fp_pose_search: a submitted Track has not been waited for (fp_track_wait)");
-  Target *t = m->find(target_name ? target_name : "");
-  FP_CHECK(t != nullptr, "[FoundationPose] unknown target_name");
+  Target *t = nullptr;
+  if (stage_target(m, "fp_pose_search", target_name, &t)) return 1;
   const DeviceMesh &mesh = t->mesh;
   const int V = mesh.V;
   const int fits = std::max((V + FP_SEARCH_MAX_POINTS - 1) / FP_SEARCH_MAX_POINTS, 1);   // the smallest step with P <= the cap
@@ -3320,21 +3332,20 @@ int fp_pose_search(fp_model *m, const char *target_name, const float *poses, int
     FP_CHECK(poses[(size_t)i * 16 + 14] >= FP_RENDER_NEAR_M, "[FoundationPose] fp_pose_search: poses[" + std::to_string(i) +
                  "] has its origin nearer than FP_RENDER_NEAR_M (0.01 m) to the camera plane, or behind it");
   }
-  FP_CHECK(m->depth != nullptr && m->H > 0, "[FoundationPose] fp_pose_search: no frame uploaded");
-  FP_CHECK(!m->frame_partial, "[FoundationPose] the last call (Track from a host frame) uploaded only its crop window: call fp_upload_frame first");
+  if (frame_ready(m, "fp_pose_search", false)) return 1;
   SearchParams S = {};
   S.H = m->H; S.W = m->W;
   S.P = (int)((V + (long long)vertex_step - 1) / vertex_step); S.vertex_step = vertex_step;
   S.n_steps = n_steps; S.step_m = step_m; S.tol_m = tol_m;
   hipStream_t s = m->stream;
-  if (grow_scratch(s, m->ps_poses, m->ps_pose_cap, (size_t)N) || grow_scratch(s, m->ps_recs, m->ps_rec_cap, (size_t)N)) return 1;
-  m->ps_poses_host.resize((size_t)N);
+  if (grow_stage(m, 0, 0, (size_t)N, 0) || grow_scratch(s, m->ps_recs, m->ps_rec_cap, (size_t)N)) return 1;
+  m->st_poses_host.resize((size_t)N);
   m->ps_recs_host.resize((size_t)N);
-  for (int i = 0; i < N; i++) m->ps_poses_host[(size_t)i] = frame_pose(m, poses + (size_t)i * 16);
-  FP_HIP_OK(hipMemcpyAsync(m->ps_poses, m->ps_poses_host.data(), (size_t)N * sizeof(FramePose), hipMemcpyHostToDevice, s));
+  for (int i = 0; i < N; i++) m->st_poses_host[(size_t)i] = frame_pose(m, poses + (size_t)i * 16);
+  FP_HIP_OK(hipMemcpyAsync(m->st_poses, m->st_poses_host.data(), (size_t)N * sizeof(FramePose), hipMemcpyHostToDevice, s));
   {
     ProfScope ps(&m->prof, s, "pose_search", 0, (double)N * S.P * (24.0 + 4.0 * n_steps));
-    launch_pose_search(s, mesh, m->ps_poses, N, m->depth, S, m->ps_recs);
+    launch_pose_search(s, mesh, m->st_poses, N, m->depth, S, m->ps_recs);
     FP_HIP_OK(hipGetLastError());
   }
   FP_HIP_OK(hipMemcpyAsync(m->ps_recs_host.data(), m->ps_recs, (size_t)N * sizeof(SearchRec), hipMemcpyDeviceToHost, s));
@@ -3353,7 +3364,7 @@ int fp_register_depth(fp_model *m, const void *rgb, const void *depth, const voi
   FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_register_depth: tol_m must be finite and >= 0 (metres; 0 = 0.005)");
   FP_CHECK(icp_iterations >= 0 && icp_iterations <= FP_ICP_MAX_ITERATIONS,
            "[FoundationPose] fp_register_depth: " + std::to_string(icp_iterations) + " iterations (0 = 15, at most FP_ICP_MAX_ITERATIONS = " + std::to_string(FP_ICP_MAX_ITERATIONS) + ")");
-  FP_CHECK(!m->track_pending, "[FoundationPose] fp_register_depth: a submitted Track has not been waited for (fp_track_wait)");
+  if (no_pending_track(m, "fp_register_depth")) return 1;
   if (top_k == 0) top_k = 16;
   if (tol_m == 0.0f) tol_m = 0.005f;
   if (icp_iterations == 0) icp_iterations = 15;

@@ -11,53 +11,53 @@ namespace fp {
 
 namespace {
 
-constexpr unsigned long long FR_EMPTY = ~0ull;   // a z-buffer entry no triangle has reached: larger than every key
-
-// (a) vertex pass: the vertex rule per vertex; a refused vertex raises its bit of *flag.
+// (a) vertex pass: the vertex rule per vertex; a refused vertex raises its bit of its pose's word.  Two forms of one body
+// (frame_vertex_store): fp_render_pose's one pose arrives by value as a kernel argument, so that call uploads nothing; the batched form
+// takes its poses from device memory, pose p of the launch (blockIdx.y) being poses_a[p] for p < n_a and poses_b[p - n_a] beyond,
+// writes pose p's vertices at snap[p V ..] (cam likewise, null: not stored) and raises flags_a[p] or flags_b[p - n_a].
 __global__ __launch_bounds__(256) void frame_vertex_kernel(const float *__restrict__ verts, int V, FramePose P, int4 *__restrict__ snap,
                                                            float4 *__restrict__ cam, int *__restrict__ flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= V) return;
-  const int bad = frame_vertex_rule(verts, (size_t)i, P, snap[i], cam[i]);
-  if (bad) atomicOr(flag, bad);
+  frame_vertex_store(verts, i, P, snap + i, cam ? cam + i : nullptr, flag);
+}
+__global__ __launch_bounds__(256) void pose_vertex_kernel(const float *__restrict__ verts, int V, const FramePose *__restrict__ poses_a, int n_a,
+                                                          const FramePose *__restrict__ poses_b, int4 *__restrict__ snap, float4 *__restrict__ cam,
+                                                          int *__restrict__ flags_a, int *__restrict__ flags_b) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y;
+  if (i >= V) return;
+  const size_t at = (size_t)p * V + i;
+  frame_vertex_store(verts, i, p < n_a ? poses_a[p] : poses_b[p - n_a], snap + at, cam ? cam + at : nullptr, p < n_a ? flags_a + p : flags_b + (p - n_a));
 }
 
 // (b) raster + resolve: one workgroup per FRAME_RENDER_TILE x FRAME_RENDER_TILE pixel tile.  The tile's z-buffer is 64-bit keys
 // bits(z) << 32 | triangle in LDS (8 KB), resolved with ds_min_u64; the threads walk all triangles, reject by bounding box against the
-// tile and rasterise the rest.  After the barrier every requested output of the tile is written once.  Tiles outside
+// tile and rasterise the rest (frame_face_walk).  After the barrier every requested output of the tile is written once.  Tiles outside
 // [tx0, tx1] x [ty0, ty1] (the host's conservative screen bound of the object) skip the walk and write background.
 __global__ __launch_bounds__(FRAME_RENDER_THREADS) void frame_raster_kernel(const int32_t *__restrict__ faces, int F, int V,
                                                                             const int4 *__restrict__ snap, const float4 *__restrict__ cam,
                                                                             const uint8_t *__restrict__ rgb, const float *__restrict__ obs,
                                                                             int H, int W, int tx0, int ty0, int tx1, int ty1, float tol,
                                                                             FrameRenderOut o) {
+  typedef FrameKeyZTri Key;
   constexpr int T = FRAME_RENDER_TILE;
-  __shared__ unsigned long long zbuf[T * T];
+  __shared__ Key::type zbuf[T * T];
   const int tid = threadIdx.x;
-  const int X0 = blockIdx.x * T, Y0 = blockIdx.y * T;
-  const int X1 = min(X0 + T - 1, W - 1), Y1 = min(Y0 + T - 1, H - 1);
-  for (int i = tid; i < T * T; i += FRAME_RENDER_THREADS) zbuf[i] = FR_EMPTY;
+  const FrameTile rect = frame_tile_rect((int)blockIdx.x, (int)blockIdx.y, H, W);
+  const int X0 = rect.X0, Y0 = rect.Y0;
+  frame_zbuf_clear<Key>(zbuf, tid);
   __syncthreads();
   const bool walk = (int)blockIdx.x >= tx0 && (int)blockIdx.x <= tx1 && (int)blockIdx.y >= ty0 && (int)blockIdx.y <= ty1;   // uniform
-  if (walk) {
-    for (int t = tid; t < F; t += FRAME_RENDER_THREADS) {
-      const int i0 = faces[(size_t)t * 3], i1 = faces[(size_t)t * 3 + 1], i2 = faces[(size_t)t * 3 + 2];
-      if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) continue;
-      const int4 a = snap[i0], b = snap[i1], c = snap[i2];
-      frame_tri_walk(a, b, c, X0, Y0, X1, Y1, [&](int px, int py, float z) {
-        atomicMin(&zbuf[(py - Y0) * T + (px - X0)], ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)t);
-      });
-    }
-  }
+  if (walk) frame_face_walk<Key>(faces, F, V, snap, rect, zbuf, tid);
   __syncthreads();
   for (int i = tid; i < T * T; i += FRAME_RENDER_THREADS) {
     const int px = X0 + (i & (T - 1)), py = Y0 + i / T;
     if (px >= W || py >= H) continue;
     const size_t at = (size_t)py * W + px;
-    const unsigned long long key = zbuf[i];
-    const bool model = key != FR_EMPTY;
-    const float z = model ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
-    const int tri = model ? (int)(unsigned)key : -1;
+    const Key::type key = zbuf[i];
+    const bool model = key != Key::EMPTY;
+    const float z = model ? Key::z(key) : 0.0f;
+    const int tri = model ? (int)Key::tri(key) : -1;
     bool visible = model;
     if (model && (o.vis || o.overlay)) visible = !frame_occluded(obs[at], z, tol);   // something observed in front of the model?
     if (o.depth) o.depth[at] = z;
@@ -80,6 +80,14 @@ __global__ __launch_bounds__(FRAME_RENDER_THREADS) void frame_raster_kernel(cons
 void launch_frame_vertex(hipStream_t s, const DeviceMesh &m, const FramePose &pose, int4 *snap, float4 *cam, int *flag) {
   FP_GEOM_LOG("frame_vertex");
   hipLaunchKernelGGL(frame_vertex_kernel, dim3((unsigned)((m.V + 255) / 256)), dim3(256), 0, s, m.verts, m.V, pose, snap, cam, flag);
+}
+
+void launch_pose_vertices(hipStream_t s, const char *log_name, const DeviceMesh &m, const FramePose *poses_a, int n_a, const FramePose *poses_b, int n_b,
+                          int4 *snap, float4 *cam, int *flags_a, int *flags_b) {
+  FP_GEOM_LOG(log_name);
+  if (n_a + n_b <= 0 || m.V <= 0) return;
+  hipLaunchKernelGGL(pose_vertex_kernel, dim3((unsigned)((m.V + 255) / 256), (unsigned)(n_a + n_b)), dim3(256), 0, s, m.verts, m.V, poses_a, n_a, poses_b,
+                     snap, cam, flags_a, flags_b);
 }
 
 void launch_frame_raster(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const uint8_t *rgb, const float *depth,

@@ -1,7 +1,9 @@
-// The raster rules of the frame-resolution renderers, each written once: fp_render_pose (fp_frame_render.hip)
-// and fp_render_scene (fp_scene_render.hip, section 4.9) promise the same pixels because their kernels call these functions.  Device
-// code only, for files compiled with -ffp-contract=off: every f32 operation below is separately rounded, in the order written, and
-// tests/frame_render_ref.py restates it operation by operation.  The 160x160 crop rasteriser of fp_geometry.hip has rules of its own.
+// The raster rules of the frame-resolution renderers, each written once: fp_render_pose (fp_frame_render.hip),
+// fp_render_scene (fp_scene_render.hip, section 4.9), fp_pose_vsd (fp_pose_vsd.hip, section 4.11) and fp_refine_depth (fp_pose_icp.hip,
+// section 4.12) promise the same pixels because their kernels call these functions; and the tile engine around the rules, which the
+// kernels that rasterise one mesh under one pose share.  Device code only, for files compiled with -ffp-contract=off: every f32
+// operation below is separately rounded, in the order written, and tests/frame_render_ref.py restates it operation by operation.  The
+// 160x160 crop rasteriser of fp_geometry.hip has rules of its own.
 #pragma once
 #include "fp_internal.h"
 
@@ -78,6 +80,70 @@ __device__ __forceinline__ void frame_tri_walk(const int4 &a, const int4 &b, con
       hit(px, py, 1.0f / ((w0 / za + w1 / zb) + w2 / zc));
     }
   }
+}
+
+// ---- the pose-tile engine: what every kernel that rasterises ONE mesh under one pose into a FRAME_RENDER_TILE x FRAME_RENDER_TILE
+// LDS z-buffer does before its own pixel loop (frame_raster_kernel, vsd_tile_kernel, icp_tile_kernel): the tile's rectangle, the
+// z-buffer's keys, the walk over all faces.  scene_raster_kernel walks per-tile lists of several objects instead of all faces of
+// one; it shares the rectangle and the keys.
+
+// the pixels [X0..X1] x [Y0..Y1] of tile (bx, by), cut to the H x W frame
+struct FrameTile {
+  int X0, Y0, X1, Y1;
+};
+__device__ __forceinline__ FrameTile frame_tile_rect(int bx, int by, int H, int W) {
+  constexpr int T = FRAME_RENDER_TILE;
+  return {bx * T, by * T, min(bx * T + T - 1, W - 1), min(by * T + T - 1, H - 1)};
+}
+// ... of tile number `tile` of a grid of ntx tiles per row
+__device__ __forceinline__ FrameTile frame_tile_rect_of(int tile, int ntx, int H, int W) { return frame_tile_rect(tile % ntx, tile / ntx, H, W); }
+
+// z-buffer keys.  EMPTY (an entry no triangle has reached) is larger than every key; positive floats order like their bit patterns, so
+// the unsigned minimum of a key is the nearest depth -- and, with the triangle below the depth, the lowest triangle among equal depths.
+// FrameKeyZ keeps the depth only: its minimum is the z of the FrameKeyZTri minimum.
+struct FrameKeyZ {
+  typedef unsigned type;
+  static constexpr type EMPTY = ~0u;
+  static __device__ __forceinline__ type pack(float z, unsigned) { return __float_as_uint(z); }
+  static __device__ __forceinline__ float z(type key) { return __uint_as_float(key); }
+};
+struct FrameKeyZTri {
+  typedef unsigned long long type;
+  static constexpr type EMPTY = ~0ull;
+  static __device__ __forceinline__ type pack(float z, unsigned tri) { return ((type)__float_as_uint(z) << 32) | tri; }
+  static __device__ __forceinline__ float z(type key) { return __uint_as_float((unsigned)(key >> 32)); }
+  static __device__ __forceinline__ unsigned tri(type key) { return (unsigned)key; }
+};
+template <typename Key>
+__device__ __forceinline__ void frame_zbuf_clear(typename Key::type *zbuf, int tid) {
+  for (int i = tid; i < FRAME_RENDER_TILE * FRAME_RENDER_TILE; i += FRAME_RENDER_THREADS) zbuf[i] = Key::EMPTY;
+}
+// the face walk: the workgroup's threads share the F faces of the mesh, skip a face with an index outside the V vertices, and
+// rasterise the others (rejected by bounding box against the tile first) into the tile's z-buffer with an LDS atomic minimum.
+// snap: the pose's own snapped vertices.  Barriers before (the clear) and after (the resolve) are the caller's.
+template <typename Key>
+__device__ __forceinline__ void frame_face_walk(const int32_t *__restrict__ faces, int F, int V, const int4 *__restrict__ snap, const FrameTile &r,
+                                                typename Key::type *zbuf, int tid) {
+  for (int t = tid; t < F; t += FRAME_RENDER_THREADS) {
+    const int i0 = faces[(size_t)t * 3], i1 = faces[(size_t)t * 3 + 1], i2 = faces[(size_t)t * 3 + 2];
+    if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) continue;
+    const int4 a = snap[i0], b = snap[i1], c = snap[i2];
+    frame_tri_walk(a, b, c, r.X0, r.Y0, r.X1, r.Y1, [&](int px, int py, float z) {
+      atomicMin(&zbuf[(py - r.Y0) * FRAME_RENDER_TILE + (px - r.X0)], Key::pack(z, (unsigned)t));
+    });
+  }
+}
+
+// the body of a vertex pass: vertex i under pose P -> the snapped vertex *snap and, where cam is not null (something is shaded, or a
+// normal is needed), its camera-space copy *cam; a refused vertex raises its bit of *flag.
+__device__ __forceinline__ void frame_vertex_store(const float *__restrict__ verts, int i, const FramePose &P, int4 *__restrict__ snap,
+                                                   float4 *__restrict__ cam, int *__restrict__ flag) {
+  int4 sn;
+  float4 cm;
+  const int bad = frame_vertex_rule(verts, (size_t)i, P, sn, cm);
+  *snap = sn;
+  if (cam) *cam = cm;
+  if (bad) atomicOr(flag, bad);
 }
 
 // a model pixel at depth z is hidden when something valid was observed more than tol in front of it (D is the RAW observed depth)

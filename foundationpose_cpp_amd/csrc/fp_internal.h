@@ -315,6 +315,9 @@ int pose_fit_split(int N);   // workgroups per hypothesis
 void launch_pose_fit(hipStream_t s, const void *img_a, size_t a_stride, const void *img_b, size_t b_stride, int N, const PoseFitTol &tol,
                      OutMode mode, unsigned long long *acc, PoseFitRec *out);
 
+// how many of the wave's 64 lanes hold b: wave-uniform, so one lane can add it to an integer counter (the tile kernels and the search)
+__device__ __forceinline__ unsigned wave_count(bool b) { return (unsigned)__popcll(__ballot(b)); }
+
 // frame-resolution rendering of one pose (fp_render_pose; fp_frame_render.hip)
 constexpr float FRAME_RENDER_NEAR = 0.01f;          // = FP_RENDER_NEAR_M: a vertex with z below it refuses the pose (there is no clipper)
 constexpr int FRAME_RENDER_SNAP_MAX = 1 << 26;      // = FP_RENDER_SNAP_MAX: largest |snapped coordinate| (1/16 px); edge functions stay below 2^56
@@ -339,6 +342,11 @@ struct FrameTileBound {
 FrameTileBound frame_tile_bound(const FramePose &pose, double radius, int H, int W);
 // snap [V] = {xi, yi, bits(z), 0}, cam [V] = {x, y, z, 0}; *flag must be zero on entry
 void launch_frame_vertex(hipStream_t s, const DeviceMesh &m, const FramePose &pose, int4 *snap, float4 *cam, int *flag);
+// the same for a batch of poses out of device memory (fp_pose_vsd, fp_refine_depth): pose p of the launch is poses_a[p] (p < n_a) or
+// poses_b[p - n_a] (n_b may be 0); snap [(n_a + n_b) V] and cam likewise (null: not stored) in the formats above; pose p raises
+// flags_a[p] or flags_b[p - n_a], which must be zero on entry.  log_name: the launch's name in the test build's launch log.
+void launch_pose_vertices(hipStream_t s, const char *log_name, const DeviceMesh &m, const FramePose *poses_a, int n_a, const FramePose *poses_b, int n_b,
+                          int4 *snap, float4 *cam, int *flags_a, int *flags_b);
 void launch_frame_raster(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const uint8_t *rgb, const float *depth,
                          int H, int W, const FrameTileBound &bound, float tol_m, const FrameRenderOut &out);
 
@@ -412,10 +420,6 @@ struct VsdParams {
   int T;                     // thresholds in use
   float thr[VSD_MAX_TAUS];   // in metres (already multiplied by the diameter when normalised)
 };
-// pose p of the launch is poses_est[p] (p < n_est: the chunk's estimates) or poses_gt[p - n_est] (its ground truths); snap
-// [(n_est + n_gt) V] in frame_vertex_kernel's format; pose p raises flags_est[p] or flags_gt[p - n_est], which must be zero on entry
-void launch_vsd_vertex(hipStream_t s, const DeviceMesh &m, const FramePose *poses_est, int n_est, const FramePose *poses_gt, int n_gt, int4 *snap,
-                       int *flags_est, int *flags_gt);
 // items [n_items] = {pose of the chunk, tile}: counters[(pose0 + pose) VSD_WORDS ..] += the tile's pixel counts.  snap_g non-null: ground
 // truth `pose` of the chunk is walked like the estimate; null: plane_g [H,W] holds the one ground truth's model depth (0 = background)
 void launch_vsd_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap_e, const int4 *snap_g, const float *plane_g, const int2 *items, int n_items,
@@ -434,8 +438,6 @@ struct IcpParams {
   float t[3];       // the pose's translation
   float pad;
 };
-// pose p of the launch is poses[p]; snap, cam [n V] in frame_vertex_kernel's formats; pose p raises flags[p], which must be zero on entry
-void launch_icp_vertex(hipStream_t s, const DeviceMesh &m, const FramePose *poses, int n, int4 *snap, float4 *cam, int *flags);
 // items [n_items] = {pose of the chunk, tile}: acc[(pose0 + pose) ICP_WORDS ..] += the tile's sums and counts, under params[pose0 + pose];
 // an item whose flags[pose0 + pose] is not zero does nothing
 void launch_icp_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const int2 *items, int n_items, const float *depth,

@@ -1,5 +1,5 @@
 // Projective point-to-plane ICP of N poses on the observed depth (fp_refine_depth): the device half.  Two kernels:
-// a vertex pass over (pose, vertex) that keeps the snapped and the camera-space vertex, and a tile kernel over (pose, tile) items that
+// the batched vertex pass over (pose, vertex), which keeps the snapped and the camera-space vertex, and here a tile kernel over (pose, tile) items that
 // rasterises the pose into a 64-bit LDS z-buffer exactly as frame_raster_kernel does, associates every model pixel with the observed
 // depth, and reduces the 6 x 6 normal system of the pose as 28 integer sums plus six pixel counts.  Every rule that decides the depth
 // and the triangle of a pixel is fp_frame_rules.h's; the rules of the residual are icp_pixel below.  Compiled with -ffp-contract=off
@@ -10,20 +10,12 @@ namespace fp {
 
 namespace {
 
-constexpr unsigned long long ICP_EMPTY = ~0ull;   // a z-buffer entry no triangle has reached: larger than every key
-constexpr int ICP_TILE = FRAME_RENDER_TILE, ICP_THREADS = FRAME_RENDER_THREADS;
-constexpr int ICP_PX_PER_THREAD = ICP_TILE * ICP_TILE / ICP_THREADS;
-constexpr int ICP_WAVES = ICP_THREADS / 64;
+typedef FrameKeyZTri Key;   // the normals need the winning triangle: frame_raster_kernel's 64-bit keys
+constexpr int ICP_PX_PER_THREAD = FRAME_RENDER_TILE * FRAME_RENDER_TILE / FRAME_RENDER_THREADS;
+constexpr int ICP_WAVES = FRAME_RENDER_THREADS / 64;
 
-// (a) vertex pass: pose p of the launch times vertex i -> the snapped vertex and its camera-space copy (the normals need it); a refused
-// vertex raises its bit of the pose's own word.
-__global__ __launch_bounds__(256) void icp_vertex_kernel(const float *__restrict__ verts, int V, const FramePose *__restrict__ poses,
-                                                         int4 *__restrict__ snap, float4 *__restrict__ cam, int *__restrict__ flags) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y;
-  if (i >= V) return;
-  const int bad = frame_vertex_rule(verts, (size_t)i, poses[p], snap[(size_t)p * V + i], cam[(size_t)p * V + i]);
-  if (bad) atomicOr(flags + p, bad);
-}
+// (a) the vertex pass is launch_pose_vertices' (fp_frame_render.hip): the poses of a chunk, the snapped vertex and its camera-space
+// copy (the normals need it).
 
 // the rules of the residual at one pixel (c, r) of a model pixel: z the model depth, p0 p1 p2 the winning triangle's camera-space
 // corners, D the RAW observed depth.  cls: 0 not valid, 1 used, 2 front, 3 behind, 4 grazing; J and e are set when used.
@@ -60,37 +52,28 @@ __device__ __forceinline__ IcpPixel icp_pixel(int c, int r, float z, const float
 }
 
 __device__ __forceinline__ long long icp_q32(float v) { return llrintf(v * 4294967296.0f); }   // (the scaling is exact)
-__device__ __forceinline__ unsigned icp_count(bool b) { return (unsigned)__popcll(__ballot(b)); }
 
 // (b) tile kernel: one workgroup per item {pose of the launch's chunk, tile}.  params / flags / acc are indexed by pose0 + pose.
-__global__ __launch_bounds__(ICP_THREADS) void icp_tile_kernel(const int32_t *__restrict__ faces, int F, int V, const int4 *__restrict__ snap,
-                                                               const float4 *__restrict__ cam, const int2 *__restrict__ items,
-                                                               const float *__restrict__ obs, int H, int W, int ntx,
-                                                               const IcpParams *__restrict__ params, const int *__restrict__ flags, int pose0,
-                                                               unsigned long long *__restrict__ acc) {
-  constexpr int T = ICP_TILE;
-  __shared__ unsigned long long zbuf[T * T];
+__global__ __launch_bounds__(FRAME_RENDER_THREADS) void icp_tile_kernel(const int32_t *__restrict__ faces, int F, int V, const int4 *__restrict__ snap,
+                                                                        const float4 *__restrict__ cam, const int2 *__restrict__ items,
+                                                                        const float *__restrict__ obs, int H, int W, int ntx,
+                                                                        const IcpParams *__restrict__ params, const int *__restrict__ flags, int pose0,
+                                                                        unsigned long long *__restrict__ acc) {
+  constexpr int T = FRAME_RENDER_TILE;
+  __shared__ Key::type zbuf[T * T];
   __shared__ long long part[ICP_WAVES][ICP_SUMS];
   __shared__ unsigned counts[ICP_COUNTS];
   const int tid = threadIdx.x;
   const int2 item = items[blockIdx.x];
   const int pose = item.x, tile = item.y;
   if (flags[pose0 + pose]) return;   // (uniform) a refused pose: its vertices were not stored, the host drops its record
-  const int X0 = (tile % ntx) * T, Y0 = (tile / ntx) * T;
-  const int X1 = min(X0 + T - 1, W - 1), Y1 = min(Y0 + T - 1, H - 1);
-  for (int i = tid; i < T * T; i += ICP_THREADS) zbuf[i] = ICP_EMPTY;
+  const FrameTile rect = frame_tile_rect_of(tile, ntx, H, W);
+  const int X0 = rect.X0, Y0 = rect.Y0;
+  frame_zbuf_clear<Key>(zbuf, tid);
   if (tid < ICP_COUNTS) counts[tid] = 0;
   __syncthreads();
-  const int4 *__restrict__ sn = snap + (size_t)pose * V;
   const float4 *__restrict__ cm = cam + (size_t)pose * V;
-  for (int t = tid; t < F; t += ICP_THREADS) {
-    const int i0 = faces[(size_t)t * 3], i1 = faces[(size_t)t * 3 + 1], i2 = faces[(size_t)t * 3 + 2];
-    if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) continue;
-    const int4 a = sn[i0], b = sn[i1], c = sn[i2];
-    frame_tri_walk(a, b, c, X0, Y0, X1, Y1, [&](int px, int py, float z) {
-      atomicMin(&zbuf[(py - Y0) * T + (px - X0)], ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)t);
-    });
-  }
+  frame_face_walk<Key>(faces, F, V, snap + (size_t)pose * V, rect, zbuf, tid);
   __syncthreads();
   const IcpParams P = params[pose0 + pose];
   long long sum[ICP_SUMS];
@@ -99,21 +82,21 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_tile_kernel(const int32_t *__
   unsigned n_model = 0, n_valid = 0, n_used = 0, n_front = 0, n_behind = 0, n_grazing = 0;   // wave-uniform
 #pragma unroll
   for (int k = 0; k < ICP_PX_PER_THREAD; k++) {
-    const int i = k * ICP_THREADS + tid;
+    const int i = k * FRAME_RENDER_THREADS + tid;
     const int px = X0 + (i & (T - 1)), py = Y0 + i / T;
     const bool in = px < W && py < H;
-    const unsigned long long key = zbuf[i];
-    const bool model = in && key != ICP_EMPTY;   // (a key exists only for a triangle whose three indices are below V)
+    const Key::type key = zbuf[i];
+    const bool model = in && key != Key::EMPTY;   // (a key exists only for a triangle whose three indices are below V)
     IcpPixel q;
     q.cls = 0;
     if (model) {
-      const float z = __uint_as_float((unsigned)(key >> 32));
-      const size_t tri = (size_t)(unsigned)key;
+      const float z = Key::z(key);
+      const size_t tri = (size_t)Key::tri(key);
       q = icp_pixel(px, py, z, cm[faces[tri * 3]], cm[faces[tri * 3 + 1]], cm[faces[tri * 3 + 2]], obs[(size_t)py * W + px], P);
     }
-    n_model += icp_count(model); n_valid += icp_count(q.cls != 0);
-    n_used += icp_count(q.cls == 1); n_front += icp_count(q.cls == 2);
-    n_behind += icp_count(q.cls == 3); n_grazing += icp_count(q.cls == 4);
+    n_model += wave_count(model); n_valid += wave_count(q.cls != 0);
+    n_used += wave_count(q.cls == 1); n_front += wave_count(q.cls == 2);
+    n_behind += wave_count(q.cls == 3); n_grazing += wave_count(q.cls == 4);
     if (q.cls == 1) {
       int j = 0;
 #pragma unroll
@@ -159,18 +142,12 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_tile_kernel(const int32_t *__
 
 }  // namespace
 
-void launch_icp_vertex(hipStream_t s, const DeviceMesh &m, const FramePose *poses, int n, int4 *snap, float4 *cam, int *flags) {
-  FP_GEOM_LOG("icp_vertex");
-  if (n <= 0 || m.V <= 0) return;
-  hipLaunchKernelGGL(icp_vertex_kernel, dim3((unsigned)((m.V + 255) / 256), (unsigned)n), dim3(256), 0, s, m.verts, m.V, poses, snap, cam, flags);
-}
-
 void launch_icp_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const int2 *items, int n_items, const float *depth,
                       int H, int W, const IcpParams *params, const int *flags, int pose0, unsigned long long *acc) {
   FP_GEOM_LOG("icp_tile");
   if (n_items <= 0) return;
-  const int ntx = (W + ICP_TILE - 1) / ICP_TILE;
-  hipLaunchKernelGGL(icp_tile_kernel, dim3((unsigned)n_items), dim3(ICP_THREADS), 0, s, m.faces, m.F, m.V, snap, cam, items, depth, H, W, ntx, params,
+  const int ntx = scene_tiles_x(W);
+  hipLaunchKernelGGL(icp_tile_kernel, dim3((unsigned)n_items), dim3(FRAME_RENDER_THREADS), 0, s, m.faces, m.F, m.V, snap, cam, items, depth, H, W, ntx, params,
                      flags, pose0, acc);
 }
 

@@ -10,8 +10,6 @@ namespace fp {
 
 namespace {
 
-__device__ __forceinline__ int search_count(bool b) { return (int)__popcll(__ballot(b)); }
-
 __global__ __launch_bounds__(SEARCH_THREADS) void pose_search_kernel(const float *__restrict__ verts, const float *__restrict__ normals,
                                                                      const FramePose *__restrict__ poses, const float *__restrict__ depth,
                                                                      SearchParams S, SearchRec *__restrict__ out) {
@@ -51,12 +49,12 @@ __global__ __launch_bounds__(SEARCH_THREADS) void pose_search_kernel(const float
       const bool seen = D >= FP_MIN_DEPTH && D <= 3.402823466e+38f;   // not missing, NaN or infinite
       const float dz = D - qz;
       const bool hit = facing && inside && seen;
-      const int n_facing = search_count(facing);
-      const int n_inlier = search_count(hit && fabsf(dz) <= S.tol_m);
-      const int n_front = search_count(hit && dz < -S.tol_m);
-      const int n_behind = search_count(hit && dz > S.tol_m);
-      const int n_outside = search_count(facing && !inside);
-      const int n_missing = search_count(facing && inside && !seen);
+      const int n_facing = (int)wave_count(facing);
+      const int n_inlier = (int)wave_count(hit && fabsf(dz) <= S.tol_m);
+      const int n_front = (int)wave_count(hit && dz < -S.tol_m);
+      const int n_behind = (int)wave_count(hit && dz > S.tol_m);
+      const int n_outside = (int)wave_count(facing && !inside);
+      const int n_missing = (int)wave_count(facing && inside && !seen);
       const bool any_near = __ballot(near) != 0ull;
       if (lane == 0) {   // integer LDS adds: the order does not matter
         if (n_facing) atomicAdd(&table[k][0], n_facing);

@@ -9,8 +9,7 @@ namespace fp {
 
 namespace {
 
-constexpr unsigned long long SC_EMPTY = ~0ull;   // a z-buffer entry no triangle has reached: larger than every key
-constexpr int SC_T = FRAME_RENDER_TILE, SC_THREADS = FRAME_RENDER_THREADS;
+typedef FrameKeyZTri Key;   // the z-buffer's keys; the triangle they carry is the GLOBAL index g
 
 // the object that owns global index g: the last o with start[o] <= g (objects without vertices / faces own nothing)
 template <typename I>
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(256) void scene_bin_kernel(const SceneTable *__rest
   if (g < total && scene_load_tri(tb, tb->vert_start, tb->face_start, tb->K, snap, g, t)) {
     FrameBox q;
     if (frame_tri_box(t.a, t.b, t.c, 0, 0, W - 1, H - 1, q) && frame_tri_area(t.a, t.b, t.c) != 0) {   // inside the grid: 0 <= p < W, H
-      tx0 = q.px0 / SC_T; tx1 = q.px1 / SC_T; ty0 = q.py0 / SC_T; ty1 = q.py1 / SC_T;
+      tx0 = q.px0 / FRAME_RENDER_TILE; tx1 = q.px1 / FRAME_RENDER_TILE; ty0 = q.py0 / FRAME_RENDER_TILE; ty1 = q.py1 / FRAME_RENDER_TILE;
     }
   }
   for (int c0 = 0; c0 < ntiles; c0 += SC_BIN_CHUNK) {   // uniform
@@ -139,12 +138,12 @@ __global__ __launch_bounds__(256) void scene_scan_kernel(const unsigned *__restr
 // (ds_min_u64), its coverage words (bit o: a triangle of object o covers the sample; 64-bit LDS OR), the offset tables and 64 x 3
 // counters.  After the barrier every requested output of the tile is written once and the tile's per-object counts are added to the
 // call's counters.  A tile with an empty list writes background and adds nothing.
-__global__ __launch_bounds__(SC_THREADS) void scene_raster_kernel(const SceneTable *__restrict__ tb, const int4 *__restrict__ snap,
-                                                                  const float4 *__restrict__ cam, const unsigned *__restrict__ offset,
-                                                                  const unsigned *__restrict__ list, const uint8_t *__restrict__ rgb,
-                                                                  const float *__restrict__ obs, int H, int W, float tol, SceneRenderOut out) {
-  constexpr int T = SC_T;
-  __shared__ unsigned long long zbuf[T * T];
+__global__ __launch_bounds__(FRAME_RENDER_THREADS) void scene_raster_kernel(const SceneTable *__restrict__ tb, const int4 *__restrict__ snap,
+                                                                            const float4 *__restrict__ cam, const unsigned *__restrict__ offset,
+                                                                            const unsigned *__restrict__ list, const uint8_t *__restrict__ rgb,
+                                                                            const float *__restrict__ obs, int H, int W, float tol, SceneRenderOut out) {
+  constexpr int T = FRAME_RENDER_TILE;
+  __shared__ Key::type zbuf[T * T];
   __shared__ unsigned long long cover[T * T];
   __shared__ unsigned long long present;                    // objects with an entry in this tile's list
   __shared__ unsigned face_start[SCENE_MAX_OBJECTS + 1];
@@ -152,18 +151,18 @@ __global__ __launch_bounds__(SC_THREADS) void scene_raster_kernel(const SceneTab
   __shared__ int cnt[SCENE_MAX_OBJECTS * 3];
   const int tid = threadIdx.x;
   const int K = tb->K;
-  const int X0 = blockIdx.x * T, Y0 = blockIdx.y * T;
-  const int X1 = min(X0 + T - 1, W - 1), Y1 = min(Y0 + T - 1, H - 1);
+  const FrameTile rect = frame_tile_rect((int)blockIdx.x, (int)blockIdx.y, H, W);
+  const int X0 = rect.X0, Y0 = rect.Y0, X1 = rect.X1, Y1 = rect.Y1;
   const unsigned tile = blockIdx.y * gridDim.x + blockIdx.x;
   const unsigned l0 = offset[tile], l1 = offset[tile + 1];   // uniform
   if (l0 != l1) {
-    for (int i = tid; i < T * T; i += SC_THREADS) { zbuf[i] = SC_EMPTY; cover[i] = 0; }
-    for (int i = tid; i <= K; i += SC_THREADS) { face_start[i] = tb->face_start[i]; vert_start[i] = tb->vert_start[i]; }
-    for (int i = tid; i < SCENE_MAX_OBJECTS * 3; i += SC_THREADS) cnt[i] = 0;
+    for (int i = tid; i < T * T; i += FRAME_RENDER_THREADS) { zbuf[i] = Key::EMPTY; cover[i] = 0; }
+    for (int i = tid; i <= K; i += FRAME_RENDER_THREADS) { face_start[i] = tb->face_start[i]; vert_start[i] = tb->vert_start[i]; }
+    for (int i = tid; i < SCENE_MAX_OBJECTS * 3; i += FRAME_RENDER_THREADS) cnt[i] = 0;
     if (tid == 0) present = 0;
     __syncthreads();
     unsigned long long mine = 0;
-    for (unsigned e = l0 + tid; e < l1; e += SC_THREADS) {
+    for (unsigned e = l0 + tid; e < l1; e += FRAME_RENDER_THREADS) {
       const unsigned g = list[e];
       SceneTri tr;
       if (!scene_load_tri(tb, vert_start, face_start, K, snap, g, tr)) continue;
@@ -171,7 +170,7 @@ __global__ __launch_bounds__(SC_THREADS) void scene_raster_kernel(const SceneTab
       mine |= obit;
       frame_tri_walk(tr.a, tr.b, tr.c, X0, Y0, X1, Y1, [&](int px, int py, float z) {
         const int at = (py - Y0) * T + (px - X0);
-        atomicMin(&zbuf[at], ((unsigned long long)__float_as_uint(z) << 32) | g);
+        atomicMin(&zbuf[at], Key::pack(z, g));
         atomicOr(&cover[at], obit);
       });
     }
@@ -180,21 +179,21 @@ __global__ __launch_bounds__(SC_THREADS) void scene_raster_kernel(const SceneTab
   }
   const bool walked = l0 != l1;   // uniform
   const unsigned long long here = walked ? present : 0;
-  for (int i = tid; i < T * T; i += SC_THREADS) {   // (a tile row per half-wave: 128-byte runs of the 4-byte outputs)
+  for (int i = tid; i < T * T; i += FRAME_RENDER_THREADS) {   // (a tile row per half-wave: 128-byte runs of the 4-byte outputs)
     const int px = X0 + (i & (T - 1)), py = Y0 + i / T;
     const bool in = px < W && py < H;
     const size_t at = (size_t)py * W + px;
-    const unsigned long long key = walked ? zbuf[i] : SC_EMPTY;
+    const Key::type key = walked ? zbuf[i] : Key::EMPTY;
     const unsigned long long bits = walked && in ? cover[i] : 0;
-    const bool model = in && key != SC_EMPTY;
+    const bool model = in && key != Key::EMPTY;
     int o = -1, tri = -1;
     bool visible = model;
     if (model) {
-      const unsigned g = (unsigned)key;
+      const unsigned g = Key::tri(key);
       o = scene_owner(face_start, K, g);
       tri = (int)(g - face_start[o]);
     }
-    const float z = model ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
+    const float z = model ? Key::z(key) : 0.0f;
     if (model && (out.vis || out.overlay || out.counters)) visible = !frame_occluded(obs[at], z, tol);   // ... in front of the nearest model?
     if (in) {
       if (out.depth) out.depth[at] = z;
@@ -267,7 +266,7 @@ void launch_scene_raster(hipStream_t s, const SceneTable *table, const int4 *sna
                          const unsigned *list, const uint8_t *rgb, const float *depth, int H, int W, float tol_m, const SceneRenderOut &out) {
   FP_GEOM_LOG("scene_raster");
   const dim3 grid((unsigned)scene_tiles_x(W), (unsigned)scene_tiles_y(H));
-  hipLaunchKernelGGL(scene_raster_kernel, grid, dim3(SC_THREADS), 0, s, table, snap, cam, offset, list, rgb, depth, H, W, tol_m, out);
+  hipLaunchKernelGGL(scene_raster_kernel, grid, dim3(FRAME_RENDER_THREADS), 0, s, table, snap, cam, offset, list, rgb, depth, H, W, tol_m, out);
 }
 
 }  // namespace fp
