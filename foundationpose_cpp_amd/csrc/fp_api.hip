@@ -2583,8 +2583,24 @@ static int no_pending_track(const fp_model *m, const std::string &fn) {
   FP_CHECK(!m->track_pending, "[FoundationPose] " + fn + ": a submitted Track has not been waited for (fp_track_wait)");
   return 0;
 }
-static int stage_target(fp_model *m, const std::string &fn, const char *target_name, Target **t) {   // no pending Track, then the target
-  if (no_pending_track(m, fn)) return 1;
+// The frame-resolution calls read fx, fy, cx, cy only (frame_pose below), so they ask for a plain pinhole matrix: a skew or a third row
+// that Register and Track would honour must not be dropped silently.  K is row-major, as fp_create took it.
+static int pinhole_camera_ok(const fp_model *m, const std::string &fn) {
+  static const int zero[4] = {1, 3, 6, 7};
+  for (int k : zero)
+    FP_CHECK(m->K[k] == 0.0f, "[FoundationPose] " + fn + ": the model's K is not a plain pinhole matrix: K[" + std::to_string(k) + "] = " + std::to_string(m->K[k]) +
+                 " must be 0 (this call reads fx, fy, cx, cy only; Register and Track take a general K)");
+  FP_CHECK(m->K[8] == 1.0f, "[FoundationPose] " + fn + ": the model's K is not a plain pinhole matrix: K[8] = " + std::to_string(m->K[8]) +
+               " must be 1 (this call reads fx, fy, cx, cy only; Register and Track take a general K)");
+  for (int k : {0, 4})
+    FP_CHECK(std::isfinite(m->K[k]) && m->K[k] > 0.0f, "[FoundationPose] " + fn + ": the model's K is not a plain pinhole matrix: K[" + std::to_string(k) + "] = " +
+                 std::to_string(m->K[k]) + " (the focal length) must be finite and positive");
+  for (int k : {2, 5})
+    FP_CHECK(std::isfinite(m->K[k]), "[FoundationPose] " + fn + ": the model's K is not a plain pinhole matrix: K[" + std::to_string(k) + "] (the principal point) must be finite");
+  return 0;
+}
+static int stage_target(fp_model *m, const std::string &fn, const char *target_name, Target **t) {   // no pending Track, a pinhole K, then the target
+  if (no_pending_track(m, fn) || pinhole_camera_ok(m, fn)) return 1;
   *t = m->find(target_name ? target_name : "");
   FP_CHECK(*t != nullptr, "[FoundationPose] unknown target_name");
   return 0;
@@ -2609,7 +2625,7 @@ static int render_preconditions(const fp_model *m, const std::string &fn, int me
   FP_CHECK(memspace == FP_HOST || memspace == FP_DEVICE, "[FoundationPose] " + fn + ": memspace must be FP_HOST or FP_DEVICE");
   FP_CHECK(any_output, "[FoundationPose] " + fn + ": no output requested");
   FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] " + fn + ": tol_m must be finite and >= 0 (metres)");
-  return no_pending_track(m, fn) || frame_ready(m, fn, true);
+  return no_pending_track(m, fn) || pinhole_camera_ok(m, fn) || frame_ready(m, fn, true);
 }
 static FramePose frame_pose(const fp_model *m, const float pose[16]) {   // pose: column-major 4 x 4
   FramePose P;
@@ -3364,7 +3380,7 @@ int fp_register_depth(fp_model *m, const void *rgb, const void *depth, const voi
   FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_register_depth: tol_m must be finite and >= 0 (metres; 0 = 0.005)");
   FP_CHECK(icp_iterations >= 0 && icp_iterations <= FP_ICP_MAX_ITERATIONS,
            "[FoundationPose] fp_register_depth: " + std::to_string(icp_iterations) + " iterations (0 = 15, at most FP_ICP_MAX_ITERATIONS = " + std::to_string(FP_ICP_MAX_ITERATIONS) + ")");
-  if (no_pending_track(m, "fp_register_depth")) return 1;
+  if (no_pending_track(m, "fp_register_depth") || pinhole_camera_ok(m, "fp_register_depth")) return 1;
   if (top_k == 0) top_k = 16;
   if (tol_m == 0.0f) tol_m = 0.005f;
   if (icp_iterations == 0) icp_iterations = 15;

@@ -91,7 +91,13 @@ const uint8_t *fp_mesh_vertex_colors(const fp_loaded_mesh *mesh);
 
 /* ---- construction: CreateFoundationPoseModel (D6F/include/.../foundationpose.hpp:99-105, src/foundationpose.cpp:108-153,448-458).
  * refiner_weights / scorer_weights: paths of packed weight files (tools/pack_weights.py; replaces the TensorRT
- * engines of simple_tests/src/test_foundationpose.cpp:13-14).  NULL = geometry-only model (NN entry points fail). */
+ * engines of simple_tests/src/test_foundationpose.cpp:13-14).  NULL = geometry-only model (NN entry points fail).
+ * K: the 3x3 intrinsics, row-major; all nine entries are copied.  Register, Track and the stage operators of their path take K as the
+ * reference does, as a matrix, so a skew K[1] is honoured there.  The seven frame-resolution calls -- fp_render_pose, fp_render_scene,
+ * fp_pose_errors, fp_pose_vsd, fp_refine_depth, fp_pose_search, fp_register_depth -- read fx = K[0], fy = K[4], cx = K[2], cy = K[5]
+ * only and REFUSE a model whose K is not a plain pinhole matrix (K[1] == K[3] == K[6] == K[7] == 0, K[8] == 1, K[0] and K[4] finite and
+ * positive, K[2] and K[5] finite): on the host, before anything is uploaded or launched, with a message that names the entry, their
+ * outputs untouched.  fx != fy and a principal point anywhere are fine everywhere. */
 fp_model *fp_create(const fp_mesh *meshes, int n_meshes, const float K[9], const char *refiner_weights,
                     const char *scorer_weights, int max_input_image_height, int max_input_image_width);
 /* The same on HIP device `device` (-1 = the calling thread's current device, which is what fp_create uses).  A model remembers its
@@ -221,7 +227,8 @@ int fp_get_depth_filter(const fp_model *m);
  * Every output pointer is optional (NULL = not wanted; all NULL is an error) and lives in `memspace`.  FP_DEVICE outputs are written
  * by the kernel directly -- visible_mask can go straight into fp_register_ex as the mask of a re-Register;
  * FP_HOST outputs are copied on the model's stream, followed by one synchronisation.  H and W are the uploaded frame's.
- * Works on geometry-only models; refuses a partially uploaded frame like the other stage operators.  Register, Track, their captured
+ * Works on geometry-only models; refuses a partially uploaded frame like the other stage operators, and a model whose K is not a plain
+ * pinhole matrix (see fp_create; so do the six calls below that share its projection).  Register, Track, their captured
  * graphs and every existing kernel are untouched: the call's buffers are its own, allocated at its first use. */
 #define FP_RENDER_NEAR_M 0.01f
 #define FP_RENDER_SNAP_MAX 67108864 /* 2^26 */
