@@ -27,6 +27,7 @@ SYMBOLS = [
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
     "fp_set_depth_filter", "fp_get_depth_filter",
     "fp_render_pose", "fp_render_scene", "fp_pose_errors", "fp_pose_vsd", "fp_refine_depth", "fp_pose_search", "fp_register_depth",
+    "fp_pose_color", "fp_resolve_symmetry",
 ]
 
 
@@ -84,6 +85,13 @@ class FpPoseSearch(C.Structure):
     """struct fp_pose_search of include/foundationpose_amd.h"""
     _fields_ = [("n_facing", C.c_int32), ("n_inlier", C.c_int32), ("n_front", C.c_int32), ("n_behind", C.c_int32), ("n_outside", C.c_int32),
                 ("n_missing", C.c_int32), ("score", C.c_int32), ("best_step", C.c_int32), ("n_points", C.c_int32), ("status", C.c_int32)]
+
+
+class FpPoseColor(C.Structure):
+    """struct fp_pose_color of include/foundationpose_amd.h"""
+    _fields_ = [("n_model", C.c_int32), ("n_visible", C.c_int32), ("n_compared", C.c_int32), ("n_nocolor", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32), ("sum_m", C.c_int64 * 3), ("sum_o", C.c_int64 * 3), ("sum_mm", C.c_int64 * 3), ("sum_oo", C.c_int64 * 3),
+                ("sum_mo", C.c_int64 * 3), ("zncc", C.c_float), ("reserved_f", C.c_float)]
 
 
 class FpDepthRegister(C.Structure):
@@ -200,6 +208,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_refine_depth": [vp, cs, vp, ci, ci, cf, ci, vp, vp],
         "fp_pose_search": [vp, cs, vp, ci, ci, cf, cf, ci, vp],
         "fp_register_depth": [vp, vp, vp, vp, ci, ci, ci, cs, ci, cf, ci, vp, vp],
+        "fp_pose_color": [vp, cs, vp, ci, cf, vp],
+        "fp_resolve_symmetry": [vp, cs, vp, vp, ci, cf, vp, vp, vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

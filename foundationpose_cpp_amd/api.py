@@ -172,6 +172,32 @@ class DepthRegister:
     refine: DepthRefine
 
 
+FP_COLOR_MIN_PIXELS = 32
+FP_COLOR_REFUSED_NEAR, FP_COLOR_REFUSED_RANGE, FP_COLOR_TOO_FEW, FP_COLOR_FLAT = 1, 2, 4, 8
+
+
+@dataclasses.dataclass(frozen=True)
+class PoseColor:
+    """struct fp_pose_color (include/foundationpose_amd.h): how the model's unshaded colour under a pose agrees with the uploaded frame's
+    RGB over the visible model pixels; pixel counts of the frame and exact integer sums per channel R, G, B"""
+    n_model: int
+    n_visible: int        # n_compared + n_nocolor
+    n_compared: int
+    n_nocolor: int        # visible pixels whose texture coordinate or colour is not a number
+    status: int           # FP_COLOR_REFUSED_NEAR | FP_COLOR_REFUSED_RANGE | FP_COLOR_TOO_FEW | FP_COLOR_FLAT
+    sum_m: tuple          # the model's values (0..255)
+    sum_o: tuple          # the frame's bytes
+    sum_mm: tuple
+    sum_oo: tuple
+    sum_mo: tuple
+    zncc: float           # zero-mean normalised cross-correlation, means per channel, one gain; 0 when a status bit is set
+
+
+def _pose_color(r):
+    return PoseColor(r.n_model, r.n_visible, r.n_compared, r.n_nocolor, r.status, tuple(r.sum_m), tuple(r.sum_o), tuple(r.sum_mm), tuple(r.sum_oo),
+                     tuple(r.sum_mo), float(r.zncc))
+
+
 def _pose_search(r):
     return PoseSearch(r.n_facing, r.n_inlier, r.n_front, r.n_behind, r.n_outside, r.n_missing, r.score, r.best_step, r.n_points, r.status)
 
@@ -618,6 +644,29 @@ class FoundationPose:
             return False, None, None
         return True, from_colmajor(out), DepthRegister(rec.hypothesis, rec.n_hypotheses, rec.n_candidates, rec.rank_key, _pose_search(rec.search),
                                                        _depth_refine(rec.refine))
+
+    # ---- colour agreement and symmetry resolution (include/foundationpose_amd.h "colour agreement") --
+    def pose_color(self, target_name: str, poses, tol_m: float = 0.005):
+        """fp_pose_color: the model's unshaded colour (texture, or vertex colours after set_vertex_colors) under poses [N,4,4] against the
+        uploaded frame's RGB over the visible model pixels -> [PoseColor] * N.  tol_m: the occlusion tolerance of render_pose.  A pose
+        that would need a clipper does not fail the call: its record carries the status bit and zncc 0."""
+        e = to_colmajor(np.asarray(poses, np.float32).reshape(-1, 4, 4))
+        out = (_lib.FpPoseColor * max(len(e), 1))()
+        self._must(self._L.fp_pose_color(self._h, target_name.encode(), _p(e), len(e), tol_m, out))
+        return [_pose_color(r) for r in out[:len(e)]]
+
+    def resolve_symmetry(self, target_name: str, pose, symmetries, tol_m: float = 0.005):
+        """fp_resolve_symmetry: of the equivalents pose * S_s of a symmetric object's pose [4,4] the one the picture shows -> (pose [4,4],
+        best_sym, [PoseColor] * (S + 1)).  symmetries: [S,4,4] in the MESH frame as for pose_errors (None = none); the identity is always
+        symmetry 0.  Raises when no equivalent has a usable record (an untextured model)."""
+        e = to_colmajor(np.asarray(pose, np.float32).reshape(4, 4))
+        s = None if symmetries is None or len(symmetries) == 0 else to_colmajor(np.asarray(symmetries, np.float32).reshape(-1, 4, 4))
+        n = 0 if s is None else len(s)
+        out_p = np.zeros(16, np.float32)
+        best = C.c_int(-1)
+        recs = (_lib.FpPoseColor * (n + 1))()
+        self._must(self._L.fp_resolve_symmetry(self._h, target_name.encode(), _p(e), _p(s), n, tol_m, _p(out_p), C.byref(best), recs))
+        return from_colmajor(out_p), best.value, [_pose_color(r) for r in recs]
 
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):

@@ -201,10 +201,12 @@ void roctx_pop() { if (roctx_api().pop) (void)roctx_api().pop(); }
 #ifdef FP_TEST_HOOKS
 static int g_icp_chunk = 0;   // fpt_icp_set_chunk: poses per chunk of fp_refine_depth (0: sized by ICP_SCRATCH_BYTES); only the test build changes it
 static int g_vsd_chunk = 0;   // fpt_vsd_set_chunk: poses per chunk of fp_pose_vsd (0: sized by VSD_SCRATCH_BYTES); only the test build changes it
+static int g_color_chunk = 0; // fpt_color_set_chunk: poses per chunk of fp_pose_color (0: sized by COLOR_SCRATCH_BYTES); only the test build changes it
 static int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;   // A/B (fpt_set_calib_opts): steps of the 8-bit calibration
 #else
 static constexpr int g_icp_chunk = 0;
 static constexpr int g_vsd_chunk = 0;
+static constexpr int g_color_chunk = 0;
 static constexpr int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;
 #endif
 
@@ -344,7 +346,7 @@ static void dev_free(T *&p) {
   if (p) (void)hipFree(p);
   p = nullptr;
 }
-// Device scratch of the stage operators (a model's st_*, fr_*, sc_*, pe_*, vsd_*, icp_*, ps_* blocks, used on stream s): grow-only,
+// Device scratch of the stage operators (a model's st_*, fr_*, sc_*, pe_*, vsd_*, icp_*, ps_*, col_* blocks, used on stream s): grow-only,
 // and nothing of the stream may still read a block that is replaced.  No captured graph reads these blocks, so unlike
 // ensure_capacity / ensure_window this leaves the allocation epoch alone.
 template <typename T>
@@ -536,8 +538,8 @@ struct fp_model {
   // record.  No buffer of its own: Register's sampler leaves the whole frame's D' there anyway, Track fills its window of it.
   bool dfilt_on = false;
 
-  // Scratch of the stage operators (DESIGN.md sections 4.8 - 4.13: fp_render_pose, fp_render_scene, fp_pose_errors, fp_pose_vsd,
-  // fp_refine_depth, fp_pose_search).  Nothing below is allocated before the first call that needs it, and every block only grows
+  // Scratch of the stage operators (DESIGN.md sections 4.8 - 4.14: fp_render_pose, fp_render_scene, fp_pose_errors, fp_pose_vsd,
+  // fp_refine_depth, fp_pose_search, fp_pose_color).  Nothing below is allocated before the first call that needs it, and every block only grows
   // (grow_scratch).  One rule makes all of it safe, and lets the calls share the st_* blocks: every one of these calls holds the
   // SerialGuard from its first line to its last and leaves the stream synchronised, so no two of them are ever live together
   // (fp_register_depth runs the search and then the ICP, each to its end); and no captured graph reads any of these blocks, so
@@ -581,6 +583,11 @@ struct fp_model {
   size_t icp_param_cap = 0, icp_acc_cap = 0;
   std::vector<IcpParams> icp_params_host;  // (owned by the model, like st_poses_host)
   std::vector<unsigned long long> icp_acc_host;
+
+  // colour agreement (fp_pose_color): likewise
+  unsigned long long *col_acc = nullptr;   // [col_acc_cap] accumulators [N, COLOR_WORDS] | refusal words [N] (32-bit, behind the accumulators)
+  size_t col_acc_cap = 0;
+  std::vector<unsigned long long> col_acc_host;
 
   // depth search (fp_pose_search): likewise
   SearchRec *ps_recs = nullptr;            // [ps_rec_cap] the records of the call's poses
@@ -885,6 +892,8 @@ extern "C" {
 void fpt_vsd_set_chunk(int poses) { g_vsd_chunk = poses > 0 ? poses : 0; }
 // the same for fp_refine_depth
 void fpt_icp_set_chunk(int poses) { g_icp_chunk = poses > 0 ? poses : 0; }
+// the same for fp_pose_color
+void fpt_color_set_chunk(int poses) { g_color_chunk = poses > 0 ? poses : 0; }
 void fpt_set_calib_opts(int sweeps, int tok, int out) { g_calib_sweeps = sweeps; g_calib_tok = tok; g_calib_out = out; }
 // A/B hook: hipGraph replay of the Track / Register bodies on or off for one model
 int fpt_model_use_graphs(fp_model *m, int on) {
@@ -1331,6 +1340,7 @@ static void destroy_model_impl(fp_model *m) {
   delete m->sc_table_host; m->sc_table_host = nullptr;
   dev_free(m->pe_mats); dev_free(m->pe_pairs); dev_free(m->pe_sums);
   dev_free(m->ps_recs); dev_free(m->icp_params); dev_free(m->icp_acc); dev_free(m->vsd_words); dev_free(m->vsd_plane);
+  dev_free(m->col_acc);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
@@ -2835,6 +2845,19 @@ void rigid_to_f32(const Rigid &x, float *o) {
 bool pose_error_matrix_ok(const float *p) {
   return matrix_finite(p) && std::fabs(p[12]) <= 1000.0f && std::fabs(p[13]) <= 1000.0f && std::fabs(p[14]) <= 1000.0f;
 }
+// the symmetries of a call in the CENTRED mesh's frame, the identity first: x' = R_s (x + c) + t_s - c, host, double (fp_pose_errors and
+// fp_resolve_symmetry).  symmetries: S column-major 4 x 4 matrices of the mesh frame.
+std::vector<Rigid> conjugated_symmetries(const DeviceMesh &mesh, const float *symmetries, int S) {
+  std::vector<Rigid> sym((size_t)S + 1);
+  sym[0] = Rigid{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
+  const double c[3] = {(double)mesh.center[0], (double)mesh.center[1], (double)mesh.center[2]};
+  for (int s = 0; s < S; s++) {
+    Rigid x = rigid_from_colmajor(symmetries + (size_t)s * 16);
+    for (int r = 0; r < 3; r++) x.t[r] = (((x.r[r * 3] * c[0] + x.r[r * 3 + 1] * c[1]) + x.r[r * 3 + 2] * c[2]) + x.t[r]) - c[r];
+    sym[(size_t)s + 1] = x;
+  }
+  return sym;
+}
 long long pose_error_vs(int V, long long step) { return ((long long)V + step - 1) / step; }
 bool pose_error_adds_fits(int N, int V, long long step) {
   const unsigned __int128 vs = (unsigned __int128)pose_error_vs(V, step);
@@ -2880,14 +2903,7 @@ int fp_pose_errors(fp_model *m, const char *target_name, const float *est_poses,
   FP_CHECK(n_pairs * Vs <= FP_POSE_ERROR_MAX_PAIRS / 64, "[FoundationPose] fp_pose_errors: " + std::to_string(N) + " poses x " + std::to_string(S1) + " symmetries x " +
                std::to_string(Vs) + " vertices is above FP_POSE_ERROR_MAX_PAIRS / 64 = " + std::to_string((long long)FP_POSE_ERROR_MAX_PAIRS / 64) + " transformed vertex pairs: raise vertex_step");
   // host, double: the conjugated symmetries x' = R_s (x + c) + t_s - c (identity first), the composites G S_s and D = E^-1 G
-  std::vector<Rigid> sym((size_t)S1);
-  sym[0] = Rigid{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
-  const double c[3] = {(double)mesh.center[0], (double)mesh.center[1], (double)mesh.center[2]};
-  for (int s = 0; s < S; s++) {
-    Rigid x = rigid_from_colmajor(symmetries + (size_t)s * 16);
-    for (int r = 0; r < 3; r++) x.t[r] = (((x.r[r * 3] * c[0] + x.r[r * 3 + 1] * c[1]) + x.r[r * 3 + 2] * c[2]) + x.t[r]) - c[r];
-    sym[(size_t)s + 1] = x;
-  }
+  const std::vector<Rigid> sym = conjugated_symmetries(mesh, symmetries, S);
   const size_t mat_floats = ((size_t)2 * N + (size_t)n_pairs) * 12;
   m->pe_mats_host.resize(mat_floats);
   float *est_h = m->pe_mats_host.data(), *rel_h = est_h + (size_t)N * 12, *comp_h = rel_h + (size_t)N * 12;
@@ -3443,6 +3459,148 @@ int fp_register_depth(fp_model *m, const void *rgb, const void *depth, const voi
     out->search = found[(size_t)order[(size_t)win]];
     out->refine = recs[(size_t)win];
   }
+  return 0;
+} FP_CATCH_INT
+
+// ---- colour agreement and symmetry resolution
+static_assert(sizeof(fp_pose_color_t) == 152, "fp_pose_color: six 32-bit words, 15 64-bit sums, two floats");
+static_assert(fp::COLOR_SUMS == 15 && fp::COLOR_COUNTS == 4, "include/foundationpose_amd.h: the sums of fp_pose_color are those of fp_internal.h");
+static_assert(FP_COLOR_REFUSED_NEAR == FRAME_RENDER_FLAG_NEAR && FP_COLOR_REFUSED_RANGE == FRAME_RENDER_FLAG_RANGE,
+              "include/foundationpose_amd.h: the refusal bits of fp_pose_color are the refusal bits of the vertex rule");
+int fp_pose_color(fp_model *m, const char *target_name, const float *poses, int N, float tol_m, fp_pose_color_t *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && poses && out, "[FoundationPose] fp_pose_color: invalid arguments");
+  if (batch_size_ok("fp_pose_color", N)) return 1;
+  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_pose_color: tol_m must be finite and >= 0 (metres)");
+  Target *t = nullptr;
+  if (stage_target(m, "fp_pose_color", target_name, &t) || matrices_finite_ok("fp_pose_color", "poses", poses, N) || frame_ready(m, "fp_pose_color", true))
+    return 1;
+  const DeviceMesh &mesh = t->mesh;
+  const int H = m->H, W = m->W, V = mesh.V;
+  FP_CHECK((long long)H * W < (1ll << 26), "[FoundationPose] fp_pose_color: a frame of 2^26 pixels or more (the sums are sized for fewer)");
+  FP_CHECK(mesh.vcol || (mesh.tex && mesh.uvs && mesh.TH > 0 && mesh.TW > 0), "[FoundationPose] fp_pose_color: the target has neither a texture nor vertex colours");
+  const int ntx = scene_tiles_x(W);
+  const long long F = std::max(mesh.F, 1);
+  // host: the poses in the kernels' form, every pose's tiles, the work they stand for (one evaluation, as fp_refine_depth counts it)
+  m->st_poses_host.resize((size_t)N);
+  std::vector<FrameTileBound> bounds((size_t)N);
+  long long work = 0;
+  for (int i = 0; i < N; i++) {
+    m->st_poses_host[(size_t)i] = frame_pose(m, poses + (size_t)i * 16);
+    bounds[(size_t)i] = frame_tile_bound(m->st_poses_host[(size_t)i], (double)mesh.max_norm, H, W);
+    work += bound_tiles(bounds[(size_t)i]) * F;
+  }
+  FP_CHECK(work <= FP_COLOR_MAX_WORK, "[FoundationPose] fp_pose_color: " + std::to_string(N) + " poses of " + std::to_string(mesh.F) + " faces walk " + std::to_string(work) +
+               " faces over their 32 x 32 px tiles, above FP_COLOR_MAX_WORK = " + std::to_string((long long)FP_COLOR_MAX_WORK) + ": pass fewer poses per call");
+  // chunks of poses: the snapped vertices of a chunk stay below COLOR_SCRATCH_BYTES, one pose at least
+  const int chunk = stage_chunk((size_t)std::max(V, 1) * sizeof(int4), COLOR_SCRATCH_BYTES, N, g_color_chunk);
+  std::vector<int2> &items = m->st_items_host;
+  items.clear();
+  std::vector<size_t> chunk_end;   // items.size() after each chunk
+  for (int i = 0; i < N; i++) {
+    append_tile_items(items, i % chunk, bounds[(size_t)i], ntx);
+    if ((i + 1) % chunk == 0 || i + 1 == N) chunk_end.push_back(items.size());
+  }
+  hipStream_t s = m->stream;
+  const size_t acc_words = (size_t)N * COLOR_WORDS + ((size_t)N + 1) / 2;
+  if (grow_stage(m, (size_t)V * chunk, 0, (size_t)N, items.size()) || grow_scratch(s, m->col_acc, m->col_acc_cap, acc_words)) return 1;
+  unsigned long long *acc = m->col_acc;
+  int *flag_d = reinterpret_cast<int *>(acc + (size_t)N * COLOR_WORDS);
+  m->col_acc_host.assign(acc_words, 0ull);
+  FP_HIP_OK(hipMemcpyAsync(m->st_poses, m->st_poses_host.data(), (size_t)N * sizeof(FramePose), hipMemcpyHostToDevice, s));
+  if (!items.empty()) FP_HIP_OK(hipMemcpyAsync(m->st_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+  FP_HIP_OK(hipMemsetAsync(acc, 0, acc_words * sizeof(unsigned long long), s));   // accumulators and refusal words together
+  size_t first = 0;
+  for (size_t c = 0; c < chunk_end.size(); c++) {
+    const int p0 = (int)c * chunk, cn = std::min(chunk, N - p0);
+    {
+      ProfScope ps(&m->prof, s, "color_vertex", 0, (double)cn * V * (12.0 + 16.0));
+      launch_pose_vertices(s, "color_vertex", mesh, m->st_poses + p0, cn, nullptr, 0, m->st_snap, nullptr, flag_d + p0, nullptr);
+      FP_HIP_OK(hipGetLastError());
+    }
+    if (chunk_end[c] > first) {
+      ProfScope ps(&m->prof, s, "color_tile", 0, (double)(chunk_end[c] - first) * (double)F * 60.0);
+      if (launch_item_runs(first, chunk_end[c], FP_COLOR_MAX_WORK, F, [&](size_t at, int cnt) {
+            launch_color_tiles(s, mesh, m->st_snap, m->st_items + at, cnt, m->rgb, m->depth, H, W, tol_m, flag_d, p0, acc);
+            FP_HIP_OK(hipGetLastError());
+            return 0;
+          }))
+        return 1;
+      first = chunk_end[c];
+    }
+  }
+  FP_HIP_OK(hipMemcpyAsync(m->col_acc_host.data(), acc, acc_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  FP_HIP_OK(hipStreamSynchronize(s));
+  const int *flag_h = reinterpret_cast<const int *>(m->col_acc_host.data() + (size_t)N * COLOR_WORDS);
+  std::vector<fp_pose_color_t> recs((size_t)N);
+  for (int i = 0; i < N; i++) {
+    fp_pose_color_t r = {};
+    r.status = flag_h[i];
+    if (!r.status) {
+      const unsigned long long *w = m->col_acc_host.data() + (size_t)i * COLOR_WORDS;
+      for (int ch = 0; ch < 3; ch++) {
+        r.sum_m[ch] = (int64_t)w[ch]; r.sum_o[ch] = (int64_t)w[3 + ch]; r.sum_mm[ch] = (int64_t)w[6 + ch];
+        r.sum_oo[ch] = (int64_t)w[9 + ch]; r.sum_mo[ch] = (int64_t)w[12 + ch];
+      }
+      r.n_model = (int32_t)w[15]; r.n_visible = (int32_t)w[16]; r.n_compared = (int32_t)w[17]; r.n_nocolor = (int32_t)w[18];
+      if (r.n_compared < FP_COLOR_MIN_PIXELS) r.status |= FP_COLOR_TOO_FEW;
+      else {
+        const double n = (double)r.n_compared;
+        double cov = 0, var_m = 0, var_o = 0;
+        for (int ch = 0; ch < 3; ch++) {
+          const double sm = (double)r.sum_m[ch], so = (double)r.sum_o[ch];
+          cov += (double)r.sum_mo[ch] - sm * so / n;
+          var_m += (double)r.sum_mm[ch] - sm * sm / n;
+          var_o += (double)r.sum_oo[ch] - so * so / n;
+        }
+        if (!(var_m > 0.0) || !(var_o > 0.0)) r.status |= FP_COLOR_FLAT;
+        else r.zncc = (float)(cov / std::sqrt(var_m * var_o));
+      }
+    }
+    recs[(size_t)i] = r;
+  }
+  std::memcpy(out, recs.data(), recs.size() * sizeof(fp_pose_color_t));
+  return 0;
+} FP_CATCH_INT
+
+int fp_resolve_symmetry(fp_model *m, const char *target_name, const float pose[16], const float *symmetries, int S, float tol_m, float out_pose[16],
+                        int *best_sym, fp_pose_color_t *records) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && pose && out_pose, "[FoundationPose] fp_resolve_symmetry: invalid arguments");
+  FP_CHECK(S >= 0 && S <= FP_MAX_SYMMETRIES, "[FoundationPose] fp_resolve_symmetry: " + std::to_string(S) + " symmetries (0..FP_MAX_SYMMETRIES = " + std::to_string(FP_MAX_SYMMETRIES) + ")");
+  FP_CHECK(S == 0 || symmetries, "[FoundationPose] fp_resolve_symmetry: invalid arguments (S > 0 without symmetries)");
+  Target *t = nullptr;
+  if (stage_target(m, "fp_resolve_symmetry", target_name, &t)) return 1;
+  FP_CHECK(matrix_finite(pose), "[FoundationPose] fp_resolve_symmetry: a non-finite entry in pose");
+  for (int i = 0; i < S; i++)
+    FP_CHECK(pose_error_matrix_ok(symmetries + (size_t)i * 16),
+             "[FoundationPose] fp_resolve_symmetry: a non-finite entry or a translation beyond +-1000 m in symmetries[" + std::to_string(i) + "]");
+  // 1. the equivalents: host, double, rounded once; E_0 is the pose itself
+  const std::vector<Rigid> sym = conjugated_symmetries(t->mesh, symmetries, S);
+  const Rigid P = rigid_from_colmajor(pose);
+  std::vector<float> eq(((size_t)S + 1) * 16);
+  std::memcpy(eq.data(), pose, 64);
+  for (int s = 1; s <= S; s++) {
+    const Rigid E = rigid_mul(P, sym[(size_t)s]);
+    float *o = eq.data() + (size_t)s * 16;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) o[c * 4 + r] = (float)E.r[r * 3 + c];
+      o[12 + r] = (float)E.t[r];
+    }
+    o[3] = pose[3]; o[7] = pose[7]; o[11] = pose[11]; o[15] = pose[15];
+  }
+  // 2. their records
+  std::vector<fp_pose_color_t> recs((size_t)S + 1);
+  if (fp_pose_color(m, target_name, eq.data(), S + 1, tol_m, recs.data())) return 1;
+  // 3. the winner
+  int win = -1;
+  for (int s = 0; s <= S; s++)
+    if (recs[(size_t)s].status == 0 && (win < 0 || recs[(size_t)s].zncc > recs[(size_t)win].zncc)) win = s;
+  FP_CHECK(win >= 0, "[FoundationPose] fp_resolve_symmetry: no usable record: every one of the " + std::to_string(S + 1) +
+               " equivalents is refused, shows fewer than FP_COLOR_MIN_PIXELS pixels or has no colour variance (an untextured model?)");
+  std::memcpy(out_pose, eq.data() + (size_t)win * 16, 64);
+  if (best_sym) *best_sym = win;
+  if (records) std::memcpy(records, recs.data(), recs.size() * sizeof(fp_pose_color_t));
   return 0;
 } FP_CATCH_INT
 

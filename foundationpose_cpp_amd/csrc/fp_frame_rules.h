@@ -1,9 +1,9 @@
 // The raster rules of the frame-resolution renderers, each written once: fp_render_pose (fp_frame_render.hip),
-// fp_render_scene (fp_scene_render.hip, section 4.9), fp_pose_vsd (fp_pose_vsd.hip, section 4.11) and fp_refine_depth (fp_pose_icp.hip,
-// section 4.12) promise the same pixels because their kernels call these functions; and the tile engine around the rules, which the
-// kernels that rasterise one mesh under one pose share.  Device code only, for files compiled with -ffp-contract=off: every f32
-// operation below is separately rounded, in the order written, and tests/frame_render_ref.py restates it operation by operation.  The
-// 160x160 crop rasteriser of fp_geometry.hip has rules of its own.
+// fp_render_scene (fp_scene_render.hip, section 4.9), fp_pose_vsd (fp_pose_vsd.hip, section 4.11), fp_refine_depth (fp_pose_icp.hip,
+// section 4.12) and fp_pose_color (fp_pose_color.hip, section 4.14) promise the same pixels because their kernels call these functions;
+// and the tile engine around the rules, which the kernels that rasterise one mesh under one pose share.  Device code only, for files
+// compiled with -ffp-contract=off: every f32 operation below is separately rounded, in the order written, and
+// tests/frame_render_ref.py restates it operation by operation.  The 160x160 crop rasteriser of fp_geometry.hip has rules of its own.
 #pragma once
 #include "fp_internal.h"
 
@@ -82,9 +82,35 @@ __device__ __forceinline__ void frame_tri_walk(const int4 &a, const int4 &b, con
   }
 }
 
+// perspective-correct weights of the sample point (16 px, 16 py) in the triangle a, b, c that won the pixel with depth z (the key's):
+// the edge functions as frame_tri_walk forms them (exact 64-bit integers, so stepping or recomputing gives the same values), the affine
+// weights w_k = e_k / A as there, then g_k = (w_k / z_k) * z with z_k the corner depths.  An attribute q with corner values q_k is
+// (g0 * q0 + g1 * q1) + g2 * q2 at the pixel (fp_pose_color).  The triangle has an area: it covered the sample.
+struct FrameWeights {
+  float g0, g1, g2;
+};
+__device__ __forceinline__ FrameWeights frame_tri_weights(const int4 &a, const int4 &b, const int4 &c, int px, int py, float z) {
+  const long long area = frame_tri_area(a, b, c);
+  const long long s = area < 0 ? -1 : 1, A = s * area;
+  const long long d0x = s * (c.x - b.x), d0y = s * (c.y - b.y);
+  const long long d1x = s * (a.x - c.x), d1y = s * (a.y - c.y);
+  const long long d2x = s * (b.x - a.x), d2y = s * (b.y - a.y);
+  const long long sx = 16ll * px, sy = 16ll * py;
+  const long long e0 = d0x * (sy - b.y) - d0y * (sx - b.x);
+  const long long e1 = d1x * (sy - c.y) - d1y * (sx - c.x);
+  const long long e2 = d2x * (sy - a.y) - d2y * (sx - a.x);
+  const float fA = (float)A;
+  const float w0 = (float)e0 / fA, w1 = (float)e1 / fA, w2 = (float)e2 / fA;
+  FrameWeights g;
+  g.g0 = (w0 / __int_as_float(a.z)) * z;
+  g.g1 = (w1 / __int_as_float(b.z)) * z;
+  g.g2 = (w2 / __int_as_float(c.z)) * z;
+  return g;
+}
+
 // ---- the pose-tile engine: what every kernel that rasterises ONE mesh under one pose into a FRAME_RENDER_TILE x FRAME_RENDER_TILE
-// LDS z-buffer does before its own pixel loop (frame_raster_kernel, vsd_tile_kernel, icp_tile_kernel): the tile's rectangle, the
-// z-buffer's keys, the walk over all faces.  scene_raster_kernel walks per-tile lists of several objects instead of all faces of
+// LDS z-buffer does before its own pixel loop (frame_raster_kernel, vsd_tile_kernel, icp_tile_kernel, color_tile_kernel): the tile's
+// rectangle, the z-buffer's keys, the walk over all faces.  scene_raster_kernel walks per-tile lists of several objects instead of all faces of
 // one; it shares the rectangle and the keys.
 
 // the pixels [X0..X1] x [Y0..Y1] of tile (bx, by), cut to the H x W frame

@@ -443,6 +443,16 @@ struct IcpParams {
 void launch_icp_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const float4 *cam, const int2 *items, int n_items, const float *depth,
                       int H, int W, const IcpParams *params, const int *flags, int pose0, unsigned long long *acc);
 
+// colour agreement (fp_pose_color; fp_pose_color.hip).  The renderings follow section 4.8's rules through
+// fp_frame_rules.h; a pose's accumulator is COLOR_WORDS 64-bit words: per channel R, G, B the sums of m, o, m m, o o, m o (m the model's
+// value, o the frame's byte; 15 words in that order), then n_model, n_visible, n_compared, n_nocolor.
+constexpr int COLOR_SUMS = 15, COLOR_COUNTS = 4, COLOR_WORDS = COLOR_SUMS + COLOR_COUNTS;
+constexpr size_t COLOR_SCRATCH_BYTES = 128u << 20;  // snapped vertices of one chunk of poses stay below this
+// items [n_items] = {pose of the chunk, tile}: acc[(pose0 + pose) COLOR_WORDS ..] += the tile's sums and counts; an item whose
+// flags[pose0 + pose] is not zero does nothing.  The colour source is the mesh's current one (vcol, else the texture).
+void launch_color_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const int2 *items, int n_items, const uint8_t *rgb, const float *depth,
+                        int H, int W, float tol_m, const int *flags, int pose0, unsigned long long *acc);
+
 // depth search (fp_pose_search; fp_pose_search.hip): per pose the sampled vertices and their normals against the
 // frame's raw depth at n_steps pushes along the ray of the pose's origin; a record is ten 32-bit words, fp_pose_search_t's layout.
 constexpr int SEARCH_THREADS = 256;

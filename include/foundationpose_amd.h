@@ -93,8 +93,8 @@ const uint8_t *fp_mesh_vertex_colors(const fp_loaded_mesh *mesh);
  * refiner_weights / scorer_weights: paths of packed weight files (tools/pack_weights.py; replaces the TensorRT
  * engines of simple_tests/src/test_foundationpose.cpp:13-14).  NULL = geometry-only model (NN entry points fail).
  * K: the 3x3 intrinsics, row-major; all nine entries are copied.  Register, Track and the stage operators of their path take K as the
- * reference does, as a matrix, so a skew K[1] is honoured there.  The seven frame-resolution calls -- fp_render_pose, fp_render_scene,
- * fp_pose_errors, fp_pose_vsd, fp_refine_depth, fp_pose_search, fp_register_depth -- read fx = K[0], fy = K[4], cx = K[2], cy = K[5]
+ * reference does, as a matrix, so a skew K[1] is honoured there.  The nine frame-resolution calls -- fp_render_pose, fp_render_scene,
+ * fp_pose_errors, fp_pose_vsd, fp_refine_depth, fp_pose_search, fp_register_depth, fp_pose_color, fp_resolve_symmetry -- read fx = K[0], fy = K[4], cx = K[2], cy = K[5]
  * only and REFUSE a model whose K is not a plain pinhole matrix (K[1] == K[3] == K[6] == K[7] == 0, K[8] == 1, K[0] and K[4] finite and
  * positive, K[2] and K[5] finite): on the host, before anything is uploaded or launched, with a message that names the entry, their
  * outputs untouched.  fx != fy and a principal point anywhere are fine everywhere. */
@@ -499,6 +499,68 @@ int fp_register_depth(fp_model *m, const void *rgb, const void *depth, const voi
                       const char *target_name, int top_k /* 0 = 16, at most 64 */, float tol_m /* 0 = 0.005 */,
                       int icp_iterations /* 0 = 15, at most FP_ICP_MAX_ITERATIONS */,
                       float out_pose[16], fp_depth_register_t *out /* may be NULL */);
+
+/* ---- colour agreement: does the picture agree with N poses? (new; the reference has no counterpart) ----
+ * fp_pose_color compares, over the visible model pixels of each pose, the model's UNSHADED colour with the uploaded frame's RGB: the only
+ * frame-resolution call that reads the colour.  Poses as in fp_pose_errors (column-major 4x4, centred-mesh -> camera); the frame is the
+ * uploaded one, its RGB and its RAW depth whether fp_set_depth_filter is on or off; K is the model's (a plain pinhole matrix).  The
+ * colour source is the target's current one: the texture, or the vertex colours after fp_set_vertex_colors.  DESIGN.md section 4.14 has
+ * the rules; every f32 operation is separately rounded.  Per pixel (c, r) of a pose:
+ *   triangle, z  exactly fp_render_pose's tri_id and model_depth; n_model counts these pixels
+ *   visible      !(D >= 0.001f && D < z - tol_m), fp_render_pose's visible_mask (missing depth, and NaN, hide nothing); n_visible
+ *   weights      a, b, c the winning triangle's snapped corners, e_0 e_1 e_2 its edge functions at (16 c, 16 r) and A its doubled area,
+ *                all exact integers as the rasteriser forms them: w_k = (float)e_k / (float)A, g_k = (w_k / z_k) * z, z_k the corner depths
+ *   texture      U = (g_0 * u_0 + g_1 * u_1) + g_2 * u_2, V likewise from the stored (u, 1 - v); fu = U - floorf(U);
+ *                tx = min((int)(fu * (float)TW), TW - 1), ty likewise with TH: the nearest texel, with wrap.  A U or V that is not finite
+ *                gives the pixel no colour (n_nocolor): it is not compared and nothing is read
+ *   vertex col.  per channel v = (g_0 * c_0 + g_1 * c_1) + g_2 * c_2, c_k the corner's byte as float; the model's value is
+ *                (int)rintf(fminf(fmaxf(v, 0), 255)); a NaN in any channel gives the pixel no colour
+ *   compared     the visible pixels with a colour (n_compared): per channel R, G, B the exact integer sums of m, o, m m, o o and m o, m the
+ *                model's value and o the frame's byte, both 0..255
+ * On the host, in double, with n = n_compared: cov = sum_ch (sum_mo - sum_m sum_o / n), var_m = sum_ch (sum_mm - sum_m^2 / n), var_o
+ * likewise, zncc = cov / sqrt(var_m var_o), rounded once.  The means are removed per channel and the gain is shared, so an illumination
+ * gain, or an offset per channel, leaves the value as it is.  zncc is 0 with FP_COLOR_TOO_FEW when n < FP_COLOR_MIN_PIXELS, and 0 with
+ * FP_COLOR_FLAT when either variance is <= 0 (the 2 x 2 grey default texture is this case).
+ * Everything but zncc is an integer count or sum, so pose i's record is byte-identical alone, in any batch and from call to call.
+ * A refused pose (a vertex at z < FP_RENDER_NEAR_M, or beyond FP_RENDER_SNAP_MAX: fp_render_pose would fail) does not fail the call:
+ * its counts and sums are 0, its zncc is 0, its status bit is set.
+ * Refused with an error before anything is launched and before `out` is written: an unknown target, N outside 1..FP_MAX_BATCH, a tol_m
+ * that is not finite or is negative, a non-finite matrix entry, no frame, a partial frame, a frame of 2^26 pixels or more, a pending
+ * Track, and more than FP_COLOR_MAX_WORK faces walked: the sum over the poses' (pose, 32 x 32 px tile) items of F.  No launch covers
+ * more than a tenth of it.  Stream-ordered on the model's stream with one synchronisation at the end; Register, Track, their captured
+ * graphs and every existing kernel are untouched: the call's buffers are its own, allocated at its first use, grow-only. */
+#define FP_COLOR_MIN_PIXELS 32
+#define FP_COLOR_REFUSED_NEAR 1      /* status bits of a record */
+#define FP_COLOR_REFUSED_RANGE 2
+#define FP_COLOR_TOO_FEW 4           /* n_compared < FP_COLOR_MIN_PIXELS */
+#define FP_COLOR_FLAT 8              /* the model's or the frame's values have no variance over the compared pixels */
+#define FP_COLOR_MAX_WORK 330000000000LL /* faces walked by one call: 0.99 s at the 3.32e11 faces/s measured for 252 poses */
+typedef struct fp_pose_color {
+  int32_t n_model, n_visible, n_compared, n_nocolor;   /* frame pixels; n_visible == n_compared + n_nocolor */
+  int32_t status, reserved;
+  int64_t sum_m[3], sum_o[3], sum_mm[3], sum_oo[3], sum_mo[3];  /* per channel R, G, B over the compared pixels */
+  float   zncc;            /* host, double, rounded once; 0 when a status bit is set */
+  float   reserved_f;
+} fp_pose_color_t;
+int fp_pose_color(fp_model *m, const char *target_name, const float *poses, int N, float tol_m,
+                  fp_pose_color_t *out /* host [N] */);
+
+/* ---- symmetry resolution: which equivalent of a pose does the picture show? (new) ----
+ * fp_resolve_symmetry takes a pose of a symmetric object -- fp_register_depth's answer is one of its equivalents -- and returns the
+ * equivalent whose colour agrees best with the frame.  It composes calls of this header and gives, byte for byte, what they give:
+ *   1. the equivalents E_s = pose * S'_s, s = 0..S: symmetry 0 is the identity (E_0 is `pose` bit for bit), the caller's S column-major
+ *      4x4 matrices of the MESH frame follow as 1..S, conjugated with the target's centre exactly as fp_pose_errors conjugates them;
+ *      formed on the host in double, rounded to f32 once; the fourth row is that of `pose`
+ *   2. fp_pose_color over the S + 1 equivalents with tol_m
+ *   3. the winner: the largest zncc among the records with status 0, ties to the lower index.  No record with status 0 (an untextured
+ *      model ends here): the call fails and says so; out_pose and best_sym are not written.
+ * S in 0..FP_MAX_SYMMETRIES (symmetries may be NULL when S is 0); a non-finite entry or a translation beyond +-1000 m in a symmetry is
+ * refused as by fp_pose_errors; otherwise the call takes the guards of the call it composes.  Continuous symmetries arrive discretised,
+ * as BOP's models_info.json has them.  records, when not NULL, receives the S + 1 records of step 2. */
+int fp_resolve_symmetry(fp_model *m, const char *target_name, const float pose[16],
+                        const float *symmetries /* S column-major 4x4, MESH frame; NULL = none */, int S,
+                        float tol_m, float out_pose[16], int *best_sym /* may be NULL */,
+                        fp_pose_color_t *records /* host [S + 1], may be NULL */);
 
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 

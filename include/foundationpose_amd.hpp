@@ -266,6 +266,24 @@ public:
                                 out_pose_in_mesh.data(), record));
   }
 
+  // colour agreement (foundationpose_amd.h "colour agreement"): the model's unshaded colour (texture, or vertex colours) under `poses`
+  // against the uploaded frame's RGB over the visible model pixels; `out` gets the integer sums and the zncc of each.  tol_m: the occlusion
+  // tolerance of RenderPose.  A pose that would need a clipper gets its status bit and zncc 0, not an error.
+  bool PoseColor(const std::string &target_name, const std::vector<Pose> &poses, std::vector<fp_pose_color_t> &out, float tol_m = 0.005f) {
+    out.resize(poses.size());
+    return ok(fp_pose_color(h_, target_name.c_str(), poses.empty() ? nullptr : poses[0].data(), (int)poses.size(), tol_m, out.data()));
+  }
+
+  // symmetry resolution (foundationpose_amd.h "symmetry resolution"): of the equivalents pose * S_s of a symmetric object's pose the one
+  // whose colour agrees best with the frame.  symmetries: mesh frame, already discretised, as for PoseErrors; the identity is always
+  // symmetry 0 of best_sym.  `records` (may be null) gets the S + 1 records.  Fails when no equivalent has a usable record (untextured).
+  bool ResolveSymmetry(const std::string &target_name, const Pose &pose, const std::vector<Pose> &symmetries, Pose &out_pose, int *best_sym = nullptr,
+                       std::vector<fp_pose_color_t> *records = nullptr, float tol_m = 0.005f) {
+    if (records) records->resize(symmetries.size() + 1);
+    return ok(fp_resolve_symmetry(h_, target_name.c_str(), pose.data(), symmetries.empty() ? nullptr : symmetries[0].data(), (int)symmetries.size(), tol_m,
+                                  out_pose.data(), best_sym, records ? records->data() : nullptr));
+  }
+
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
 
