@@ -27,7 +27,7 @@ SYMBOLS = [
     "fp_mesh_color_source", "fp_mesh_vertex_colors", "fp_set_vertex_colors", "fp_get_color_source",
     "fp_set_depth_filter", "fp_get_depth_filter",
     "fp_render_pose", "fp_render_scene", "fp_pose_errors", "fp_pose_vsd", "fp_refine_depth", "fp_pose_search", "fp_register_depth",
-    "fp_pose_color", "fp_resolve_symmetry",
+    "fp_pose_color", "fp_resolve_symmetry", "fp_mask_distance", "fp_pose_silhouette",
 ]
 
 
@@ -92,6 +92,13 @@ class FpPoseColor(C.Structure):
     _fields_ = [("n_model", C.c_int32), ("n_visible", C.c_int32), ("n_compared", C.c_int32), ("n_nocolor", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_int32), ("sum_m", C.c_int64 * 3), ("sum_o", C.c_int64 * 3), ("sum_mm", C.c_int64 * 3), ("sum_oo", C.c_int64 * 3),
                 ("sum_mo", C.c_int64 * 3), ("zncc", C.c_float), ("reserved_f", C.c_float)]
+
+
+class FpPoseSilhouette(C.Structure):
+    """struct fp_pose_silhouette of include/foundationpose_amd.h"""
+    _fields_ = [("n_model", C.c_int32), ("n_visible", C.c_int32), ("n_inter", C.c_int32), ("n_spill", C.c_int32), ("n_mask", C.c_int32),
+                ("n_miss", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32), ("sum_spill_d2", C.c_int64), ("sum_miss_d2", C.c_int64),
+                ("iou", C.c_float), ("rms_spill_px", C.c_float), ("rms_miss_px", C.c_float), ("reserved_f", C.c_float)]
 
 
 class FpDepthRegister(C.Structure):
@@ -210,6 +217,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_register_depth": [vp, vp, vp, vp, ci, ci, ci, cs, ci, cf, ci, vp, vp],
         "fp_pose_color": [vp, cs, vp, ci, cf, vp],
         "fp_resolve_symmetry": [vp, cs, vp, vp, ci, cf, vp, vp, vp],
+        "fp_mask_distance": [vp, vp, ci, vp, vp],
+        "fp_pose_silhouette": [vp, cs, vp, ci, vp, ci, cf, ci, ci, vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

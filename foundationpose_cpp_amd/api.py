@@ -198,6 +198,34 @@ def _pose_color(r):
                      tuple(r.sum_mo), float(r.zncc))
 
 
+FP_SIL_AMODAL = 1
+FP_SIL_D2_NONE = 0x7FFFFFFF
+FP_SIL_REFUSED_NEAR, FP_SIL_REFUSED_RANGE, FP_SIL_EMPTY = 1, 2, 4
+
+
+@dataclasses.dataclass(frozen=True)
+class PoseSilhouette:
+    """struct fp_pose_silhouette (include/foundationpose_amd.h): how the (visible) silhouette of the model under a pose agrees with a mask
+    of the uploaded frame; pixel counts, and exact integer sums of squared pixel distances to the mask's outline"""
+    n_model: int
+    n_visible: int        # n_inter + n_spill
+    n_inter: int          # visible and mask
+    n_spill: int          # visible and not mask
+    n_mask: int           # the mask pixels of the frame
+    n_miss: int           # n_mask - n_inter
+    status: int           # FP_SIL_REFUSED_NEAR | FP_SIL_REFUSED_RANGE | FP_SIL_EMPTY
+    sum_spill_d2: int     # over the spill pixels: squared distance to the mask, clipped to trunc_px^2 when trunc_px > 0
+    sum_miss_d2: int      # over the mask pixels outside the visible model: squared distance to the background, clipped likewise
+    iou: float            # n_inter / (n_mask + n_spill)
+    rms_spill_px: float
+    rms_miss_px: float
+
+
+def _pose_silhouette(r):
+    return PoseSilhouette(r.n_model, r.n_visible, r.n_inter, r.n_spill, r.n_mask, r.n_miss, r.status, r.sum_spill_d2, r.sum_miss_d2, float(r.iou),
+                          float(r.rms_spill_px), float(r.rms_miss_px))
+
+
 def _pose_search(r):
     return PoseSearch(r.n_facing, r.n_inlier, r.n_front, r.n_behind, r.n_outside, r.n_missing, r.score, r.best_step, r.n_points, r.status)
 
@@ -667,6 +695,37 @@ class FoundationPose:
         recs = (_lib.FpPoseColor * (n + 1))()
         self._must(self._L.fp_resolve_symmetry(self._h, target_name.encode(), _p(e), _p(s), n, tol_m, _p(out_p), C.byref(best), recs))
         return from_colmajor(out_p), best.value, [_pose_color(r) for r in recs]
+
+    # ---- silhouette agreement (include/foundationpose_amd.h "silhouette agreement") ----------------
+    def _frame_mask(self, fn: str, mask):
+        """the u8 mask of a call, which must have the uploaded frame's size (the library cannot know the size of what it is handed)"""
+        mask = np.ascontiguousarray(mask, np.uint8)
+        hw = getattr(self, "_hw", None)
+        if hw is None or mask.shape != tuple(hw):
+            self.last_error = f"[FoundationPose] {fn}: " + ("no frame uploaded" if hw is None else f"a mask of shape {mask.shape}, the uploaded frame is {tuple(hw)}")
+            raise FoundationPoseError(self.last_error)
+        return mask
+
+    def mask_distance(self, mask):
+        """fp_mask_distance: the exact squared Euclidean distance transform of a mask [H,W] (a mask pixel: byte > 0) of the uploaded frame's
+        size -> (d2_to_mask, d2_to_bg) [H,W] u32: per pixel the squared distance in pixels to the nearest mask pixel / to the nearest other
+        pixel, FP_SIL_D2_NONE where there is none."""
+        mask = self._frame_mask("fp_mask_distance", mask)
+        a, b = np.zeros(mask.shape, np.uint32), np.zeros(mask.shape, np.uint32)
+        self._must(self._L.fp_mask_distance(self._h, _p(mask), FP_HOST, _p(a), _p(b)))
+        return a, b
+
+    def pose_silhouette(self, target_name: str, mask, poses, tol_m: float = 0.005, trunc_px: int = 0, amodal: bool = False):
+        """fp_pose_silhouette: the visible silhouette of the model under poses [N,4,4] against a mask [H,W] u8 of the uploaded frame ->
+        [PoseSilhouette] * N.  tol_m: the occlusion tolerance of render_pose; trunc_px > 0 clips every squared distance to trunc_px^2;
+        amodal: every model pixel counts as visible and the depth is not read.  A pose that would need a clipper does not fail the call:
+        its record carries the status bit and nothing else."""
+        mask = self._frame_mask("fp_pose_silhouette", mask)
+        e = to_colmajor(np.asarray(poses, np.float32).reshape(-1, 4, 4))
+        out = (_lib.FpPoseSilhouette * max(len(e), 1))()
+        self._must(self._L.fp_pose_silhouette(self._h, target_name.encode(), _p(mask), FP_HOST, _p(e), len(e), tol_m, int(trunc_px),
+                                              FP_SIL_AMODAL if amodal else 0, out))
+        return [_pose_silhouette(r) for r in out[:len(e)]]
 
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):

@@ -202,11 +202,13 @@ void roctx_pop() { if (roctx_api().pop) (void)roctx_api().pop(); }
 static int g_icp_chunk = 0;   // fpt_icp_set_chunk: poses per chunk of fp_refine_depth (0: sized by ICP_SCRATCH_BYTES); only the test build changes it
 static int g_vsd_chunk = 0;   // fpt_vsd_set_chunk: poses per chunk of fp_pose_vsd (0: sized by VSD_SCRATCH_BYTES); only the test build changes it
 static int g_color_chunk = 0; // fpt_color_set_chunk: poses per chunk of fp_pose_color (0: sized by COLOR_SCRATCH_BYTES); only the test build changes it
+static int g_sil_chunk = 0;   // fpt_silhouette_set_chunk: poses per chunk of fp_pose_silhouette (0: sized by SIL_SCRATCH_BYTES); only the test build changes it
 static int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;   // A/B (fpt_set_calib_opts): steps of the 8-bit calibration
 #else
 static constexpr int g_icp_chunk = 0;
 static constexpr int g_vsd_chunk = 0;
 static constexpr int g_color_chunk = 0;
+static constexpr int g_sil_chunk = 0;
 static constexpr int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;
 #endif
 
@@ -346,7 +348,7 @@ static void dev_free(T *&p) {
   if (p) (void)hipFree(p);
   p = nullptr;
 }
-// Device scratch of the stage operators (a model's st_*, fr_*, sc_*, pe_*, vsd_*, icp_*, ps_*, col_* blocks, used on stream s): grow-only,
+// Device scratch of the stage operators (a model's st_*, fr_*, sc_*, pe_*, vsd_*, icp_*, ps_*, col_*, sil_* blocks, used on stream s): grow-only,
 // and nothing of the stream may still read a block that is replaced.  No captured graph reads these blocks, so unlike
 // ensure_capacity / ensure_window this leaves the allocation epoch alone.
 template <typename T>
@@ -538,8 +540,8 @@ struct fp_model {
   // record.  No buffer of its own: Register's sampler leaves the whole frame's D' there anyway, Track fills its window of it.
   bool dfilt_on = false;
 
-  // Scratch of the stage operators (DESIGN.md sections 4.8 - 4.14: fp_render_pose, fp_render_scene, fp_pose_errors, fp_pose_vsd,
-  // fp_refine_depth, fp_pose_search, fp_pose_color).  Nothing below is allocated before the first call that needs it, and every block only grows
+  // Scratch of the stage operators (DESIGN.md sections 4.8 - 4.15: fp_render_pose, fp_render_scene, fp_pose_errors, fp_pose_vsd,
+  // fp_refine_depth, fp_pose_search, fp_pose_color, fp_pose_silhouette).  Nothing below is allocated before the first call that needs it, and every block only grows
   // (grow_scratch).  One rule makes all of it safe, and lets the calls share the st_* blocks: every one of these calls holds the
   // SerialGuard from its first line to its last and leaves the stream synchronised, so no two of them are ever live together
   // (fp_register_depth runs the search and then the ICP, each to its end); and no captured graph reads any of these blocks, so
@@ -588,6 +590,15 @@ struct fp_model {
   unsigned long long *col_acc = nullptr;   // [col_acc_cap] accumulators [N, COLOR_WORDS] | refusal words [N] (32-bit, behind the accumulators)
   size_t col_acc_cap = 0;
   std::vector<unsigned long long> col_acc_host;
+
+  // silhouette agreement (fp_mask_distance / fp_pose_silhouette): likewise
+  uint8_t *sil_mask = nullptr;             // [sil_mask_cap] the copy of a host mask
+  uint16_t *sil_g = nullptr;               // [sil_g_cap] the column distances of the two seed sets, [2, H, W]
+  uint32_t *sil_d2 = nullptr;              // [sil_d2_cap] the squared distances to the mask | to the other pixels, [2, H, W]
+  size_t sil_mask_cap = 0, sil_g_cap = 0, sil_d2_cap = 0;
+  unsigned long long *sil_acc = nullptr;   // [sil_acc_cap] {n_mask, T} | accumulators [N, SIL_WORDS] | 32-bit words: seeds [2], refusals [N]
+  size_t sil_acc_cap = 0;
+  std::vector<unsigned long long> sil_acc_host;
 
   // depth search (fp_pose_search): likewise
   SearchRec *ps_recs = nullptr;            // [ps_rec_cap] the records of the call's poses
@@ -894,6 +905,8 @@ void fpt_vsd_set_chunk(int poses) { g_vsd_chunk = poses > 0 ? poses : 0; }
 void fpt_icp_set_chunk(int poses) { g_icp_chunk = poses > 0 ? poses : 0; }
 // the same for fp_pose_color
 void fpt_color_set_chunk(int poses) { g_color_chunk = poses > 0 ? poses : 0; }
+// the same for fp_pose_silhouette
+void fpt_silhouette_set_chunk(int poses) { g_sil_chunk = poses > 0 ? poses : 0; }
 void fpt_set_calib_opts(int sweeps, int tok, int out) { g_calib_sweeps = sweeps; g_calib_tok = tok; g_calib_out = out; }
 // A/B hook: hipGraph replay of the Track / Register bodies on or off for one model
 int fpt_model_use_graphs(fp_model *m, int on) {
@@ -1341,6 +1354,7 @@ static void destroy_model_impl(fp_model *m) {
   dev_free(m->pe_mats); dev_free(m->pe_pairs); dev_free(m->pe_sums);
   dev_free(m->ps_recs); dev_free(m->icp_params); dev_free(m->icp_acc); dev_free(m->vsd_words); dev_free(m->vsd_plane);
   dev_free(m->col_acc);
+  dev_free(m->sil_mask); dev_free(m->sil_g); dev_free(m->sil_d2); dev_free(m->sil_acc);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
@@ -3601,6 +3615,162 @@ int fp_resolve_symmetry(fp_model *m, const char *target_name, const float pose[1
   std::memcpy(out_pose, eq.data() + (size_t)win * 16, 64);
   if (best_sym) *best_sym = win;
   if (records) std::memcpy(records, recs.data(), recs.size() * sizeof(fp_pose_color_t));
+  return 0;
+} FP_CATCH_INT
+
+// ---- silhouette agreement
+static_assert(sizeof(fp_pose_silhouette_t) == 64, "fp_pose_silhouette: eight 32-bit words, two 64-bit sums, four floats");
+static_assert(FP_SIL_REFUSED_NEAR == FRAME_RENDER_FLAG_NEAR && FP_SIL_REFUSED_RANGE == FRAME_RENDER_FLAG_RANGE,
+              "include/foundationpose_amd.h: the refusal bits of fp_pose_silhouette are the refusal bits of the vertex rule");
+static_assert((long long)FP_SIL_MAX_TRUNC_PX * FP_SIL_MAX_TRUNC_PX < FP_SIL_D2_NONE && 2ll * (FP_SIL_MAX_DIM - 1) * (FP_SIL_MAX_DIM - 1) < FP_SIL_D2_NONE,
+              "fp_pose_silhouette: a clip and every squared distance of a frame stay below FP_SIL_D2_NONE");
+// what both calls ask of the mask and of the frame, after their own pointer checks
+static int silhouette_frame_ok(const fp_model *m, const std::string &fn, int memspace) {
+  FP_CHECK(memspace == FP_HOST || memspace == FP_DEVICE, "[FoundationPose] " + fn + ": memspace must be FP_HOST or FP_DEVICE");
+  if (frame_ready(m, fn, false)) return 1;
+  FP_CHECK(m->H <= FP_SIL_MAX_DIM && m->W <= FP_SIL_MAX_DIM, "[FoundationPose] " + fn + ": a frame of " + std::to_string(m->W) + " x " + std::to_string(m->H) +
+               " pixels, above FP_SIL_MAX_DIM = " + std::to_string(FP_SIL_MAX_DIM) + " in a dimension");
+  return 0;
+}
+// The distance transform of the call's mask on the model's stream: a host mask goes up by one stream-ordered copy, a device mask is read
+// where it is; *mask_d is the mask the kernels read, m->sil_d2 [2, H, W] the two maps.  tot {n_mask, T} and any [2] are device words the
+// caller has zeroed on the stream.
+static int silhouette_maps(fp_model *m, const void *mask, int memspace, long long t2, unsigned long long *tot, int *any, const uint8_t **mask_d) {
+  hipStream_t s = m->stream;
+  const int H = m->H, W = m->W;
+  const size_t px = (size_t)H * W;
+  if (grow_scratch(s, m->sil_g, m->sil_g_cap, 2 * px) || grow_scratch(s, m->sil_d2, m->sil_d2_cap, 2 * px)) return 1;
+  if (memspace == FP_HOST) {
+    if (grow_scratch(s, m->sil_mask, m->sil_mask_cap, px)) return 1;
+    FP_HIP_OK(hipMemcpyAsync(m->sil_mask, mask, px, hipMemcpyHostToDevice, s));
+    *mask_d = m->sil_mask;
+  } else {
+    *mask_d = static_cast<const uint8_t *>(mask);
+  }
+  {
+    ProfScope ps(&m->prof, s, "mask_edt_cols", 0, (double)px * (2.0 + 4.0 * 3.0));
+    launch_mask_edt_cols(s, *mask_d, H, W, m->sil_g, any);
+    FP_HIP_OK(hipGetLastError());
+  }
+  {
+    ProfScope ps(&m->prof, s, "mask_edt_rows", 0, (double)px * (4.0 + 8.0));
+    launch_mask_edt_rows(s, m->sil_g, any, H, W, m->sil_d2, t2, tot);
+    FP_HIP_OK(hipGetLastError());
+  }
+  return 0;
+}
+
+int fp_mask_distance(fp_model *m, const void *mask, int memspace, uint32_t *d2_to_mask, uint32_t *d2_to_bg) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && mask && (d2_to_mask || d2_to_bg), "[FoundationPose] fp_mask_distance: invalid arguments");
+  if (pinhole_camera_ok(m, "fp_mask_distance") || silhouette_frame_ok(m, "fp_mask_distance", memspace)) return 1;
+  hipStream_t s = m->stream;
+  const size_t px = (size_t)m->H * m->W;
+  if (grow_scratch(s, m->sil_acc, m->sil_acc_cap, (size_t)3)) return 1;
+  FP_HIP_OK(hipMemsetAsync(m->sil_acc, 0, 3 * sizeof(unsigned long long), s));
+  const uint8_t *mask_d = nullptr;
+  if (silhouette_maps(m, mask, memspace, 0, m->sil_acc, reinterpret_cast<int *>(m->sil_acc + 2), &mask_d)) return 1;
+  if (d2_to_mask) FP_HIP_OK(hipMemcpyAsync(d2_to_mask, m->sil_d2, px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (d2_to_bg) FP_HIP_OK(hipMemcpyAsync(d2_to_bg, m->sil_d2 + px, px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  FP_HIP_OK(hipStreamSynchronize(s));
+  return 0;
+} FP_CATCH_INT
+
+int fp_pose_silhouette(fp_model *m, const char *target_name, const void *mask, int memspace, const float *poses, int N, float tol_m, int trunc_px,
+                       int flags, fp_pose_silhouette_t *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && mask && poses && out, "[FoundationPose] fp_pose_silhouette: invalid arguments");
+  if (batch_size_ok("fp_pose_silhouette", N)) return 1;
+  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_pose_silhouette: tol_m must be finite and >= 0 (metres)");
+  FP_CHECK(trunc_px >= 0 && trunc_px <= FP_SIL_MAX_TRUNC_PX, "[FoundationPose] fp_pose_silhouette: trunc_px " + std::to_string(trunc_px) +
+               " (0..FP_SIL_MAX_TRUNC_PX = " + std::to_string(FP_SIL_MAX_TRUNC_PX) + ")");
+  FP_CHECK((flags & ~FP_SIL_AMODAL) == 0, "[FoundationPose] fp_pose_silhouette: unknown flag bits in " + std::to_string(flags));
+  Target *t = nullptr;
+  if (stage_target(m, "fp_pose_silhouette", target_name, &t) || matrices_finite_ok("fp_pose_silhouette", "poses", poses, N) ||
+      silhouette_frame_ok(m, "fp_pose_silhouette", memspace))
+    return 1;
+  const DeviceMesh &mesh = t->mesh;
+  const int H = m->H, W = m->W, V = mesh.V;
+  const bool amodal = (flags & FP_SIL_AMODAL) != 0;
+  const long long t2 = (long long)trunc_px * trunc_px;
+  const int ntx = scene_tiles_x(W);
+  const long long F = std::max(mesh.F, 1);
+  // host: the poses in the kernels' form, every pose's tiles, the work they stand for (as fp_pose_color counts it)
+  m->st_poses_host.resize((size_t)N);
+  std::vector<FrameTileBound> bounds((size_t)N);
+  long long work = 0;
+  for (int i = 0; i < N; i++) {
+    m->st_poses_host[(size_t)i] = frame_pose(m, poses + (size_t)i * 16);
+    bounds[(size_t)i] = frame_tile_bound(m->st_poses_host[(size_t)i], (double)mesh.max_norm, H, W);
+    work += bound_tiles(bounds[(size_t)i]) * F;
+  }
+  FP_CHECK(work <= FP_SIL_MAX_WORK, "[FoundationPose] fp_pose_silhouette: " + std::to_string(N) + " poses of " + std::to_string(mesh.F) + " faces walk " +
+               std::to_string(work) + " faces over their 32 x 32 px tiles, above FP_SIL_MAX_WORK = " + std::to_string((long long)FP_SIL_MAX_WORK) +
+               ": pass fewer poses per call");
+  // chunks of poses: the snapped vertices of a chunk stay below SIL_SCRATCH_BYTES, one pose at least
+  const int chunk = stage_chunk((size_t)std::max(V, 1) * sizeof(int4), SIL_SCRATCH_BYTES, N, g_sil_chunk);
+  std::vector<int2> &items = m->st_items_host;
+  items.clear();
+  std::vector<size_t> chunk_end;   // items.size() after each chunk
+  for (int i = 0; i < N; i++) {
+    append_tile_items(items, i % chunk, bounds[(size_t)i], ntx);
+    if ((i + 1) % chunk == 0 || i + 1 == N) chunk_end.push_back(items.size());
+  }
+  hipStream_t s = m->stream;
+  const size_t acc_words = (size_t)2 + (size_t)N * SIL_WORDS + ((size_t)N + 3) / 2;
+  if (grow_stage(m, (size_t)V * chunk, 0, (size_t)N, items.size()) || grow_scratch(s, m->sil_acc, m->sil_acc_cap, acc_words)) return 1;
+  unsigned long long *tot = m->sil_acc, *acc = tot + 2;
+  int *any_d = reinterpret_cast<int *>(acc + (size_t)N * SIL_WORDS), *flag_d = any_d + 2;
+  m->sil_acc_host.assign(acc_words, 0ull);
+  FP_HIP_OK(hipMemcpyAsync(m->st_poses, m->st_poses_host.data(), (size_t)N * sizeof(FramePose), hipMemcpyHostToDevice, s));
+  if (!items.empty()) FP_HIP_OK(hipMemcpyAsync(m->st_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+  FP_HIP_OK(hipMemsetAsync(tot, 0, acc_words * sizeof(unsigned long long), s));   // totals, accumulators, seed and refusal words together
+  const uint8_t *mask_d = nullptr;
+  if (silhouette_maps(m, mask, memspace, t2, tot, any_d, &mask_d)) return 1;
+  size_t first = 0;
+  for (size_t c = 0; c < chunk_end.size(); c++) {
+    const int p0 = (int)c * chunk, cn = std::min(chunk, N - p0);
+    {
+      ProfScope ps(&m->prof, s, "silhouette_vertex", 0, (double)cn * V * (12.0 + 16.0));
+      launch_pose_vertices(s, "silhouette_vertex", mesh, m->st_poses + p0, cn, nullptr, 0, m->st_snap, nullptr, flag_d + p0, nullptr);
+      FP_HIP_OK(hipGetLastError());
+    }
+    if (chunk_end[c] > first) {
+      ProfScope ps(&m->prof, s, "silhouette_tile", 0, (double)(chunk_end[c] - first) * (double)F * 60.0);
+      if (launch_item_runs(first, chunk_end[c], FP_SIL_MAX_WORK, F, [&](size_t at, int cnt) {
+            launch_silhouette_tiles(s, mesh, m->st_snap, m->st_items + at, cnt, m->depth, mask_d, m->sil_d2, H, W, tol_m, t2, amodal, flag_d, p0, acc);
+            FP_HIP_OK(hipGetLastError());
+            return 0;
+          }))
+        return 1;
+      first = chunk_end[c];
+    }
+  }
+  FP_HIP_OK(hipMemcpyAsync(m->sil_acc_host.data(), tot, acc_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  FP_HIP_OK(hipStreamSynchronize(s));
+  const unsigned long long *tot_h = m->sil_acc_host.data();
+  const int *flag_h = reinterpret_cast<const int *>(tot_h + 2 + (size_t)N * SIL_WORDS) + 2;
+  const int64_t n_mask = (int64_t)tot_h[0], T = (int64_t)tot_h[1];
+  std::vector<fp_pose_silhouette_t> recs((size_t)N);
+  for (int i = 0; i < N; i++) {
+    fp_pose_silhouette_t r = {};
+    r.status = flag_h[i];
+    if (!r.status) {
+      const unsigned long long *w = tot_h + 2 + (size_t)i * SIL_WORDS;
+      r.n_model = (int32_t)w[0]; r.n_visible = (int32_t)w[1]; r.n_inter = (int32_t)w[2]; r.n_spill = (int32_t)w[3];
+      r.n_mask = (int32_t)n_mask;
+      r.n_miss = (int32_t)(n_mask - (int64_t)w[2]);
+      r.sum_spill_d2 = (int64_t)w[4];
+      r.sum_miss_d2 = T - (int64_t)w[5];
+      const int64_t uni = n_mask + r.n_spill;
+      if (uni == 0) r.status |= FP_SIL_EMPTY;
+      else r.iou = (float)((double)r.n_inter / (double)uni);
+      if (r.n_spill) r.rms_spill_px = (float)std::sqrt((double)r.sum_spill_d2 / (double)r.n_spill);
+      if (r.n_miss) r.rms_miss_px = (float)std::sqrt((double)r.sum_miss_d2 / (double)r.n_miss);
+    }
+    recs[(size_t)i] = r;
+  }
+  std::memcpy(out, recs.data(), recs.size() * sizeof(fp_pose_silhouette_t));
   return 0;
 } FP_CATCH_INT
 

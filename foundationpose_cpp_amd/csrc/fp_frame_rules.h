@@ -1,6 +1,7 @@
 // The raster rules of the frame-resolution renderers, each written once: fp_render_pose (fp_frame_render.hip),
 // fp_render_scene (fp_scene_render.hip, section 4.9), fp_pose_vsd (fp_pose_vsd.hip, section 4.11), fp_refine_depth (fp_pose_icp.hip,
-// section 4.12) and fp_pose_color (fp_pose_color.hip, section 4.14) promise the same pixels because their kernels call these functions;
+// section 4.12), fp_pose_color (fp_pose_color.hip, section 4.14) and fp_pose_silhouette (fp_pose_silhouette.hip, section 4.15) promise the
+// same pixels because their kernels call these functions;
 // and the tile engine around the rules, which the kernels that rasterise one mesh under one pose share.  Device code only, for files
 // compiled with -ffp-contract=off: every f32 operation below is separately rounded, in the order written, and
 // tests/frame_render_ref.py restates it operation by operation.  The 160x160 crop rasteriser of fp_geometry.hip has rules of its own.
@@ -109,7 +110,7 @@ __device__ __forceinline__ FrameWeights frame_tri_weights(const int4 &a, const i
 }
 
 // ---- the pose-tile engine: what every kernel that rasterises ONE mesh under one pose into a FRAME_RENDER_TILE x FRAME_RENDER_TILE
-// LDS z-buffer does before its own pixel loop (frame_raster_kernel, vsd_tile_kernel, icp_tile_kernel, color_tile_kernel): the tile's
+// LDS z-buffer does before its own pixel loop (frame_raster_kernel, vsd_tile_kernel, icp_tile_kernel, color_tile_kernel, silhouette_tile): the tile's
 // rectangle, the z-buffer's keys, the walk over all faces.  scene_raster_kernel walks per-tile lists of several objects instead of all faces of
 // one; it shares the rectangle and the keys.
 

@@ -453,6 +453,23 @@ constexpr size_t COLOR_SCRATCH_BYTES = 128u << 20;  // snapped vertices of one c
 void launch_color_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const int2 *items, int n_items, const uint8_t *rgb, const float *depth,
                         int H, int W, float tol_m, const int *flags, int pose0, unsigned long long *acc);
 
+// silhouette agreement (fp_pose_silhouette / fp_mask_distance; fp_pose_silhouette.hip).  The exact squared
+// Euclidean distance transform of a u8 mask [H, W] (a mask pixel: byte > 0), H and W at most FP_SIL_MAX_DIM, in two launches:
+//   columns  g [2, H, W] = per set (0: the mask pixels, 1: the others) the distance along the column to its nearest seed, 0xFFFF: the column
+//            has none; any [2] (zero on entry) |= 1 where a set has a seed at all
+//   rows     d2 [2, H, W] = the squared distance to the nearest seed of each set, FP_SIL_D2_NONE where the set is empty; tot [2] (zero on
+//            entry) += {the mask pixels, the sum over them of d2[1], clipped to t2 where t2 > 0}
+void launch_mask_edt_cols(hipStream_t s, const uint8_t *mask, int H, int W, uint16_t *g, int *any);
+void launch_mask_edt_rows(hipStream_t s, const uint16_t *g, const int *any, int H, int W, uint32_t *d2, long long t2, unsigned long long *tot);
+// a pose's accumulator is SIL_WORDS 64-bit words: n_model, n_visible, n_inter, n_spill, the sum of clip(d2[0]) over the spill pixels, the
+// sum of clip(d2[1]) over the inter pixels.  items [n_items] = {pose of the chunk, tile}: acc[(pose0 + pose) SIL_WORDS ..] += the tile's
+// counts and sums; an item whose flags[pose0 + pose] is not zero does nothing.  amodal: every model pixel is visible, depth is not read.
+constexpr int SIL_WORDS = 6;
+constexpr size_t SIL_SCRATCH_BYTES = 128u << 20;  // snapped vertices of one chunk of poses stay below this
+void launch_silhouette_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const int2 *items, int n_items, const float *depth,
+                             const uint8_t *mask, const uint32_t *d2, int H, int W, float tol_m, long long t2, bool amodal, const int *flags, int pose0,
+                             unsigned long long *acc);
+
 // depth search (fp_pose_search; fp_pose_search.hip): per pose the sampled vertices and their normals against the
 // frame's raw depth at n_steps pushes along the ray of the pose's origin; a record is ten 32-bit words, fp_pose_search_t's layout.
 constexpr int SEARCH_THREADS = 256;

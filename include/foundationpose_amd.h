@@ -93,8 +93,9 @@ const uint8_t *fp_mesh_vertex_colors(const fp_loaded_mesh *mesh);
  * refiner_weights / scorer_weights: paths of packed weight files (tools/pack_weights.py; replaces the TensorRT
  * engines of simple_tests/src/test_foundationpose.cpp:13-14).  NULL = geometry-only model (NN entry points fail).
  * K: the 3x3 intrinsics, row-major; all nine entries are copied.  Register, Track and the stage operators of their path take K as the
- * reference does, as a matrix, so a skew K[1] is honoured there.  The nine frame-resolution calls -- fp_render_pose, fp_render_scene,
- * fp_pose_errors, fp_pose_vsd, fp_refine_depth, fp_pose_search, fp_register_depth, fp_pose_color, fp_resolve_symmetry -- read fx = K[0], fy = K[4], cx = K[2], cy = K[5]
+ * reference does, as a matrix, so a skew K[1] is honoured there.  The eleven frame-resolution calls -- fp_render_pose, fp_render_scene,
+ * fp_pose_errors, fp_pose_vsd, fp_refine_depth, fp_pose_search, fp_register_depth, fp_pose_color, fp_resolve_symmetry,
+ * fp_mask_distance, fp_pose_silhouette -- read fx = K[0], fy = K[4], cx = K[2], cy = K[5]
  * only and REFUSE a model whose K is not a plain pinhole matrix (K[1] == K[3] == K[6] == K[7] == 0, K[8] == 1, K[0] and K[4] finite and
  * positive, K[2] and K[5] finite): on the host, before anything is uploaded or launched, with a message that names the entry, their
  * outputs untouched.  fx != fy and a principal point anywhere are fine everywhere. */
@@ -561,6 +562,62 @@ int fp_resolve_symmetry(fp_model *m, const char *target_name, const float pose[1
                         const float *symmetries /* S column-major 4x4, MESH frame; NULL = none */, int S,
                         float tol_m, float out_pose[16], int *best_sym /* may be NULL */,
                         fp_pose_color_t *records /* host [S + 1], may be NULL */);
+
+/* ---- silhouette agreement: does the segmentation mask agree with N poses? (new; the reference has no counterpart) ----
+ * fp_pose_silhouette compares, over the pixels of each pose, the model's (visible) silhouette with a mask of the uploaded frame, and
+ * weighs every pixel of disagreement with its exact squared Euclidean distance to the other side of the mask's outline.  Poses as in
+ * fp_pose_errors (column-major 4x4, centred-mesh -> camera); the frame is the uploaded one, its RAW depth whether fp_set_depth_filter is on
+ * or off; K is the model's (a plain pinhole matrix).  DESIGN.md section 4.15 has the rules.  The only f32 arithmetic is fp_render_pose's;
+ * everything new is integer.
+ *   mask         u8 [H, W] in `memspace`, H and W the uploaded frame's; a pixel is a MASK pixel when its byte is > 0 (the convention of
+ *                fp_register's mask).  The caller's mask is never modified.
+ *   distance     for a seed set S, d2_S(r, c) = min over (r', c') in S of (r - r')^2 + (c - c')^2: an exact integer, FP_SIL_D2_NONE when S
+ *                is empty; nothing outside the frame is a seed.  d2_to_mask has S = the mask pixels (0 on the mask), d2_to_bg has S = the
+ *                other pixels (0 off the mask, >= 1 on it).  fp_mask_distance returns the two maps (u32 [H, W], host; either may be NULL).
+ * Per pixel of a pose:
+ *   model, z     exactly fp_render_pose's model_mask and model_depth; n_model counts these pixels
+ *   visible      !(D >= 0.001f && D < z - tol_m) on the raw depth, fp_render_pose's visible_mask; with FP_SIL_AMODAL simply `model`, and the
+ *                depth is not read; n_visible
+ *   inter        visible and mask (n_inter);   spill: visible and not mask (n_spill)
+ *   clip(v)      min(v, trunc_px * trunc_px) when trunc_px > 0, else v
+ * Per record: n_mask the mask pixels of the frame (the same in every record of a call), n_miss = n_mask - n_inter,
+ *   sum_spill_d2 = sum of clip(d2_to_mask) over the spill pixels,
+ *   sum_miss_d2  = T - sum of clip(d2_to_bg) over the inter pixels, T = the sum of clip(d2_to_bg) over all mask pixels (once per call): the
+ *                  sum over the mask pixels the pose does not explain, weighted by how deep inside the mask they lie.
+ * On the host, in double, rounded once: iou = n_inter / (n_mask + n_spill), rms_spill_px = sqrt(sum_spill_d2 / n_spill), rms_miss_px =
+ * sqrt(sum_miss_d2 / n_miss); each is 0 when its denominator is 0.  FP_SIL_EMPTY is set when n_mask + n_spill == 0.
+ * Every field is an integer or a host formula of integers, so pose i's record is byte-identical alone, in any batch, under any chunking
+ * and from call to call.  A refused pose (a vertex at z < FP_RENDER_NEAR_M, or beyond FP_RENDER_SNAP_MAX: fp_render_pose would fail) does
+ * not fail the call: its status bit is set and every other field is 0.
+ * Refused with an error before anything is launched and before `out` is written: NULL arguments, a memspace that is neither FP_HOST nor
+ * FP_DEVICE, N outside 1..FP_MAX_BATCH, a tol_m that is not finite or is negative (also with FP_SIL_AMODAL), trunc_px outside
+ * 0..FP_SIL_MAX_TRUNC_PX, unknown flag bits, a pending Track, a K that is not a plain pinhole matrix, an unknown target, a non-finite
+ * matrix entry, no frame, a partial frame, H or W above FP_SIL_MAX_DIM, and more than FP_SIL_MAX_WORK faces walked: the sum over the
+ * poses' (pose, 32 x 32 px tile) items of F, as fp_pose_color counts them.  No launch covers more than a tenth of it.  fp_mask_distance
+ * takes the pointer, memspace, camera, frame and dimension guards only.  Both work on geometry-only models, are stream-ordered on the model's stream with
+ * one synchronisation at the end, and leave Register, Track, their captured graphs and every existing kernel untouched: the calls'
+ * buffers (mask copy, the two maps, the column distances, the accumulators) are their own, allocated at first use, grow-only. */
+#define FP_SIL_AMODAL 1              /* flags: every model pixel counts as visible; the depth is not read */
+#define FP_SIL_D2_NONE 0x7fffffff    /* squared distance where the seed set is empty */
+#define FP_SIL_MAX_DIM 8192          /* H and W of the frame, for these two calls */
+#define FP_SIL_MAX_TRUNC_PX 32767
+#define FP_SIL_REFUSED_NEAR 1        /* status bits of a record; 1 and 2 are the vertex rule's, as in fp_pose_color */
+#define FP_SIL_REFUSED_RANGE 2
+#define FP_SIL_EMPTY 4               /* n_mask + n_spill == 0 */
+#define FP_SIL_MAX_WORK 340000000000LL /* faces walked by one call: 0.99 s at the 3.43e11 faces/s measured for 252 poses */
+typedef struct fp_pose_silhouette {
+  int32_t n_model, n_visible, n_inter, n_spill;   /* pixels of the pose; n_visible == n_inter + n_spill */
+  int32_t n_mask, n_miss;                         /* mask pixels of the frame; n_mask - n_inter */
+  int32_t status, reserved;
+  int64_t sum_spill_d2, sum_miss_d2;
+  float   iou, rms_spill_px, rms_miss_px;         /* host, double, rounded once */
+  float   reserved_f;
+} fp_pose_silhouette_t;
+int fp_mask_distance(fp_model *m, const void *mask, int memspace,
+                     uint32_t *d2_to_mask, uint32_t *d2_to_bg /* host [H,W]; either may be NULL, not both */);
+int fp_pose_silhouette(fp_model *m, const char *target_name, const void *mask, int memspace,
+                       const float *poses, int N, float tol_m, int trunc_px, int flags,
+                       fp_pose_silhouette_t *out /* host [N] */);
 
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 

@@ -284,6 +284,25 @@ public:
                                   out_pose.data(), best_sym, records ? records->data() : nullptr));
   }
 
+  // silhouette agreement (foundationpose_amd.h "silhouette agreement"): the exact squared Euclidean distance transform of a u8 mask of the
+  // uploaded frame's size (a mask pixel: byte > 0): per pixel the squared distance to the nearest mask pixel and to the nearest other
+  // pixel, FP_SIL_D2_NONE where there is none.  Either output may be null, not both; they are resized to `pixels` = H * W of the frame.
+  bool MaskDistance(const uint8_t *mask, size_t pixels, std::vector<uint32_t> *d2_to_mask, std::vector<uint32_t> *d2_to_bg, int memspace = FP_HOST) {
+    if (d2_to_mask) d2_to_mask->resize(pixels);
+    if (d2_to_bg) d2_to_bg->resize(pixels);
+    return ok(fp_mask_distance(h_, mask, memspace, d2_to_mask ? d2_to_mask->data() : nullptr, d2_to_bg ? d2_to_bg->data() : nullptr));
+  }
+
+  // ... and the (visible) silhouette of the model under `poses` against that mask; `out` gets the counts, the integer sums and the IoU of
+  // each.  tol_m: the occlusion tolerance of RenderPose; trunc_px > 0 clips every squared distance to trunc_px^2; flags: FP_SIL_AMODAL.
+  // A pose that would need a clipper gets its status bit and nothing else, not an error.
+  bool PoseSilhouette(const std::string &target_name, const uint8_t *mask, const std::vector<Pose> &poses, std::vector<fp_pose_silhouette_t> &out,
+                      float tol_m = 0.005f, int trunc_px = 0, int flags = 0, int memspace = FP_HOST) {
+    out.resize(poses.size());
+    return ok(fp_pose_silhouette(h_, target_name.c_str(), mask, memspace, poses.empty() ? nullptr : poses[0].data(), (int)poses.size(), tol_m, trunc_px,
+                                 flags, out.data()));
+  }
+
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
 
