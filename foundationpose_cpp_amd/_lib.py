@@ -28,6 +28,7 @@ SYMBOLS = [
     "fp_set_depth_filter", "fp_get_depth_filter",
     "fp_render_pose", "fp_render_scene", "fp_pose_errors", "fp_pose_vsd", "fp_refine_depth", "fp_pose_search", "fp_register_depth",
     "fp_pose_color", "fp_resolve_symmetry", "fp_mask_distance", "fp_pose_silhouette",
+    "fp_refine_silhouette",
 ]
 
 
@@ -99,6 +100,14 @@ class FpPoseSilhouette(C.Structure):
     _fields_ = [("n_model", C.c_int32), ("n_visible", C.c_int32), ("n_inter", C.c_int32), ("n_spill", C.c_int32), ("n_mask", C.c_int32),
                 ("n_miss", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32), ("sum_spill_d2", C.c_int64), ("sum_miss_d2", C.c_int64),
                 ("iou", C.c_float), ("rms_spill_px", C.c_float), ("rms_miss_px", C.c_float), ("reserved_f", C.c_float)]
+
+
+class FpSilhouetteRefine(C.Structure):
+    """struct fp_silhouette_refine of include/foundationpose_amd.h"""
+    _fields_ = [("n_model", C.c_int32), ("n_contour", C.c_int32), ("n_used", C.c_int32), ("n_occluded", C.c_int32), ("n_far", C.c_int32),
+                ("n_flat", C.c_int32), ("n_steep", C.c_int32), ("iterations", C.c_int32), ("rank", C.c_int32), ("status", C.c_int32),
+                ("rms_px", C.c_float), ("scale_px", C.c_float), ("cond", C.c_float), ("last_rot_rad", C.c_float), ("last_trans_m", C.c_float),
+                ("reserved_f", C.c_float), ("sums_q24", C.c_int64 * 28)]
 
 
 class FpDepthRegister(C.Structure):
@@ -219,6 +228,7 @@ def _declare(L: C.CDLL) -> C.CDLL:
         "fp_resolve_symmetry": [vp, cs, vp, vp, ci, cf, vp, vp, vp],
         "fp_mask_distance": [vp, vp, ci, vp, vp],
         "fp_pose_silhouette": [vp, cs, vp, ci, vp, ci, cf, ci, ci, vp],
+        "fp_refine_silhouette": [vp, cs, vp, ci, vp, ci, ci, ci, cf, ci, vp, vp],
     }
     for name, at in sigs.items():
         f = getattr(L, name)

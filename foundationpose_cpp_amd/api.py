@@ -226,6 +226,37 @@ def _pose_silhouette(r):
                           float(r.rms_spill_px), float(r.rms_miss_px))
 
 
+FP_SILREF_TRANSLATION_ONLY, FP_SILREF_OCCLUSION = 1, 2
+FP_SILREF_CONVERGED, FP_SILREF_TOO_FEW, FP_SILREF_REFUSED_NEAR, FP_SILREF_REFUSED_RANGE = 1, 2, 4, 8
+
+
+@dataclasses.dataclass(frozen=True)
+class SilhouetteRefine:
+    """struct fp_silhouette_refine (include/foundationpose_amd.h): how the outline of a pose returned by refine_silhouette lies on the
+    mask's outline, and how the iteration ended"""
+    n_model: int
+    n_contour: int        # n_used + n_occluded + n_far + n_flat + n_steep
+    n_used: int
+    n_occluded: int
+    n_far: int
+    n_flat: int
+    n_steep: int
+    iterations: int       # updates applied
+    rank: int
+    status: int           # FP_SILREF_CONVERGED | FP_SILREF_TOO_FEW | FP_SILREF_REFUSED_NEAR | FP_SILREF_REFUSED_RANGE
+    rms_px: float         # the outline's distance to the mask's outline at the returned pose
+    scale_px: float       # the object's radius in pixels there
+    cond: float
+    last_rot_rad: float
+    last_trans_m: float
+    sums_q24: tuple
+
+
+def _silhouette_refine(r):
+    return SilhouetteRefine(r.n_model, r.n_contour, r.n_used, r.n_occluded, r.n_far, r.n_flat, r.n_steep, r.iterations, r.rank, r.status, float(r.rms_px),
+                            float(r.scale_px), float(r.cond), float(r.last_rot_rad), float(r.last_trans_m), tuple(r.sums_q24))
+
+
 def _pose_search(r):
     return PoseSearch(r.n_facing, r.n_inlier, r.n_front, r.n_behind, r.n_outside, r.n_missing, r.score, r.best_step, r.n_points, r.status)
 
@@ -726,6 +757,22 @@ class FoundationPose:
         self._must(self._L.fp_pose_silhouette(self._h, target_name.encode(), _p(mask), FP_HOST, _p(e), len(e), tol_m, int(trunc_px),
                                               FP_SIL_AMODAL if amodal else 0, out))
         return [_pose_silhouette(r) for r in out[:len(e)]]
+
+    def refine_silhouette(self, target_name: str, mask, poses, iterations: int = 15, gate_px: int = 0, tol_m: float = 0.005,
+                          translation_only: bool = False, occlusion: bool = False):
+        """fp_refine_silhouette: poses [N,4,4] moved until the model's outline lies on the outline of mask [H,W] u8 of the uploaded frame
+        -> (poses [N,4,4] f32, [SilhouetteRefine] * N).  No depth is read unless occlusion is set (then the outline pixels render_pose
+        would call occluded at tol_m are dropped).  gate_px > 0 drops outline pixels farther than that from the mask's outline;
+        translation_only leaves the rotation alone (an outline that a rotation does not move cannot determine it).  iterations = 0 only
+        measures.  A pose that would need a clipper does not fail the call: it comes back unchanged with its status bit."""
+        mask = self._frame_mask("fp_refine_silhouette", mask)
+        e = to_colmajor(np.asarray(poses, np.float32).reshape(-1, 4, 4))
+        out_p = np.zeros_like(e)
+        out = (_lib.FpSilhouetteRefine * max(len(e), 1))()
+        flags = (FP_SILREF_TRANSLATION_ONLY if translation_only else 0) | (FP_SILREF_OCCLUSION if occlusion else 0)
+        self._must(self._L.fp_refine_silhouette(self._h, target_name.encode(), _p(mask), FP_HOST, _p(e), len(e), int(iterations), int(gate_px), tol_m,
+                                                flags, _p(out_p), out))
+        return from_colmajor(out_p), [_silhouette_refine(r) for r in out[:len(e)]]
 
     # ---- depth filter (include/foundationpose_amd.h "depth filter") --------------------------------
     def set_depth_filter(self, on: bool):

@@ -202,12 +202,14 @@ void roctx_pop() { if (roctx_api().pop) (void)roctx_api().pop(); }
 static int g_icp_chunk = 0;   // fpt_icp_set_chunk: poses per chunk of fp_refine_depth (0: sized by ICP_SCRATCH_BYTES); only the test build changes it
 static int g_vsd_chunk = 0;   // fpt_vsd_set_chunk: poses per chunk of fp_pose_vsd (0: sized by VSD_SCRATCH_BYTES); only the test build changes it
 static int g_color_chunk = 0; // fpt_color_set_chunk: poses per chunk of fp_pose_color (0: sized by COLOR_SCRATCH_BYTES); only the test build changes it
+static int g_silref_chunk = 0;   // fpt_silref_set_chunk: poses per chunk of fp_refine_silhouette (0: sized by SIL_SCRATCH_BYTES); only the test build changes it
 static int g_sil_chunk = 0;   // fpt_silhouette_set_chunk: poses per chunk of fp_pose_silhouette (0: sized by SIL_SCRATCH_BYTES); only the test build changes it
 static int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;   // A/B (fpt_set_calib_opts): steps of the 8-bit calibration
 #else
 static constexpr int g_icp_chunk = 0;
 static constexpr int g_vsd_chunk = 0;
 static constexpr int g_color_chunk = 0;
+static constexpr int g_silref_chunk = 0;
 static constexpr int g_sil_chunk = 0;
 static constexpr int g_calib_sweeps = 2, g_calib_tok = 1, g_calib_out = 1;
 #endif
@@ -540,8 +542,8 @@ struct fp_model {
   // record.  No buffer of its own: Register's sampler leaves the whole frame's D' there anyway, Track fills its window of it.
   bool dfilt_on = false;
 
-  // Scratch of the stage operators (DESIGN.md sections 4.8 - 4.15: fp_render_pose, fp_render_scene, fp_pose_errors, fp_pose_vsd,
-  // fp_refine_depth, fp_pose_search, fp_pose_color, fp_pose_silhouette).  Nothing below is allocated before the first call that needs it, and every block only grows
+  // Scratch of the stage operators (DESIGN.md sections 4.8 - 4.16: fp_render_pose, fp_render_scene, fp_pose_errors, fp_pose_vsd,
+  // fp_refine_depth, fp_pose_search, fp_pose_color, fp_pose_silhouette, fp_refine_silhouette).  Nothing below is allocated before the first call that needs it, and every block only grows
   // (grow_scratch).  One rule makes all of it safe, and lets the calls share the st_* blocks: every one of these calls holds the
   // SerialGuard from its first line to its last and leaves the stream synchronised, so no two of them are ever live together
   // (fp_register_depth runs the search and then the ICP, each to its end); and no captured graph reads any of these blocks, so
@@ -599,6 +601,14 @@ struct fp_model {
   unsigned long long *sil_acc = nullptr;   // [sil_acc_cap] {n_mask, T} | accumulators [N, SIL_WORDS] | 32-bit words: seeds [2], refusals [N]
   size_t sil_acc_cap = 0;
   std::vector<unsigned long long> sil_acc_host;
+  // silhouette refinement (fp_refine_silhouette): likewise; the mask copy, the column distances and the two maps are the block above
+  int32_t *silref_sd = nullptr;            // [silref_sd_cap] the signed squared distance of the call's mask, [H, W]
+  size_t silref_sd_cap = 0;
+  SilrefParams *silref_params = nullptr;   // [silref_param_cap] of the poses of one evaluation pass
+  unsigned long long *silref_acc = nullptr;   // [silref_acc_cap] {n_mask, T} | seeds (two 32-bit words) | accumulators [n, SILREF_WORDS] | refusal words [n] (32-bit)
+  size_t silref_param_cap = 0, silref_acc_cap = 0;
+  std::vector<SilrefParams> silref_params_host;
+  std::vector<unsigned long long> silref_acc_host;
 
   // depth search (fp_pose_search): likewise
   SearchRec *ps_recs = nullptr;            // [ps_rec_cap] the records of the call's poses
@@ -907,6 +917,8 @@ void fpt_icp_set_chunk(int poses) { g_icp_chunk = poses > 0 ? poses : 0; }
 void fpt_color_set_chunk(int poses) { g_color_chunk = poses > 0 ? poses : 0; }
 // the same for fp_pose_silhouette
 void fpt_silhouette_set_chunk(int poses) { g_sil_chunk = poses > 0 ? poses : 0; }
+// the same for fp_refine_silhouette
+void fpt_silref_set_chunk(int poses) { g_silref_chunk = poses > 0 ? poses : 0; }
 void fpt_set_calib_opts(int sweeps, int tok, int out) { g_calib_sweeps = sweeps; g_calib_tok = tok; g_calib_out = out; }
 // A/B hook: hipGraph replay of the Track / Register bodies on or off for one model
 int fpt_model_use_graphs(fp_model *m, int on) {
@@ -1355,6 +1367,7 @@ static void destroy_model_impl(fp_model *m) {
   dev_free(m->ps_recs); dev_free(m->icp_params); dev_free(m->icp_acc); dev_free(m->vsd_words); dev_free(m->vsd_plane);
   dev_free(m->col_acc);
   dev_free(m->sil_mask); dev_free(m->sil_g); dev_free(m->sil_d2); dev_free(m->sil_acc);
+  dev_free(m->silref_sd); dev_free(m->silref_params); dev_free(m->silref_acc);
   if (m->fit_io) (void)hipHostFree(m->fit_io);
   for (int i = 0; i < N_PREC; i++) {
     if (m->refiner_p[i]) net_free(m->refiner_p[i]);
@@ -3145,12 +3158,13 @@ struct IcpSolve {
   int rank;
   double cond;
 };
-IcpSolve icp_solve(const int64_t *sums, bool translation_only) {
+// (quantum: what one unit of a sum stands for, 2^32 for fp_refine_depth's records and 2^24 for fp_refine_silhouette's)
+IcpSolve icp_solve(const int64_t *sums, double quantum, bool translation_only) {
   double A[36], b[6];
   int j = 0;
   for (int r = 0; r < 6; r++)
-    for (int c = r; c < 6; c++) A[r * 6 + c] = A[c * 6 + r] = (double)sums[j++] / 4294967296.0;
-  for (int r = 0; r < 6; r++) b[r] = (double)sums[21 + r] / 4294967296.0;
+    for (int c = r; c < 6; c++) A[r * 6 + c] = A[c * 6 + r] = (double)sums[j++] / quantum;
+  for (int r = 0; r < 6; r++) b[r] = (double)sums[21 + r] / quantum;
   const int n = translation_only ? 3 : 6, o = 6 - n;
   double a[36], w[6], v[36];
   for (int r = 0; r < n; r++)
@@ -3320,7 +3334,7 @@ int fp_refine_depth(fp_model *m, const char *target_name, const float *poses, in
       r.rms_m = r.n_used ? (float)(std::sqrt((double)r.sums_q32[27] / 4294967296.0 / (double)r.n_used) * (double)rad) : 0.0f;
       if (p.state == 1 || pass == iterations) { p.state = 2; continue; }
       if (r.n_used < FP_ICP_MIN_PIXELS) { r.status |= FP_ICP_TOO_FEW; p.state = 2; continue; }
-      const IcpSolve S = icp_solve(r.sums_q32, (flags & FP_ICP_TRANSLATION_ONLY) != 0);
+      const IcpSolve S = icp_solve(r.sums_q32, 4294967296.0, (flags & FP_ICP_TRANSLATION_ONLY) != 0);
       const double ups[3] = {S.xi[3] * (double)rad, S.xi[4] * (double)rad, S.xi[5] * (double)rad};
       const double rot = std::sqrt(S.xi[0] * S.xi[0] + S.xi[1] * S.xi[1] + S.xi[2] * S.xi[2]);
       const double trans = std::sqrt(ups[0] * ups[0] + ups[1] * ups[1] + ups[2] * ups[2]);
@@ -3771,6 +3785,208 @@ int fp_pose_silhouette(fp_model *m, const char *target_name, const void *mask, i
     recs[(size_t)i] = r;
   }
   std::memcpy(out, recs.data(), recs.size() * sizeof(fp_pose_silhouette_t));
+  return 0;
+} FP_CATCH_INT
+
+// ---- silhouette refinement
+namespace {
+struct SilrefState {
+  double R[9], t[3], R_prev[9], t_prev[3];
+  FramePose P, P_prev;   // the f32 form the device sees
+  int state;             // 0 active, 1 one more evaluation (the record of a converged pose), 2 stopped
+  fp_silhouette_refine_t rec;
+};
+// the per-pose constants of section 4.16 in f32, each operation separately rounded (this file is compiled without contraction)
+SilrefParams silref_params_of(const FramePose &P, float rad) {
+  SilrefParams q = {};
+  q.fx = P.fx; q.fy = P.fy; q.cx = P.cx; q.cy = P.cy;
+  q.rad = rad;
+  for (int k = 0; k < 3; k++) q.t[k] = P.t[k];
+  const float fr = P.fx * rad, gr = P.fy * rad;
+  q.s = fr / P.t[2];
+  q.kx = fr / q.s; q.ky = gr / q.s;
+  return q;
+}
+}  // namespace
+static_assert(sizeof(fp_silhouette_refine_t) == 288, "fp_refine_silhouette: ten 32-bit words, six floats, 28 64-bit sums");
+static_assert(FP_SILREF_MAX_TERM == fp::SILREF_MAX_TERM && fp::SILREF_SUMS == 28 && fp::SILREF_COUNTS == 7,
+              "include/foundationpose_amd.h: the constants of fp_refine_silhouette are those of fp_internal.h");
+static_assert(FP_SILREF_REFUSED_NEAR == FRAME_RENDER_FLAG_NEAR << 2 && FP_SILREF_REFUSED_RANGE == FRAME_RENDER_FLAG_RANGE << 2 &&
+                  FP_SILREF_CONVERGED == FP_ICP_CONVERGED && FP_SILREF_TOO_FEW == FP_ICP_TOO_FEW,
+              "include/foundationpose_amd.h: the status bits of fp_refine_silhouette are fp_refine_depth's");
+int fp_refine_silhouette(fp_model *m, const char *target_name, const void *mask, int memspace, const float *poses, int N, int iterations, int gate_px,
+                         float tol_m, int flags, float *out_poses, fp_silhouette_refine_t *out) try {
+  SerialGuard serial(m ? m->device : -1);
+  FP_CHECK(m && mask && poses && out_poses && out, "[FoundationPose] fp_refine_silhouette: invalid arguments");
+  if (batch_size_ok("fp_refine_silhouette", N)) return 1;
+  FP_CHECK(iterations >= 0 && iterations <= FP_SILREF_MAX_ITERATIONS, "[FoundationPose] fp_refine_silhouette: " + std::to_string(iterations) +
+               " iterations (0..FP_SILREF_MAX_ITERATIONS = " + std::to_string(FP_SILREF_MAX_ITERATIONS) + ")");
+  FP_CHECK(std::isfinite(tol_m) && tol_m >= 0.0f, "[FoundationPose] fp_refine_silhouette: tol_m must be finite and >= 0 (metres)");
+  FP_CHECK(gate_px >= 0 && gate_px <= FP_SIL_MAX_TRUNC_PX, "[FoundationPose] fp_refine_silhouette: gate_px " + std::to_string(gate_px) +
+               " (0..FP_SIL_MAX_TRUNC_PX = " + std::to_string(FP_SIL_MAX_TRUNC_PX) + ")");
+  FP_CHECK((flags & ~(FP_SILREF_TRANSLATION_ONLY | FP_SILREF_OCCLUSION)) == 0, "[FoundationPose] fp_refine_silhouette: unknown flag bits in " + std::to_string(flags));
+  Target *t = nullptr;
+  if (stage_target(m, "fp_refine_silhouette", target_name, &t) || matrices_finite_ok("fp_refine_silhouette", "poses", poses, N) ||
+      silhouette_frame_ok(m, "fp_refine_silhouette", memspace))
+    return 1;
+  const DeviceMesh &mesh = t->mesh;
+  const int H = m->H, W = m->W, V = mesh.V;
+  const bool occlusion = (flags & FP_SILREF_OCCLUSION) != 0;
+  const int gate2 = gate_px * gate_px;
+  const int ntx = scene_tiles_x(W);
+  const long long F = std::max(mesh.F, 1);
+  std::vector<SilrefState> st((size_t)N);
+  long long work = 0;
+  for (int i = 0; i < N; i++) {
+    SilrefState &s = st[(size_t)i];
+    s.P = frame_pose(m, poses + (size_t)i * 16);
+    for (int k = 0; k < 9; k++) s.R[k] = s.P.r[k];
+    for (int k = 0; k < 3; k++) s.t[k] = s.P.t[k];
+    s.state = 0;
+    s.rec = fp_silhouette_refine_t{};
+    work += bound_tiles(frame_tile_bound(s.P, (double)mesh.max_norm, H, W)) * F * (iterations + 1);
+  }
+  FP_CHECK(work <= FP_SILREF_MAX_WORK, "[FoundationPose] fp_refine_silhouette: " + std::to_string(N) + " poses of " + std::to_string(mesh.F) + " faces walk " +
+               std::to_string(work) + " faces over their 32 x 32 px tiles in " + std::to_string(iterations + 1) + " evaluations, above FP_SILREF_MAX_WORK = " +
+               std::to_string((long long)FP_SILREF_MAX_WORK) + ": pass fewer poses or iterations per call");
+  const float rad = mesh.diameter * 0.5f;
+  // chunks of poses: the snapped vertices of a chunk stay below SIL_SCRATCH_BYTES, one pose at least
+  const int chunk = stage_chunk((size_t)std::max(V, 1) * sizeof(int4), SIL_SCRATCH_BYTES, N, g_silref_chunk);
+  hipStream_t s = m->stream;
+  // the accumulator block: {n_mask, T} | the two seed words | per pass the accumulators [n, SILREF_WORDS] and the refusal words [n]
+  constexpr size_t HEAD = 3;
+  if (grow_stage(m, (size_t)V * chunk, 0, (size_t)N, 0) || grow_scratch(s, m->silref_params, m->silref_param_cap, (size_t)N) ||
+      grow_scratch(s, m->silref_acc, m->silref_acc_cap, HEAD + (size_t)N * SILREF_WORDS + ((size_t)N + 1) / 2) ||
+      grow_scratch(s, m->silref_sd, m->silref_sd_cap, (size_t)H * W))
+    return 1;
+  // ---- once per call: the distance transform of the mask and the signed map.  Whether the mask has both sides comes back with the
+  // first evaluation's read-back (the seed words), so the call keeps to one synchronisation per evaluation.
+  FP_HIP_OK(hipMemsetAsync(m->silref_acc, 0, HEAD * sizeof(unsigned long long), s));
+  const uint8_t *mask_d = nullptr;
+  if (silhouette_maps(m, mask, memspace, 0, m->silref_acc, reinterpret_cast<int *>(m->silref_acc + 2), &mask_d)) return 1;
+  {
+    ProfScope ps(&m->prof, s, "mask_signed_d2", 0, (double)H * W * (1.0 + 8.0 + 4.0));
+    launch_mask_signed_d2(s, mask_d, m->sil_d2, H, W, m->silref_sd);
+    FP_HIP_OK(hipGetLastError());
+  }
+  std::vector<int> active;
+  for (int pass = 0; pass <= iterations; pass++) {
+    active.clear();
+    for (int i = 0; i < N; i++)
+      if (st[(size_t)i].state != 2) active.push_back(i);
+    if (active.empty()) break;
+    // ---- one evaluation of the active poses: vertex pass and tile kernel per chunk, one read-back, one synchronisation
+    const int n = (int)active.size();
+    const size_t acc_words = HEAD + (size_t)n * SILREF_WORDS + ((size_t)n + 1) / 2;
+    m->st_poses_host.resize((size_t)n);
+    m->silref_params_host.resize((size_t)n);
+    m->silref_acc_host.assign(acc_words, 0ull);
+    std::vector<int2> &items = m->st_items_host;
+    items.clear();
+    std::vector<size_t> chunk_end;   // items.size() after each chunk
+    for (int a = 0; a < n; a++) {
+      const SilrefState &p = st[(size_t)active[(size_t)a]];
+      m->st_poses_host[(size_t)a] = p.P;
+      m->silref_params_host[(size_t)a] = silref_params_of(p.P, rad);
+      // (a pose whose origin is nearer than the near constant has no scale: refused below, its tiles are not walked)
+      if (p.P.t[2] >= FRAME_RENDER_NEAR) append_tile_items(items, a % chunk, frame_tile_bound(p.P, (double)mesh.max_norm, H, W), ntx);
+      if ((a + 1) % chunk == 0 || a + 1 == n) chunk_end.push_back(items.size());
+    }
+    if (grow_stage(m, 0, 0, 0, items.size())) return 1;
+    unsigned long long *acc = m->silref_acc + HEAD;
+    int *flag_d = reinterpret_cast<int *>(acc + (size_t)n * SILREF_WORDS);
+    FP_HIP_OK(hipMemcpyAsync(m->st_poses, m->st_poses_host.data(), (size_t)n * sizeof(FramePose), hipMemcpyHostToDevice, s));
+    FP_HIP_OK(hipMemcpyAsync(m->silref_params, m->silref_params_host.data(), (size_t)n * sizeof(SilrefParams), hipMemcpyHostToDevice, s));
+    if (!items.empty()) FP_HIP_OK(hipMemcpyAsync(m->st_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    FP_HIP_OK(hipMemsetAsync(acc, 0, (acc_words - HEAD) * sizeof(unsigned long long), s));   // accumulators and refusal words together
+    size_t first = 0;
+    for (size_t c = 0; c < chunk_end.size(); c++) {
+      const int a0 = (int)c * chunk, cn = std::min(chunk, n - a0);
+      {
+        ProfScope ps(&m->prof, s, "silref_vertex", 0, (double)cn * V * (12.0 + 16.0));
+        launch_pose_vertices(s, "silref_vertex", mesh, m->st_poses + a0, cn, nullptr, 0, m->st_snap, nullptr, flag_d + a0, nullptr);
+        FP_HIP_OK(hipGetLastError());
+      }
+      if (chunk_end[c] > first) {
+        ProfScope ps(&m->prof, s, "silref_tile", 0, (double)(chunk_end[c] - first) * (double)F * 60.0);
+        if (launch_item_runs(first, chunk_end[c], FP_SILREF_MAX_WORK, F, [&](size_t at, int cnt) {
+              launch_silref_tiles(s, mesh, m->st_snap, m->st_items + at, cnt, m->depth, m->silref_sd, H, W, gate2, tol_m, occlusion, m->silref_params, flag_d,
+                                  a0, acc);
+              FP_HIP_OK(hipGetLastError());
+              return 0;
+            }))
+          return 1;
+        first = chunk_end[c];
+      }
+    }
+    FP_HIP_OK(hipMemcpyAsync(m->silref_acc_host.data(), m->silref_acc, acc_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    FP_HIP_OK(hipStreamSynchronize(s));
+    if (pass == 0) {
+      const int *any_h = reinterpret_cast<const int *>(m->silref_acc_host.data() + 2);
+      FP_CHECK(any_h[0] != 0, "[FoundationPose] fp_refine_silhouette: the mask is empty (no pixel has a byte > 0): it has no outline");
+      FP_CHECK(any_h[1] != 0, "[FoundationPose] fp_refine_silhouette: the mask covers the whole frame: it has no outline");
+    }
+    const unsigned long long *acc_h = m->silref_acc_host.data() + HEAD;
+    const int *flag_h = reinterpret_cast<const int *>(acc_h + (size_t)n * SILREF_WORDS);
+    // ---- per pose: the record of this evaluation, then the update (or the reason to stop)
+    for (int a = 0; a < n; a++) {
+      SilrefState &p = st[(size_t)active[(size_t)a]];
+      fp_silhouette_refine_t &r = p.rec;
+      const int refused = flag_h[a] | (p.P.t[2] >= FRAME_RENDER_NEAR ? 0 : FRAME_RENDER_FLAG_NEAR);
+      if (refused) {   // fp_render_pose would refuse: the input stays as it is, an updated pose goes back to what it was (and to that record)
+        r.status |= refused << 2;
+        if (pass > 0) {
+          std::memcpy(p.R, p.R_prev, sizeof(p.R)); std::memcpy(p.t, p.t_prev, sizeof(p.t));
+          p.P = p.P_prev;
+          r.iterations--;
+        }
+        p.state = 2;
+        continue;
+      }
+      const unsigned long long *w = acc_h + (size_t)a * SILREF_WORDS;
+      const SilrefParams &q = m->silref_params_host[(size_t)a];
+      for (int k = 0; k < SILREF_SUMS; k++) r.sums_q24[k] = (int64_t)w[k];
+      r.n_model = (int32_t)w[28]; r.n_contour = (int32_t)w[29]; r.n_used = (int32_t)w[30]; r.n_occluded = (int32_t)w[31];
+      r.n_far = (int32_t)w[32]; r.n_flat = (int32_t)w[33]; r.n_steep = (int32_t)w[34];
+      r.scale_px = q.s;
+      r.rms_px = r.n_used ? (float)(std::sqrt((double)r.sums_q24[27] / 16777216.0 / (double)r.n_used) * (double)q.s) : 0.0f;
+      if (p.state == 1 || pass == iterations) { p.state = 2; continue; }
+      if (r.n_used < FP_SILREF_MIN_PIXELS) { r.status |= FP_SILREF_TOO_FEW; p.state = 2; continue; }
+      IcpSolve S = icp_solve(r.sums_q24, 16777216.0, (flags & FP_SILREF_TRANSLATION_ONLY) != 0);
+      const double rot = std::sqrt(S.xi[0] * S.xi[0] + S.xi[1] * S.xi[1] + S.xi[2] * S.xi[2]);
+      const double radii = std::sqrt(S.xi[3] * S.xi[3] + S.xi[4] * S.xi[4] + S.xi[5] * S.xi[5]);
+      const double trans = radii * (double)rad;
+      // the step cap: the whole twist is scaled, so its direction stays the solve's
+      double scale = 1.0;
+      if (rot > FP_SILREF_MAX_STEP_RAD) scale = std::min(scale, FP_SILREF_MAX_STEP_RAD / rot);
+      if (radii > FP_SILREF_MAX_STEP_RADII) scale = std::min(scale, FP_SILREF_MAX_STEP_RADII / radii);
+      if (scale < 1.0)
+        for (int k = 0; k < 6; k++) S.xi[k] *= scale;
+      const double ups[3] = {S.xi[3] * (double)rad, S.xi[4] * (double)rad, S.xi[5] * (double)rad};
+      r.rank = S.rank; r.cond = (float)S.cond; r.last_rot_rad = (float)(rot * scale); r.last_trans_m = (float)(trans * scale);
+      std::memcpy(p.R_prev, p.R, sizeof(p.R)); std::memcpy(p.t_prev, p.t, sizeof(p.t));
+      p.P_prev = p.P;
+      icp_apply(p.R, p.t, S.xi, ups);
+      for (int k = 0; k < 9; k++) p.P.r[k] = (float)p.R[k];
+      for (int k = 0; k < 3; k++) p.P.t[k] = (float)p.t[k];
+      r.iterations++;
+      if (rot < (double)FP_SILREF_EPS_ROT_RAD && trans < (double)FP_SILREF_EPS_TRANS_M) {
+        r.status |= FP_SILREF_CONVERGED;
+        p.state = std::memcmp(&p.P, &p.P_prev, sizeof(FramePose)) == 0 ? 2 : 1;   // the same f32 pose: the record is already that of the returned pose
+      }
+    }
+  }
+  for (int i = 0; i < N; i++) {
+    const SilrefState &p = st[(size_t)i];
+    const float *in = poses + (size_t)i * 16;
+    float *o = out_poses + (size_t)i * 16;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) o[c * 4 + r] = p.P.r[r * 3 + c];
+      o[12 + r] = p.P.t[r];
+    }
+    o[3] = in[3]; o[7] = in[7]; o[11] = in[11]; o[15] = in[15];
+    out[i] = p.rec;
+  }
   return 0;
 } FP_CATCH_INT
 

@@ -470,6 +470,27 @@ void launch_silhouette_tiles(hipStream_t s, const DeviceMesh &m, const int4 *sna
                              const uint8_t *mask, const uint32_t *d2, int H, int W, float tol_m, long long t2, bool amodal, const int *flags, int pose0,
                              unsigned long long *acc);
 
+// silhouette refinement (fp_refine_silhouette; fp_refine_silhouette.hip).  sd [H, W] is the signed squared distance
+// of the call's mask: -d2[1] on a mask pixel, d2[0] elsewhere (never 0).  A pose's accumulator is SILREF_WORDS 64-bit words: the 21
+// upper-triangle entries of sum J J^T (row-major), the 6 of sum J e, sum e^2 -- each term llrintf(product * 2^24) -- then n_model,
+// n_contour, n_used, n_occluded, n_far, n_flat, n_steep.
+constexpr int SILREF_SUMS = 28, SILREF_COUNTS = 7, SILREF_WORDS = SILREF_SUMS + SILREF_COUNTS;
+constexpr float SILREF_MAX_TERM = 64.0f;            // = FP_SILREF_MAX_TERM
+struct SilrefParams {
+  float fx, fy, cx, cy;
+  float kx, ky;     // (fx * rad) / s, (fy * rad) / s
+  float s, rad;     // the object's radius in pixels, (fx * rad) / t.z; diameter * 0.5f
+  float t[3];       // the pose's translation
+  float pad;
+};
+void launch_mask_signed_d2(hipStream_t s, const uint8_t *mask, const uint32_t *d2, int H, int W, int32_t *sd);
+// items [n_items] = {pose of the chunk, tile}: acc[(pose0 + pose) SILREF_WORDS ..] += the tile's sums and counts, under params[pose0 + pose];
+// an item whose flags[pose0 + pose] is not zero does nothing.  gate2 > 0: a contour pixel with |sd| > gate2 is far.  occlusion: a contour
+// pixel that frame_occluded(depth, z, tol_m) hides is dropped; otherwise the depth is not read.
+void launch_silref_tiles(hipStream_t s, const DeviceMesh &m, const int4 *snap, const int2 *items, int n_items, const float *depth,
+                         const int32_t *sd, int H, int W, int gate2, float tol_m, bool occlusion, const SilrefParams *params, const int *flags,
+                         int pose0, unsigned long long *acc);
+
 // depth search (fp_pose_search; fp_pose_search.hip): per pose the sampled vertices and their normals against the
 // frame's raw depth at n_steps pushes along the ray of the pose's origin; a record is ten 32-bit words, fp_pose_search_t's layout.
 constexpr int SEARCH_THREADS = 256;

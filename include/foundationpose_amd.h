@@ -93,9 +93,9 @@ const uint8_t *fp_mesh_vertex_colors(const fp_loaded_mesh *mesh);
  * refiner_weights / scorer_weights: paths of packed weight files (tools/pack_weights.py; replaces the TensorRT
  * engines of simple_tests/src/test_foundationpose.cpp:13-14).  NULL = geometry-only model (NN entry points fail).
  * K: the 3x3 intrinsics, row-major; all nine entries are copied.  Register, Track and the stage operators of their path take K as the
- * reference does, as a matrix, so a skew K[1] is honoured there.  The eleven frame-resolution calls -- fp_render_pose, fp_render_scene,
+ * reference does, as a matrix, so a skew K[1] is honoured there.  The twelve frame-resolution calls -- fp_render_pose, fp_render_scene,
  * fp_pose_errors, fp_pose_vsd, fp_refine_depth, fp_pose_search, fp_register_depth, fp_pose_color, fp_resolve_symmetry,
- * fp_mask_distance, fp_pose_silhouette -- read fx = K[0], fy = K[4], cx = K[2], cy = K[5]
+ * fp_mask_distance, fp_pose_silhouette, fp_refine_silhouette -- read fx = K[0], fy = K[4], cx = K[2], cy = K[5]
  * only and REFUSE a model whose K is not a plain pinhole matrix (K[1] == K[3] == K[6] == K[7] == 0, K[8] == 1, K[0] and K[4] finite and
  * positive, K[2] and K[5] finite): on the host, before anything is uploaded or launched, with a message that names the entry, their
  * outputs untouched.  fx != fy and a principal point anywhere are fine everywhere. */
@@ -618,6 +618,73 @@ int fp_mask_distance(fp_model *m, const void *mask, int memspace,
 int fp_pose_silhouette(fp_model *m, const char *target_name, const void *mask, int memspace,
                        const float *poses, int N, float tol_m, int trunc_px, int flags,
                        fp_pose_silhouette_t *out /* host [N] */);
+
+/* ---- silhouette refinement: N poses moved onto the mask's outline, no depth needed (new; the reference has no counterpart) ----
+ * fp_refine_silhouette improves N poses of one target from a mask of the uploaded frame alone: each iteration renders every pose at
+ * frame resolution, takes the pixels of the pose's own outline, reads at each the signed distance to the mask's outline and its gradient,
+ * sums the 6 x 6 normal system of "move the outline onto the mask's" on the device in integers and solves it on the host in double.
+ * Poses, mask, memspace, K and the frame guards are fp_pose_silhouette's; the iteration protocol is fp_refine_depth's.  DESIGN.md section
+ * 4.16 has the rules; in short (every f32 operation separately rounded):
+ *   signed map   once per call, from fp_mask_distance's two maps: sd(r, c) = mask ? -d2_to_bg : d2_to_mask (an i32, never 0);
+ *                psi = sd > 0 ? sqrtf((float)sd) : sd == 0 ? 0 : 1 - sqrtf((float)(-sd)): 0 on the mask's own contour pixels, 1 on the
+ *                first ring outside, negative inside.  A mask that is empty or covers the whole frame fails the call.
+ *   contour      a model pixel (fp_render_pose's model_mask, z its model_depth) with at least one of its four neighbours INSIDE the frame
+ *                that is not a model pixel (a neighbour outside the frame is not background)
+ *   classes      of a contour pixel, tested in this order:  occluded  only with FP_SILREF_OCCLUSION: D >= 0.001f && D < z - tol_m on the raw
+ *                depth;  far  gate_px > 0 and |sd| > gate_px * gate_px;  flat  gx == 0 && gy == 0, with
+ *                gx = (psi(r, min(c + 1, W - 1)) - psi(r, max(c - 1, 0))) * 0.5f and gy likewise over rows;  steep  one of J, e below is a
+ *                NaN or above FP_SILREF_MAX_TERM in magnitude;  used  otherwise.  n_contour is the sum of the five.
+ *   per pose     (host, f32) rad = diameter * 0.5f, s = (fx * rad) / t.z (the radius in pixels), kx = (fx * rad) / s, ky = (fy * rad) / s;
+ *                a pose with !(t.z >= FP_RENDER_NEAR_M) is refused like one with such a vertex
+ *   used:        X = ((float)c - cx) / fx, Y = ((float)r - cy) / fy, a = ((gx * kx) / z, (gy * ky) / z, -(ax * X + ay * Y)),
+ *                pc = ((z * X - t.x) / rad, (z * Y - t.y) / rad, (z - t.z) / rad), J = (pc x a, a), e = -psi / s
+ *   the 28 products J_i J_j (i <= j), J_i e, e e are one f32 multiplication each and enter 64-bit sums as llrintf(v * 2^24)
+ * so pose i's record and pose are byte-identical alone, in any batch, under any chunking and from call to call.  Per iteration the host
+ * solves (sum J J^T) xi = sum J e as fp_refine_depth does (the same decomposition, the same FP_ICP_RANK_EPS), scales the whole xi by
+ * min(1, FP_SILREF_MAX_STEP_RAD / |omega|, 0.5 / |upsilon / rad|), and applies R <- exp(omega) R, t <- t + upsilon.
+ * FP_SILREF_TRANSLATION_ONLY solves the 3 x 3 translation block alone: an outline that a rotation or a change of depth does not move
+ * (a sphere's, an ellipsoid's about its axis) does not determine them.  `iterations` = I allows at most I updates and I + 1 evaluations;
+ * I = 0 measures only.  A pose stops when its update BEFORE the scaling is below both epsilons (FP_SILREF_CONVERGED; the update is applied,
+ * and the pose is evaluated once more unless its f32 form did not change), when fewer than FP_SILREF_MIN_PIXELS pixels are used
+ * (FP_SILREF_TOO_FEW, no update), or when fp_render_pose would refuse the updated pose (the status bit; the pose before that update and
+ * its record are returned, `iterations` does not count it).  The record always describes the returned pose.  A pose refused at the input
+ * does not fail the call: its output equals its input, its counts are 0, its status bit is set.  There is no depth term: chain
+ * fp_refine_depth afterwards where the depth is good.
+ * Refused with an error before anything is launched and before the outputs are written: everything fp_pose_silhouette refuses (tol_m is
+ * checked with and without FP_SILREF_OCCLUSION; gate_px in the place of trunc_px), iterations outside 0..FP_SILREF_MAX_ITERATIONS, and
+ * more than FP_SILREF_MAX_WORK faces walked: (iterations + 1) times the sum over the input poses' (pose, 32 x 32 px tile) items of F.  No
+ * launch covers more than a tenth of it.  An empty or full mask fails the call after the distance transform, before the outputs are
+ * written.  Works on geometry-only models; stream-ordered on the model's stream with one synchronisation per evaluation; Register, Track,
+ * their captured graphs and every existing kernel are untouched: the call's buffers are its own or fp_pose_silhouette's, grow-only. */
+#define FP_SILREF_MAX_ITERATIONS 32
+#define FP_SILREF_TRANSLATION_ONLY 1     /* flags: solve the 3 x 3 translation block only (symmetric outlines) */
+#define FP_SILREF_OCCLUSION 2            /* flags: drop the contour pixels that fp_render_pose would call occluded (reads the depth) */
+#define FP_SILREF_MAX_TERM 64.0f         /* a pixel with |J_i| or |e| above it is steep, not used: no sum can reach 2^62 */
+#define FP_SILREF_MAX_STEP_RAD 0.2       /* the update is scaled down to at most this rotation ... */
+#define FP_SILREF_MAX_STEP_RADII 0.5     /* ... and at most this translation, in object radii */
+#define FP_SILREF_MIN_PIXELS 16          /* fewer used pixels: the pose stops */
+#define FP_SILREF_EPS_ROT_RAD FP_ICP_EPS_ROT_RAD
+#define FP_SILREF_EPS_TRANS_M FP_ICP_EPS_TRANS_M
+#define FP_SILREF_MAX_WORK 250000000000LL /* faces walked by one call: 1.00 s at the 2.50e11 faces/s measured for 252 poses */
+#define FP_SILREF_CONVERGED 1            /* status bits of a record, as FP_ICP_* */
+#define FP_SILREF_TOO_FEW 2
+#define FP_SILREF_REFUSED_NEAR 4
+#define FP_SILREF_REFUSED_RANGE 8
+typedef struct fp_silhouette_refine {
+  int32_t n_model, n_contour, n_used, n_occluded, n_far, n_flat, n_steep;  /* frame pixels; n_contour is the sum of the five after it */
+  int32_t iterations;      /* updates applied to this pose */
+  int32_t rank;            /* directions kept by the last solve (0 when none was made) */
+  int32_t status;
+  float   rms_px;          /* sqrt(sum e^2 / n_used) * scale_px at the RETURNED pose; 0 when n_used == 0 */
+  float   scale_px;        /* s, the object's radius in pixels at the returned pose */
+  float   cond;            /* lambda_min / lambda_max of the last solve (0 when none was made) */
+  float   last_rot_rad, last_trans_m;   /* size of the last update as applied (after the scaling) */
+  float   reserved_f;
+  int64_t sums_q24[28];    /* at the RETURNED pose: 21 upper-triangle entries of sum J J^T (row-major), 6 of sum J e, sum e^2 */
+} fp_silhouette_refine_t;
+int fp_refine_silhouette(fp_model *m, const char *target_name, const void *mask, int memspace,
+                         const float *poses, int N, int iterations /* 0..32 */, int gate_px /* 0 = none, else 1..FP_SIL_MAX_TRUNC_PX */,
+                         float tol_m, int flags, float *out_poses /* host [N*16] */, fp_silhouette_refine_t *out /* host [N] */);
 
 /* ---- stage-level operators (what the reference's orchestrator calls; used by the parity tests) ---- */
 

@@ -303,6 +303,19 @@ public:
                                  flags, out.data()));
   }
 
+  // silhouette refinement (foundationpose_amd.h "silhouette refinement"): `poses` moved until the model's outline lies on the outline of
+  // that mask; `refined` gets the poses, `out` the counts, the integer sums and how each iteration ended.  No depth is read unless flags
+  // has FP_SILREF_OCCLUSION (tol_m is RenderPose's tolerance then); gate_px > 0 drops outline pixels farther than that from the mask's
+  // outline; FP_SILREF_TRANSLATION_ONLY leaves the rotation alone.  A pose that would need a clipper comes back unchanged with its status bit.
+  bool RefineSilhouette(const std::string &target_name, const uint8_t *mask, const std::vector<Pose> &poses, std::vector<Pose> &refined,
+                        std::vector<fp_silhouette_refine_t> &out, int iterations = 15, int gate_px = 0, float tol_m = 0.005f, int flags = 0,
+                        int memspace = FP_HOST) {
+    refined.resize(poses.size());
+    out.resize(poses.size());
+    return ok(fp_refine_silhouette(h_, target_name.c_str(), mask, memspace, poses.empty() ? nullptr : poses[0].data(), (int)poses.size(), iterations,
+                                   gate_px, tol_m, flags, refined.empty() ? nullptr : refined[0].data(), out.data()));
+  }
+
   const std::string &last_error() const { return err_; }
   fp_model *handle() { return h_; }
 
